@@ -17,17 +17,20 @@ gathered on rank 0 over RCCL: total work is fixed, so "scaling" is "strong".
 On one GPU every frame is enqueued as ONE hipGraph launch (GaussianScene.capture_frame: all ~23
 kernel launches of a frame are recorded once and replayed; --no-graphs enqueues them one by one).
 `value` follows SURVEY.md 8(d): W*H over the MEDIAN of hipEvent-bracketed single frames with one frame
-in flight (--repeats x --steps of them); `ms_per_step` is the contract's wall-clock region (K such
-frames between fences).  The rate with 3 frames in flight on 3 HIP streams (--streams) is reported
-beside it as `value_frames_in_flight`.
+in flight (one batch of K of them after the timed steps, at most VALUE_WINDOW_S; --full: --repeats batches);
+`ms_per_step` is the contract's wall-clock region (the K timed steps between fences).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run does only what `value` and `ms_per_step` need: set-up, W warm-up steps, the K timed steps,
+--dump-outputs DIR (the last timed step's frame as DIR/frame.npy, float32), the batch of event-bracketed
+frames, one JSON line.  --full adds everything else, and rank 0's line then also carries
+  value_frames_in_flight  the rate with 3 frames in flight on 3 HIP streams (--streams);
   roofline      the dominant kernel (tile compositing): algorithmic bytes per launch over its
                 average duration, measured live with HIP events on the launch stream;
   cpu_baseline  the oracle's C restatement timed on this host's cores on a bounded sample of
                 the same workload (rank 0, N = 1 only), plus the scalar Python restatement on
                 one tile (the stand-in for the reference's pure-Python loop);
-  max_abs_dpixel  max |GPU - CPU| over the sampled window (parity, target <= 1e-4).
+  max_abs_dpixel  max |GPU - CPU| over the sampled window (parity, target <= 1e-4);
+and the moving-camera, per-stage, tile-list, reference-fixture and multi-GPU records.
 """
 from __future__ import annotations
 
@@ -84,6 +87,26 @@ FP32_LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9   # 256 CU x 4 SIMD x 32 lanes/clk x 
 # blend_tile16_kernel: per trip (2 records x 4 pixels of a lane) 18 unpacked +
 # 32 packed (2 lane-ops each) + 8 v_exp_f32 = 90 lane-ops in 58 issue slots, i.e. 11.25 per pair.
 VALU_OPS_PER_PAIR = 11.25
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+VALUE_WINDOW_S = 10.0          # a plain run times at most this much of event-bracketed frames for `value`
+
+
+def dump_outputs(path: str, frame: torch.Tensor) -> None:
+    """--dump-outputs: the frame the timed path returned in its last step, as ``path``/frame.npy (float32, the layout the
+    caller receives).  A frame larger than DUMP_BYTES is written as a fixed sample of its pixels instead -- the same pixels
+    in every run (seed 0): frame_sample.npy (pixels x 3) and their flat pixel indices, frame_sample_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    a = frame.detach().to(torch.float32).cpu().numpy()
+    if a.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(path, "frame.npy"), a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    k = DUMP_BYTES // 2 // (px.shape[1] * 4)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], k, replace=False))
+    np.save(os.path.join(path, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(path, "frame_sample_index.npy"), idx.astype(np.float64))
+
+
 # PMC passes of the same command, committed under profiles/ (tools/profile_round.sh; the newest round that has the file)
 def _pmc_file(name: str):
     for tag in ("r6", "r5", "r4", "r3"):
@@ -469,6 +492,8 @@ def bench_notebook(args, device) -> None:
     for _ in range(args.steps):
         image = scene.render_image_cuda(1, tile_size=tile)     # the drop-in's method, whole flow, per call
     ms_per_step = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, image)
     med = lambda v: float(np.median(np.asarray(v)))  # noqa: E731
     native_ms, pre_ms, flow_ms = med(t_native) * 1e3, med(t_pre) * 1e3, med(t_flow) * 1e3
     out = {
@@ -488,7 +513,7 @@ def bench_notebook(args, device) -> None:
                                 "note": "stated context: other hardware, and the reference kernel visits every Gaussian "
                                         "at every pixel (splat/c/render.cu:49-81) where libgsx bins them into tiles"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the CUDA kernel's rules restated in C (oracle/raster_cpu.c:orc_render_cuda_semantics, parity unpinned: the
         # reference kernel cannot run here) on a 640x640 window of the frame -- it walks all N per pixel like the
         # kernel it restates -- compared on the window's interior (means are truncated toward zero: a splat
@@ -763,9 +788,16 @@ def main() -> None:
                     help="frames in flight: consecutive frames alternate over this many HIP streams, so one "
                          "frame's latency-bound sorts overlap another's VALU-bound compositing (N > 1: the strips of "
                          "consecutive frames, strips.StripPipeline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside `value` and `ms_per_step`: --repeats, frames in flight, "
+                         "separate launches, the moving camera, per-stage times and rooflines, tile-list lengths, the CPU "
+                         "baseline and the comparisons with the reference's fixtures, the multi-GPU records")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last one returned to DIR/frame.npy (float32; a frame "
+                         "over 64 MB as a fixed sample of its pixels, DIR/frame_sample.npy + frame_sample_index.npy)")
     ap.add_argument("--repeats", type=int, default=25,
-                    help="the --steps hipEvent-bracketed single frames are repeated this many times; `value` is W*H over "
-                         "the MEDIAN frame time of all of them (SURVEY.md 8(d))")
+                    help="--full: the batch of --steps hipEvent-bracketed single frames is repeated this many times (a plain "
+                         "run: once, at most 10 s of frames); `value` is W*H over the MEDIAN frame time of all of them (SURVEY.md 8(d))")
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="untimed frames rendered during setup, before the --warmup steps, for this many ms")
     ap.add_argument("--no-graphs", action="store_true",
@@ -854,7 +886,7 @@ def main() -> None:
             os.path.basename(args.ply), n, scene.gaussians.sh_degree, width, height)
     else:
         n_orbit = 0
-        if args.camera_path != "none" and not multi and args.strip_of <= 1 and args.semantics == "ref_cpu":
+        if args.full and args.camera_path != "none" and not multi and args.strip_of <= 1 and args.semantics == "ref_cpu":
             kind, _, cnt = args.camera_path.partition(":")
             if kind != "orbit" or not (cnt or "61").isdigit() or int(cnt or 61) < 3:
                 raise SystemExit("--camera-path: orbit:N with N >= 3, or none")
@@ -936,16 +968,17 @@ def main() -> None:
 
     step.count = 0
     strip_cache = {}
-    streams = [torch.cuda.Stream(device) for _ in range(args.streams)] if (not multi and args.streams > 1) else []
+    # (the frames-in-flight legs, --full only, run step(); the timed steps run single_frame())
+    streams = [torch.cuda.Stream(device) for _ in range(args.streams)] if (args.full and not multi and args.streams > 1) else []
     outs = {st: torch.empty((width, height, 3), dtype=torch.float32, device=device) for st in streams}
     single_out = torch.empty((width, height, 3), dtype=torch.float32, device=device) if not multi else None
     # N > 1: strips of consecutive frames in flight on side streams, gathers in frame order on this stream
     pipeline = None
-    if multi and args.streams > 1 and not args.sync_frames:
+    if args.full and multi and args.streams > 1 and not args.sync_frames:
         pipeline = strips.StripPipeline(render_strip, width, height, tile, layout, device, depth=args.streams,
                                         semantics=sem, plan=strip_plan)
     use_graphs = not multi and not args.no_graphs and not args.sync_frames
-    gstreams = (streams or [torch.cuda.Stream(device)]) if use_graphs else []
+    gstreams = (streams or [torch.cuda.Stream(device)]) if (use_graphs and args.full) else []
     graphs = {st: scene.capture_frame(1, tile_size=tile, layout=layout, semantics=sem) for st in gstreams}
     lat_stream = torch.cuda.Stream(device)
     one = scene.capture_frame(1, tile_size=tile, layout=layout, semantics=sem) if use_graphs else None
@@ -1032,13 +1065,17 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and frame is not None:     # (N > 1: rank 0 holds the gathered frame)
+        dump_outputs(args.dump_outputs, frame)
 
-    # ---- median of hipEvent-bracketed single frames; the K-step batch is repeated so that a
-    #      fresh box's first milliseconds do not decide the number
+    # ---- median of hipEvent-bracketed single frames (not inside the K steps: an event pair around every
+    #      step costs it ~3 %).  One batch of K frames, at most VALUE_WINDOW_S of them; --full repeats the K-step batch
+    #      --repeats times so that a fresh box's first milliseconds do not decide the number
+    batches = [args.steps] * args.repeats if args.full else [min(args.steps, max(1, int(VALUE_WINDOW_S * 1e3 / ms_per_step)))]
     frame_ms = []
     with torch.cuda.stream(lat_stream):
-        for _ in range(args.repeats):
-            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for batch in batches:
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(batch)]
             for e0, e1 in evs:
                 e0.record()
                 single_frame()
@@ -1098,7 +1135,7 @@ def main() -> None:
     if respeculated:
         raise SystemExit("speculative frames missed their instance hint %d times: timing invalid" % respeculated)
 
-    moving = moving_camera_leg(args, scene, sc, tile, layout, sem, lat_stream) if (not multi and len(scene.images) > 3) else None
+    moving = moving_camera_leg(args, scene, sc, tile, layout, sem, lat_stream) if (args.full and not multi and len(scene.images) > 3) else None
 
     # per-stage HIP-event times of this rank's share (live, same process, separate loop)
     stage = {}
@@ -1108,7 +1145,7 @@ def main() -> None:
     if multi:
         plan = strip_plan or strips.strip_plan(strips.tiles_along(width, tile, sem), world)[1]
         window = (plan[rank][0], plan[rank][1], 0, strips.tiles_along(height, tile, sem))
-    for _ in range(reps):
+    for _ in range(reps if args.full else 0):
         stats = {}
         scene.render_image_hip(1, tile_size=tile, layout=layout, tile_window=window, stats=stats, timing=True,
                                semantics=sem)
@@ -1117,7 +1154,7 @@ def main() -> None:
 
     # how long the tile lists are (GsxParams.tile_counts): the compositing kernel lasts as long as its longest
     tile_list = None
-    if not multi and strip_window is None:
+    if args.full and not multi and strip_window is None:
         ntx_, nty_ = strips.tiles_along(width, tile, sem), strips.tiles_along(height, tile, sem)
         if ntx_ * nty_ > 0:
             tc = torch.zeros(ntx_ * nty_, dtype=torch.int32, device=device)
@@ -1127,7 +1164,7 @@ def main() -> None:
                          "p99": float(tcs[int(0.99 * (len(tcs) - 1))]), "max": float(tcs[-1]), "tiles": int(len(tcs))}
 
     strips_ok = None
-    if multi:
+    if args.full and multi:
         # the gathered frame must equal the single-GPU frame bit for bit
         last = single_frame()
         torch.cuda.synchronize()
@@ -1138,7 +1175,7 @@ def main() -> None:
         dist.barrier()
     # what the process group actually was (the first multi-GPU run has to explain itself): every rank's device and strip
     dist_info = None
-    if multi:
+    if args.full and multi:
         mine = {"rank": rank, "local_rank": local_rank, "device": torch.cuda.get_device_name(device),
                 "tile_columns": [int(window[0]), int(window[1])], "n_kept": int(stats.get("n_kept") or 0),
                 "tile_instances": int(stats.get("n_instances") or 0), "stage_ms_total": round(stage.get("total", 0.0), 4)}
@@ -1175,6 +1212,30 @@ def main() -> None:
                                           "all_gather_object, the gather and a grouped send / recv pair have executed against "
                                           "the real backend; no data crossed a link")
     if rank == 0:
+        out = {
+            "metric": "Mpixels/sec forward raster (1M Gaussians, 1080p) + max |dpixel| vs CPU ref",
+            # SURVEY.md 8(d): W*H over the MEDIAN of hipEvent-bracketed single frames, one frame in flight
+            "value": round(mpix, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "user-supplied .ply" if args.ply else "synthetic",
+            "frame_ms": {"median": round(median_ms, 4), "min": round(float(frame_ms[0]), 4),
+                         "max": round(float(frame_ms[-1]), 4), "p90": round(float(frame_ms[int(0.9 * (len(frame_ms) - 1))]), 4),
+                         "frames": int(len(frame_ms)),
+                         "how": "hipEvent pair around every frame, one frame in flight, %d x %d frames%s" % (
+                             len(batches), batches[0], "; largest per-rank median" if multi else "")},
+            "config": {"workload": desc, "n_gaussians": n, "width": width, "height": height, "tile": tile,
+                       "semantics": sem, "layout": layout,
+                       "frames_in_flight": 1,
+                       "launch": "one hipGraph replay per frame" if one is not None else "separate kernel launches",
+                       "frame_sync": "host reads instance count every frame" if args.sync_frames
+                       else "speculative (GSX_FLAG_NO_SYNC), counts confirmed after the timed region",
+                       "parallelism": "1 GPU" if not multi else "%d column strips + RCCL gather (%s)" % (
+                           world, "sub-strips sent while the next is composited, %d parts" % args.substrips if overlapped["on"]
+                           else "one gather behind the frame" + ("; overlapped path failed: %s" % overlapped["why"] if overlapped["why"] else "")),
+                       "strip_plan": None if not multi else (strip_plan or "equal")},
+            "fps": round(1e3 / median_ms, 2),
+        }
+    if rank == 0 and args.full:
         d, nvis = int(stats["n_instances"]), int(stats["n_visible"])
         my_tiles = int(stats["n_tiles"])
         blend_ms = stage.get("blend", 0.0)
@@ -1192,36 +1253,17 @@ def main() -> None:
         plain_instance = ref_rules and tile == 16 and (bool(getattr(one, "_plain_footprints", False)) if one is not None
                                                        else bool(stats.get("plain_footprints")))
         pmc_traffic, pmc_valu, pmc_file = pmc_record(args.workload, world, args.strip_of, args.spatial_order) if ref_rules else (None, None, None)
-        out = {
-            "metric": "Mpixels/sec forward raster (1M Gaussians, 1080p) + max |dpixel| vs CPU ref",
-            # SURVEY.md 8(d): W*H over the MEDIAN of hipEvent-bracketed single frames, one frame in flight
-            "value": round(mpix, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "user-supplied .ply" if args.ply else "synthetic",
-            "frame_ms": {"median": round(median_ms, 4), "min": round(float(frame_ms[0]), 4),
-                         "max": round(float(frame_ms[-1]), 4), "p90": round(float(frame_ms[int(0.9 * (len(frame_ms) - 1))]), 4),
-                         "frames": int(len(frame_ms)),
-                         "how": "hipEvent pair around every frame, one frame in flight, %d x %d frames%s" % (
-                             args.repeats, args.steps, "; largest per-rank median" if multi else "")},
-            # whole-job rate with several frames in flight on separate HIP streams (not the contract's number)
-            "value_frames_in_flight": None if inflight_ms is None else round(width * height / (inflight_ms * 1e-3) / 1e6, 2),
-            "config": {"workload": desc, "n_gaussians": n, "width": width, "height": height, "tile": tile,
-                       "semantics": sem, "layout": layout, "n_visible": nvis, "n_kept": int(stats.get("n_kept") or 0), "tile_instances": d,
-                       # tiles (and long-tile quarters) that held an ill-conditioned footprint, evaluated in the reference's
-                       # operation order; 0: a large window's later frames take GSX_FLAG_PLAIN_FOOTPRINTS
-                       "tiles_redone": int(stats.get("n_redo") or 0),
-                       "frames_in_flight": 1,
-                       "launch": "one hipGraph replay per frame" if one is not None else "separate kernel launches",
-                       "ms_per_frame_in_flight": None if inflight_ms is None else round(inflight_ms, 4),
-                       "frames_in_flight_for_that": (max(1, len(streams)) if not multi else (pipeline.depth if pipeline else 1)),
-                       "ms_per_frame_separate_launches": None if launches_ms is None else round(launches_ms, 4),
-                       "frame_sync": "host reads instance count every frame" if args.sync_frames
-                       else "speculative (GSX_FLAG_NO_SYNC), counts confirmed after the timed region",
-                       "parallelism": "1 GPU" if not multi else "%d column strips + RCCL gather (%s)" % (
-                           world, "sub-strips sent while the next is composited, %d parts" % args.substrips if overlapped["on"]
-                           else "one gather behind the frame" + ("; overlapped path failed: %s" % overlapped["why"] if overlapped["why"] else "")),
-                       "strip_plan": None if not multi else (strip_plan or "equal")},
-            "fps": round(1e3 / median_ms, 2),
+        # whole-job rate with several frames in flight on separate HIP streams (not the contract's number)
+        out["value_frames_in_flight"] = None if inflight_ms is None else round(width * height / (inflight_ms * 1e-3) / 1e6, 2)
+        out["config"].update({
+            "n_visible": nvis, "n_kept": int(stats.get("n_kept") or 0), "tile_instances": d,
+            # tiles (and long-tile quarters) that held an ill-conditioned footprint, evaluated in the reference's
+            # operation order; 0: a large window's later frames take GSX_FLAG_PLAIN_FOOTPRINTS
+            "tiles_redone": int(stats.get("n_redo") or 0),
+            "ms_per_frame_in_flight": None if inflight_ms is None else round(inflight_ms, 4),
+            "frames_in_flight_for_that": (max(1, len(streams)) if not multi else (pipeline.depth if pipeline else 1)),
+            "ms_per_frame_separate_launches": None if launches_ms is None else round(launches_ms, 4)})
+        out.update({
             "roofline": {"bound": "hbm", "kernel": ("blend_tile16_kernel<1> (GSX_FLAG_PLAIN_FOOTPRINTS)" if plain_instance else "blend_tile16_ref_kernel") if ref_rules
                          else "blend_rules_kernel",
                          "achieved": round(achieved, 2),
@@ -1244,7 +1286,7 @@ def main() -> None:
                                "unit": "GB/s", "frac": round(frame_bytes / (median_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
             "stage_ms": {k: round(v, 4) for k, v in stage.items()},
             "tile_list_length": tile_list,
-        }
+        })
         if stage.get("project", 0.0) > 0.0 and not multi:
             # the HBM-bound stage: 56 B read + 60 B written per Gaussian that reaches a tile (record 48, key 4,
             # rectangle 8); the HIP-event bracket includes the launch, the kernel alone is ~3 us shorter (profiles/)
@@ -1299,6 +1341,7 @@ def main() -> None:
                 out["parity_ok"] = bool(err <= 1e-4 and (inst is None or d <= inst) and
                                         base["threshold_flip_pixels"] <= 2 + 1e-5 * base["window_pixels"] and
                                         base["max_abs_dpixel_incl_flips"] < 0.006)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if multi:
         dist.barrier()

@@ -12,6 +12,7 @@ the absent third-party ``plyfile`` module (only used for an IO side effect of th
     python oracle/capture_golden.py small      # only those whose name contains "small"
     python oracle/capture_golden.py tiles_     # the reference-rendered tiles of the 1M-Gaussian 1080p scenes (~10 min)
     python oracle/capture_golden.py fuzz_tiles # reference-rendered tiles of 24 random scenes (~8 min)
+    python oracle/capture_golden.py fuzz_stage1  # stage 1 of 8 random scenes: hashes + what happened at equal depths (~10 s)
 """
 from __future__ import annotations
 
@@ -446,6 +447,74 @@ def capture_fuzz_tiles(name: str, seeds, GaussianScene, Gaussians) -> None:
     print("wrote %s (%d tiles of %d scenes, %.0f KB)" % (path, len(blocks), len(seeds), os.path.getsize(path) / 1024), flush=True)
 
 
+# the stage-1 cases of tests/test_oracle_golden.py::test_fuzz_against_the_reference_itself: (seed, also through the numpy
+# restatement) -- fuzz_vs_reference.py --cases 6 --renders 0 --seed 7000 --also 1016,1152
+FUZZ_STAGE1_FIXTURES = {"fuzz_stage1_seeds_7000": [(s, s % 4 == 0) for s in range(7000, 7006)] + [(1016, True), (1152, True)]}
+
+
+def capture_fuzz_stage1(name: str, cases, GaussianScene, Gaussians) -> None:
+    """The reference's ``GaussianScene.preprocess`` on random cases of oracle/fuzz_vs_reference.py, small enough to commit: per
+    case (keys ``s<seed>_*``) its camera constants, the SHA-256 of every stage-1 array put back in original Gaussian order
+    (float32 bits, culled rows zero; sigmoid_opacity with the rows inside runs of equal depths zero as well), of the permutation
+    outside those runs, and inside them the reference's own order and sigmoid_opacity (position dependent: cpu_ref.sigmoid_torch)."""
+    import torch
+
+    from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import fuzz_vs_reference
+
+    rows, out = [], {}
+    for seed, numpy_too in cases:
+        case = fuzz_vs_reference.random_case(seed, False)
+        sc = case["gen"](**case["args"])
+        sc.pop("sh", None)
+        sc.pop("sh_degree", None)
+        n = sc["points"].shape[0]
+        with tempfile.TemporaryDirectory() as tmp, torch.no_grad():
+            write_colmap_text(os.path.join(tmp, "colmap"), sc)
+            g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
+            g.points = torch.from_numpy(sc["points"]).float()
+            g.scales = torch.from_numpy(sc["scales"]).float()
+            g.quaternions = torch.from_numpy(sc["quaternions"]).float()
+            g.opacity = torch.from_numpy(sc["opacity"]).float()
+            scene = GaussianScene(os.path.join(tmp, "colmap"), g)
+            cam = scene.images[1]
+            from splat.utils import in_view_frustum
+
+            in_view = in_view_frustum(points=g.points, view_matrix=cam.world2view)
+            pre = scene.preprocess(1)
+            hom = torch.cat([g.points[in_view], torch.ones(int(in_view.sum()), 1)], dim=1)
+            perm = torch.argsort((hom @ cam.world2view)[:, 2])
+            assert torch.equal((hom @ cam.world2view)[:, 2][perm], pre.depths), "argsort is not reproducible"
+            assert np.array_equal(g.colors.numpy(), sc["colors_0_255"].astype(np.float32) / np.float32(256.0))
+        ref_order = np.nonzero(in_view.numpy())[0][perm.numpy()].astype(np.int64)
+        tied = tie_runs(pre.depths.numpy())
+        p = "s%d_" % seed
+        for f in fuzz_vs_reference.FIELDS:
+            ra = np.ascontiguousarray(getattr(pre, f).detach().numpy(), np.float32)
+            if f == "sigmoid_opacity":
+                out[p + "tie_sigmoid_opacity"] = ra[tied]
+                ra = np.where(tied.reshape((-1,) + (1,) * (ra.ndim - 1)), np.float32(0.0), ra)
+            a = np.zeros((n,) + ra.shape[1:], np.float32)
+            a[ref_order] = ra
+            out[p + "sha256_" + f] = np.array(sha256(a))
+        out.update({p + "order_outside_ties_sha256": np.array(sha256(ref_order[~tied])),
+                    p + "tie_positions": np.nonzero(tied)[0].astype(np.int32), p + "tie_order": ref_order[tied].astype(np.int32),
+                    p + "inputs_sha256": np.array(sha256(np.concatenate([sc[k].reshape(-1) for k in ("points", "colors_0_255", "scales",
+                                                                                                     "quaternions", "opacity")]))),
+                    p + "world2view": cam.world2view.numpy(), p + "full_proj_transform": cam.full_proj_transform.numpy(),
+                    p + "tan_fovX": cam.tan_fovX.numpy(), p + "tan_fovY": cam.tan_fovY.numpy(), p + "f_x": cam.f_x.numpy(),
+                    p + "f_y": cam.f_y.numpy()})
+        rows.append((seed, int(numpy_too), n, ref_order.size, int(cam.width.item()), int(cam.height.item()), int(tied.sum())))
+        print("  %s seed %d %-9s n=%7d visible=%7d tied=%5d" % (name, seed, case["kind"], n, ref_order.size, int(tied.sum())), flush=True)
+    out.update(columns=np.array("seed numpy_too n n_visible width height tied".split()), rows=np.array(rows, dtype=np.int64),
+               torch_num_threads=np.int64(torch.get_num_threads()))       # the sigmoid's chunking depends on it
+    path = os.path.join(OUT_DIR, name + ".npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s (%d cases, %.0f KB)" % (path, len(cases), os.path.getsize(path) / 1024), flush=True)
+
+
 def capture(name: str, spec: dict, GaussianScene, Gaussians) -> None:
     import torch
 
@@ -607,6 +676,9 @@ def main() -> None:
     for name, seeds in FUZZ_TILE_FIXTURES.items():
         if only in name:
             capture_fuzz_tiles(name, seeds, GaussianScene, Gaussians)
+    for name, cases in FUZZ_STAGE1_FIXTURES.items():
+        if only in name:
+            capture_fuzz_stage1(name, cases, GaussianScene, Gaussians)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,8 @@
 
 TEST INFRASTRUCTURE, BUILD CONTAINER ONLY: it imports the reference from /root/reference (never copied), which does
 not exist on the GPU box -- ``python oracle/fuzz_vs_reference.py`` exits 0 with a "skipped" line there, and
-tests/test_oracle_golden.py::test_fuzz_against_the_reference_itself skips.  The 22 committed fixtures pin the oracle on
+tests/test_oracle_golden.py::test_fuzz_against_the_reference_itself holds the restatements against the reference's outputs
+on its seeds as recorded in tests/golden/fuzz_stage1_seeds_7000.npz (capture_golden.py).  The committed fixtures pin the oracle on
 the scenes somebody chose; this pins it on scenes nobody chose.
 
 Bar: every stage-1 array (depth, pixel position, 2D covariance, its inverse, radius, the four bounding-box arrays,

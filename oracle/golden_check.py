@@ -159,6 +159,29 @@ def rows_in_reference_order(pre_order, g):
 FUZZ_TILE_FIXTURE_NAMES = ["fuzz_tiles_seeds_8000"]
 
 
+def fuzz_stage1_cases(g):
+    """Per case of a ``fuzz_stage1_*`` fixture (oracle/capture_golden.py: capture_fuzz_stage1 -- the reference's own preprocess of
+    random scenes): (seed, whether the numpy restatement is held against it too, the scene's arrays regenerated from the seed and
+    checked against the hash of what the reference was given, the reference's camera as a cpu_ref.Camera, the case's record: its row
+    and its ``s<seed>_*`` arrays under their names without the prefix)."""
+    from oracle import cpu_ref, fuzz_vs_reference
+
+    cols = [str(c) for c in g["columns"]]
+    for r in g["rows"]:
+        rec = dict(zip(cols, (int(v) for v in r)))
+        p = "s%d_" % rec["seed"]
+        rec.update({k[len(p):]: g[k] for k in g.files if k.startswith(p)})
+        case = fuzz_vs_reference.random_case(rec["seed"], False)
+        sc = case["gen"](**case["args"])
+        sc.pop("sh", None)
+        sc.pop("sh_degree", None)
+        assert sha256(np.concatenate([sc[k].reshape(-1) for k in ("points", "colors_0_255", "scales", "quaternions", "opacity")])) \
+            == str(rec["inputs_sha256"]), "the generator no longer makes the scene the reference was given (seed %d)" % rec["seed"]
+        cam = cpu_ref.Camera(rec["world2view"], rec["full_proj_transform"], rec["tan_fovX"][0], rec["tan_fovY"][0], rec["f_x"][0],
+                             rec["f_y"][0], rec["width"], rec["height"])
+        yield rec["seed"], bool(rec["numpy_too"]), sc, cam, rec
+
+
 def fuzz_tiles_cases(g):
     """Per scene of a ``fuzz_tiles_*`` fixture (oracle/capture_golden.py: capture_fuzz_tiles -- random scenes whose tiles the REFERENCE's
     own ``render_tile`` composited): (seed, the scene's arrays regenerated from the seed, its row dict, [(tx, ty, list length, block)])."""

@@ -1256,7 +1256,7 @@ def test_ranks_sharing_one_gpu_assemble_the_single_gpu_frame(world, extra):
 
     tool = os.path.join(ROOT, "tools", "bench_two_ranks_one_gpu.py")
     r = subprocess.run([sys.executable, tool, str(world), "--workload", "c2", "--steps", "3", "--warmup", "1", "--repeats", "1",
-                        "--no-cpu-baseline", "--streams", "1"] + extra, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--streams", "1", "--full"] + extra, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -2071,7 +2071,7 @@ def test_multi_gpu_path_meets_rccl_with_a_world_of_one():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-preflight", "--workload", "c2",
-                          "--steps", "3", "--warmup", "1", "--repeats", "2", "--settle-ms", "10"],
+                          "--steps", "3", "--warmup", "1", "--repeats", "2", "--settle-ms", "10", "--full"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])

@@ -334,7 +334,6 @@ def test_tie_order_effect_at_the_benchmark_sizes(name):
     assert d.max() <= 1e-4 and int((d > 1e-4).sum()) == 0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="build container only: imports the reference from /root/reference")
 @pytest.mark.parametrize("name", FUZZ_TILE_FIXTURE_NAMES)
 def test_reference_rendered_tiles_of_random_scenes(name, tmp_path):
     """tests/golden/fuzz_tiles_*: 24 scenes nobody chose (oracle/fuzz_vs_reference.py's generators: uniform, clustered, trained-like,
@@ -366,18 +365,49 @@ def test_reference_rendered_tiles_of_random_scenes(name, tmp_path):
 
 
 def test_fuzz_against_the_reference_itself():
-    """oracle/fuzz_vs_reference.py on a few seeds nobody looked at before (random generator, size, pose, frame): every
-    stage-1 array of the C restatement (and of the numpy one on every fourth case) carries the reference's bits, the
-    permutation is the reference's outside equal depths.  The script's default run (24 + 6 cases, images included) is the
-    one to repeat after touching an oracle; this keeps a slice of it in the suite."""
-    import subprocess
-    import sys
+    """oracle/fuzz_vs_reference.py's stage-1 cases on a few seeds nobody looked at before (random generator, size, pose, frame),
+    held against the reference's own preprocess of them as recorded by oracle/capture_golden.py (capture_fuzz_stage1,
+    tests/golden/fuzz_stage1_seeds_7000.npz): every stage-1 array of the C restatement (and of the numpy one on every fourth
+    case) carries the reference's bits, the permutation is the reference's outside equal depths.  The script's default run
+    (24 + 6 cases, images included) against the reference itself is the one to repeat after touching an oracle; this keeps a
+    slice of it in the suite."""
+    from oracle.fuzz_vs_reference import FIELDS, bits
+    from oracle.golden_check import fuzz_stage1_cases
 
-    # (a child process: importing the reference stubs an absent third-party module and extends sys.path)
     # (fixed seeds: the suite is the same run every time; `python oracle/fuzz_vs_reference.py --seed N` is where new ones are
     # tried.  1016 / 1152: of 200 cases run in round 6 the two in which the NUMPY port stood one bit off the reference -- its
     # float64 stand-in for libm's expf on the tail of a torch thread's chunk -- and the C port did not)
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "fuzz_vs_reference.py"), "--cases", "6", "--renders", "0",
-                          "--seed", "7000", "--also", "1016,1152"], capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-2000:]
-    assert "0 differing bits outside equal depths" in run.stdout, run.stdout[-3000:]
+    g = load_golden("fuzz_stage1_seeds_7000")
+    diffs, seeds = {}, []
+    for seed, numpy_too, sc, cam, rec in fuzz_stage1_cases(g):
+        seeds.append(seed)
+        colors = sc["colors_0_255"].astype(np.float32) / np.float32(256.0)      # splat/gaussians.py:20-22
+        tied = rec["tie_positions"].astype(np.int64)
+        for label, fn in [("c", c_oracle.preprocess)] + ([("numpy", cpu_ref.preprocess)] if numpy_too else []):
+            mine = fn(sc["points"], colors, sc["scales"], sc["quaternions"], sc["opacity"], cam)
+            key = "%d:%s:" % (seed, label)
+            order = np.asarray(mine.order, np.int64)
+            if order.size != rec["n_visible"]:
+                diffs[key + "n_visible"] = abs(order.size - rec["n_visible"])
+                continue
+            outside = np.ones(order.size, bool)
+            outside[tied] = False
+            if sha256(order[outside]) != str(rec["order_outside_ties_sha256"]):
+                diffs[key + "order_outside_ties"] = 1
+            for f in FIELDS:
+                v = np.asarray(getattr(mine, f), np.float32).reshape(order.size, -1)
+                if f == "sigmoid_opacity":
+                    # position dependent (cpu_ref.sigmoid_torch): inside runs of equal depths compared where the Gaussian sits at the
+                    # reference's position; a Gaussian the tie order moved is not a difference of the arithmetic
+                    same = order[tied] == rec["tie_order"]
+                    ref_tied = rec["tie_sigmoid_opacity"].reshape(tied.size, v.shape[1])
+                    if not np.array_equal(bits(v[tied][same]), bits(ref_tied[same])):
+                        diffs[key + f + "@ties"] = int(np.count_nonzero(bits(v[tied][same]) != bits(ref_tied[same])))
+                    v = v.copy()
+                    v[tied] = 0.0
+                a = np.zeros((rec["n"], v.shape[1]), np.float32)
+                a[order] = v
+                if sha256(a) != str(rec["sha256_" + f]):
+                    diffs[key + f] = 1
+    assert seeds == list(range(7000, 7006)) + [1016, 1152]
+    assert not diffs, "stage-1 arrays differing from the reference's: %r" % diffs

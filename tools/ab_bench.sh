@@ -9,7 +9,7 @@ cd $R
 for w in "$@"; do
   for side in new old; do
     if [ $side = old ]; then export GSX_TEST_LIB_PATH=$R/$OLD; else unset GSX_TEST_LIB_PATH; fi
-    python bench.py --workload $w --test-lib --no-cpu-baseline --repeats 10 > $O/ab_${w}_$side.json 2> $O/ab_${w}_$side.err
+    python bench.py --full --workload $w --test-lib --no-cpu-baseline --repeats 10 > $O/ab_${w}_$side.json 2> $O/ab_${w}_$side.err
     python - $O/ab_${w}_$side.json $w $side <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ cd $R
 for rep in $(seq $REPS); do
   for side in default knob; do
     if [ $side = knob ]; then export "$KV"; else unset ${KV%%=*}; fi
-    python bench.py --workload $W --test-lib --no-cpu-baseline --repeats 10 --camera-path none > $O/env_${W}_$side.json 2> $O/env_${W}_$side.err
+    python bench.py --full --workload $W --test-lib --no-cpu-baseline --repeats 10 --camera-path none > $O/env_${W}_$side.json 2> $O/env_${W}_$side.err
     python - $O/env_${W}_$side.json $W "$side ($KV)" <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ cd $R
 for rep in 1 2; do
 for side in new old; do
   if [ $side = old ]; then export GSX_TEST_LIB_PATH=$R/$OLD; else unset GSX_TEST_LIB_PATH; fi
-  python bench.py --workload c4 --strip-of 8 --test-lib --repeats 10 > $O/strip_$side.json 2> $O/strip_$side.err
+  python bench.py --full --workload c4 --strip-of 8 --test-lib --repeats 10 > $O/strip_$side.json 2> $O/strip_$side.err
   python - $O/strip_$side.json $side <<'PY'
 import json, sys
 try:

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-P="python3 $R/bench.py --steps 5 --warmup 1 --repeats 1 --no-cpu-baseline --streams 1 --camera-path none --workload c4 --strip-of 8"
+P="python3 $R/bench.py --full --steps 5 --warmup 1 --repeats 1 --no-cpu-baseline --streams 1 --camera-path none --workload c4 --strip-of 8"
 for so in plain spatial; do
   A=""; [ $so = spatial ] && A="--spatial-order"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/p_fetch_$so -o p -- $P $A > /dev/null 2>&1

@@ -10,8 +10,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --streams 1 --camera-path none"
-P="python3 $R/bench.py --steps 5 --warmup 1 --repeats 1 --no-cpu-baseline --streams 1 --camera-path none"
+B="python3 $R/bench.py --full --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --streams 1 --camera-path none"
+P="python3 $R/bench.py --full --steps 5 --warmup 1 --repeats 1 --no-cpu-baseline --streams 1 --camera-path none"
 for w in c3 c2 c4 c3_clustered c3_trainedlike strip strip_spatial; do
   if [ $w = strip ]; then A="--workload c4 --strip-of 8"; elif [ $w = strip_spatial ]; then A="--workload c4 --strip-of 8 --spatial-order"; else A="--workload $w"; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o $w -- $B $A > $O/prof_$w.log 2>&1
@@ -44,11 +44,11 @@ PY
   done
 done
 cd $R
-for w in c1 c2 c3 c4 c3_clustered c3_trainedlike c3_1m2 notebook; do python bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; done
-python bench.py --workload c4 --strip-of 8 > $O/bench_strip.json 2> $O/bench_strip.err
-python bench.py --workload c4 --strip-of 8 --spatial-order > $O/bench_strip_spatial.json 2> $O/bench_strip_spatial.err
-python bench.py --semantics std_3dgs > $O/bench_c3_std3dgs.json 2> $O/bench_c3_std3dgs.err
+for w in c1 c2 c3 c4 c3_clustered c3_trainedlike c3_1m2 notebook; do python bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; done
+python bench.py --full --workload c4 --strip-of 8 > $O/bench_strip.json 2> $O/bench_strip.err
+python bench.py --full --workload c4 --strip-of 8 --spatial-order > $O/bench_strip_spatial.json 2> $O/bench_strip_spatial.err
+python bench.py --full --semantics std_3dgs > $O/bench_c3_std3dgs.json 2> $O/bench_c3_std3dgs.err
 python tools/make_synthetic_ply.py /tmp/c3_deg3.ply 1000000 3 > /dev/null 2>&1
-python bench.py --workload c3 --ply /tmp/c3_deg3.ply > $O/bench_c3_sh3.json 2> $O/bench_c3_sh3.err
+python bench.py --full --workload c3 --ply /tmp/c3_deg3.ply > $O/bench_c3_sh3.json 2> $O/bench_c3_sh3.err
 python __graft_entry__.py smoke 2>&1 | tail -1
 du -sh $O; ls -la $O | sort -k5 -n | tail -5

@@ -114,7 +114,7 @@ def pmc_summary(w):
     nty = (cfg["height"] - 1) // 16 if cfg["height"] % 16 else cfg["height"] // 16 - 1
     ntx = (cfg["width"] - 1) // 16 if cfg["width"] % 16 else cfg["width"] // 16 - 1
     ntiles = (int(m.group(2)) - int(m.group(1))) * nty if m else ntx * nty
-    out = {"source": "rocprofv3 --pmc <counters> --kernel-trace (one pass per counter set) -- python3 bench.py --steps 5 --warmup 1 "
+    out = {"source": "rocprofv3 --pmc <counters> --kernel-trace (one pass per counter set) -- python3 bench.py --full --steps 5 --warmup 1 "
                      "--repeats 1 --no-cpu-baseline --streams 1 (%s), MI355X, ROCm 7.2" % LABELS[w],
            "units": "FETCH_SIZE / WRITE_SIZE are KiB per dispatch (bytes = value*1024); on gfx950 FETCH_SIZE reports 1/2 of "
                     "coalesced read bytes (MI355X_MICROARCH.md, HBM section), re-calibrated on the whole-frame project_pack_kernel "
