@@ -376,6 +376,27 @@ GSX_API int gsx_render_forward(const GsxCamera *camera, const float *means3d, co
                        void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Backward pass of gsx_render_forward under GSX_SEM_REF_CPU: the gradients the reference's autograd produces for
+ * L(frame), with grad_image = dL/dframe (same layout as the frame, GsxParams.layout), with respect to the colours
+ * (grad_colors, n x 3) and the opacity logits (grad_opacity_logit, n x 1).  The means, scales and quaternions get none:
+ * the reference's Gaussian weight is a Python float (splat/utils.py:357-365).  `image` is the frame gsx_render_forward
+ * produced from the same inputs and params (its pixels enter every gradient).  Projection, depth order and binning are
+ * run again (deterministic: the same lists as the forward's); GsxParams.hints is neither read nor written.  Every row
+ * of both outputs is written (0 for a Gaussian on no tile list).  Same inputs, same bits: no float atomics.
+ * Refused with GSX_ERR_INVALID_ARGUMENT: other semantics, GsxParams.sh, a tile window, an output window, substrips,
+ * GSX_FLAG_NO_SYNC, camera_device.  workspace: gsx_backward_workspace_bytes(n, width, height, tile, pairs) with at
+ * least the frame's pair count (GsxFrameStats.n_instances of the forward); fewer: GSX_ERR_WORKSPACE_TOO_SMALL.
+ * Synchronises `stream`.
+ */
+GSX_API int gsx_render_backward(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                        const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                        const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                        const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_render_backward needs (0 on invalid arguments). */
+GSX_API size_t gsx_backward_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =
  * (R S)(R S)^T from linear scales (n,3) and quaternions (n,4) (w,x,y,z), the quaternion
  * normalised twice as the reference does.  The render entry points compute this inline; the

@@ -98,6 +98,9 @@ SIGNATURES = {
                                 POINTER(GsxParams), POINTER(GsxFrameStats), c_void_p, c_size_t, c_void_p]),
     "gsx_render_forward": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32, _FP,
                            POINTER(GsxParams), POINTER(GsxFrameStats), c_void_p, c_size_t, c_void_p]),
+    "gsx_render_backward": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 4 +
+                            [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
+    "gsx_backward_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),
     "gsx_covariance_3d": (ctypes.c_int, [_FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_covariance_2d": (ctypes.c_int, [POINTER(GsxCamera), _FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_project_points": (ctypes.c_int, [POINTER(GsxCamera), _FP, c_int64, _FP, c_void_p, c_void_p]),
@@ -109,6 +112,7 @@ DEBUG_SIGNATURES = {
     "gsx_debug_sort_pairs": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t,
                                             c_void_p]),
     "gsx_debug_set_blend_probe": (ctypes.c_int, [c_void_p]),
+    "gsx_debug_backward_stage_ms": (ctypes.c_int, [POINTER(c_float)]),
     "gsx_debug_depth_sort": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_uint32,
                                             c_int64, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
 }

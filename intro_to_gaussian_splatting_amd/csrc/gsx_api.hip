@@ -6,6 +6,9 @@
 #include <string.h>
 
 #include "gsx_internal.h"
+#ifdef GSX_TEST_HOOKS
+#include "gsx_debug.h"
+#endif
 
 namespace {
 
@@ -257,6 +260,50 @@ int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles,
     return GSX_OK;
 }
 
+// gsx_render_backward's workspace: the forward's carve for `cap` pairs, then per Gaussian its raw stage-1 record
+// (launch_project_raw), its rank and the emission prefix, the scan's block sums, and one float4 slot per pair.
+struct BackwardCarve {
+    Carve fwd;
+    size_t raw, rank_of, prefix, bsum, slots, total;
+};
+BackwardCarve backward_carve(int64_t n, int64_t cap, int64_t max_tiles) {
+    BackwardCarve b;
+    b.fwd = carve(n, cap, max_tiles, binning_temp_bytes(n, cap));
+    const size_t nn = (size_t)(n > 0 ? n : 1), cc = (size_t)(cap > 0 ? cap : 1);
+    size_t off = b.fwd.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes);
+        return at;
+    };
+    b.raw = take(nn * kRecordBytes);
+    b.rank_of = take(nn * 4);
+    b.prefix = take((nn + 1) * 4);
+    b.bsum = take((nn / 1024 + 2) * 4);
+    b.slots = take(cc * 16);
+    b.total = off;
+    return b;
+}
+int64_t backward_capacity_for(size_t bytes, int64_t n, int64_t max_tiles) {
+    auto fits = [&](int64_t cap) { return backward_carve(n, cap, max_tiles).total <= bytes; };
+    if (!fits(1)) return -1;
+    int64_t lo = 1, hi = kMaxPairs;
+    if (fits(hi)) return hi;
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (fits(mid))
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+#ifdef GSX_TEST_HOOKS
+// test library only (gsx_debug.h: gsx_debug_backward_stage_ms): the last gsx_render_backward call's stages under GSX_FLAG_TIMING
+thread_local float g_backward_ms[3] = {0.0f, 0.0f, 0.0f};
+#endif
+
 }  // namespace
 
 extern "C" {
@@ -464,6 +511,126 @@ int gsx_render_forward(const GsxCamera *camera, const float *means3d, const floa
     return bin_and_blend(p, c, ws, n, cap, (const gsx::TileRect *)(ws + c.rrect), v0, counters + kCtrKept,
                          counters + kCtrCulled, sampled, stats_host, tm, s, fh);
 }
+
+size_t gsx_backward_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    if (n < 0 || width <= 0 || height <= 0 || tile <= 0 || max_instances < 0) return 0;
+    if (n >= (int64_t)1 << 31 || max_instances >= (int64_t)1 << 31) return 0;
+    return backward_carve(n, max_instances, max_tiles_of(width, height, tile)).total;
+}
+
+int gsx_render_backward(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                        const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                        const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                        const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    Plan p;
+    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
+    if (rc != GSX_OK) return rc;
+    // what the backward pass covers: the reference's own frame, whole, RGB colours
+    if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward supports GSX_SEM_REF_CPU only");
+    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes RGB colours, not GsxParams.sh");
+    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward renders the whole frame: no tile window");
+    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes the whole frame: no output window");
+    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward does not take substrips");
+    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward synchronises: no GSX_FLAG_NO_SYNC");
+    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward reads the camera argument: no camera_device");
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld out of range", (long long)n);
+    if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
+    if (n > 0 && (!means3d || !scales || !quats || !opacity_logit || !colors)) return fail(GSX_ERR_INVALID_ARGUMENT, "an input array is NULL");
+    if (p.original_index && !p.row_of_index) return fail(GSX_ERR_INVALID_ARGUMENT, "original_index needs row_of_index (its inverse)");
+    const uint32_t *row_of = p.original_index ? (const uint32_t *)p.row_of_index : nullptr;
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    const int64_t max_tiles = max_tiles_of(camera->width, camera->height, tile_size);
+    const int64_t cap = backward_capacity_for(workspace_bytes, n, max_tiles);
+    if (cap < 0)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes cannot hold %lld Gaussians", workspace_bytes, (long long)n);
+    const BackwardCarve bc = backward_carve(n, cap, max_tiles);
+    const Carve &c = bc.fwd;
+    char *ws = (char *)workspace;
+    StageTimer tm;
+    tm.begin(p.timing, s);
+    // every row of both outputs: a Gaussian on no tile list has zero gradients
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_colors, (size_t)n * 3, s));
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_opacity_logit, (size_t)n, s));
+    if (n == 0 || p.grid.count() == 0) {
+        GSX_HIP(hipStreamSynchronize(s));
+        return GSX_OK;
+    }
+    // ---- the forward's stages on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
+    uint32_t *k0 = (uint32_t *)(ws + c.keys0), *k1 = (uint32_t *)(ws + c.keys1);
+    uint32_t *v0 = (uint32_t *)(ws + c.vals0), *v1 = (uint32_t *)(ws + c.vals1);
+    uint32_t *counters = (uint32_t *)(ws + c.counters);
+    gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
+    const gsx::DepthRoute route = gsx::depth_sort_route(n, p.kept_hint);
+    const bool sampled = route != gsx::kDepthLsd;
+    gsx::SortHints sh{nullptr, nullptr, nullptr, false};
+    gsx::SampleHint presample;
+    if (sampled && gsx::knob("GSX_PRESAMPLE", 1) != 0)
+        presample = gsx::depth_presample(route, ws + c.temp, n, gsx::emit_chunk_sums(ws + c.temp, n, cap), row_of);
+    GSX_HIP(gsx::launch_project_pack(*camera, nullptr, in, n, p.grid, p.semantics, p.tight, p.small_batch, -1, k0,
+                                     (gsx::Record *)(ws + c.rec), (gsx::TileRect *)(ws + c.rect), counters, (float4 *)(ws + c.bbox),
+                                     gsx::ScheduleHint{nullptr, nullptr, nullptr, 0u, 0u}, nullptr, s, presample));
+    if (sampled)
+        GSX_HIP(gsx::sort_depth_sampled(route, ws + c.temp, k0, k1, v0, v1, n, p.kept_hint, counters + kCtrKept,
+                                        counters + kCtrCulled, (const gsx::TileRect *)(ws + c.rect),
+                                        (gsx::TileRect *)(ws + c.rrect), 0, gsx::emit_chunk_sums(ws + c.temp, n, cap), sh, s, row_of,
+                                        presample.splitters != nullptr));
+    else
+        GSX_HIP(gsx::sort_depth_compact(ws + c.temp, k0, k1, v0, v1, n, counters + kCtrKept, counters + kCtrCulled,
+                                        (const gsx::TileRect *)(ws + c.rect), (gsx::TileRect *)(ws + c.rrect), s, nullptr,
+                                        nullptr, nullptr, row_of));
+    int64_t *dev2 = (int64_t *)(counters + 4);
+    uint2 *ranges = (uint2 *)(ws + c.ranges);
+    gsx::BinCounts bcnt{dev2, nullptr, counters + kCtrPairs, counters + kCtrLong, (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
+    GSX_HIP(gsx::emit_instances(ws + c.temp, (const gsx::TileRect *)(ws + c.rrect), v0, counters + kCtrKept, n, cap, p.grid,
+                                ws + c.tkeys0, (uint32_t *)(ws + c.tvals0), ranges, bcnt, sampled, p.kept_hint, s));
+    const uint32_t *sorted_vals = nullptr;
+    gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
+    GSX_HIP(gsx::sort_instances(ws + c.temp, cap, p.grid, ws + c.tkeys0, ws + c.tkeys1, (uint32_t *)(ws + c.tvals0),
+                                (uint32_t *)(ws + c.tvals1), ranges, counters + kCtrPairs, lt, &sorted_vals, s));
+    int64_t host2[3] = {0, 0, 0};
+    GSX_HIP(hipMemcpyAsync(host2, dev2, 24, hipMemcpyDeviceToHost, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    tm.mark();  // 1: the forward's stages
+    if (host2[1] > cap)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "frame needs %lld tile instances, workspace holds %lld",
+                    (long long)host2[1], (long long)cap);
+    const uint32_t m = (uint32_t)host2[2];
+    if (m == 0 || host2[1] == 0) return GSX_OK;
+    // ---- the backward kernels
+    gsx::Record *raw = (gsx::Record *)(ws + bc.raw);
+    uint32_t *prefix = (uint32_t *)(ws + bc.prefix), *rank_of = (uint32_t *)(ws + bc.rank_of);
+    float4 *slots = (float4 *)(ws + bc.slots);
+    GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
+    GSX_HIP(gsx::launch_backward_prefix((const gsx::TileRect *)(ws + c.rrect), v0, m, prefix, rank_of, (uint32_t *)(ws + bc.bsum), s));
+    gsx::BackwardTiles bt{raw, sorted_vals, ranges, rank_of, prefix, (const gsx::TileRect *)(ws + c.rrect), image, grad_image, slots};
+    GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
+    tm.mark();  // 2: raw records, prefix, compositing backward
+    GSX_HIP(gsx::launch_backward_sums(slots, prefix, v0, raw, m, grad_colors, grad_opacity_logit, s));
+    tm.mark();  // 3: sums
+    GSX_HIP(hipStreamSynchronize(s));
+#ifdef GSX_TEST_HOOKS
+    if (p.timing) {
+        GsxFrameStats st;
+        memset(&st, 0, sizeof st);
+        tm.finish(&st);
+        for (int i = 0; i < 3; ++i) g_backward_ms[i] = st.stage_ms[i];
+    }
+#endif
+    return GSX_OK;
+}
+
+#ifdef GSX_TEST_HOOKS
+int gsx_debug_backward_stage_ms(float *out3) {
+    if (!out3) return fail(GSX_ERR_INVALID_ARGUMENT, "out3 is NULL");
+    for (int i = 0; i < 3; ++i) out3[i] = g_backward_ms[i];
+    return GSX_OK;
+}
+#endif
 
 int gsx_sh_to_rgb(const float *means3d, const float *sh, int32_t degree, int64_t n, const float *camera_center_host,
                   float *colors_out, void *stream) {

@@ -44,6 +44,11 @@ GSX_API int gsx_debug_depth_sort(uint32_t *keys, int64_t n, const void *rect, vo
  * << 31, such batches | such records << 12, list length) per tile at 2^18 + tile (tools/attic/ref_probe.py). */
 GSX_API int gsx_debug_set_blend_probe(void *device_buffer);
 
+/* The stages of the last gsx_render_backward call of this thread that carried GSX_FLAG_TIMING, in ms: out3[0] = the
+ * forward's stages run again (projection, depth order, pairs, tile sort, the count read-back), out3[1] = raw records +
+ * emission prefix + compositing backward, out3[2] = the per-Gaussian sums (tools/bench_backward.py). */
+GSX_API int gsx_debug_backward_stage_ms(float *out3);
+
 #ifdef __cplusplus
 }
 #endif

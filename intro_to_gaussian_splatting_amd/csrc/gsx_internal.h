@@ -143,6 +143,8 @@ hipError_t launch_project_full(const Record *stage, const uint32_t *order, const
                                const StageOneOut &out, hipStream_t s);
 hipError_t launch_pack_preprocessed(const PreprocessedIn &in, int64_t n, const TileGrid &grid, int semantics,
                                     Record *rec, TileRect *rect, float4 *bbox, hipStream_t s);
+// The backward pass: per row, (x, y, Q00, Q01), (Q10, Q11, op, sigmoid(logit)), (r, g, b, 0) -- project_raw_kernel.
+hipError_t launch_project_raw(const GsxCamera &cam, const GaussiansIn &in, int64_t n, int visible_rows, Record *raw, hipStream_t s);
 hipError_t launch_covariance3d(const float *scales, const float *quats, int64_t n, float *out, hipStream_t s);
 hipError_t launch_covariance2d(const GsxCamera &cam, const float *points, const float *cov3d, int64_t n, float *out,
                                hipStream_t s);
@@ -266,5 +268,25 @@ hipError_t launch_blend(const Record *rec, const float4 *bbox, const uint32_t *s
 bool blend_splits_long_tiles(const TileGrid &grid, int semantics, bool generic);
 hipError_t launch_clear(const ClearPlan &cp, float *base, hipStream_t s);   // the zero fill alone
 hipError_t launch_zero_words(uint32_t *p, size_t n, hipStream_t s);
+
+// ---- gsx_backward.hip (GSX_SEM_REF_CPU): gradients of the frame with respect to the colours and opacity logits
+// Exclusive scan of the tile counts of the rank-ordered rectangles rrect[0 .. m): prefix[r] = emission slot of rank r's
+// first pair (gsx_binning.hip emits a Gaussian's pairs over its rectangle, column by column), prefix[m] = D.  Also
+// rank_of[order[r]] = r.  bsum: one word per 1024 ranks (+1).
+hipError_t launch_backward_prefix(const TileRect *rrect, const uint32_t *order, uint32_t m, uint32_t *prefix,
+                                  uint32_t *rank_of, uint32_t *bsum, hipStream_t s);
+struct BackwardTiles {
+    const Record *raw;            // launch_project_raw, by row
+    const uint32_t *vals;         // sorted pair list: row of each entry, tile by tile
+    const uint2 *ranges;          // [first, last) of every window tile's list
+    const uint32_t *rank_of, *prefix;
+    const TileRect *rrect;
+    const float *image, *grad_image;   // the forward's frame and dL/dframe, layout of `out`
+    float4 *slots;                // one per pair, in emission order: (dL/dc rgb, sum over the tile of dL/dalpha * alpha)
+};
+hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
+// slots of each rank summed in emission order, the sigmoid chain applied, scattered to rows (order[r])
+hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *raw,
+                                uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
 
 }  // namespace gsx

@@ -992,6 +992,30 @@ static void launch_project_pack_deg(const GsxCamera &cam, const GsxCamera *cam_d
 #undef GSX_LAUNCH_PP
 }
 
+namespace {
+// The backward pass (gsx_backward.hip): per ROW, the reference's own float32 stage-1 values of every Gaussian -- pixel mean,
+// raw conic, the opacity factor sigmoid(sigmoid(logit)) and sigmoid(logit) itself, the RGB colour -- by the operations the
+// whole-path projection runs (project, sigmoid_torch, sigmoidf: same bits), for the backward compositing kernel's
+// alpha_ref.  a = (x, y, Q00, Q01)  b = (Q10, Q11, op, s)  c = (r, g, b, 0).  Rows behind the cull plane get whatever the
+// arithmetic gives: no tile list names them.
+__global__ void __launch_bounds__(kBlock)
+    project_raw_kernel(GsxCamera cam, GaussiansIn in, int64_t n, int vis, Record *__restrict__ raw) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= n) return;
+    const float *p = in.means3d + 3 * g, *sc = in.scales + 3 * g, *q = in.quats + 4 * g, *c = in.colors + 3 * g;
+    const float p0 = p[0], p1 = p[1], p2 = p[2];
+    const float tz = row4_view(p0, p1, p2, cam.world2view, 2, vis);
+    Projected o;
+    project(cam, p0, p1, p2, tz, sc[0], sc[1], sc[2], q[0], q[1], q[2], q[3], o, vis);
+    const float s = sigmoid_torch(in.opacity_logit[g]);
+    Record r;
+    r.a = make_float4(o.x, o.y, o.q00, o.q01);
+    r.b = make_float4(o.q10, o.q11, sigmoidf(s), s);
+    r.c = make_float4(c[0], c[1], c[2], 0.0f);
+    raw[g] = r;
+}
+}  // namespace
+
 // sh_degree < 0: in.colors is (n,3) RGB; 0..3: in.colors is (n, (degree+1)^2, 3) spherical harmonics.
 hipError_t launch_project_pack(const GsxCamera &cam, const GsxCamera *cam_device, const GaussiansIn &in, int64_t n,
                                const TileGrid &grid, int semantics, bool tight_rects, int visible_rows, int sh_degree,
@@ -1019,6 +1043,12 @@ hipError_t launch_pack_preprocessed(const PreprocessedIn &in, int64_t n, const T
                                     Record *rec, TileRect *rect, float4 *bbox, hipStream_t s) {
     if (n == 0) return hipSuccess;
     pack_preprocessed_kernel<<<blocks_for(n), kBlock, 0, s>>>(in, n, grid, semantics, rec, rect, bbox);
+    return hipGetLastError();
+}
+
+hipError_t launch_project_raw(const GsxCamera &cam, const GaussiansIn &in, int64_t n, int visible_rows, Record *raw, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    project_raw_kernel<<<blocks_for(n), kBlock, 0, s>>>(cam, in, n, visible_rows ? visible_rows : rows_class(n), raw);
     return hipGetLastError();
 }
 

@@ -224,6 +224,47 @@ class CapturedFrame:
         return self.out
 
 
+def _wants_grad(g) -> bool:
+    """Gradients are recorded for this render: grad mode is on and the colours or the opacity logits require grad."""
+    return torch.is_grad_enabled() and (getattr(g.colors, "requires_grad", False) or
+                                        getattr(g.opacity, "requires_grad", False))
+
+
+def _refuse_with_grad(what: str) -> None:
+    raise ValueError("gradients of the frame (gaussians.colors / gaussians.opacity require grad) are not available with %s: "
+                     "only the whole ref_cpu frame of RGB colours is differentiable (gsx_render_backward); call it under "
+                     "torch.no_grad() or without requires_grad" % what)
+
+
+class _RenderImageFunction(torch.autograd.Function):
+    """The ref_cpu frame as a function of (points, scales, quaternions, opacity, colors).  Forward: the frame
+    ``render_image_hip`` returns without gradients, bit for bit.  Backward: gsx_render_backward -- dL/dcolors and
+    dL/dopacity (logits); points, scales and quaternions get None, as in the reference.  The five tensors are saved, so
+    autograd's version counters catch an in-place edit between forward and backward."""
+
+    @staticmethod
+    def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors):
+        kw = dict(kw)
+        user_stats, st = kw.pop("stats", None), {}
+        frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
+        if user_stats is not None:
+            user_stats.update(st)
+        ctx.scene, ctx.image_idx, ctx.tile_size, ctx.layout = scene, image_idx, tile_size, layout
+        ctx.n_instances, ctx.n_visible = int(st["n_instances"]), int(st["n_visible"])
+        ctx.save_for_backward(points, scales, quaternions, opacity, colors, frame)
+        return frame
+
+    @staticmethod
+    def backward(ctx, grad_frame):
+        points, scales, quaternions, opacity, colors, frame = ctx.saved_tensors
+        scene = ctx.scene
+        gc, go = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
+                                        ctx.n_instances, ctx.n_visible)
+        want_o, want_c = ctx.needs_input_grad[8], ctx.needs_input_grad[9]
+        return (None, None, None, None, None, None, None, None,
+                go.view(opacity.shape) if want_o else None, gc.view(colors.shape) if want_c else None)
+
+
 class GaussianScene:
     def __init__(self, colmap_path: str, gaussians: Gaussians) -> None:
         cameras = read_camera_file(colmap_path)
@@ -387,6 +428,21 @@ class GaussianScene:
         synchronises) before the images are trusted -- it re-renders, on the normal path, any frame
         whose pair count exceeded the workspace capacity it was enqueued with.
         """
+        if _private is None and _wants_grad(self.gaussians):
+            # gradients with respect to the colours / opacity logits (gsx_render_backward): the whole ref_cpu frame only
+            refused = [("semantics=%r" % semantics, semantics != "ref_cpu"),
+                       ("an SH scene (gaussians.sh)", getattr(self.gaussians, "sh", None) is not None),
+                       ("tile_window", tile_window is not None), ("out", out is not None),
+                       ("substrips", substrips is not None), ("no_sync", bool(no_sync)),
+                       ("camera_buffer", camera_buffer is not None)]
+            for what, bad in refused:
+                if bad:
+                    _refuse_with_grad(what)
+            g = self.gaussians
+            kw = dict(stats=stats, timing=timing, generic_kernels=generic_kernels, tile_counts=tile_counts,
+                      split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints)
+            return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
+                                              g.opacity, g.colors)
         lib = _ffi.load()
         dev, n, tensors = self._inputs(image_idx, inline_sh=True)
         g_ = self.gaussians
@@ -597,6 +653,40 @@ class GaussianScene:
                 stats["stage_ms"] = {k: float(st.stage_ms[i]) for i, k in enumerate(_ffi.STAGE_NAMES)}
         return out
 
+    def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
+                         n_instances: int, n_visible: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
+        ``grad_frame``.  The projection, depth order and binning run again in the library (the same lists as the
+        forward's); the scene's hints buffers are not touched."""
+        lib = _ffi.load()
+        with torch.no_grad():
+            dev, n, tensors = self._inputs(image_idx)
+            tensors = [t.detach() for t in tensors]
+            cam = self.images[image_idx].gsx_camera()
+            params = _ffi.default_params()
+            params.layout = _ffi.GSX_LAYOUT_WH3 if layout == "wh3" else _ffi.GSX_LAYOUT_HW3
+            params.semantics = _ffi.GSX_SEM_REF_CPU
+            params.flags |= max(_ffi.visible_rows_flag(n, n_visible, 0), 0)      # the row class the forward ended up with
+            oi = self._original_index(dev, n)
+            if oi is not None:
+                params.original_index, params.row_of_index = oi.data_ptr(), self.gaussians.row_of_index.data_ptr()
+            gf = _check_f32("grad_frame", grad_frame.detach(), dev)
+            img = _check_f32("frame", frame.detach(), dev)
+            if tuple(gf.shape) != tuple(img.shape):
+                raise ValueError("grad_frame has shape %s, the frame %s" % (tuple(gf.shape), tuple(img.shape)))
+            gc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            go = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            cap = int(n_instances) + 4096
+            with torch.cuda.device(dev):
+                nbytes = lib.gsx_backward_workspace_bytes(n, cam.width, cam.height, tile_size, cap)
+                if nbytes == 0:
+                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_backward_workspace_bytes rejected the sizes")
+                ws = _WORKSPACE.get(dev, nbytes)
+                rc = lib.gsx_render_backward(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(img), _ptr(gf),
+                                             _ptr(gc), _ptr(go), ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
+            _ffi.check(rc)
+        return gc, go
+
     def _note_count(self, cap_key, n_instances: int, n_kept: int = 0, n_redo: Optional[int] = None) -> None:
         self._instances_hint = max(self._instances_hint, int(n_instances * 1.1))
         self._cap_hints[cap_key] = int(n_instances * 1.1) + 4096
@@ -651,6 +741,8 @@ class GaussianScene:
         camera centre of that buffer).  The graph holds room for ``headroom`` x the pair count of the captured view; a replay
         that needs more (another camera may) is reported by ``confirm()``.  Possible because the
         no-sync frame has no host dependency at all."""
+        if _wants_grad(self.gaussians):
+            _refuse_with_grad("capture_frame")
         dev = self.gaussians.points.device
         _require_gpu(dev)
         cam = self.images[image_idx].gsx_camera()
@@ -719,6 +811,8 @@ class GaussianScene:
         generator has yielded two more (copy it if it has to live longer).  At 1M Gaussians / 1080p the 25 MB copy
         is longer than the render (0.36 ms): the loop runs at the copy's pace, 0.68 ms per frame measured, where
         ``render_image`` called per frame pays render + copy + two synchronisations, 0.97-1.02 ms (bench.py: host_frames)."""
+        if _wants_grad(self.gaussians):
+            _refuse_with_grad("render_images")
         dev = self.gaussians.points.device
         _require_gpu(dev)
         copy_stream = torch.cuda.Stream(dev)

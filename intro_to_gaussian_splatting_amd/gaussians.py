@@ -3,8 +3,13 @@
 ``points (N,3)``, ``colors (N,3)`` = rgb/256, ``scales (N,3)`` linear (no exp), ``quaternions
 (N,4)`` (w,x,y,z), ``opacity (N,1)`` logit -- float32 PyTorch-ROCm tensors resident in HBM.
 Differences from the reference, on purpose: the constructor has no file side effect (the
-reference writes ``point_cloud.ply``, gaussians.py:17-18) and never tracks gradients (the
-reference's path is forward-only).
+reference writes ``point_cloud.ply``, gaussians.py:17-18) and does not track gradients on its own.
+The reference's image IS differentiable -- with respect to ``colors`` and ``opacity`` only: its
+Gaussian weight is a Python float (splat/utils.py:357-365, ``.item()``), which cuts every path
+through the means and the covariances.  Here gradients are opt-in: ``g.colors.requires_grad_(True)``
+and / or ``g.opacity.requires_grad_(True)``, and ``GaussianScene.render_image`` /
+``render_image_hip`` then return a frame with a ``grad_fn`` whose backward runs in libgsx
+(gsx_render_backward); points, scales and quaternions get no gradient, like the reference's.
 """
 from __future__ import annotations
 

@@ -1,0 +1,89 @@
+"""Gradient fixtures of the backward pass: runs the REFERENCE ITSELF under autograd and stores data only.
+
+Build container only (it needs the reference checkout, which never travels to the GPU box).  The reference's Python is
+imported through oracle.capture_golden's own recipe (_import_reference, _generate); nothing under oracle/ is changed.
+For every scene: L = sum(image * W) with W seeded standard-normal float32 in the image's (x, y, c) layout, and
+torch.autograd.grad(L, [colors, opacity]) of the reference's render_image.  The reference cuts every path through the
+means and covariances (splat/utils.py:357-365 returns `.item()`), so only colours and opacity logits get gradients.
+
+    python tools/capture_grad_golden.py            # all scenes (~20 min of reference time)
+    python tools/capture_grad_golden.py small      # only those whose name contains "small"
+
+Writes tests/golden/grad_<scene>.npz: the scene arguments, W, the reference's image, grad_colors (N,3) and
+grad_opacity (N,1).
+"""
+from __future__ import annotations
+
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
+
+SCENES = ["small_64x48_n300", "small_80x64_n120_tile8", "tile2_40x32_n80", "dense_48x48_n1500", "tiny_48x48_n600",
+          "needle_160x160_n110", "defaults_64x64_n800", "trainedlike_128x128_n3000"]
+
+
+def capture(name: str, GaussianScene, Gaussians) -> None:
+    import torch
+
+    from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
+
+    spec = dict(FIXTURES[name])
+    tile = spec.pop("tile")
+    defaults = spec.pop("defaults", False)
+    sc = _generate(spec)
+    with tempfile.TemporaryDirectory() as tmp:
+        write_colmap_text(os.path.join(tmp, "colmap"), sc)
+        g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
+        with torch.no_grad():
+            g.points = torch.from_numpy(sc["points"]).float()
+            if defaults:        # the constructor's own scales / quaternions / opacity are the fixture's inputs
+                sc["scales"] = g.scales.detach().numpy().astype(np.float32)
+                sc["quaternions"] = g.quaternions.detach().numpy().astype(np.float32)
+                sc["opacity"] = g.opacity.detach().numpy().astype(np.float32)
+            else:
+                g.scales = torch.from_numpy(sc["scales"]).float()
+                g.quaternions = torch.from_numpy(sc["quaternions"]).float()
+        colors = g.colors.detach().clone().requires_grad_(True)
+        opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone().requires_grad_(True)
+        g.colors, g.opacity = colors, opacity
+        scene = GaussianScene(os.path.join(tmp, "colmap"), g)
+        t0 = time.time()
+        image = scene.render_image(1, tile_size=tile)
+        t_fwd = time.time() - t0
+        W = torch.from_numpy(np.random.default_rng(1000 + len(name)).standard_normal(tuple(image.shape)).astype(np.float32))
+        loss = (image * W).sum()
+        t0 = time.time()
+        gc, go = torch.autograd.grad(loss, [colors, opacity], allow_unused=True)
+        t_bwd = time.time() - t0
+    n = sc["points"].shape[0]
+    gc = np.zeros((n, 3), np.float32) if gc is None else gc.numpy()
+    go = np.zeros((n, 1), np.float32) if go is None else go.numpy()
+    out = dict(sc)      # the generator's arrays and camera: enough to build the scene again
+    out.update(opacity=np.asarray(sc["opacity"], np.float32), colors=colors.detach().numpy(), tile=np.int64(tile),
+               W=W.numpy(), image=image.detach().numpy(), grad_colors=gc, grad_opacity=go,
+               reference_forward_seconds=np.float64(t_fwd), reference_backward_seconds=np.float64(t_bwd))
+    path = os.path.join(OUT_DIR, "grad_" + name + ".npz")
+    np.savez_compressed(path, **out)
+    print("grad_%s: N=%d rows with a colour gradient=%d max|gc|=%.3g max|go|=%.3g fwd=%.1fs bwd=%.1fs (%.0f KB)" % (
+        name, n, int((np.abs(gc).sum(1) > 0).sum()), np.abs(gc).max(), np.abs(go).max(), t_fwd, t_bwd,
+        os.path.getsize(path) / 1024), flush=True)
+
+
+def main() -> None:
+    only = sys.argv[1] if len(sys.argv) > 1 else ""
+    GaussianScene, Gaussians = _import_reference()
+    for name in SCENES:
+        if only in name:
+            capture(name, GaussianScene, Gaussians)
+
+
+if __name__ == "__main__":
+    main()
