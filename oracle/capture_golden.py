@@ -65,6 +65,11 @@ FIXTURES = {
     # ... and ONE visible Gaussian (of seven; alone): products with world2view take yet another order on one row
     "onevisible_48x48_n7": dict(n=7, width=48, height=48, seed=43, tile=16, generator="few", visible=1),
     "single_48x48_n1": dict(n=1, width=48, height=48, seed=47, tile=16),
+    # tile shapes of more than 256 pixels or not a multiple of 64 (the backward's chunked and part-wave paths):
+    # 32 -> 2x2 tiles of 1024 px; 20 -> 3x3 tiles of 400 px; 12 -> 4x3 tiles of 144 px with lists of more than 64
+    "tile32_96x96_n400": dict(n=400, width=96, height=96, seed=53, tile=32),
+    "tile20_64x64_n300": dict(n=300, width=64, height=64, seed=59, tile=20),
+    "tile12_dense_52x40_n900": dict(n=900, width=52, height=40, seed=61, tile=12),
 }
 
 # Stage 1 only (the reference's preprocess takes 0.3 .. 1.3 s at these sizes; its render_image would take days):

@@ -14,10 +14,18 @@ from conftest import ROOT, golden_preprocessed, load_golden
 import backward_restatement
 
 GRAD_SCENES = ["small_64x48_n300", "small_80x64_n120_tile8", "tile2_40x32_n80", "dense_48x48_n1500", "tiny_48x48_n600",
-               "needle_160x160_n110", "defaults_64x64_n800", "trainedlike_128x128_n3000"]
+               "needle_160x160_n110", "defaults_64x64_n800", "trainedlike_128x128_n3000",
+               # tiles of 1024, 400 and 144 pixels: backward_tile_kernel's later chunks and part-filled waves
+               "tile32_96x96_n400", "tile20_64x64_n300", "tile12_dense_52x40_n900"]
 # max |restatement - reference| <= REL x max |reference gradient|.  Measured: colours <= 4.7e-7, opacity logits <= 4.2e-6
 # (dense_48x48_n1500: pixels that stop; the reference's own float32 chain is what differs).
 REL = 1e-5
+# Per Gaussian: |gradient - restatement| <= TOL x that Gaussian's own error scale (backward_restatement: scale_c, scale_o),
+# whatever its size next to the largest gradient.  Measured maxima of error / scale -- the reference's own autograd on
+# every GRAD_SCENES fixture: colours 7.1e-7, opacity logits 1.1e-7 (trainedlike_128x128_n3000); gsx_render_backward on
+# an MI355X over every scene of test_hip_backward_edges.py: colours 2.2e-6 (trainedlike_128x128_n3000), opacity logits
+# 4.2e-7 (test_faint_gaussians_keep_their_gradient).  A wrong slot, chunk or skipped record is off by 0.1 .. 1.
+TOL = 8e-6
 
 
 def test_header_declares_and_ffi_binds_the_backward():
@@ -41,6 +49,51 @@ def test_restatement_matches_reference_autograd(scene):
     assert np.abs(ref_c).max() > 0 and np.abs(ref_o).max() > 0
     assert np.abs(gc - ref_c).max() <= REL * np.abs(ref_c).max()
     assert np.abs(go - ref_o).max() <= REL * np.abs(ref_o).max()
+
+
+@pytest.mark.parametrize("scene", GRAD_SCENES)
+def test_reference_autograd_meets_the_per_gaussian_bound(scene):
+    """The per-Gaussian bound is not stricter than the reference itself: its float32 autograd is within TOL x scale of
+    the float64 restatement on every Gaussian, the faintest included."""
+    gg = load_golden("grad_" + scene)
+    pre = golden_preprocessed(load_golden(scene))
+    n = gg["points"].shape[0]
+    gc, go, sc, so = backward_restatement.backward(pre, gg["image"], gg["W"], int(gg["width"]), int(gg["height"]),
+                                                   int(gg["tile"]), n, with_scale=True)
+    ref_c, ref_o = gg["grad_colors"], gg["grad_opacity"]
+    # the scales bound the gradients themselves (up to the restatement's own rounding)
+    assert (np.abs(gc) <= sc[:, None] * (1 + 1e-12)).all() and (np.abs(go[:, 0]) <= so * (1 + 1e-12)).all()
+    ec, eo = backward_restatement.per_gaussian_error(ref_c, ref_o, gc, go, sc, so)
+    print("%s: reference autograd, max error / scale: colours %.3g, opacity logits %.3g" % (scene, ec, eo))
+    assert ec <= TOL and eo <= TOL, (ec, eo)
+
+
+def test_restatement_takes_any_tile_size():
+    """backward() at tile sizes the fixtures do not use (1, 12, 20, 32, 64): every rendered pixel of the tile is walked
+    (the region [0, 2T) x [0, T) of W fills the first two tiles; W = 0 elsewhere gives the same result as naming those
+    two tiles) and the scales bound the gradients.  The fixtures anchor 2, 8, 12, 16, 20 and 32 to the reference."""
+    from oracle import cpu_ref
+
+    pre = golden_preprocessed(load_golden("small_64x48_n300"))
+    n = pre.order.shape[0]
+    rng = np.random.default_rng(7)
+    size = 192                     # frame extent the restatement is told: at least two rendered tiles of 64
+    frame = rng.random((size, size, 3))
+    for tile in (1, 12, 20, 32, 64):
+        assert len(cpu_ref.tile_origins(size, tile)) >= 2
+        W = np.zeros((size, size, 3))
+        W[:2 * tile, :tile] = rng.standard_normal((2 * tile, tile, 3))
+        gc, go, sc, so = backward_restatement.backward(pre, frame, W, size, size, tile, n, with_scale=True)
+        two = backward_restatement.backward(pre, frame, W, size, size, tile, n, tiles=[(0, 0), (tile, 0)], with_scale=True)
+        for u, v in zip((gc, go, sc, so), two):
+            assert np.array_equal(u, v), tile
+        assert np.abs(gc).max() > 0 and np.abs(go).max() > 0, tile
+        assert (np.abs(gc) <= sc[:, None] * (1 + 1e-12)).all() and (np.abs(go[:, 0]) <= so * (1 + 1e-12)).all(), tile
+        # a Gaussian on neither tile's list has zero gradients and zero scales
+        on = np.zeros(n, bool)
+        for x0 in (0, tile):
+            on[np.asarray(pre.order)[cpu_ref.tile_list(pre, x0, 0, tile)]] = True
+        assert not gc[~on].any() and not go[~on].any() and not sc[~on].any() and not so[~on].any(), tile
 
 
 def test_gradient_fixtures_are_data_of_the_stated_size():

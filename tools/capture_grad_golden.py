@@ -27,7 +27,9 @@ sys.path.insert(0, ROOT)
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["small_64x48_n300", "small_80x64_n120_tile8", "tile2_40x32_n80", "dense_48x48_n1500", "tiny_48x48_n600",
-          "needle_160x160_n110", "defaults_64x64_n800", "trainedlike_128x128_n3000"]
+          "needle_160x160_n110", "defaults_64x64_n800", "trainedlike_128x128_n3000",
+          # the tile shapes the backward branches on: > 256 pixels, not a multiple of 64 (oracle/capture_golden.py)
+          "tile32_96x96_n400", "tile20_64x64_n300", "tile12_dense_52x40_n900"]
 
 
 def capture(name: str, GaussianScene, Gaussians) -> None:
