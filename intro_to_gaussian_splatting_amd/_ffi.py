@@ -54,6 +54,13 @@ def visible_rows_flag(n: int, n_visible: int, flags: int) -> int:
     return true if true else -1
 
 
+def rows_flag(n: int, n_visible: int) -> int:
+    """The row class (GSX_FLAG_SMALL_BATCH / _ONE_VISIBLE, or 0) a frame over ``n`` Gaussians ended up with when
+    ``n_visible`` of them were visible: what a call that has to meet that frame again carries (capture_frame, the
+    backward pass)."""
+    return max(visible_rows_flag(n, n_visible, 0), 0)
+
+
 def with_rows_flag(flags: int, again: int) -> int:
     """``flags`` with the row class ``visible_rows_flag`` asked for (-1: neither flag)."""
     return (flags & ~(GSX_FLAG_SMALL_BATCH | GSX_FLAG_ONE_VISIBLE)) | max(int(again), 0)

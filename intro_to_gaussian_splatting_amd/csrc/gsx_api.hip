@@ -77,25 +77,155 @@ int make_plan_or_fail(int32_t width, int32_t height, int32_t tile, float *out_im
     return rc == GSX_OK ? GSX_OK : fail(rc, "%s", msg);
 }
 
-// Steps shared by both render entry points once records and rank-ordered tile rectangles exist.
-// `order` = Gaussian index of each depth rank (nullptr: rows are already in compositing order);
-// `m_dev` = number of ranks on the device (nullptr: n); `culled_dev` = Gaussians behind the cull plane.
-// The pair count D never has to reach the host for the frame to be enqueued: the kernels read
-// it from device memory and their grids are sized by the workspace capacity.  The normal call
-// synchronises ONCE, after the last launch, to report the counts and to detect D > capacity;
-// GSX_FLAG_NO_SYNC skips even that (the counts then arrive in pinned memory on their own).
-// fh: the frame's use of GsxParams.hints (FrameHints below; all null / false without a hints buffer).
+// n, the input arrays and GsxParams.original_index / row_of_index of the whole-path entry points.
+int check_inputs(const Plan &p, int64_t n, const float *means3d, const float *scales, const float *quats,
+                 const float *opacity_logit, const float *colors) {
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld out of range", (long long)n);
+    if (n > 0 && (!means3d || !scales || !quats || !opacity_logit || (!colors && !p.sh)))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "an input array is NULL");
+    if (p.original_index && !p.row_of_index) return fail(GSX_ERR_INVALID_ARGUMENT, "original_index needs row_of_index (its inverse)");
+    return GSX_OK;
+}
+
+// backward: gsx_render_backward's workspace (carve(.., backward), gsx_plan.h).
+int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles, Carve &c, int64_t &cap, bool backward = false) {
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    cap = capacity_for(bytes, n, max_tiles, backward);   // never above 2^31 - 1 pairs, whatever the buffer size
+    if (cap < 0)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes cannot hold %lld Gaussians", bytes, (long long)n);
+    c = carve(n, cap, max_tiles, binning_temp_bytes(n, cap), backward);
+    return GSX_OK;
+}
+
+// gsx_workspace_bytes / gsx_backward_workspace_bytes: 0 for sizes no call accepts.
+size_t workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances, bool backward) {
+    if (n < 0 || width <= 0 || height <= 0 || tile <= 0 || max_instances < 0) return 0;
+    if (n >= (int64_t)1 << 31 || max_instances >= (int64_t)1 << 31) return 0;
+    return carve(n, max_instances, max_tiles_of(width, height, tile), binning_temp_bytes(n, max_instances), backward).total;
+}
+
+// The frame's use of GsxParams.hints (all null / false without a hints buffer).
 struct FrameHints {
     gsx::BlendHints blend = gsx::BlendHints{nullptr, nullptr, nullptr, nullptr, 0u};
     const uint32_t *sched = nullptr;   // hints.sched, put together from the previous frame's list lengths, or null
     uint32_t *sched_region = nullptr;  // the hints buffer's schedule region (whether or not it holds a schedule yet), or null
 };
 
+// ---- The stage chain of a whole-path frame, up to the tile lists.  gsx_render_backward runs these same functions on the
+// same inputs -- without the hints buffer, which never changes a list -- so its tile lists are the forward frame's.
+
+// The depth-sort route, the projection (depth keys, records and tile rectangles by row) and the sampled or LSD depth sort
+// (the rectangles by rank).  fh: filled in with the frame's use of GsxParams.hints; nullptr: the buffer is neither read
+// nor written.  tm: nullptr = no stage marks.  On return order[r] = the row of depth rank r; sampled: a sampled route
+// left the emission's chunk sums.
+int project_and_sort(const Plan &p, const Carve &c, char *ws, const GsxCamera &camera, const gsx::GaussiansIn &in,
+                     int64_t n, int64_t cap, FrameHints *fh, StageTimer *tm, hipStream_t s, const uint32_t *&order,
+                     bool &sampled) {
+    uint32_t *k0 = (uint32_t *)(ws + c.keys0), *k1 = (uint32_t *)(ws + c.keys1);
+    uint32_t *v0 = (uint32_t *)(ws + c.vals0), *v1 = (uint32_t *)(ws + c.vals1);
+    uint32_t *counters = (uint32_t *)(ws + c.counters);
+    const uint32_t *row_of = p.original_index ? (const uint32_t *)p.row_of_index : nullptr;
+    // GsxParams.hints: what the previous frame of this view left (splitters, tile-list lengths) and what this one
+    // leaves.  Only where every producer and consumer exists: the tile-16 REF_CPU compositing kernel (lengths,
+    // ranked samples), the 256-bucket depth sort (splitters; the LSD passes of larger scenes only take the schedule).
+    const gsx::DepthRoute route = gsx::depth_sort_route(n, p.kept_hint);
+    sampled = route != gsx::kDepthLsd;
+    gsx::SortHints sh{nullptr, nullptr, nullptr, false};
+    gsx::ScheduleHint sched_hint{nullptr, nullptr, nullptr, 0u};
+    if (fh && p.hints && (route == gsx::kDepth256 || route == gsx::kDepthLsd) && n >= gsx::kSortSamples && p.grid.count() > 0 &&
+        gsx::blend_splits_long_tiles(p.grid, p.semantics, p.generic)) {
+        const gsx::HintsLayout hl = gsx::hints_layout(max_tiles_of(p.grid.width, p.grid.height, p.grid.tile),
+                                                      max_axis_tiles_of(p.grid.width, p.grid.height, p.grid.tile));
+        uint32_t *hdr = (uint32_t *)p.hints;
+        // (the LSD passes of larger scenes have no use for splitters, but they leave the sample all the same: the next
+        // frame of the view may take the 256-bucket route -- a rank's strip does once its kept count is known)
+        sh = gsx::SortHints{hdr, (const uint32_t *)(p.hints + hl.splitters), (uint32_t *)(p.hints + hl.samples),
+                            p.hints_valid && route == gsx::kDepth256};
+        // the 256-bucket route leaves the next frame's splitters itself -- the exact quantiles of this frame's keys (bucket_sort_kernel)
+        // -- and the compositing launch has no sample to rank; the LSD route still leaves a sample for it
+        const bool exact = route == gsx::kDepth256 && gsx::knob("GSX_EXACT_SPLITTERS", 1) != 0;
+        if (exact) sh.next_splitters = (uint32_t *)(p.hints + hl.splitters);
+        fh->blend = gsx::BlendHints{hdr, exact ? nullptr : sh.samples, (uint32_t *)(p.hints + hl.splitters), (uint32_t *)(p.hints + hl.lens), 0u};
+        fh->sched_region = (uint32_t *)(p.hints + hl.sched);
+        // the schedule costs nothing here (a spare workgroup of the projection launch): every window of more than two
+        // tiles per SIMD gets one, unless told not to
+        if (p.hints_valid && p.schedule != 0 && p.grid.count() > 2048) {
+            sched_hint = gsx::ScheduleHint{(const uint32_t *)(p.hints + hl.lens), (uint32_t *)(p.hints + hl.sched), hdr,
+                                           (uint32_t)p.grid.count(), (uint32_t)p.grid.nwy()};
+            fh->sched = sched_hint.sched;
+        }
+    }
+    // no splitters on file (a view's first frame, a caller without a hints buffer): the projection launch ranks a sample itself
+    gsx::SampleHint presample;
+    if (sampled && !sh.use && gsx::knob("GSX_PRESAMPLE", 1) != 0)
+        presample = gsx::depth_presample(route, ws + c.temp, n, gsx::emit_chunk_sums(ws + c.temp, n, cap), row_of);
+    GSX_HIP(gsx::launch_project_pack(camera, p.camera_device, in, n, p.grid, p.semantics, p.tight, p.small_batch, p.sh_degree, k0, (gsx::Record *)(ws + c.rec),
+                                     (gsx::TileRect *)(ws + c.rect), counters,
+                                     p.semantics != GSX_SEM_STD_3DGS ? (float4 *)(ws + c.bbox) : nullptr, sched_hint,
+                                     c.temp_bytes >= (size_t)(n / GSX_BOUNDS_ROWS + 1) ? (uint8_t *)(ws + c.temp) : nullptr, s, presample));
+    if (tm) tm->mark();  // 1: project (+ depth keys)
+    // the sampled routes also leave the per-chunk tile counts the pair emission starts from (one kernel less)
+    if (sampled)
+        GSX_HIP(gsx::sort_depth_sampled(route, ws + c.temp, k0, k1, v0, v1, n, p.kept_hint, counters + kCtrKept,
+                                        counters + kCtrCulled, (const gsx::TileRect *)(ws + c.rect),
+                                        (gsx::TileRect *)(ws + c.rrect), 0, gsx::emit_chunk_sums(ws + c.temp, n, cap), sh, s, row_of,
+                                        presample.splitters != nullptr));
+    else {
+        // the LSD passes carry the rectangles along, packed into 4 bytes, when tile coordinates fit 8 bits; the two
+        // arrays they travel in are the pair lists' value arrays, which nothing uses before the emission
+        const bool carry = p.grid.ntx <= 256 && p.grid.nty <= 256 && cap >= n && gsx::knob("GSX_LSD_CARRY", 1) != 0;
+        GSX_HIP(gsx::sort_depth_compact(ws + c.temp, k0, k1, v0, v1, n, counters + kCtrKept, counters + kCtrCulled,
+                                        (const gsx::TileRect *)(ws + c.rect), (gsx::TileRect *)(ws + c.rrect), s, sh.samples,
+                                        carry ? (uint32_t *)(ws + c.tvals0) : nullptr,
+                                        carry ? (uint32_t *)(ws + c.tvals1) : nullptr, row_of));
+    }
+    if (tm) tm->mark();  // 2: depth sort (drops what reaches no tile, leaves the rectangles in rank order)
+    order = v0;
+    return GSX_OK;
+}
+
+// The pair lists from the rank-ordered rectangles (order, m_dev: see bin_and_blend): the emission, which leaves the
+// frame's counts in bc, then -- unless the window is empty -- the stable tile sort: ranges = every tile's [first, last)
+// (long tiles flagged as lt says), sorted_vals = the rows of the sorted pairs.  tm: nullptr = no stage mark.
+int bin_pairs(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t cap, const gsx::TileRect *rrect,
+              const uint32_t *order, const uint32_t *m_dev, bool sums_ready, const gsx::BinCounts &bc,
+              const gsx::LongTiles &lt, StageTimer *tm, hipStream_t s, const uint32_t *&sorted_vals) {
+    uint2 *ranges = (uint2 *)(ws + c.ranges);
+    GSX_HIP(gsx::emit_instances(ws + c.temp, rrect, order, m_dev, n, cap, p.grid, ws + c.tkeys0, (uint32_t *)(ws + c.tvals0),
+                                ranges, bc, sums_ready, p.kept_hint, s));
+    if (tm) tm->mark();  // 3: scan + emit
+    if (p.grid.count() > 0)
+        GSX_HIP(gsx::sort_instances(ws + c.temp, cap, p.grid, ws + c.tkeys0, ws + c.tkeys1, (uint32_t *)(ws + c.tvals0),
+                                    (uint32_t *)(ws + c.tvals1), ranges, bc.d32, lt, &sorted_vals, s));
+    return GSX_OK;
+}
+
+// The synchronous read-back: counts = (n_visible, D, M) (zeros unless on_device) and, if redo is given, n_redo's device
+// word; then D > cap -- pairs were dropped -- is GSX_ERR_WORKSPACE_TOO_SMALL, with the counts valid all the same.
+int read_counts(const Carve &c, char *ws, int64_t cap, bool on_device, uint32_t *redo, int64_t (&counts)[3], hipStream_t s) {
+    counts[0] = counts[1] = counts[2] = 0;
+    if (on_device) GSX_HIP(hipMemcpyAsync(counts, ws + c.counters + 16, 24, hipMemcpyDeviceToHost, s));
+    if (redo) GSX_HIP(hipMemcpyAsync(redo, ws + c.redo, 4, hipMemcpyDeviceToHost, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    if (counts[1] > cap)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "frame needs %lld tile instances, workspace holds %lld",
+                    (long long)counts[1], (long long)cap);
+    return GSX_OK;
+}
+
+// Steps shared by both render entry points once records and rank-ordered tile rectangles exist.  The pair lists
+// (bin_pairs) and the count read-back (read_counts) are the ones gsx_render_backward runs: it runs the forward's own chain.
+// `order` = Gaussian index of each depth rank (nullptr: rows are already in compositing order);
+// `m_dev` = number of ranks on the device (nullptr: n); `culled_dev` = Gaussians behind the cull plane.
+// The pair count D never has to reach the host for the frame to be enqueued: the kernels read
+// it from device memory and their grids are sized by the workspace capacity.  The normal call
+// synchronises ONCE, after the last launch, to report the counts and to detect D > capacity;
+// GSX_FLAG_NO_SYNC skips even that (the counts then arrive in pinned memory on their own).
 int bin_and_blend(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t cap, const gsx::TileRect *rrect,
                   const uint32_t *order, const uint32_t *m_dev, const uint32_t *culled_dev, bool sums_ready,
                   GsxFrameStats *stats, StageTimer &tm, hipStream_t s, const FrameHints &fh = FrameHints()) {
     uint32_t *counters = (uint32_t *)(ws + c.counters);
-    void *temp = ws + c.temp;
     int64_t *dev2 = (int64_t *)(counters + 4);
     uint2 *ranges = (uint2 *)(ws + c.ranges);
     bool counts_on_device = false, counts_in_host = false;
@@ -130,26 +260,23 @@ int bin_and_blend(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t ca
                 (void)hipGetLastError();
             }
         }
-        GSX_HIP(gsx::emit_instances(temp, rrect, order, m_dev, n, cap, p.grid, ws + c.tkeys0, (uint32_t *)(ws + c.tvals0),
-                                    ranges, bc, sums_ready, p.kept_hint, s));
+        const bool split = p.split && cap > 0 && gsx::blend_splits_long_tiles(p.grid, p.semantics, p.generic);
+        gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), split ? gsx::kMaxLongTiles : 0u};
+        lt.redo = (uint32_t *)(ws + c.redo);
+        if (fh.blend.lens) {        // GsxParams.hints: the tiles' costs decide who is long (tile_ranges_kernel)
+            lt.cost = fh.blend.lens;
+            lt.header = fh.blend.header;
+            lt.cost_pct = (uint32_t)gsx::knob("GSX_LONG_COST_PCT", 30);      // (test library only)
+            lt.stay_pct = (uint32_t)gsx::knob("GSX_LONG_STAY_PCT", 75);
+            if (!fh.sched || lt.cost_pct == 0) lt.header = nullptr;
+        }
+        const uint32_t *sorted_vals = nullptr;
+        const int rc = bin_pairs(p, c, ws, n, cap, rrect, order, m_dev, sums_ready, bc, lt, &tm, s, sorted_vals);
+        if (rc != GSX_OK) return rc;
         counts_on_device = true;
-        tm.mark();  // 3: scan + emit
         if (p.grid.count() == 0) {
             GSX_HIP(gsx::launch_clear(make_clear_plan(p, true), p.out.ptr, s));
         } else {
-            const uint32_t *sorted_vals = nullptr;
-            const bool split = p.split && cap > 0 && gsx::blend_splits_long_tiles(p.grid, p.semantics, p.generic);
-            gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), split ? gsx::kMaxLongTiles : 0u};
-            lt.redo = (uint32_t *)(ws + c.redo);
-            if (fh.blend.lens) {        // GsxParams.hints: the tiles' costs decide who is long (tile_ranges_kernel)
-                lt.cost = fh.blend.lens;
-                lt.header = fh.blend.header;
-                lt.cost_pct = (uint32_t)gsx::knob("GSX_LONG_COST_PCT", 30);      // (test library only)
-                lt.stay_pct = (uint32_t)gsx::knob("GSX_LONG_STAY_PCT", 75);
-                if (!fh.sched || lt.cost_pct == 0) lt.header = nullptr;
-            }
-            GSX_HIP(gsx::sort_instances(temp, cap, p.grid, ws + c.tkeys0, ws + c.tkeys1, (uint32_t *)(ws + c.tvals0),
-                                        (uint32_t *)(ws + c.tvals1), ranges, counters + kCtrPairs, lt, &sorted_vals, s));
             if (p.tile_counts) GSX_HIP(gsx::launch_tile_counts(ranges, p.grid.count(), p.tile_counts, s));
             const uint32_t *sched = fh.sched;      // handed over by the previous frame (GsxParams.hints): no kernel
             gsx::BlendHints bh = fh.blend;
@@ -230,11 +357,10 @@ int bin_and_blend(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t ca
         }
         return GSX_OK;
     }
-    int64_t host2[3] = {0, 0, 0};
+    int64_t host2[3];
     uint32_t redo_host = 0;
-    if (counts_on_device) GSX_HIP(hipMemcpyAsync(host2, dev2, 24, hipMemcpyDeviceToHost, s));
-    if (redo_counted) GSX_HIP(hipMemcpyAsync(&redo_host, ws + c.redo, 4, hipMemcpyDeviceToHost, s));
-    GSX_HIP(hipStreamSynchronize(s));
+    const int rc = read_counts(c, ws, cap, counts_on_device, redo_counted ? &redo_host : nullptr, host2, s);
+    if (rc != GSX_OK && rc != GSX_ERR_WORKSPACE_TOO_SMALL) return rc;
     if (stats) {
         stats->n_visible = host2[0];
         stats->n_instances = host2[1];
@@ -244,59 +370,7 @@ int bin_and_blend(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t ca
         stats->reserved = 0;
     }
     tm.finish(stats);
-    if (host2[1] > cap)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "frame needs %lld tile instances, workspace holds %lld",
-                    (long long)host2[1], (long long)cap);
-    return GSX_OK;
-}
-
-int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles, Carve &c, int64_t &cap) {
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    cap = capacity_for(bytes, n, max_tiles);   // never above 2^31 - 1 pairs, whatever the buffer size
-    if (cap < 0)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes cannot hold %lld Gaussians", bytes, (long long)n);
-    c = carve(n, cap, max_tiles, binning_temp_bytes(n, cap));
-    return GSX_OK;
-}
-
-// gsx_render_backward's workspace: the forward's carve for `cap` pairs, then per Gaussian its raw stage-1 record
-// (launch_project_raw), its rank and the emission prefix, the scan's block sums, and one float4 slot per pair.
-struct BackwardCarve {
-    Carve fwd;
-    size_t raw, rank_of, prefix, bsum, slots, total;
-};
-BackwardCarve backward_carve(int64_t n, int64_t cap, int64_t max_tiles) {
-    BackwardCarve b;
-    b.fwd = carve(n, cap, max_tiles, binning_temp_bytes(n, cap));
-    const size_t nn = (size_t)(n > 0 ? n : 1), cc = (size_t)(cap > 0 ? cap : 1);
-    size_t off = b.fwd.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes);
-        return at;
-    };
-    b.raw = take(nn * kRecordBytes);
-    b.rank_of = take(nn * 4);
-    b.prefix = take((nn + 1) * 4);
-    b.bsum = take((nn / 1024 + 2) * 4);
-    b.slots = take(cc * 16);
-    b.total = off;
-    return b;
-}
-int64_t backward_capacity_for(size_t bytes, int64_t n, int64_t max_tiles) {
-    auto fits = [&](int64_t cap) { return backward_carve(n, cap, max_tiles).total <= bytes; };
-    if (!fits(1)) return -1;
-    int64_t lo = 1, hi = kMaxPairs;
-    if (fits(hi)) return hi;
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (fits(mid))
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
+    return rc;
 }
 
 #ifdef GSX_TEST_HOOKS
@@ -328,11 +402,7 @@ size_t gsx_hints_bytes(int32_t width, int32_t height, int32_t tile) {
 }
 
 size_t gsx_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
-    if (n < 0 || width <= 0 || height <= 0 || tile <= 0 || max_instances < 0) return 0;
-    if (n >= (int64_t)1 << 31 || max_instances >= (int64_t)1 << 31) return 0;
-    size_t temp = binning_temp_bytes(n, max_instances);
-    if (temp == 0) return 0;
-    return carve(n, max_instances, max_tiles_of(width, height, tile), temp).total;
+    return workspace_bytes(n, width, height, tile, max_instances, false);
 }
 
 int gsx_preprocess(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
@@ -428,7 +498,8 @@ int gsx_render_forward(const GsxCamera *camera, const float *means3d, const floa
     Plan p;
     int rc = make_plan_or_fail(camera->width, camera->height, tile_size, out_image, params, p);
     if (rc != GSX_OK) return rc;
-    if (n < 0 || n >= (int64_t)1 << 31) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld out of range", (long long)n);
+    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
+    if (rc != GSX_OK) return rc;
     if (p.n_parts > 0) {
         // substrip_events are recorded with plain hipEventRecord: inside a stream capture they would become nodes of
         // the graph, and the caller's hipStreamWaitEvent on another stream would fail or invalidate the capture
@@ -437,85 +508,26 @@ int gsx_render_forward(const GsxCamera *camera, const float *means3d, const floa
         if (cs != hipStreamCaptureStatusNone)
             return fail(GSX_ERR_UNSUPPORTED, "n_substrips cannot be combined with stream capture (the part events are recorded on the stream)");
     }
-    if (n > 0 && (!means3d || !scales || !quats || !opacity_logit || (!colors && !p.sh)))
-        return fail(GSX_ERR_INVALID_ARGUMENT, "an input array is NULL");
-    if (p.original_index && !p.row_of_index) return fail(GSX_ERR_INVALID_ARGUMENT, "original_index needs row_of_index (its inverse)");
-    const uint32_t *row_of = p.original_index ? (const uint32_t *)p.row_of_index : nullptr;
     Carve c;
     int64_t cap;
     rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap);
     if (rc != GSX_OK) return rc;
     char *ws = (char *)workspace;
-    uint32_t *k0 = (uint32_t *)(ws + c.keys0), *k1 = (uint32_t *)(ws + c.keys1);
-    uint32_t *v0 = (uint32_t *)(ws + c.vals0), *v1 = (uint32_t *)(ws + c.vals1);
     StageTimer tm;
     tm.begin(p.timing, s);
-    gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, p.sh ? p.sh : colors, p.original_index, (const float4 *)p.block_bounds};
-    uint32_t *counters = (uint32_t *)(ws + c.counters);
-    // GsxParams.hints: what the previous frame of this view left (splitters, tile-list lengths) and what this one
-    // leaves.  Only where every producer and consumer exists: the tile-16 REF_CPU compositing kernel (lengths,
-    // ranked samples), the 256-bucket depth sort (splitters; the LSD passes of larger scenes only take the schedule).
-    const gsx::DepthRoute route = gsx::depth_sort_route(n, p.kept_hint);
-    const bool sampled = route != gsx::kDepthLsd;
+    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, p.sh ? p.sh : colors, p.original_index, (const float4 *)p.block_bounds};
     FrameHints fh;
-    gsx::SortHints sh{nullptr, nullptr, nullptr, false};
-    gsx::ScheduleHint sched_hint{nullptr, nullptr, nullptr, 0u};
-    if (p.hints && (route == gsx::kDepth256 || route == gsx::kDepthLsd) && n >= gsx::kSortSamples && p.grid.count() > 0 &&
-        gsx::blend_splits_long_tiles(p.grid, p.semantics, p.generic)) {
-        const gsx::HintsLayout hl = gsx::hints_layout(max_tiles_of(camera->width, camera->height, tile_size),
-                                                      max_axis_tiles_of(camera->width, camera->height, tile_size));
-        uint32_t *hdr = (uint32_t *)p.hints;
-        // (the LSD passes of larger scenes have no use for splitters, but they leave the sample all the same: the next
-        // frame of the view may take the 256-bucket route -- a rank's strip does once its kept count is known)
-        sh = gsx::SortHints{hdr, (const uint32_t *)(p.hints + hl.splitters), (uint32_t *)(p.hints + hl.samples),
-                            p.hints_valid && route == gsx::kDepth256};
-        // the 256-bucket route leaves the next frame's splitters itself -- the exact quantiles of this frame's keys (bucket_sort_kernel)
-        // -- and the compositing launch has no sample to rank; the LSD route still leaves a sample for it
-        const bool exact = route == gsx::kDepth256 && gsx::knob("GSX_EXACT_SPLITTERS", 1) != 0;
-        if (exact) sh.next_splitters = (uint32_t *)(p.hints + hl.splitters);
-        fh.blend = gsx::BlendHints{hdr, exact ? nullptr : sh.samples, (uint32_t *)(p.hints + hl.splitters), (uint32_t *)(p.hints + hl.lens), 0u};
-        fh.sched_region = (uint32_t *)(p.hints + hl.sched);
-        // the schedule costs nothing here (a spare workgroup of the projection launch): every window of more than two
-        // tiles per SIMD gets one, unless told not to
-        if (p.hints_valid && p.schedule != 0 && p.grid.count() > 2048) {
-            sched_hint = gsx::ScheduleHint{(const uint32_t *)(p.hints + hl.lens), (uint32_t *)(p.hints + hl.sched), hdr,
-                                           (uint32_t)p.grid.count(), (uint32_t)p.grid.nwy()};
-            fh.sched = sched_hint.sched;
-        }
-    }
-    // no splitters on file (a view's first frame, a caller without a hints buffer): the projection launch ranks a sample itself
-    gsx::SampleHint presample;
-    if (sampled && !sh.use && gsx::knob("GSX_PRESAMPLE", 1) != 0)
-        presample = gsx::depth_presample(route, ws + c.temp, n, gsx::emit_chunk_sums(ws + c.temp, n, cap), row_of);
-    GSX_HIP(gsx::launch_project_pack(*camera, p.camera_device, in, n, p.grid, p.semantics, p.tight, p.small_batch, p.sh_degree, k0, (gsx::Record *)(ws + c.rec),
-                                     (gsx::TileRect *)(ws + c.rect), counters,
-                                     p.semantics != GSX_SEM_STD_3DGS ? (float4 *)(ws + c.bbox) : nullptr, sched_hint,
-                                     c.temp_bytes >= (size_t)(n / GSX_BOUNDS_ROWS + 1) ? (uint8_t *)(ws + c.temp) : nullptr, s, presample));
-    tm.mark();  // 1: project (+ depth keys)
-    // the sampled routes also leave the per-chunk tile counts the pair emission starts from (one kernel less)
-    if (sampled)
-        GSX_HIP(gsx::sort_depth_sampled(route, ws + c.temp, k0, k1, v0, v1, n, p.kept_hint, counters + kCtrKept,
-                                        counters + kCtrCulled, (const gsx::TileRect *)(ws + c.rect),
-                                        (gsx::TileRect *)(ws + c.rrect), 0, gsx::emit_chunk_sums(ws + c.temp, n, cap), sh, s, row_of,
-                                        presample.splitters != nullptr));
-    else {
-        // the LSD passes carry the rectangles along, packed into 4 bytes, when tile coordinates fit 8 bits; the two
-        // arrays they travel in are the pair lists' value arrays, which nothing uses before the emission
-        const bool carry = p.grid.ntx <= 256 && p.grid.nty <= 256 && cap >= n && gsx::knob("GSX_LSD_CARRY", 1) != 0;
-        GSX_HIP(gsx::sort_depth_compact(ws + c.temp, k0, k1, v0, v1, n, counters + kCtrKept, counters + kCtrCulled,
-                                        (const gsx::TileRect *)(ws + c.rect), (gsx::TileRect *)(ws + c.rrect), s, sh.samples,
-                                        carry ? (uint32_t *)(ws + c.tvals0) : nullptr,
-                                        carry ? (uint32_t *)(ws + c.tvals1) : nullptr, row_of));
-    }
-    tm.mark();  // 2: depth sort (drops what reaches no tile, leaves the rectangles in rank order)
-    return bin_and_blend(p, c, ws, n, cap, (const gsx::TileRect *)(ws + c.rrect), v0, counters + kCtrKept,
+    const uint32_t *order;
+    bool sampled;
+    rc = project_and_sort(p, c, ws, *camera, in, n, cap, &fh, &tm, s, order, sampled);
+    if (rc != GSX_OK) return rc;
+    uint32_t *counters = (uint32_t *)(ws + c.counters);
+    return bin_and_blend(p, c, ws, n, cap, (const gsx::TileRect *)(ws + c.rrect), order, counters + kCtrKept,
                          counters + kCtrCulled, sampled, stats_host, tm, s, fh);
 }
 
 size_t gsx_backward_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
-    if (n < 0 || width <= 0 || height <= 0 || tile <= 0 || max_instances < 0) return 0;
-    if (n >= (int64_t)1 << 31 || max_instances >= (int64_t)1 << 31) return 0;
-    return backward_carve(n, max_instances, max_tiles_of(width, height, tile)).total;
+    return workspace_bytes(n, width, height, tile, max_instances, true);
 }
 
 int gsx_render_backward(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
@@ -537,19 +549,13 @@ int gsx_render_backward(const GsxCamera *camera, const float *means3d, const flo
     if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward does not take substrips");
     if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward synchronises: no GSX_FLAG_NO_SYNC");
     if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward reads the camera argument: no camera_device");
-    if (n < 0 || n >= (int64_t)1 << 31) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld out of range", (long long)n);
+    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
+    if (rc != GSX_OK) return rc;
     if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
-    if (n > 0 && (!means3d || !scales || !quats || !opacity_logit || !colors)) return fail(GSX_ERR_INVALID_ARGUMENT, "an input array is NULL");
-    if (p.original_index && !p.row_of_index) return fail(GSX_ERR_INVALID_ARGUMENT, "original_index needs row_of_index (its inverse)");
-    const uint32_t *row_of = p.original_index ? (const uint32_t *)p.row_of_index : nullptr;
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    const int64_t max_tiles = max_tiles_of(camera->width, camera->height, tile_size);
-    const int64_t cap = backward_capacity_for(workspace_bytes, n, max_tiles);
-    if (cap < 0)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes cannot hold %lld Gaussians", workspace_bytes, (long long)n);
-    const BackwardCarve bc = backward_carve(n, cap, max_tiles);
-    const Carve &c = bc.fwd;
+    Carve c;
+    int64_t cap;
+    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, true);
+    if (rc != GSX_OK) return rc;
     char *ws = (char *)workspace;
     StageTimer tm;
     tm.begin(p.timing, s);
@@ -560,57 +566,36 @@ int gsx_render_backward(const GsxCamera *camera, const float *means3d, const flo
         GSX_HIP(hipStreamSynchronize(s));
         return GSX_OK;
     }
-    // ---- the forward's stages on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
-    uint32_t *k0 = (uint32_t *)(ws + c.keys0), *k1 = (uint32_t *)(ws + c.keys1);
-    uint32_t *v0 = (uint32_t *)(ws + c.vals0), *v1 = (uint32_t *)(ws + c.vals1);
+    // ---- the forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
+    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
+    const uint32_t *order;
+    bool sampled;
+    rc = project_and_sort(p, c, ws, *camera, in, n, cap, nullptr, nullptr, s, order, sampled);
+    if (rc != GSX_OK) return rc;
     uint32_t *counters = (uint32_t *)(ws + c.counters);
-    gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const gsx::DepthRoute route = gsx::depth_sort_route(n, p.kept_hint);
-    const bool sampled = route != gsx::kDepthLsd;
-    gsx::SortHints sh{nullptr, nullptr, nullptr, false};
-    gsx::SampleHint presample;
-    if (sampled && gsx::knob("GSX_PRESAMPLE", 1) != 0)
-        presample = gsx::depth_presample(route, ws + c.temp, n, gsx::emit_chunk_sums(ws + c.temp, n, cap), row_of);
-    GSX_HIP(gsx::launch_project_pack(*camera, nullptr, in, n, p.grid, p.semantics, p.tight, p.small_batch, -1, k0,
-                                     (gsx::Record *)(ws + c.rec), (gsx::TileRect *)(ws + c.rect), counters, (float4 *)(ws + c.bbox),
-                                     gsx::ScheduleHint{nullptr, nullptr, nullptr, 0u, 0u}, nullptr, s, presample));
-    if (sampled)
-        GSX_HIP(gsx::sort_depth_sampled(route, ws + c.temp, k0, k1, v0, v1, n, p.kept_hint, counters + kCtrKept,
-                                        counters + kCtrCulled, (const gsx::TileRect *)(ws + c.rect),
-                                        (gsx::TileRect *)(ws + c.rrect), 0, gsx::emit_chunk_sums(ws + c.temp, n, cap), sh, s, row_of,
-                                        presample.splitters != nullptr));
-    else
-        GSX_HIP(gsx::sort_depth_compact(ws + c.temp, k0, k1, v0, v1, n, counters + kCtrKept, counters + kCtrCulled,
-                                        (const gsx::TileRect *)(ws + c.rect), (gsx::TileRect *)(ws + c.rrect), s, nullptr,
-                                        nullptr, nullptr, row_of));
-    int64_t *dev2 = (int64_t *)(counters + 4);
-    uint2 *ranges = (uint2 *)(ws + c.ranges);
-    gsx::BinCounts bcnt{dev2, nullptr, counters + kCtrPairs, counters + kCtrLong, (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
-    GSX_HIP(gsx::emit_instances(ws + c.temp, (const gsx::TileRect *)(ws + c.rrect), v0, counters + kCtrKept, n, cap, p.grid,
-                                ws + c.tkeys0, (uint32_t *)(ws + c.tvals0), ranges, bcnt, sampled, p.kept_hint, s));
+    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
+    const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
+                              (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
+    const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
     const uint32_t *sorted_vals = nullptr;
-    gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
-    GSX_HIP(gsx::sort_instances(ws + c.temp, cap, p.grid, ws + c.tkeys0, ws + c.tkeys1, (uint32_t *)(ws + c.tvals0),
-                                (uint32_t *)(ws + c.tvals1), ranges, counters + kCtrPairs, lt, &sorted_vals, s));
-    int64_t host2[3] = {0, 0, 0};
-    GSX_HIP(hipMemcpyAsync(host2, dev2, 24, hipMemcpyDeviceToHost, s));
-    GSX_HIP(hipStreamSynchronize(s));
+    rc = bin_pairs(p, c, ws, n, cap, rrect, order, counters + kCtrKept, sampled, bcnt, lt, nullptr, s, sorted_vals);
+    if (rc != GSX_OK) return rc;
+    int64_t counts[3];
+    rc = read_counts(c, ws, cap, true, nullptr, counts, s);
     tm.mark();  // 1: the forward's stages
-    if (host2[1] > cap)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "frame needs %lld tile instances, workspace holds %lld",
-                    (long long)host2[1], (long long)cap);
-    const uint32_t m = (uint32_t)host2[2];
-    if (m == 0 || host2[1] == 0) return GSX_OK;
+    if (rc != GSX_OK) return rc;
+    const uint32_t m = (uint32_t)counts[2];
+    if (m == 0 || counts[1] == 0) return GSX_OK;
     // ---- the backward kernels
-    gsx::Record *raw = (gsx::Record *)(ws + bc.raw);
-    uint32_t *prefix = (uint32_t *)(ws + bc.prefix), *rank_of = (uint32_t *)(ws + bc.rank_of);
-    float4 *slots = (float4 *)(ws + bc.slots);
+    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
+    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
+    float4 *slots = (float4 *)(ws + c.slots);
     GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
-    GSX_HIP(gsx::launch_backward_prefix((const gsx::TileRect *)(ws + c.rrect), v0, m, prefix, rank_of, (uint32_t *)(ws + bc.bsum), s));
-    gsx::BackwardTiles bt{raw, sorted_vals, ranges, rank_of, prefix, (const gsx::TileRect *)(ws + c.rrect), image, grad_image, slots};
+    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
+    const gsx::BackwardTiles bt{raw, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots};
     GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
     tm.mark();  // 2: raw records, prefix, compositing backward
-    GSX_HIP(gsx::launch_backward_sums(slots, prefix, v0, raw, m, grad_colors, grad_opacity_logit, s));
+    GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
     tm.mark();  // 3: sums
     GSX_HIP(hipStreamSynchronize(s));
 #ifdef GSX_TEST_HOOKS

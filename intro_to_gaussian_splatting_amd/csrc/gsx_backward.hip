@@ -22,32 +22,15 @@
 // by column.  (2) backward_sum_kernel: one wave per Gaussian sums its contiguous slots (lane-strided, then the same
 // butterfly), applies the sigmoid chain and scatters to the Gaussian's row.  Same inputs, same bits.
 //
-// alpha is evaluated in the reference's operation order for every record (alpha_ref, the same operations as
-// gsx_blend.hip's) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
+// alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
+// forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
 #include "gsx_internal.h"
 
 namespace gsx {
 namespace {
 
-constexpr float kStopRefCpu = 0.000001f;  // gaussian_scene.py:153
 constexpr int kScanThreads = 256, kScanPer = 4, kScanItems = kScanThreads * kScanPer;
 constexpr int kNpx = 4;                   // pixels per lane of the tile kernel (a chunk = 256 pixels of the tile)
-
-__device__ __forceinline__ uint32_t rect_tiles(TileRect r) {
-    return r.x0 > r.x1 ? 0u : (uint32_t)(r.x1 - r.x0 + 1) * (uint32_t)(r.y1 - r.y0 + 1);
-}
-
-// The reference's alpha of one pixel, operation for operation (as gsx_blend.hip's alpha_ref; this file is compiled with
-// -ffp-contract=off).  px, py: the pixel in frame coordinates.
-__device__ __forceinline__ float alpha_ref(float x, float y, float q00, float q01, float q10, float q11, float op,
-                                           float px, float py) {
-    const float e0 = x - px, e1 = y - py;
-    const float d0 = -0.5f * e0, d1 = -0.5f * e1;
-    const float t0 = __builtin_fmaf(d1, q10, d0 * q00);
-    const float t1 = __builtin_fmaf(d1, q11, d0 * q01);
-    const float power = t0 * e0 + t1 * e1;
-    return __builtin_amdgcn_exp2f(power * 1.44269504088896340736f) * op;
-}
 
 // Sum of (a, b, c, d) over the 64 lanes of the wave in a fixed order, left in lane 16 v of component v: halves are
 // exchanged (32: (a,b) | (c,d); 16: one of the two), then the remaining value is reduced over the 16 lanes.  7 shuffles.
@@ -93,7 +76,7 @@ __global__ void __launch_bounds__(kScanThreads)
     for (int k = 0; k < kScanPer; ++k) {
         const uint32_t r = r0 + k;
         if (r < m) {
-            sum += rect_tiles(rrect[r]);
+            sum += tiles_of(rrect[r]);
             rank_of[order[r]] = r;
         }
     }
@@ -126,7 +109,7 @@ __global__ void __launch_bounds__(kScanThreads)
     uint32_t cnt[kScanPer], sum = 0;
 #pragma unroll
     for (int k = 0; k < kScanPer; ++k) {
-        cnt[k] = r0 + k < m ? rect_tiles(rrect[r0 + k]) : 0u;
+        cnt[k] = r0 + k < m ? tiles_of(rrect[r0 + k]) : 0u;
         sum += cnt[k];
     }
     uint32_t total;

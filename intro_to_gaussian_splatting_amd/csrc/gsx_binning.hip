@@ -41,16 +41,6 @@ static_assert(kChunk == kEmitChunk, "gsx_plan.h sizes the chunk sums with this")
 // scan_sums_kernel turns them into prefixes first (one more launch where frames take milliseconds).
 constexpr int kSelfScanChunks = 2048;
 
-__device__ __forceinline__ uint32_t load_count(const uint32_t *n_dev, uint32_t bound) {
-    if (!n_dev) return bound;
-    const uint32_t n = *n_dev;
-    return n < bound ? n : bound;
-}
-
-__device__ __forceinline__ uint32_t tiles_of(const TileRect &r) {
-    return r.x0 > r.x1 ? 0u : (uint32_t)(r.x1 - r.x0 + 1) * (uint32_t)(r.y1 - r.y0 + 1);
-}
-
 // A thread's four consecutive rectangles: two 16-byte loads.
 __device__ __forceinline__ void load_rects(const TileRect *__restrict__ rrect, uint32_t first, uint32_t m,
                                            TileRect (&r)[kPerThread]) {

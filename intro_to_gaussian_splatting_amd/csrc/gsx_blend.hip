@@ -79,7 +79,6 @@ constexpr uint32_t kProbeSecond = 1u << 17;     // a second record per workgroup
 namespace gsx {
 namespace {
 
-constexpr float kStopRefCpu = 0.000001f;  // gaussian_scene.py:153
 constexpr uint32_t kBatchCost = 5;        // staging a batch of 64 costs about as much as compositing five records (a tile's cost, gsx_plan.h)
 // A staged batch holds up to 64 records followed by kPad NULL records (log2 op = -inf: alpha = exp2(-inf) = 0 at every
 // pixel, colour 0), so that the compositing loops always take whole trips of 4 or 8 records with no per-record branch
@@ -172,7 +171,7 @@ __global__ void __launch_bounds__(64) clear_kernel(ClearPlan cp, float *__restri
 // Record kinds (Record.c.z, set by pack_record in gsx_project.hip): the completed square; the monomial fallback (a
 // caller-given inverse covariance without a finite factorisation); REFERENCE ORDER -- an ill-conditioned footprint, on
 // which the reference's float32 evaluation of d Q d^T (splat/utils.py:363-364) is executed operation for operation
-// (alpha_ref below): its rounding there is part of the reference's result (1e-4 .. 1e-3 of alpha on 100:1 needles).
+// (alpha_ref, gsx_internal.h): its rounding there is part of the reference's result (1e-4 .. 1e-3 of alpha on 100:1 needles).
 constexpr float kRefOrderFlag = 2.0f;      // (the monomial fallback: 1.0f)
 enum { kKindSquare = 0, kKindMono = 1, kKindRefOrder = 2 };
 
@@ -190,22 +189,6 @@ __device__ __forceinline__ Splat read_splat(const Staged &sh, uint32_t k) {
     const float4 A = sh.rec[0][k], B = sh.rec[1][k], C = sh.rec[2][k];
     return Splat{A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w, C.x, C.y,
                  C.z == kRefOrderFlag ? kKindRefOrder : (C.z != 0.0f ? kKindMono : kKindSquare), __float_as_uint(C.w)};
-}
-
-// The reference's alpha of one pixel, operation for operation (splat/utils.py:357-365 as torch executes it,
-// oracle/probe_torch_order.py; splat/gaussian_scene.py:164): d = -1/2 (mean - pixel) -- exact --, (1,2) @ (2,2) one FMA
-// per output, the final (1,2) @ (2,1) two rounded products and a sum (this file is compiled with -ffp-contract=off),
-// exp, times the opacity factor.  px, py: the pixel in FRAME coordinates (integers: exact as floats).  The exponential
-// is v_exp_f32 of power * log2(e): within 2 ulp of expf plus 6e-8 |power| log2(e), i.e. < 2e-6 of alpha wherever
-// alpha >= 1e-7 -- the one step that is not the reference's bit for bit.
-__device__ __forceinline__ float alpha_ref(float x, float y, float q00, float q01, float q10, float q11, float op,
-                                           float px, float py) {
-    const float e0 = x - px, e1 = y - py;
-    const float d0 = -0.5f * e0, d1 = -0.5f * e1;
-    const float t0 = __builtin_fmaf(d1, q10, d0 * q00);
-    const float t1 = __builtin_fmaf(d1, q11, d0 * q01);
-    const float power = t0 * e0 + t1 * e1;
-    return __builtin_amdgcn_exp2f(power * 1.44269504088896340736f) * op;
 }
 
 // Exponent of one pixel.  px, p = the pixel's offsets inside the tile (px shared by the lane's pixels); g.mx, g.my =

@@ -50,6 +50,39 @@ struct TileRect {
 static_assert(sizeof(TileRect) == kTileRectBytes && sizeof(float4) == kBboxBytes && sizeof(uint2) == kRangeBytes,
               "gsx_plan.h sizes the workspace with these");
 
+// ---- device helpers of more than one translation unit
+// Tiles a rectangle covers: the pairs the emission writes for it (gsx_binning.hip, gsx_backward.hip).
+__device__ __forceinline__ uint32_t tiles_of(const TileRect &r) {
+    return r.x0 > r.x1 ? 0u : (uint32_t)(r.x1 - r.x0 + 1) * (uint32_t)(r.y1 - r.y0 + 1);
+}
+
+// min(*n_dev, bound), or bound when n_dev == nullptr: an element count that lives on the device (gsx_binning.hip, gsx_sort.hip).
+__device__ __forceinline__ uint32_t load_count(const uint32_t *n_dev, uint32_t bound) {
+    if (!n_dev) return bound;
+    const uint32_t n = *n_dev;
+    return n < bound ? n : bound;
+}
+
+// REF_CPU's stop rule: a pixel stops before the record that would take its transmittance below this (gaussian_scene.py:153).
+constexpr float kStopRefCpu = 0.000001f;
+
+// The reference's alpha of one pixel, operation for operation (splat/utils.py:357-365 as torch executes it,
+// oracle/probe_torch_order.py; splat/gaussian_scene.py:164): d = -1/2 (mean - pixel) -- exact --, (1,2) @ (2,2) one FMA
+// per output, the final (1,2) @ (2,1) two rounded products and a sum (every file is compiled with -ffp-contract=off),
+// exp, times the opacity factor.  px, py: the pixel in FRAME coordinates (integers: exact as floats).  The exponential
+// is v_exp_f32 of power * log2(e): within 2 ulp of expf plus 6e-8 |power| log2(e), i.e. < 2e-6 of alpha wherever
+// alpha >= 1e-7 -- the one step that is not the reference's bit for bit.  The forward's compositing kernels
+// (gsx_blend.hip) and the backward's (gsx_backward.hip) both evaluate it.
+__device__ __forceinline__ float alpha_ref(float x, float y, float q00, float q01, float q10, float q11, float op,
+                                           float px, float py) {
+    const float e0 = x - px, e1 = y - py;
+    const float d0 = -0.5f * e0, d1 = -0.5f * e1;
+    const float t0 = __builtin_fmaf(d1, q10, d0 * q00);
+    const float t1 = __builtin_fmaf(d1, q11, d0 * q01);
+    const float power = t0 * e0 + t1 * e1;
+    return __builtin_amdgcn_exp2f(power * 1.44269504088896340736f) * op;
+}
+
 // Tiles whose list is much longer than the frame's average are composited by FOUR waves (a quarter of the
 // tile's pixels each, one pixel per lane, eight records per trip) instead of one: a lone wave walks its list
 // at ~430 cycles per record, so one 20 000-entry tile would outlast the rest of the frame several times over.

@@ -195,6 +195,7 @@ struct Carve {
     size_t rec, rect, rrect, bbox;          // per Gaussian: record, tile rectangle by index / by depth rank
     size_t tkeys0, tkeys1, tvals0, tvals1;  // cap x u32: tile ids / Gaussian indices (ping-pong)
     size_t ranges, longs, redo, sched_header, sched, counters, temp, temp_bytes, total;
+    size_t raw, rank_of, prefix, bsum, slots;   // gsx_render_backward only (carve(.., backward)); 0 otherwise
 };
 
 // The 64-byte `counters` block: what the kernels of one frame hand to each other on the device.
@@ -203,8 +204,10 @@ struct Carve {
 //   i64 at byte 16: n_visible, D (the first two fields of a GsxFrameStats), M again (GsxFrameStats.n_kept)
 enum { kCtrCulled = 0, kCtrKept = 1, kCtrPairs = 2, kCtrLong = 3 };
 
-inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes) {
-    Carve c;
+// backward: gsx_render_backward's workspace -- the forward's regions for `cap` pairs, then per Gaussian its raw stage-1
+// record (launch_project_raw), its rank and the emission prefix, the scan's block sums, and one float4 slot per pair.
+inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes, bool backward = false) {
+    Carve c = {};
     size_t off = 0;
     auto take = [&](size_t bytes) {
         size_t at = off;
@@ -229,6 +232,13 @@ inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes)
     c.counters = take(64);
     c.temp = take(temp_bytes);
     c.temp_bytes = temp_bytes;
+    if (backward) {
+        c.raw = take(nn * kRecordBytes);
+        c.rank_of = take(nn * 4);
+        c.prefix = take((nn + 1) * 4);
+        c.bsum = take((nn / 1024 + 2) * 4);
+        c.slots = take(cc * 16);
+    }
     c.total = off;
     return c;
 }
@@ -245,9 +255,9 @@ inline int64_t max_axis_tiles_of(int32_t width, int32_t height, int32_t tile) {
 // bisection, exact -- what gsx_workspace_bytes(n, .., cap) asks for always yields at least cap); -1 when not
 // even the per-Gaussian part fits.  The kernels index pairs with 32 bits and gsx_workspace_bytes sizes for
 // < 2^31 pairs: a larger buffer (a 288 GB part can hand over 68 GB and more) does not raise the capacity
-// beyond that.
-inline int64_t capacity_for(size_t bytes, int64_t n, int64_t max_tiles) {
-    auto fits = [&](int64_t cap) { return carve(n, cap, max_tiles, binning_temp_bytes(n, cap)).total <= bytes; };
+// beyond that.  backward: the capacity of gsx_render_backward's carve.
+inline int64_t capacity_for(size_t bytes, int64_t n, int64_t max_tiles, bool backward = false) {
+    auto fits = [&](int64_t cap) { return carve(n, cap, max_tiles, binning_temp_bytes(n, cap), backward).total <= bytes; };
     if (!fits(1)) return -1;
     int64_t lo = 1, hi = kMaxPairs;       // invariant: fits(lo), and hi is an upper bound of the answer
     if (fits(hi)) return hi;

@@ -421,7 +421,7 @@ __device__ __forceinline__ void pack_record(int semantics, float x, float y, flo
         // Beyond 3e-5 -- rho op > 340, axis ratios from ~20:1 -- the completed square, which is exact to 1e-5, is no
         // longer "the reference's result to 1e-4": the record is flagged, its raw float32 conic goes to the Gaussian's
         // slot of the side array (`qraw`: the workspace's per-Gaussian float4, which only REF_CUDA uses otherwise) and
-        // the compositing kernels execute the reference's operations on it, one for one (alpha_ref in gsx_blend.hip).
+        // the compositing kernels execute the reference's operations on it, one for one (alpha_ref in gsx_internal.h).
         // (float32 and the approximate reciprocal square root are plenty for a threshold)
         const float cc = 0.5f * fabsf(q01 + q10) * __builtin_amdgcn_rsqf(q00 * q11);
         // (c >= 1: the float32 conic is not even positive definite -- the right-hand side is <= 0 and the record is flagged)

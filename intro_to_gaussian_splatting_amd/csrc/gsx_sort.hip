@@ -68,12 +68,6 @@ constexpr bool kXcdChunks = true;      // scatter_kernel: an XCD's workgroups ta
 constexpr int kModePlain = 0, kModeFirst = 1, kModeFinal = 2;
 constexpr int kSamples = kSortSamples;   // sample keys of the sample-partitioned depth sort (8 per bucket)
 
-__device__ __forceinline__ uint32_t load_count(const uint32_t *n_dev, uint32_t bound) {
-    if (!n_dev) return bound;
-    uint32_t n = *n_dev;
-    return n < bound ? n : bound;
-}
-
 // SPLIT passes (sort_depth_sampled): the "digit" of a key is its bucket among NB - 1 sorted splitters,
 // bucket(k) = #{j in 1..NB-1 : spl[j] <= k}, spl[0] = 0 -- monotone in k, equal keys share a bucket.
 template <int NB>

@@ -337,6 +337,21 @@ class GaussianScene:
             raise ValueError("gaussians.original_index must be a contiguous int32 tensor of %d entries on %s" % (n, dev))
         return oi
 
+    def _frame_params(self, dev, n: int, layout: str, semantics: str):
+        """(GsxParams, original_index or None) of a whole-path call: the layout, the rule set and, for spatially ordered
+        rows, GsxParams.original_index / row_of_index, both checked.  render_image_hip and the backward start from it."""
+        params = _ffi.default_params()
+        oi = self._original_index(dev, n)
+        if oi is not None:          # spatially ordered rows (Gaussians.spatially_ordered): same frame, bit for bit
+            ro = getattr(self.gaussians, "row_of_index", None)
+            if ro is None or ro.device != dev or ro.dtype != torch.int32 or not ro.is_contiguous() or ro.numel() != n:
+                raise ValueError("gaussians.row_of_index (the inverse of original_index) must be a contiguous int32 tensor "
+                                 "of %d entries on %s" % (n, dev))
+            params.original_index, params.row_of_index = oi.data_ptr(), ro.data_ptr()
+        params.layout = _ffi.GSX_LAYOUT_WH3 if layout == "wh3" else _ffi.GSX_LAYOUT_HW3
+        params.semantics = _SEMANTICS[semantics]
+        return params, oi
+
     # ------------------------------------------------------------------ stage 1
     def preprocess(self, image_idx: int) -> PreprocessedScene:
         """Projection + depth sort on the GPU (gsx_preprocess); fields as splat/schema.py:13-25."""
@@ -448,22 +463,16 @@ class GaussianScene:
         g_ = self.gaussians
         cam = self.images[image_idx].gsx_camera()
         width, height = cam.width, cam.height
-        params = _ffi.default_params()
+        params, oi = self._frame_params(dev, n, layout, semantics)
         sh_flat = None
         if tensors[4] is None:      # SH scene: the projection kernel evaluates the view-dependent colour itself
             g = self.gaussians
             k = (int(g.sh_degree) + 1) ** 2
             sh_flat = _check_f32("sh", g.sh.reshape(n, k, 3), dev)
             params.sh, params.sh_degree = sh_flat.data_ptr(), int(g.sh_degree)
-        oi = self._original_index(dev, n)
-        if oi is not None:          # spatially ordered rows (Gaussians.spatially_ordered): same frame, bit for bit
-            ro = getattr(g_, "row_of_index", None)
-            if ro is None or ro.device != dev or ro.dtype != torch.int32 or not ro.is_contiguous() or ro.numel() != n:
-                raise ValueError("gaussians.row_of_index (the inverse of original_index) must be a contiguous int32 tensor "
-                                 "of %d entries on %s" % (n, dev))
-            params.original_index, params.row_of_index = oi.data_ptr(), ro.data_ptr()
-            # ... and a strip's projection drops whole blocks of 256 rows after reading their box (recomputed here when
-            # points / scales were modified since: Gaussians.current_block_bounds)
+        if oi is not None:
+            # a strip's projection drops whole blocks of 256 rows of a spatially ordered scene after reading their box
+            # (recomputed here when points / scales were modified since: Gaussians.current_block_bounds)
             bb = g_.current_block_bounds() if hasattr(g_, "current_block_bounds") else getattr(g_, "block_bounds", None)
             if bb is not None:
                 if bb.device != dev or bb.dtype != torch.float32 or not bb.is_contiguous() or \
@@ -471,8 +480,6 @@ class GaussianScene:
                     raise ValueError("gaussians.block_bounds must be a contiguous float32 (%d, 8) tensor on %s "
                                      "(Gaussians.refresh_block_bounds)" % (-(-n // _ffi.GSX_BOUNDS_ROWS), dev))
                 params.block_bounds = bb.data_ptr()
-        params.layout = _ffi.GSX_LAYOUT_WH3 if layout == "wh3" else _ffi.GSX_LAYOUT_HW3
-        params.semantics = _SEMANTICS[semantics]
         params.background[0], params.background[1], params.background[2] = [float(v) for v in background]
         if timing:
             params.flags |= _ffi.GSX_FLAG_TIMING
@@ -654,22 +661,18 @@ class GaussianScene:
         return out
 
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
-                         n_instances: int, n_visible: int) -> Tuple[torch.Tensor, torch.Tensor]:
+                         n_instances: int, n_visible: int, flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
         ``grad_frame``.  The projection, depth order and binning run again in the library (the same lists as the
-        forward's); the scene's hints buffers are not touched."""
+        forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
+        library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
         lib = _ffi.load()
         with torch.no_grad():
             dev, n, tensors = self._inputs(image_idx)
             tensors = [t.detach() for t in tensors]
             cam = self.images[image_idx].gsx_camera()
-            params = _ffi.default_params()
-            params.layout = _ffi.GSX_LAYOUT_WH3 if layout == "wh3" else _ffi.GSX_LAYOUT_HW3
-            params.semantics = _ffi.GSX_SEM_REF_CPU
-            params.flags |= max(_ffi.visible_rows_flag(n, n_visible, 0), 0)      # the row class the forward ended up with
-            oi = self._original_index(dev, n)
-            if oi is not None:
-                params.original_index, params.row_of_index = oi.data_ptr(), self.gaussians.row_of_index.data_ptr()
+            params, _ = self._frame_params(dev, n, layout, "ref_cpu")
+            params.flags |= _ffi.rows_flag(n, n_visible) | int(flags)     # the row class the forward ended up with
             gf = _check_f32("grad_frame", grad_frame.detach(), dev)
             img = _check_f32("frame", frame.detach(), dev)
             if tuple(gf.shape) != tuple(img.shape):
@@ -767,7 +770,7 @@ class GaussianScene:
         # whose frame held no ill-conditioned footprint, where it pays (confirm() checks every replay's n_redo); a movable
         # camera may turn to such footprints
         private = dict(cap=cap, workspace=torch.empty(nbytes, dtype=torch.uint8, device=dev), kept=int(st["n_kept"]),
-                       rows_flag=0 if semantics == "std_3dgs" else max(_ffi.visible_rows_flag(n, int(st["n_visible"]), 0), 0),
+                       rows_flag=0 if semantics == "std_3dgs" else _ffi.rows_flag(n, int(st["n_visible"])),
                        plain=(not movable_camera) and int(st.get("n_redo", 1)) == 0 and
                        int(st.get("n_tiles", 0)) >= _PLAIN_MIN_TILES,
                        pinned=torch.zeros(ctypes.sizeof(_ffi.GsxFrameStats), dtype=torch.uint8).pin_memory(), inputs=[],

@@ -1,6 +1,7 @@
 // Host-side planning arithmetic of libgsx (intro_to_gaussian_splatting_amd/csrc/gsx_plan.h) under
-// AddressSanitizer + UndefinedBehaviorSanitizer: carve / capacity_for / make_plan / make_clear_plan swept over
-// Gaussian counts, pair capacities, tile sizes, frames and windows up to the 2^31 limits.  No GPU, no HIP:
+// AddressSanitizer + UndefinedBehaviorSanitizer: carve / capacity_for (the forward's and gsx_render_backward's) /
+// make_plan / make_clear_plan swept over Gaussian counts, pair capacities, tile sizes, frames and windows up to the
+// 2^31 limits.  No GPU, no HIP:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include \
 //       -I intro_to_gaussian_splatting_amd/csrc tests/host/plan_sanitize.cpp -o plan_sanitize && ./plan_sanitize
 // (tests/test_host_sanitize.py does exactly this.)  Exit code 0 and "ok" = every invariant held.
@@ -33,22 +34,37 @@ static uint64_t rnd() {
 static int64_t rnd_in(int64_t lo, int64_t hi) { return lo + (int64_t)(rnd() % (uint64_t)(hi - lo + 1)); }
 
 // Regions of a carve: disjoint, 256-byte aligned, inside [0, total), each large enough for what it holds.
-static void check_carve(int64_t n, int64_t cap, int64_t max_tiles) {
+// backward: gsx_render_backward's carve -- the forward's regions where the forward has them, then its own.
+static void check_carve(int64_t n, int64_t cap, int64_t max_tiles, bool backward = false) {
     const size_t temp = binning_temp_bytes(n, cap);
-    const Carve c = carve(n, cap, max_tiles, temp);
+    const Carve c = carve(n, cap, max_tiles, temp, backward);
     const size_t nn = (size_t)(n > 0 ? n : 1), cc = (size_t)(cap > 0 ? cap : 1), tt = (size_t)(max_tiles > 0 ? max_tiles : 1);
     struct R { size_t off, bytes; };
     const R regs[] = {{c.keys0, nn * 4}, {c.keys1, nn * 4}, {c.vals0, nn * 4}, {c.vals1, nn * 4},
                       {c.rec, nn * kRecordBytes}, {c.rect, nn * kTileRectBytes}, {c.rrect, nn * kTileRectBytes},
                       {c.bbox, nn * kBboxBytes}, {c.tkeys0, cc * 4}, {c.tkeys1, cc * 4}, {c.tvals0, cc * 4},
                       {c.tvals1, cc * 4}, {c.ranges, tt * kRangeBytes}, {c.longs, kMaxLongTiles * 4},
-                      {c.counters, 64}, {c.temp, temp}};
+                      {c.counters, 64}, {c.temp, temp},
+                      // gsx_render_backward: raw record, rank and emission prefix per Gaussian, the scan's block sums, a slot per pair
+                      {c.raw, backward ? nn * kRecordBytes : 0}, {c.rank_of, backward ? nn * 4 : 0},
+                      {c.prefix, backward ? (nn + 1) * 4 : 0}, {c.bsum, backward ? (nn / 1024 + 2) * 4 : 0},
+                      {c.slots, backward ? cc * 16 : 0}};
     size_t prev_end = 0;
     for (const R &r : regs) {
+        if (r.bytes == 0) {     // a forward carve has no backward regions
+            CHECK(!backward && r.off == 0);
+            continue;
+        }
         CHECK(r.off % 256 == 0);
         CHECK(r.off >= prev_end);
         CHECK(r.off + r.bytes <= c.total);
         prev_end = r.off + r.bytes;
+    }
+    if (backward) {     // the forward's regions, at the forward's offsets
+        const Carve f = carve(n, cap, max_tiles, temp);
+        CHECK(c.keys0 == f.keys0 && c.rec == f.rec && c.rrect == f.rrect && c.tvals1 == f.tvals1 && c.ranges == f.ranges &&
+              c.longs == f.longs && c.redo == f.redo && c.sched == f.sched && c.counters == f.counters && c.temp == f.temp);
+        CHECK(c.raw >= f.total && c.total > f.total);
     }
     // the digit table of the larger sort and the chunk sums both fit `temp`
     const int64_t items = n > cap ? n : cap;
@@ -61,18 +77,20 @@ static void check_carve(int64_t n, int64_t cap, int64_t max_tiles) {
     CHECK(binning_sums_offset(n, cap) + (nchunks + 1) * 8 <= temp);
 }
 
-static void check_capacity(int64_t n, int64_t cap, int32_t w, int32_t h, int32_t tile) {
+// backward: gsx_backward_workspace_bytes and gsx_render_backward's capacity.
+static void check_capacity(int64_t n, int64_t cap, int32_t w, int32_t h, int32_t tile, bool backward = false) {
     const int64_t max_tiles = max_tiles_of(w, h, tile);
-    const Carve want = carve(n, cap, max_tiles, binning_temp_bytes(n, cap));
-    const int64_t got = capacity_for(want.total, n, max_tiles);
+    const Carve want = carve(n, cap, max_tiles, binning_temp_bytes(n, cap), backward);
+    const int64_t got = capacity_for(want.total, n, max_tiles, backward);
     CHECK(got >= cap);                    // the bytes gsx_workspace_bytes asks for hold the pairs asked for
     CHECK(got <= kMaxPairs);
-    const Carve fit = carve(n, got, max_tiles, binning_temp_bytes(n, got));
+    const Carve fit = carve(n, got, max_tiles, binning_temp_bytes(n, got), backward);
     CHECK(fit.total <= want.total);       // and the capacity derived from them fits them
-    if (want.total > 4096) CHECK(capacity_for(want.total - 4096, n, max_tiles) <= got);
-    CHECK(capacity_for(0, n, max_tiles) == -1);
-    CHECK(cap == 0 || got == cap || carve(n, got + 1, max_tiles, binning_temp_bytes(n, got + 1)).total > want.total || got == kMaxPairs);
-    check_carve(n, got, max_tiles);
+    if (want.total > 4096) CHECK(capacity_for(want.total - 4096, n, max_tiles, backward) <= got);
+    CHECK(capacity_for(0, n, max_tiles, backward) == -1);
+    CHECK(cap == 0 || got == cap || carve(n, got + 1, max_tiles, binning_temp_bytes(n, got + 1), backward).total > want.total ||
+          got == kMaxPairs);
+    check_carve(n, got, max_tiles, backward);
 }
 
 static void check_plan(int32_t w, int32_t h, int32_t tile, int sem, int layout, const int32_t win[4], bool strip_buffer) {
@@ -142,20 +160,22 @@ int main() {
     const int64_t big = ((int64_t)1 << 31) - 1;
     const int64_t ns[] = {0, 1, 2047, 2048, 2049, 131072, 131073, 1000000, 5000000, 20000000, 500000000, big};
     const int64_t caps[] = {0, 1, 4095, 4096, 2048 * 64, 2048 * 64 + 1, 4700000, 85000000, 1000000000, big};
-    for (int64_t n : ns)
-        for (int64_t cap : caps) {
-            check_carve(n, cap, 32400);
-            check_capacity(n, cap, 3840, 2160, 16);
+    for (bool backward : {false, true}) {
+        for (int64_t n : ns)
+            for (int64_t cap : caps) {
+                check_carve(n, cap, 32400, backward);
+                check_capacity(n, cap, 3840, 2160, 16, backward);
+            }
+        for (int it = 0; it < 200000; ++it) {
+            const int shift_n = (int)rnd_in(0, 31), shift_c = (int)rnd_in(0, 31);
+            const int64_t n = rnd_in(0, ((int64_t)1 << shift_n) - 1 + (shift_n == 31 ? 0 : 0));
+            const int64_t cap = rnd_in(0, ((int64_t)1 << shift_c) - 1);
+            const int32_t tile = (int32_t)rnd_in(1, 64), w = (int32_t)rnd_in(1, 8192), h = (int32_t)rnd_in(1, 8192);
+            check_capacity(n, cap, w, h, tile, backward);
         }
-    for (int it = 0; it < 200000; ++it) {
-        const int shift_n = (int)rnd_in(0, 31), shift_c = (int)rnd_in(0, 31);
-        const int64_t n = rnd_in(0, ((int64_t)1 << shift_n) - 1 + (shift_n == 31 ? 0 : 0));
-        const int64_t cap = rnd_in(0, ((int64_t)1 << shift_c) - 1);
-        const int32_t tile = (int32_t)rnd_in(1, 64), w = (int32_t)rnd_in(1, 8192), h = (int32_t)rnd_in(1, 8192);
-        check_capacity(n, cap, w, h, tile);
+        // a buffer far larger than any frame needs (a 288 GB part can hand over > 68 GB): the capacity stays < 2^31
+        CHECK(capacity_for((size_t)200 << 30, 1000000, 8100, backward) == kMaxPairs);
     }
-    // a buffer far larger than any frame needs (a 288 GB part can hand over > 68 GB): the capacity stays < 2^31
-    CHECK(capacity_for((size_t)200 << 30, 1000000, 8100) == kMaxPairs);
     // ---- GsxParams.hints: the per-XCD schedule of ANY window of up to max_tiles tiles fits the region hints_layout
     //      reserves (the projection launch's spare workgroups write 8 x sched_cap(nt) entries behind h.sched)
     {

@@ -45,7 +45,6 @@ def run(name, n, steps, warmup):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
-    from intro_to_gaussian_splatting_amd.gaussian_scene import _WORKSPACE, _ptr, _stream_handle
     from intro_to_gaussian_splatting_amd.synthetic import make_scene, write_colmap_text
 
     sc = make_scene(n, 1920, 1080, seed=0)
@@ -63,20 +62,9 @@ def run(name, n, steps, warmup):
         bwd_ms = _median_ms(bwd, steps, warmup)
         # the stages, once per step, under GSX_FLAG_TIMING
         lib = _ffi.load()
-        dev, n_, tensors = scene._inputs(1)
-        cam = scene.images[1].gsx_camera()
-        params = _ffi.default_params()
-        params.flags |= _ffi.GSX_FLAG_TIMING
-        gc = torch.empty((n, 3), device=dev)
-        go = torch.empty((n, 1), device=dev)
-        cap = int(st["n_instances"]) + 4096
-        nbytes = lib.gsx_backward_workspace_bytes(n, 1920, 1080, 16, cap)
-        ws = _WORKSPACE.get(dev, nbytes)
         stages = []
         for _ in range(steps):
-            _ffi.check(lib.gsx_render_backward(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, 16, _ptr(frame), _ptr(W),
-                                               _ptr(gc), _ptr(go), ctypes.byref(params), _ptr(ws), nbytes,
-                                               _stream_handle(dev)))
+            scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"], flags=_ffi.GSX_FLAG_TIMING)
             ms = (ctypes.c_float * 3)()
             _ffi.check(lib.gsx_debug_backward_stage_ms(ms))
             stages.append(list(ms))
