@@ -378,8 +378,9 @@ GSX_API int gsx_render_forward(const GsxCamera *camera, const float *means3d, co
 /*
  * Backward pass of gsx_render_forward under GSX_SEM_REF_CPU: the gradients the reference's autograd produces for
  * L(frame), with grad_image = dL/dframe (same layout as the frame, GsxParams.layout), with respect to the colours
- * (grad_colors, n x 3) and the opacity logits (grad_opacity_logit, n x 1).  The means, scales and quaternions get none:
- * the reference's Gaussian weight is a Python float (splat/utils.py:357-365).  `image` is the frame gsx_render_forward
+ * (grad_colors, n x 3) and the opacity logits (grad_opacity_logit, n x 1).  The means, scales and quaternions get none
+ * here, as under the reference's autograd, whose Gaussian weight is a Python float (splat/utils.py:357-365): use
+ * gsx_render_backward_geometry for those.  `image` is the frame gsx_render_forward
  * produced from the same inputs and params (its pixels enter every gradient).  Projection, depth order and binning are
  * run again (deterministic: the same lists as the forward's); GsxParams.hints is neither read nor written.  Every row
  * of both outputs is written (0 for a Gaussian on no tile list).  Same inputs, same bits: no float atomics.
@@ -395,6 +396,26 @@ GSX_API int gsx_render_backward(const GsxCamera *camera, const float *means3d, c
 
 /* Bytes of device workspace gsx_render_backward needs (0 on invalid arguments). */
 GSX_API size_t gsx_backward_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
+ * gsx_render_backward plus the geometry: also dL/dmeans3d (grad_means3d, n x 3), dL/dscales (grad_scales, n x 3, linear
+ * scales) and dL/dquats (grad_quats, n x 4, (w,x,y,z); orthogonal to the quaternion up to rounding, since the forward
+ * normalises it) -- what the reference's graph gives once its Gaussian weight stays a tensor: through the pixel mean and
+ * the inverse 2D covariance of every composited (Gaussian, pixel), the floored determinant (floored: the adjugate alone
+ * carries gradient), the EWA projection with its 1.3 tan(fov / 2) clamp, Sigma = (R S)(R S)^T and the quaternion normalised
+ * twice.  The tile rectangle, radius, culling and depth order are piecewise constant: no gradient.  All five outputs are
+ * written for every row (exact zeros for a Gaussian that is culled or on no tile list); grad_colors and
+ * grad_opacity_logit hold the bits gsx_render_backward writes.  Same refusals, same synchronisation, no hints touched,
+ * no float atomics: same inputs, same bits.  workspace: gsx_backward_geometry_workspace_bytes.
+ */
+GSX_API int gsx_render_backward_geometry(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                                 const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                                 const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                                 float *grad_means3d, float *grad_scales, float *grad_quats, const GsxParams *params,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_render_backward_geometry needs (0 on invalid arguments). */
+GSX_API size_t gsx_backward_geometry_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
 
 /*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =

@@ -87,8 +87,8 @@ int check_inputs(const Plan &p, int64_t n, const float *means3d, const float *sc
     return GSX_OK;
 }
 
-// backward: gsx_render_backward's workspace (carve(.., backward), gsx_plan.h).
-int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles, Carve &c, int64_t &cap, bool backward = false) {
+// backward: the carve mode (gsx_plan.h: kCarveBackward = gsx_render_backward's workspace, kCarveGeometry = gsx_render_backward_geometry's).
+int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles, Carve &c, int64_t &cap, int backward = kCarveForward) {
     if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
     if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
     cap = capacity_for(bytes, n, max_tiles, backward);   // never above 2^31 - 1 pairs, whatever the buffer size
@@ -98,8 +98,8 @@ int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles,
     return GSX_OK;
 }
 
-// gsx_workspace_bytes / gsx_backward_workspace_bytes: 0 for sizes no call accepts.
-size_t workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances, bool backward) {
+// gsx_workspace_bytes / gsx_backward_workspace_bytes / gsx_backward_geometry_workspace_bytes: 0 for sizes no call accepts.
+size_t workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances, int backward) {
     if (n < 0 || width <= 0 || height <= 0 || tile <= 0 || max_instances < 0) return 0;
     if (n >= (int64_t)1 << 31 || max_instances >= (int64_t)1 << 31) return 0;
     return carve(n, max_instances, max_tiles_of(width, height, tile), binning_temp_bytes(n, max_instances), backward).total;
@@ -378,6 +378,102 @@ int bin_and_blend(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t ca
 thread_local float g_backward_ms[3] = {0.0f, 0.0f, 0.0f};
 #endif
 
+// The three outputs gsx_render_backward_geometry adds.
+struct GeometryGrads {
+    float *means3d, *scales, *quats;
+};
+
+// gsx_render_backward (geo == nullptr) and gsx_render_backward_geometry: one body.  The geometry call carves the third
+// workspace mode, runs the tile kernel's geometry instance and, after the colour sums, the per-Gaussian chain.
+int render_backward(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                    const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, const float *image,
+                    const float *grad_image, float *grad_colors, float *grad_opacity_logit, const GeometryGrads *geo,
+                    const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    Plan p;
+    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
+    if (rc != GSX_OK) return rc;
+    // what the backward pass covers: the reference's own frame, whole, RGB colours
+    if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward supports GSX_SEM_REF_CPU only");
+    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes RGB colours, not GsxParams.sh");
+    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward renders the whole frame: no tile window");
+    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes the whole frame: no output window");
+    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward does not take substrips");
+    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward synchronises: no GSX_FLAG_NO_SYNC");
+    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward reads the camera argument: no camera_device");
+    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
+    if (rc != GSX_OK) return rc;
+    if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
+    Carve c;
+    int64_t cap;
+    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap,
+                         geo ? kCarveGeometry : kCarveBackward);
+    if (rc != GSX_OK) return rc;
+    char *ws = (char *)workspace;
+    StageTimer tm;
+    tm.begin(p.timing, s);
+    // every row of both outputs: a Gaussian on no tile list has zero gradients
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_colors, (size_t)n * 3, s));
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_opacity_logit, (size_t)n, s));
+    if (geo) {
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means3d, (size_t)n * 3, s));
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->scales, (size_t)n * 3, s));
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->quats, (size_t)n * 4, s));
+    }
+    if (n == 0 || p.grid.count() == 0) {
+        GSX_HIP(hipStreamSynchronize(s));
+        return GSX_OK;
+    }
+    // ---- the forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
+    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
+    const uint32_t *order;
+    bool sampled;
+    rc = project_and_sort(p, c, ws, *camera, in, n, cap, nullptr, nullptr, s, order, sampled);
+    if (rc != GSX_OK) return rc;
+    uint32_t *counters = (uint32_t *)(ws + c.counters);
+    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
+    const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
+                              (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
+    const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
+    const uint32_t *sorted_vals = nullptr;
+    rc = bin_pairs(p, c, ws, n, cap, rrect, order, counters + kCtrKept, sampled, bcnt, lt, nullptr, s, sorted_vals);
+    if (rc != GSX_OK) return rc;
+    int64_t counts[3];
+    rc = read_counts(c, ws, cap, true, nullptr, counts, s);
+    tm.mark();  // 1: the forward's stages
+    if (rc != GSX_OK) return rc;
+    const uint32_t m = (uint32_t)counts[2];
+    if (m == 0 || counts[1] == 0) return GSX_OK;
+    // ---- the backward kernels
+    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
+    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
+    float4 *slots = (float4 *)(ws + c.slots), *geo_slots = geo ? (float4 *)(ws + c.geo_slots) : nullptr;
+    GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
+    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
+    const gsx::BackwardTiles bt{raw, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots,
+                                  geo_slots};
+    GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
+    tm.mark();  // 2: raw records, prefix, compositing backward
+    GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
+    if (geo)
+        GSX_HIP(gsx::launch_backward_geometry(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
+                                              geo->scales, geo->quats, s));
+    tm.mark();  // 3: sums (and the geometry chain)
+    GSX_HIP(hipStreamSynchronize(s));
+#ifdef GSX_TEST_HOOKS
+    if (p.timing) {
+        GsxFrameStats st;
+        memset(&st, 0, sizeof st);
+        tm.finish(&st);
+        for (int i = 0; i < 3; ++i) g_backward_ms[i] = st.stage_ms[i];
+    }
+#endif
+    return GSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -527,86 +623,31 @@ int gsx_render_forward(const GsxCamera *camera, const float *means3d, const floa
 }
 
 size_t gsx_backward_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
-    return workspace_bytes(n, width, height, tile, max_instances, true);
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveBackward);
+}
+
+size_t gsx_backward_geometry_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveGeometry);
 }
 
 int gsx_render_backward(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
                         const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
                         const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
                         const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
-    Plan p;
-    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
-    if (rc != GSX_OK) return rc;
-    // what the backward pass covers: the reference's own frame, whole, RGB colours
-    if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward supports GSX_SEM_REF_CPU only");
-    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes RGB colours, not GsxParams.sh");
-    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward renders the whole frame: no tile window");
-    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes the whole frame: no output window");
-    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward does not take substrips");
-    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward synchronises: no GSX_FLAG_NO_SYNC");
-    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward reads the camera argument: no camera_device");
-    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
-    if (rc != GSX_OK) return rc;
-    if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
-    Carve c;
-    int64_t cap;
-    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, true);
-    if (rc != GSX_OK) return rc;
-    char *ws = (char *)workspace;
-    StageTimer tm;
-    tm.begin(p.timing, s);
-    // every row of both outputs: a Gaussian on no tile list has zero gradients
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_colors, (size_t)n * 3, s));
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_opacity_logit, (size_t)n, s));
-    if (n == 0 || p.grid.count() == 0) {
-        GSX_HIP(hipStreamSynchronize(s));
-        return GSX_OK;
-    }
-    // ---- the forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
-    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const uint32_t *order;
-    bool sampled;
-    rc = project_and_sort(p, c, ws, *camera, in, n, cap, nullptr, nullptr, s, order, sampled);
-    if (rc != GSX_OK) return rc;
-    uint32_t *counters = (uint32_t *)(ws + c.counters);
-    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
-    const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
-                              (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
-    const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
-    const uint32_t *sorted_vals = nullptr;
-    rc = bin_pairs(p, c, ws, n, cap, rrect, order, counters + kCtrKept, sampled, bcnt, lt, nullptr, s, sorted_vals);
-    if (rc != GSX_OK) return rc;
-    int64_t counts[3];
-    rc = read_counts(c, ws, cap, true, nullptr, counts, s);
-    tm.mark();  // 1: the forward's stages
-    if (rc != GSX_OK) return rc;
-    const uint32_t m = (uint32_t)counts[2];
-    if (m == 0 || counts[1] == 0) return GSX_OK;
-    // ---- the backward kernels
-    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
-    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
-    float4 *slots = (float4 *)(ws + c.slots);
-    GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
-    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
-    const gsx::BackwardTiles bt{raw, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots};
-    GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
-    tm.mark();  // 2: raw records, prefix, compositing backward
-    GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
-    tm.mark();  // 3: sums
-    GSX_HIP(hipStreamSynchronize(s));
-#ifdef GSX_TEST_HOOKS
-    if (p.timing) {
-        GsxFrameStats st;
-        memset(&st, 0, sizeof st);
-        tm.finish(&st);
-        for (int i = 0; i < 3; ++i) g_backward_ms[i] = st.stage_ms[i];
-    }
-#endif
-    return GSX_OK;
+    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                           grad_colors, grad_opacity_logit, nullptr, params, workspace, workspace_bytes, stream);
+}
+
+int gsx_render_backward_geometry(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                                 const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                                 const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                                 float *grad_means3d, float *grad_scales, float *grad_quats, const GsxParams *params,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    if (!grad_means3d || !grad_scales || !grad_quats)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
+    const GeometryGrads geo{grad_means3d, grad_scales, grad_quats};
+    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
 }
 
 #ifdef GSX_TEST_HOOKS

@@ -22,6 +22,12 @@
 // by column.  (2) backward_sum_kernel: one wave per Gaussian sums its contiguous slots (lane-strided, then the same
 // butterfly), applies the sigmoid chain and scatters to the Gaussian's row.  Same inputs, same bits.
 //
+// gsx_render_backward_geometry adds dL/dpoint, dL/dscale, dL/dquaternion -- the gradients the reference's graph gives once
+// its weight stays a tensor.  (1') backward_tile_geometry_kernel, the tile kernel's second instance
+// (gsx_backward_tile.inc), also sums five moments of u = dL/dalpha alpha per record into a second slot array;
+// (2') backward_geometry_sum_kernel sums them per Gaussian and backward_geometry_chain_kernel carries them through stage 1's
+// derivative (geometry_chain, below).  The colour-only kernels and their slots are the same code and layout either way.
+//
 // alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
 #include "gsx_internal.h"
@@ -122,103 +128,28 @@ __global__ void __launch_bounds__(kScanThreads)
     if (blockIdx.x == 0 && threadIdx.x == 0) prefix[m] = bsum[nb];
 }
 
-// One wave per window tile.  Its pixels are taken 256 at a time (a 16x16 tile: once), four per lane; the list is staged
-// 64 records per batch.  For a tile of more than 256 pixels the later chunks add their sums to the slots the first one
-// stored (same wave, program order: no atomics).
-__global__ void __launch_bounds__(64) backward_tile_kernel(BackwardTiles bt, TileGrid grid, OutDesc out) {
-    __shared__ float4 sa[64], sb[64], sc[64];
-    __shared__ uint32_t sslot[64];
-    __shared__ float ssum[64 * 4];
-    const uint32_t t = blockIdx.x;
-    const int lane = threadIdx.x;
-    const uint32_t nwy = (uint32_t)grid.nwy();
-    const int tx = grid.wx0 + (int)(t / nwy), ty = grid.wy0 + (int)(t % nwy);
-    const uint2 rg = bt.ranges[t];
-    const uint32_t first = rg.x, last = rg.y & ~kLongFlag;
-    const int T = grid.tile;
-    const int64_t npx = (int64_t)T * T;
-    const float ox = (float)tx * (float)T, oy = (float)ty * (float)T;
-    for (int64_t chunk = 0; chunk < npx; chunk += 64 * kNpx) {
-        float fx[kNpx], fy[kNpx], Tr[kNpx], C0[kNpx], C1[kNpx], C2[kNpx], F0[kNpx], F1[kNpx], F2[kNpx], G0[kNpx], G1[kNpx],
-            G2[kNpx];
-        bool live[kNpx];
+// Sum of one value over the 64 lanes in a fixed order (the butterfly of wave_sum4's last steps), left in every lane.
+__device__ __forceinline__ float wave_sum1(float v) {
 #pragma unroll
-        for (int j = 0; j < kNpx; ++j) {
-            const int64_t p = chunk + j * 64 + lane;
-            live[j] = p < npx;
-            const int x = live[j] ? (int)(p % T) : 0, y = live[j] ? (int)(p / T) : 0;
-            fx[j] = ox + (float)x;
-            fy[j] = oy + (float)y;
-            Tr[j] = 1.0f;
-            C0[j] = C1[j] = C2[j] = 0.0f;
-            F0[j] = F1[j] = F2[j] = G0[j] = G1[j] = G2[j] = 0.0f;
-            if (live[j]) {
-                const int64_t at = (int64_t)(tx * T + x - out.x0) * out.stride_x + (int64_t)(ty * T + y - out.y0) * out.stride_y;
-                F0[j] = bt.image[at]; F1[j] = bt.image[at + 1]; F2[j] = bt.image[at + 2];
-                G0[j] = bt.grad_image[at]; G1[j] = bt.grad_image[at + 1]; G2[j] = bt.grad_image[at + 2];
-            }
-        }
-        for (uint32_t b = first; b < last; b += 64) {
-            const uint32_t cnt = min(64u, last - b);
-            if ((uint32_t)lane < cnt) {
-                const uint32_t row = bt.vals[b + lane];
-                const Record r = bt.raw[row];
-                const uint32_t rank = bt.rank_of[row];
-                const TileRect R = bt.rrect[rank];
-                const uint32_t h = (uint32_t)(R.y1 - R.y0) + 1u;
-                sa[lane] = r.a;
-                sb[lane] = r.b;
-                sc[lane] = r.c;
-                sslot[lane] = bt.prefix[rank] + (uint32_t)(tx - R.x0) * h + (uint32_t)(ty - R.y0);
-            }
-            __syncthreads();
-            for (uint32_t k = 0; k < cnt; ++k) {
-                bool any = false;
-#pragma unroll
-                for (int j = 0; j < kNpx; ++j) any |= live[j];
-                float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, du = 0.0f;
-                if (__any(any)) {
-                    const float4 A = sa[k], B = sb[k], Cc = sc[k];
-#pragma unroll
-                    for (int j = 0; j < kNpx; ++j) {
-                        if (!live[j]) continue;
-                        const float alpha = alpha_ref(A.x, A.y, A.z, A.w, B.x, B.y, B.z, fx[j], fy[j]);
-                        const float ta = Tr[j] * alpha;
-                        const float test = Tr[j] - ta;
-                        if (!(test >= kStopRefCpu)) {   // the pixel stops before this record (the forward's rule; NaN stops too)
-                            live[j] = false;
-                            continue;
-                        }
-                        C0[j] = __builtin_fmaf(ta, Cc.x, C0[j]);
-                        C1[j] = __builtin_fmaf(ta, Cc.y, C1[j]);
-                        C2[j] = __builtin_fmaf(ta, Cc.z, C2[j]);
-                        const float cg = (Cc.x * G0[j] + Cc.y * G1[j]) + Cc.z * G2[j];
-                        const float rest = ((F0[j] - C0[j]) * G0[j] + (F1[j] - C1[j]) * G1[j]) + (F2[j] - C2[j]) * G2[j];
-                        const float da = Tr[j] * cg - rest / (1.0f - alpha);
-                        d0 = __builtin_fmaf(ta, G0[j], d0);
-                        d1 = __builtin_fmaf(ta, G1[j], d1);
-                        d2 = __builtin_fmaf(ta, G2[j], d2);
-                        du = __builtin_fmaf(da, alpha, du);
-                        Tr[j] = test;
-                    }
-                }
-                const float v = wave_sum4(d0, d1, d2, du, lane);
-                if ((lane & 15) == 0) ssum[k * 4 + (lane >> 4)] = v;
-            }
-            __syncthreads();
-            if ((uint32_t)lane < cnt) {
-                float4 v = make_float4(ssum[lane * 4], ssum[lane * 4 + 1], ssum[lane * 4 + 2], ssum[lane * 4 + 3]);
-                float4 *dst = bt.slots + sslot[lane];
-                if (chunk > 0) {
-                    const float4 o = *dst;
-                    v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
-                }
-                *dst = v;
-            }
-            __syncthreads();
-        }
-    }
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    return v;
 }
+
+// backward_tile_kernel and backward_tile_geometry_kernel: one text, two instances (gsx_backward_tile.inc)
+#define GSX_TILE_KERNEL backward_tile_kernel
+#define GSX_TILE_GEOMETRY false
+#define GSX_TILE_ATTR
+#include "gsx_backward_tile.inc"
+#undef GSX_TILE_KERNEL
+#undef GSX_TILE_GEOMETRY
+#undef GSX_TILE_ATTR
+#define GSX_TILE_KERNEL backward_tile_geometry_kernel
+#define GSX_TILE_GEOMETRY true
+#define GSX_TILE_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
+#include "gsx_backward_tile.inc"
+#undef GSX_TILE_KERNEL
+#undef GSX_TILE_GEOMETRY
+#undef GSX_TILE_ATTR
 
 // One wave per depth rank: its slots [prefix[r], prefix[r + 1]) summed lane-strided, then over the wave; lane 0 applies
 // the sigmoid chain and writes the Gaussian's row.
@@ -248,6 +179,230 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// ---- gsx_render_backward_geometry: from a Gaussian's moment sums to dL/dpoint, dL/dscale, dL/dquaternion.
+// What stage 1 computes (gsx_project.hip: project), differentiated by hand in float32.  With d = mean - pixel,
+// power = -1/2 d^T Q d and u = dL/dpower:
+//     dL/dQ_ij = -1/2 sum u d_i d_j              dL/dmean = -1/2 (Q + Q^T) sum u d
+// (1) Q = adj(cov2d) / max(det, 1e-3), det = c00 c11 - c01 c10: where det is floored only the adjugate carries gradient
+// (2) cov2d = (T Sigma T^T)[:2,:2], T = J W: dL/dSigma = T^T G T, dL/dT = G T Sigma^T + G^T T Sigma, dL/dJ = dL/dT W^T;
+//     J00 = fx / z, J02 = -fx cx / z^2, J11 = fy / z, J12 = -fy cy / z^2 with cx = clamp(tx / z, +-1.3 tan_fovx) z:
+//     where the clamp is active d cx / d tx = 0 and d cx / d z = the clamp value
+// (3) Sigma = M M^T, M = R diag(s): dL/dM = (dL/dSigma + dL/dSigma^T) M, dL/ds_j = sum_i dL/dM_ij R_ij, dL/dR_ij = dL/dM_ij s_j
+// (4) R of the quaternion normalised twice: each normalisation b = a / |a| maps g to (g - b (b . g)) / |a|
+// (5) pixel mean = ((h_xy / h_w) + 1)(dim - 1) / 2, h = [p, 1] @ full_proj
+// (6) dL/dpoint = (5) through full_proj plus the view-space point's gradient of (2) through world2view
+// The branch decisions of (1) and (2) are taken on float32 values computed by the forward's operations in the forward's
+// order (ewa_covariance and finish_projection of gsx_project.hip, rows class kRowsMany); the rest of the forward values
+// this needs are recomputed in whatever order is shortest: they enter the gradient as factors, not as decisions.
+struct GeoCamera {
+    float V[16], F[16];            // world2view, full_proj (row vector times matrix)
+    float fx, fy, limx, limy, sx, sy;   // focal lengths, 1.3 tan(fov / 2), (width - 1) / 2, (height - 1) / 2
+};
+
+__device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float *__restrict__ p, const float *__restrict__ sc,
+                                               const float *__restrict__ qin, const float4 QA, const float4 QB,
+                                               float S1, float S2, float S3, float S4, float S5, float *__restrict__ gp,
+                                               float *__restrict__ gs, float *__restrict__ gq) {
+    const float *V = cam.V, *F = cam.F;
+    const float p0 = p[0], p1 = p[1], p2 = p[2];
+    // ---- forward values
+    // rotation, as covariance3d (gsx_project.hip) forms it
+    const float n1 = fmaxf(sqrtf(((qin[0] * qin[0] + qin[1] * qin[1]) + qin[2] * qin[2]) + qin[3] * qin[3]), 1e-12f);
+    const float a0 = qin[0] / n1, a1 = qin[1] / n1, a2 = qin[2] / n1, a3 = qin[3] / n1;
+    const float n2 = sqrtf(((a0 * a0 + a1 * a1) + a2 * a2) + a3 * a3);
+    const float w = a0 / n2, x = a1 / n2, y = a2 / n2, z = a3 / n2;
+    float R[3][3], M[3][3], Sg[3][3];
+    R[0][0] = 1.0f - 2.0f * (y * y + z * z);
+    R[0][1] = 2.0f * (x * y - w * z);
+    R[0][2] = 2.0f * (x * z + w * y);
+    R[1][0] = 2.0f * (x * y + w * z);
+    R[1][1] = 1.0f - 2.0f * (x * x + z * z);
+    R[1][2] = 2.0f * (y * z - w * x);
+    R[2][0] = 2.0f * (x * z - w * y);
+    R[2][1] = 2.0f * (y * z + w * x);
+    R[2][2] = 1.0f - 2.0f * (x * x + y * y);
+    const float s3[3] = {sc[0], sc[1], sc[2]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M[i][j] = R[i][j] * s3[j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Sg[i][j] = (M[i][0] * M[j][0] + M[i][1] * M[j][1]) + M[i][2] * M[j][2];
+    // view-space point and the clamp, as ewa_covariance forms them
+    float t[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        t[c] = __builtin_fmaf(p2, V[8 + c], __builtin_fmaf(p1, V[4 + c], p0 * V[c])) + V[12 + c];
+    const float tz = t[2];
+    const float rx = t[0] / tz, ry = t[1] / tz;
+    const float kx = fminf(fmaxf(rx, -cam.limx), cam.limx), ky = fminf(fmaxf(ry, -cam.limy), cam.limy);
+    const bool inx = rx >= -cam.limx && rx <= cam.limx, iny = ry >= -cam.limy && ry <= cam.limy;
+    const float cx = kx * tz, cy = ky * tz;
+    const float z2 = tz * tz;
+    const float j00 = cam.fx / tz, j02 = -(cam.fx * cx) / z2, j11 = cam.fy / tz, j12 = -(cam.fy * cy) / z2;
+    float T[2][3], B[2][3], C[2][3];       // T = J W, W[i][j] = V[j * 4 + i]; B = T Sigma; C = B W^T
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        T[0][j] = __builtin_fmaf(j02, V[j * 4 + 2], j00 * V[j * 4 + 0]);
+        T[1][j] = __builtin_fmaf(j12, V[j * 4 + 2], j11 * V[j * 4 + 1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[i][j] = (T[i][0] * Sg[0][j] + T[i][1] * Sg[1][j]) + T[i][2] * Sg[2][j];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            C[i][j] = __builtin_fmaf(B[i][2], V[2 * 4 + j], __builtin_fmaf(B[i][1], V[1 * 4 + j], B[i][0] * V[0 * 4 + j]));
+    const float ca = C[0][0] * j00 + C[0][2] * j02, cb = C[0][1] * j11 + C[0][2] * j12;
+    const float cc = C[1][0] * j00 + C[1][2] * j02, cd = C[1][1] * j11 + C[1][2] * j12;
+    const float det_raw = ca * cd - cb * cc;
+    const float det = fmaxf(det_raw, 1e-3f);
+    const bool floored = det_raw < 1e-3f;
+    // ---- compositing: dL/dQ and dL/dmean (Q as the record stores it)
+    const float q00 = QA.z, q01 = QA.w, q10 = QB.x, q11 = QB.y;
+    const float gq00 = -0.5f * S3, gq01 = -0.5f * S4, gq11 = -0.5f * S5;       // gq10 = gq01
+    const float gmx = -0.5f * (2.0f * q00 * S1 + (q01 + q10) * S2);
+    const float gmy = -0.5f * ((q01 + q10) * S1 + 2.0f * q11 * S2);
+    // ---- (1)
+    float g_ca = gq11 / det, g_cd = gq00 / det, g_cb = -gq01 / det, g_cc = -gq01 / det;
+    if (!floored) {
+        const float g_det = -(((gq00 * q00 + gq01 * q01) + gq01 * q10) + gq11 * q11) / det;
+        g_ca += g_det * cd;
+        g_cd += g_det * ca;
+        g_cb -= g_det * cc;
+        g_cc -= g_det * cb;
+    }
+    // ---- (2): G = [[g_ca, g_cb], [g_cc, g_cd]]
+    float GT[2][3], GtT[2][3];             // G T and G^T T
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        GT[0][j] = g_ca * T[0][j] + g_cb * T[1][j];
+        GT[1][j] = g_cc * T[0][j] + g_cd * T[1][j];
+        GtT[0][j] = g_ca * T[0][j] + g_cc * T[1][j];
+        GtT[1][j] = g_cb * T[0][j] + g_cd * T[1][j];
+    }
+    float dS[3][3], dT[2][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dS[i][j] = T[0][i] * GT[0][j] + T[1][i] * GT[1][j];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            dT[i][j] = ((GT[i][0] * Sg[j][0] + GT[i][1] * Sg[j][1]) + GT[i][2] * Sg[j][2]) +
+                       ((GtT[i][0] * Sg[0][j] + GtT[i][1] * Sg[1][j]) + GtT[i][2] * Sg[2][j]);
+    // dL/dJ_ik = sum_j dT_ij W_kj, W_kj = V[j * 4 + k]
+    const float gj00 = (dT[0][0] * V[0] + dT[0][1] * V[4]) + dT[0][2] * V[8];
+    const float gj02 = (dT[0][0] * V[2] + dT[0][1] * V[6]) + dT[0][2] * V[10];
+    const float gj11 = (dT[1][0] * V[1] + dT[1][1] * V[5]) + dT[1][2] * V[9];
+    const float gj12 = (dT[1][0] * V[2] + dT[1][1] * V[6]) + dT[1][2] * V[10];
+    const float z3 = z2 * tz;
+    float g_t[3];
+    const float g_cx = -gj02 * cam.fx / z2, g_cy = -gj12 * cam.fy / z2;
+    g_t[2] = (-(gj00 * cam.fx) / z2 - (gj11 * cam.fy) / z2) + (gj02 * (2.0f * cam.fx * cx) / z3 + gj12 * (2.0f * cam.fy * cy) / z3);
+    g_t[2] += g_cx * kx + g_cy * ky;
+    const float g_rx = inx ? g_cx * tz : 0.0f, g_ry = iny ? g_cy * tz : 0.0f;
+    g_t[0] = g_rx / tz;
+    g_t[1] = g_ry / tz;
+    g_t[2] -= (g_rx * t[0] + g_ry * t[1]) / z2;
+    // ---- (3)
+    float dM[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            dM[i][j] = ((dS[i][0] + dS[0][i]) * M[0][j] + (dS[i][1] + dS[1][i]) * M[1][j]) + (dS[i][2] + dS[2][i]) * M[2][j];
+    float dR[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        gs[j] = (dM[0][j] * R[0][j] + dM[1][j] * R[1][j]) + dM[2][j] * R[2][j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) dR[i][j] = dM[i][j] * s3[j];
+    }
+    // ---- (4)
+    float gb[4];
+    gb[0] = 2.0f * (((z * (dR[1][0] - dR[0][1])) + (y * (dR[0][2] - dR[2][0]))) + (x * (dR[2][1] - dR[1][2])));
+    gb[1] = 2.0f * ((((y * (dR[0][1] + dR[1][0])) + (z * (dR[0][2] + dR[2][0]))) + (w * (dR[2][1] - dR[1][2]))) -
+                    2.0f * x * (dR[1][1] + dR[2][2]));
+    gb[2] = 2.0f * ((((x * (dR[0][1] + dR[1][0])) + (z * (dR[1][2] + dR[2][1]))) + (w * (dR[0][2] - dR[2][0]))) -
+                    2.0f * y * (dR[0][0] + dR[2][2]));
+    gb[3] = 2.0f * ((((x * (dR[0][2] + dR[2][0])) + (y * (dR[1][2] + dR[2][1]))) + (w * (dR[1][0] - dR[0][1]))) -
+                    2.0f * z * (dR[0][0] + dR[1][1]));
+    const float b4[4] = {w, x, y, z}, a4[4] = {a0, a1, a2, a3};
+    const float bg = ((b4[0] * gb[0] + b4[1] * gb[1]) + b4[2] * gb[2]) + b4[3] * gb[3];
+    float ga[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ga[i] = (gb[i] - b4[i] * bg) / n2;
+    const float ag = ((a4[0] * ga[0] + a4[1] * ga[1]) + a4[2] * ga[2]) + a4[3] * ga[3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) gq[i] = (ga[i] - a4[i] * ag) / n1;
+    // ---- (5), (6)
+    const float h0 = __builtin_fmaf(p2, F[8], __builtin_fmaf(p1, F[4], p0 * F[0])) + F[12];
+    const float h1 = __builtin_fmaf(p2, F[9], __builtin_fmaf(p1, F[5], p0 * F[1])) + F[13];
+    const float h3 = __builtin_fmaf(p2, F[11], __builtin_fmaf(p1, F[7], p0 * F[3])) + F[15];
+    const float gn0 = gmx * cam.sx, gn1 = gmy * cam.sy;
+    const float gh0 = gn0 / h3, gh1 = gn1 / h3;
+    const float gh3 = -(gn0 * h0 + gn1 * h1) / (h3 * h3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        gp[k] = ((gh0 * F[k * 4] + gh1 * F[k * 4 + 1]) + gh3 * F[k * 4 + 3]) +
+                ((g_t[0] * V[k * 4] + g_t[1] * V[k * 4 + 1]) + g_t[2] * V[k * 4 + 2]);
+}
+
+// One wave per depth rank: the Gaussian's geometry slots [prefix[r], prefix[r + 1]) summed as backward_sum_kernel sums
+// the colour slots (lane-strided, then the fixed butterflies).  The five sums go back into the Gaussian's FIRST slot:
+// only this wave reads the slots of rank r, and it has read them all by then.
+__global__ void __launch_bounds__(256)
+    backward_geometry_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m) {
+    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= m) return;
+    const uint32_t b = prefix[r], e = prefix[r + 1];
+    if (b == e) return;
+    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f;
+    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
+        const float4 v = geo_slots[2 * (size_t)i], v5 = geo_slots[2 * (size_t)i + 1];
+        a1 += v.x; a2 += v.y; a3 += v.z; a4 += v.w; a5 += v5.x;
+    }
+    const float v = wave_sum4(a1, a2, a3, a4, lane);
+    const float S5 = wave_sum1(a5);
+    const float S2 = __shfl(v, 16), S3 = __shfl(v, 32), S4 = __shfl(v, 48);
+    if (lane == 0) {
+        geo_slots[2 * (size_t)b] = make_float4(v, S2, S3, S4);
+        geo_slots[2 * (size_t)b + 1] = make_float4(S5, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+// One thread per depth rank: the chain on the sums backward_geometry_sum_kernel left, the Gaussian's three rows written.
+__global__ void __launch_bounds__(256)
+    backward_geometry_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                   const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m, GeoCamera cam,
+                                   const float *__restrict__ means3d, const float *__restrict__ scales,
+                                   const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                                   float *__restrict__ grad_scales, float *__restrict__ grad_quats) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t b = prefix[r];
+    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
+    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
+    const int64_t row = order[r];
+    const Record rec = raw[row];
+    float gp[3], gs[3], gq[4];
+    geometry_chain(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        grad_means3d[3 * row + k] = gp[k];
+        grad_scales[3 * row + k] = gs[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
+}
+
 }  // namespace
 
 hipError_t launch_backward_prefix(const TileRect *rrect, const uint32_t *order, uint32_t m, uint32_t *prefix,
@@ -262,7 +417,10 @@ hipError_t launch_backward_prefix(const TileRect *rrect, const uint32_t *order, 
 
 hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s) {
     if (grid.count() <= 0) return hipSuccess;
-    backward_tile_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
+    if (bt.geo_slots)
+        backward_tile_geometry_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
+    else
+        backward_tile_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
     return hipGetLastError();
 }
 
@@ -271,6 +429,28 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
     if (m == 0) return hipSuccess;
     backward_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(slots, prefix, order, raw, m, grad_colors,
                                                                           grad_opacity_logit);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                    const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
+                                    const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
+                                    float *grad_quats, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    GeoCamera cam;
+    for (int i = 0; i < 16; ++i) {
+        cam.V[i] = camera.world2view[i];
+        cam.F[i] = camera.full_proj[i];
+    }
+    cam.fx = camera.fx;
+    cam.fy = camera.fy;
+    cam.limx = 1.3f * camera.tan_fovx;
+    cam.limy = 1.3f * camera.tan_fovy;
+    cam.sx = ((float)camera.width - 1.0f) * 0.5f;
+    cam.sy = ((float)camera.height - 1.0f) * 0.5f;
+    backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
+    backward_geometry_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
+        geo_slots, prefix, order, raw, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats);
     return hipGetLastError();
 }
 

@@ -1,0 +1,138 @@
+// The compositing backward's tile kernel, included twice by gsx_backward.hip (inside its anonymous namespace):
+//   GSX_TILE_KERNEL = backward_tile_kernel,          GSX_TILE_GEOMETRY = false: gsx_render_backward's, the colour-only instance
+//   GSX_TILE_KERNEL = backward_tile_geometry_kernel, GSX_TILE_GEOMETRY = true:  gsx_render_backward_geometry's
+// Two plain kernels from one text rather than a template or a shared device function: the colour-only kernel keeps its
+// name and compiles to the instructions it had before the geometry instance existed.
+//
+// One wave per window tile.  Its pixels are taken 256 at a time (a 16x16 tile: once), four per lane; the list is staged
+// 64 records per batch.  For a tile of more than 256 pixels the later chunks add their sums to the slots the first one
+// stored (same wave, program order: no atomics).
+// GEO (gsx_render_backward_geometry): with u = dL/dalpha alpha = dL/dpower and d = mean - pixel, also the five moments
+// S1 = sum u d0, S2 = sum u d1, S3 = sum u d0^2, S4 = sum u d0 d1, S5 = sum u d1^2 of every record over the tile's
+// pixels, into the pair's two float4 of bt.geo_slots: (S1, S2, S3, S4), (S5, 0, 0, 0).  Same walk, same stop rule; the
+// four colour sums take the same operations in the same order as in the colour-only instance, whose code GEO = false
+// leaves as it was.
+__global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTiles bt, TileGrid grid, OutDesc out) {
+    constexpr bool GEO = GSX_TILE_GEOMETRY;
+    __shared__ float4 sa[64], sb[64], sc[64];
+    __shared__ uint32_t sslot[64];
+    __shared__ float ssum[64 * 4];
+    __shared__ float sgeo[GEO ? 64 * 5 : 1];
+    const uint32_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t nwy = (uint32_t)grid.nwy();
+    const int tx = grid.wx0 + (int)(t / nwy), ty = grid.wy0 + (int)(t % nwy);
+    const uint2 rg = bt.ranges[t];
+    const uint32_t first = rg.x, last = rg.y & ~kLongFlag;
+    const int T = grid.tile;
+    const int64_t npx = (int64_t)T * T;
+    const float ox = (float)tx * (float)T, oy = (float)ty * (float)T;
+    for (int64_t chunk = 0; chunk < npx; chunk += 64 * kNpx) {
+        float fx[kNpx], fy[kNpx], Tr[kNpx], C0[kNpx], C1[kNpx], C2[kNpx], F0[kNpx], F1[kNpx], F2[kNpx], G0[kNpx], G1[kNpx],
+            G2[kNpx];
+        bool live[kNpx];
+#pragma unroll
+        for (int j = 0; j < kNpx; ++j) {
+            const int64_t p = chunk + j * 64 + lane;
+            live[j] = p < npx;
+            const int x = live[j] ? (int)(p % T) : 0, y = live[j] ? (int)(p / T) : 0;
+            fx[j] = ox + (float)x;
+            fy[j] = oy + (float)y;
+            Tr[j] = 1.0f;
+            C0[j] = C1[j] = C2[j] = 0.0f;
+            F0[j] = F1[j] = F2[j] = G0[j] = G1[j] = G2[j] = 0.0f;
+            if (live[j]) {
+                const int64_t at = (int64_t)(tx * T + x - out.x0) * out.stride_x + (int64_t)(ty * T + y - out.y0) * out.stride_y;
+                F0[j] = bt.image[at]; F1[j] = bt.image[at + 1]; F2[j] = bt.image[at + 2];
+                G0[j] = bt.grad_image[at]; G1[j] = bt.grad_image[at + 1]; G2[j] = bt.grad_image[at + 2];
+            }
+        }
+        for (uint32_t b = first; b < last; b += 64) {
+            const uint32_t cnt = min(64u, last - b);
+            if ((uint32_t)lane < cnt) {
+                const uint32_t row = bt.vals[b + lane];
+                const Record r = bt.raw[row];
+                const uint32_t rank = bt.rank_of[row];
+                const TileRect R = bt.rrect[rank];
+                const uint32_t h = (uint32_t)(R.y1 - R.y0) + 1u;
+                sa[lane] = r.a;
+                sb[lane] = r.b;
+                sc[lane] = r.c;
+                sslot[lane] = bt.prefix[rank] + (uint32_t)(tx - R.x0) * h + (uint32_t)(ty - R.y0);
+            }
+            __syncthreads();
+            for (uint32_t k = 0; k < cnt; ++k) {
+                bool any = false;
+#pragma unroll
+                for (int j = 0; j < kNpx; ++j) any |= live[j];
+                float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, du = 0.0f;
+                float m1 = 0.0f, m2 = 0.0f, m3 = 0.0f, m4 = 0.0f, m5 = 0.0f;
+                if (__any(any)) {
+                    const float4 A = sa[k], B = sb[k], Cc = sc[k];
+#pragma unroll
+                    for (int j = 0; j < kNpx; ++j) {
+                        if (!live[j]) continue;
+                        const float alpha = alpha_ref(A.x, A.y, A.z, A.w, B.x, B.y, B.z, fx[j], fy[j]);
+                        const float ta = Tr[j] * alpha;
+                        const float test = Tr[j] - ta;
+                        if (!(test >= kStopRefCpu)) {   // the pixel stops before this record (the forward's rule; NaN stops too)
+                            live[j] = false;
+                            continue;
+                        }
+                        C0[j] = __builtin_fmaf(ta, Cc.x, C0[j]);
+                        C1[j] = __builtin_fmaf(ta, Cc.y, C1[j]);
+                        C2[j] = __builtin_fmaf(ta, Cc.z, C2[j]);
+                        const float cg = (Cc.x * G0[j] + Cc.y * G1[j]) + Cc.z * G2[j];
+                        const float rest = ((F0[j] - C0[j]) * G0[j] + (F1[j] - C1[j]) * G1[j]) + (F2[j] - C2[j]) * G2[j];
+                        const float da = Tr[j] * cg - rest / (1.0f - alpha);
+                        d0 = __builtin_fmaf(ta, G0[j], d0);
+                        d1 = __builtin_fmaf(ta, G1[j], d1);
+                        d2 = __builtin_fmaf(ta, G2[j], d2);
+                        du = __builtin_fmaf(da, alpha, du);
+                        if constexpr (GEO) {
+                            const float u = da * alpha, e0 = A.x - fx[j], e1 = A.y - fy[j];
+                            const float u0 = u * e0, u1 = u * e1;
+                            m1 += u0;
+                            m2 += u1;
+                            m3 = __builtin_fmaf(u0, e0, m3);
+                            m4 = __builtin_fmaf(u0, e1, m4);
+                            m5 = __builtin_fmaf(u1, e1, m5);
+                        }
+                        Tr[j] = test;
+                    }
+                }
+                const float v = wave_sum4(d0, d1, d2, du, lane);
+                if ((lane & 15) == 0) ssum[k * 4 + (lane >> 4)] = v;
+                if constexpr (GEO) {
+                    const float w = wave_sum4(m1, m2, m3, m4, lane), w5 = wave_sum1(m5);
+                    if ((lane & 15) == 0) sgeo[k * 5 + (lane >> 4)] = w;
+                    if (lane == 0) sgeo[k * 5 + 4] = w5;
+                }
+            }
+            __syncthreads();
+            if ((uint32_t)lane < cnt) {
+                float4 v = make_float4(ssum[lane * 4], ssum[lane * 4 + 1], ssum[lane * 4 + 2], ssum[lane * 4 + 3]);
+                float4 *dst = bt.slots + sslot[lane];
+                if (chunk > 0) {
+                    const float4 o = *dst;
+                    v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+                }
+                *dst = v;
+                if constexpr (GEO) {
+                    float4 g0 = make_float4(sgeo[lane * 5], sgeo[lane * 5 + 1], sgeo[lane * 5 + 2], sgeo[lane * 5 + 3]);
+                    float4 g1 = make_float4(sgeo[lane * 5 + 4], 0.0f, 0.0f, 0.0f);
+                    float4 *gdst = bt.geo_slots + 2 * (size_t)sslot[lane];
+                    if (chunk > 0) {
+                        const float4 o0 = gdst[0], o1 = gdst[1];
+                        g0 = make_float4(o0.x + g0.x, o0.y + g0.y, o0.z + g0.z, o0.w + g0.w);
+                        g1.x += o1.x;
+                    }
+                    gdst[0] = g0;
+                    gdst[1] = g1;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+

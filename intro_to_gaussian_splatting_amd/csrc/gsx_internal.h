@@ -302,7 +302,8 @@ bool blend_splits_long_tiles(const TileGrid &grid, int semantics, bool generic);
 hipError_t launch_clear(const ClearPlan &cp, float *base, hipStream_t s);   // the zero fill alone
 hipError_t launch_zero_words(uint32_t *p, size_t n, hipStream_t s);
 
-// ---- gsx_backward.hip (GSX_SEM_REF_CPU): gradients of the frame with respect to the colours and opacity logits
+// ---- gsx_backward.hip (GSX_SEM_REF_CPU): gradients of the frame with respect to the colours and opacity logits, and
+// (gsx_render_backward_geometry) the points, scales and quaternions
 // Exclusive scan of the tile counts of the rank-ordered rectangles rrect[0 .. m): prefix[r] = emission slot of rank r's
 // first pair (gsx_binning.hip emits a Gaussian's pairs over its rectangle, column by column), prefix[m] = D.  Also
 // rank_of[order[r]] = r.  bsum: one word per 1024 ranks (+1).
@@ -316,10 +317,20 @@ struct BackwardTiles {
     const TileRect *rrect;
     const float *image, *grad_image;   // the forward's frame and dL/dframe, layout of `out`
     float4 *slots;                // one per pair, in emission order: (dL/dc rgb, sum over the tile of dL/dalpha * alpha)
+    // gsx_render_backward_geometry (else null: the colour-only instance runs): two per pair, the moments of
+    // u = dL/dalpha * alpha over the tile with d = mean - pixel: (sum u d0, u d1, u d0^2, u d0 d1), (sum u d1^2, 0, 0, 0)
+    float4 *geo_slots = nullptr;
 };
 hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
 // slots of each rank summed in emission order, the sigmoid chain applied, scattered to rows (order[r])
 hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *raw,
                                 uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
+// gsx_render_backward_geometry: geometry slots of each rank summed in emission order (one wave per rank; the sums are
+// left in the rank's first slot), then one thread per rank runs the chain from dL/dQ and dL/dmean to the inputs
+// (gsx_backward.hip: geometry_chain) and scatters to rows (order[r])
+hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                    const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
+                                    const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
+                                    float *grad_quats, hipStream_t s);
 
 }  // namespace gsx

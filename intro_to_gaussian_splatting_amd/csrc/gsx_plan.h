@@ -196,7 +196,14 @@ struct Carve {
     size_t tkeys0, tkeys1, tvals0, tvals1;  // cap x u32: tile ids / Gaussian indices (ping-pong)
     size_t ranges, longs, redo, sched_header, sched, counters, temp, temp_bytes, total;
     size_t raw, rank_of, prefix, bsum, slots;   // gsx_render_backward only (carve(.., backward)); 0 otherwise
+    size_t geo_slots;                           // gsx_render_backward_geometry only (kCarveGeometry); 0 otherwise
 };
+
+// Which entry point a workspace is carved for: the forward's regions alone, with gsx_render_backward's behind them, or
+// with gsx_render_backward_geometry's second slot array behind those.  (An int, so that the callers of the two-mode
+// carve that pass `true` keep meaning kCarveBackward.)
+enum { kCarveForward = 0, kCarveBackward = 1, kCarveGeometry = 2 };
+constexpr size_t kGeoSlotBytes = 32;   // two float4 per pair: (S1, S2, S3, S4), (S5, 0, 0, 0) -- gsx_backward.hip
 
 // The 64-byte `counters` block: what the kernels of one frame hand to each other on the device.
 //   u32 [0] Gaussians behind the cull plane   [1] Gaussians kept by the depth sort (M)
@@ -206,7 +213,8 @@ enum { kCtrCulled = 0, kCtrKept = 1, kCtrPairs = 2, kCtrLong = 3 };
 
 // backward: gsx_render_backward's workspace -- the forward's regions for `cap` pairs, then per Gaussian its raw stage-1
 // record (launch_project_raw), its rank and the emission prefix, the scan's block sums, and one float4 slot per pair.
-inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes, bool backward = false) {
+// kCarveGeometry: the same layout byte for byte, then kGeoSlotBytes more per pair.
+inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes, int backward = kCarveForward) {
     Carve c = {};
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -239,6 +247,7 @@ inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes,
         c.bsum = take((nn / 1024 + 2) * 4);
         c.slots = take(cc * 16);
     }
+    if (backward == kCarveGeometry) c.geo_slots = take(cc * kGeoSlotBytes);
     c.total = off;
     return c;
 }
@@ -255,8 +264,8 @@ inline int64_t max_axis_tiles_of(int32_t width, int32_t height, int32_t tile) {
 // bisection, exact -- what gsx_workspace_bytes(n, .., cap) asks for always yields at least cap); -1 when not
 // even the per-Gaussian part fits.  The kernels index pairs with 32 bits and gsx_workspace_bytes sizes for
 // < 2^31 pairs: a larger buffer (a 288 GB part can hand over 68 GB and more) does not raise the capacity
-// beyond that.  backward: the capacity of gsx_render_backward's carve.
-inline int64_t capacity_for(size_t bytes, int64_t n, int64_t max_tiles, bool backward = false) {
+// beyond that.  backward: the carve mode (kCarveBackward: the capacity of gsx_render_backward's carve).
+inline int64_t capacity_for(size_t bytes, int64_t n, int64_t max_tiles, int backward = kCarveForward) {
     auto fits = [&](int64_t cap) { return carve(n, cap, max_tiles, binning_temp_bytes(n, cap), backward).total <= bytes; };
     if (!fits(1)) return -1;
     int64_t lo = 1, hi = kMaxPairs;       // invariant: fits(lo), and hi is an upper bound of the answer

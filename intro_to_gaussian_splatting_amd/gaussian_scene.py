@@ -224,27 +224,32 @@ class CapturedFrame:
         return self.out
 
 
-def _wants_grad(g) -> bool:
-    """Gradients are recorded for this render: grad mode is on and the colours or the opacity logits require grad."""
-    return torch.is_grad_enabled() and (getattr(g.colors, "requires_grad", False) or
-                                        getattr(g.opacity, "requires_grad", False))
+def _wants_grad(g, geometry: bool = False) -> bool:
+    """Gradients are recorded for this render: grad mode is on and the colours or the opacity logits require grad --
+    or, with ``geometry`` (``geometry_gradients=True``), the points, scales or quaternions."""
+    names = ("colors", "opacity") + (("points", "scales", "quaternions") if geometry else ())
+    return torch.is_grad_enabled() and any(getattr(getattr(g, name, None), "requires_grad", False) for name in names)
 
 
 def _refuse_with_grad(what: str) -> None:
     raise ValueError("gradients of the frame (gaussians.colors / gaussians.opacity require grad) are not available with %s: "
-                     "only the whole ref_cpu frame of RGB colours is differentiable (gsx_render_backward); call it under "
-                     "torch.no_grad() or without requires_grad" % what)
+                     "only the whole ref_cpu frame of RGB colours is differentiable (gsx_render_backward, and with "
+                     "geometry_gradients=True gsx_render_backward_geometry); call it under torch.no_grad() or without "
+                     "requires_grad" % what)
 
 
 class _RenderImageFunction(torch.autograd.Function):
     """The ref_cpu frame as a function of (points, scales, quaternions, opacity, colors).  Forward: the frame
     ``render_image_hip`` returns without gradients, bit for bit.  Backward: gsx_render_backward -- dL/dcolors and
-    dL/dopacity (logits); points, scales and quaternions get None, as in the reference.  The five tensors are saved, so
-    autograd's version counters catch an in-place edit between forward and backward."""
+    dL/dopacity (logits); points, scales and quaternions get None, as in the reference.  With
+    ``geometry_gradients=True``: gsx_render_backward_geometry -- also dL/dpoints, dL/dscales (linear scales) and
+    dL/dquaternions, each for the tensors that require grad; the colour and opacity gradients are the same bits.  The
+    five tensors are saved, so autograd's version counters catch an in-place edit between forward and backward."""
 
     @staticmethod
     def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors):
         kw = dict(kw)
+        ctx.geometry = bool(kw.pop("geometry_gradients", False))
         user_stats, st = kw.pop("stats", None), {}
         frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
         if user_stats is not None:
@@ -258,11 +263,17 @@ class _RenderImageFunction(torch.autograd.Function):
     def backward(ctx, grad_frame):
         points, scales, quaternions, opacity, colors, frame = ctx.saved_tensors
         scene = ctx.scene
-        gc, go = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
-                                        ctx.n_instances, ctx.n_visible)
-        want_o, want_c = ctx.needs_input_grad[8], ctx.needs_input_grad[9]
-        return (None, None, None, None, None, None, None, None,
-                go.view(opacity.shape) if want_o else None, gc.view(colors.shape) if want_c else None)
+        want = ctx.needs_input_grad
+        geometry = ctx.geometry and any(want[5:8])      # the colour-only call gives the same colour and opacity bits
+        grads = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
+                                       ctx.n_instances, ctx.n_visible, geometry=geometry)
+        gc, go = grads[:2]
+        gp, gs, gq = grads[2:] if geometry else (None, None, None)
+        return (None, None, None, None, None,
+                gp.view(points.shape) if gp is not None and want[5] else None,
+                gs.view(scales.shape) if gs is not None and want[6] else None,
+                gq.view(quaternions.shape) if gq is not None and want[7] else None,
+                go.view(opacity.shape) if want[8] else None, gc.view(colors.shape) if want[9] else None)
 
 
 class GaussianScene:
@@ -413,7 +424,7 @@ class GaussianScene:
                          tile_counts: Optional[torch.Tensor] = None, split_long_tiles: bool = True,
                          tile_schedule: Optional[bool] = None, use_hints: bool = True,
                          substrips: Optional[Sequence[int]] = None, substrip_events: Optional[list] = None,
-                         _private: Optional[dict] = None) -> torch.Tensor:
+                         _private: Optional[dict] = None, geometry_gradients: bool = False) -> torch.Tensor:
         """Full forward render in libgsx (gsx_render_forward).
 
         semantics: "ref_cpu" (the reference's ``render_image``), "ref_cuda" (its CUDA kernel's rules
@@ -442,9 +453,14 @@ class GaussianScene:
         counts arrive later in pinned memory and ``confirm_frames()`` must be called (it
         synchronises) before the images are trusted -- it re-renders, on the normal path, any frame
         whose pair count exceeded the workspace capacity it was enqueued with.
+        ``geometry_gradients``: the frame is differentiable whenever grad mode is on and ``gaussians.colors`` or
+        ``gaussians.opacity`` require grad (gsx_render_backward: those two gradients, ``None`` for the geometry, as
+        under the reference's autograd).  ``geometry_gradients=True`` also records gradients when only ``points``,
+        ``scales`` or ``quaternions`` require grad, and delivers dL/dpoints, dL/dscales and dL/dquaternions
+        (gsx_render_backward_geometry) to those of the three that do.  The frame is the same bits either way.
         """
-        if _private is None and _wants_grad(self.gaussians):
-            # gradients with respect to the colours / opacity logits (gsx_render_backward): the whole ref_cpu frame only
+        if _private is None and _wants_grad(self.gaussians, bool(geometry_gradients)):
+            # gradients (gsx_render_backward, gsx_render_backward_geometry): the whole ref_cpu frame of RGB colours only
             refused = [("semantics=%r" % semantics, semantics != "ref_cpu"),
                        ("an SH scene (gaussians.sh)", getattr(self.gaussians, "sh", None) is not None),
                        ("tile_window", tile_window is not None), ("out", out is not None),
@@ -455,7 +471,8 @@ class GaussianScene:
                     _refuse_with_grad(what)
             g = self.gaussians
             kw = dict(stats=stats, timing=timing, generic_kernels=generic_kernels, tile_counts=tile_counts,
-                      split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints)
+                      split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
+                      geometry_gradients=bool(geometry_gradients))
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
                                               g.opacity, g.colors)
         lib = _ffi.load()
@@ -661,9 +678,10 @@ class GaussianScene:
         return out
 
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
-                         n_instances: int, n_visible: int, flags: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                         n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False) -> Tuple[torch.Tensor, ...]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
-        ``grad_frame``.  The projection, depth order and binning run again in the library (the same lists as the
+        ``grad_frame``; with ``geometry`` gsx_render_backward_geometry: those two and (dL/dpoints (N,3), dL/dscales (N,3),
+        dL/dquaternions (N,4)).  The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
         lib = _ffi.load()
@@ -679,16 +697,21 @@ class GaussianScene:
                 raise ValueError("grad_frame has shape %s, the frame %s" % (tuple(gf.shape), tuple(img.shape)))
             gc = torch.empty((n, 3), dtype=torch.float32, device=dev)
             go = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            outs = [gc, go]
+            if geometry:
+                outs += [torch.empty((n, k), dtype=torch.float32, device=dev) for k in (3, 3, 4)]
             cap = int(n_instances) + 4096
+            size_fn = lib.gsx_backward_geometry_workspace_bytes if geometry else lib.gsx_backward_workspace_bytes
+            entry = lib.gsx_render_backward_geometry if geometry else lib.gsx_render_backward
             with torch.cuda.device(dev):
-                nbytes = lib.gsx_backward_workspace_bytes(n, cam.width, cam.height, tile_size, cap)
+                nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
                 if nbytes == 0:
-                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_backward_workspace_bytes rejected the sizes")
+                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "the backward workspace function rejected the sizes")
                 ws = _WORKSPACE.get(dev, nbytes)
-                rc = lib.gsx_render_backward(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(img), _ptr(gf),
-                                             _ptr(gc), _ptr(go), ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
+                rc = entry(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(img), _ptr(gf),
+                           *[_ptr(t) for t in outs], ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
             _ffi.check(rc)
-        return gc, go
+        return tuple(outs)
 
     def _note_count(self, cap_key, n_instances: int, n_kept: int = 0, n_redo: Optional[int] = None) -> None:
         self._instances_hint = max(self._instances_hint, int(n_instances * 1.1))
@@ -790,13 +813,13 @@ class GaussianScene:
         frame._plain_footprints = bool(private["plain"])
         return frame
 
-    def render_image(self, image_idx: int, tile_size: int = 16) -> torch.Tensor:
+    def render_image(self, image_idx: int, tile_size: int = 16, geometry_gradients: bool = False) -> torch.Tensor:
         """(W,H,3) float32 indexed [x,y]; same result as the reference's pure-Python
         ``render_image`` (gaussian_scene.py:200-238), computed on the GPU and -- like the reference,
         whose image is a CPU tensor (gaussian_scene.py:206) -- returned in host memory, so that
         ``plt.imshow(scene.render_image(i))`` keeps working.  ``render_image_hip`` is the same frame
-        left on the device."""
-        frame = self.render_image_hip(image_idx, tile_size=tile_size, layout="wh3")
+        left on the device.  ``geometry_gradients``: as in ``render_image_hip``."""
+        frame = self.render_image_hip(image_idx, tile_size=tile_size, layout="wh3", geometry_gradients=geometry_gradients)
         # page-locked destination (torch's caching host allocator keeps the pages registered between
         # calls): the copy runs at PCIe rate instead of through a pageable staging loop
         host = torch.empty(frame.shape, dtype=frame.dtype, pin_memory=True)
