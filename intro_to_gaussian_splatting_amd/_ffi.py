@@ -121,7 +121,6 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "gsx_debug_sort_pairs": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t,
                                             c_void_p]),
-    "gsx_debug_set_blend_probe": (ctypes.c_int, [c_void_p]),
     "gsx_debug_backward_stage_ms": (ctypes.c_int, [POINTER(c_float)]),
     "gsx_debug_depth_sort": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_uint32,
                                             c_int64, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),

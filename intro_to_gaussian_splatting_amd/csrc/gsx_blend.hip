@@ -69,13 +69,6 @@
 #include "gsx_internal.h"
 #include "gsx_schedule_device.h"
 
-#ifdef GSX_TEST_HOOKS
-// Test library only (gsx_debug.h: gsx_debug_set_blend_probe): when set, every workgroup of blend_tile16_kernel leaves
-// (cycles, tile, list length, records staged | flags << 24) there, indexed by blockIdx.x -- who is the frame waiting for?
-__device__ uint4 *g_blend_probe = nullptr;
-constexpr uint32_t kProbeSecond = 1u << 17;     // a second record per workgroup starts here, the REF instance's per-tile records at twice this (the buffer holds 3 x 2^17)
-#endif
-
 namespace gsx {
 namespace {
 
@@ -300,6 +293,7 @@ __device__ __forceinline__ void composite(float px, const float (&e_p)[NPX], con
 constexpr uint32_t kSkipBudget = 1u << 23;   // 2^-17 of colour per block and channel, in units of 2^-40 (colours are < 1)
 // (kBatchRefOrder: kKindRefOrder records among regular ones; kBatchRefWild: and a D1 < 0 record as well; neither holds a monomial one)
 enum { kBatchRegular = 0, kBatchWild = 1, kBatchMono = 2, kBatchRefOrder = 3, kBatchRefWild = 4, kBatchKindMask = 7, kBatchHasRef = 8 };
+static_assert(kBatchMono < kBatchRefOrder, "the plain instances stop at kind >= kBatchRefOrder and composite a monomial-only batch");
 enum { kStageWhole = 0, kStageBlocks = 1, kStageOneBlock = 2 };
 
 // Which of the three classes of far-away records does this batch still skip in one block?  bound: the lane's record's
@@ -677,13 +671,8 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
                                                         const uint2 *__restrict__ ranges, const TileGrid &g,
                                                         const OutDesc &out, uint32_t t, int quarter,
                                                         Staged &sh, uint32_t budget, uint32_t *cost_out, uint32_t *redo) {
-    const int lane = REF ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;      // (REF: four independent waves per workgroup)
-#ifdef GSX_TEST_HOOKS
-    const unsigned long long probe_t0 = __builtin_readcyclecounter();
-    const uint32_t probe_w0h = (uint32_t)wall_clock64();
-    uint32_t probe_staged = 0, probe_checked_at = 0xFFFFFFu, probe_batch = 0;
-    uint32_t probe_qc[3] = {0u, 0u, 0u}, probe_qtrips = 0, probe_qref = 0;      // cycles: staging, plain trips, trips with a ref-order record
-#endif
+    // (one wave per workgroup in both instances: the mask changes no value, but without it the REF instance compiles to other instructions)
+    const int lane = REF ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
     const int tx = g.wx0 + (int)(t / (uint32_t)g.nwy()), ty = g.wy0 + (int)(t % (uint32_t)g.nwy());
     const bool y_contig = out.stride_y < out.stride_x;
     // a quarter = block `quarter` of the tile (see Staged): 8 x 8 pixels; WH3: lanes run along y (96 contiguous bytes per
@@ -715,9 +704,6 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
     if (rg.x + 64u + (uint32_t)lane < rg.y) idx2 = vals[rg.x + 64u + lane];
     for (uint32_t base = rg.x; base < rg.y; base += 64) {
         uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - base));
-#ifdef GSX_TEST_HOOKS
-        const unsigned long long probe_q0 = __builtin_readcyclecounter();
-#endif
         const float4 ra = na, rb = nb4, rc = nc;
         const uint32_t idx0 = idx1;       // (this batch's list entry: the Gaussian's slot of the side array)
         if (base + 64u + (uint32_t)lane < rg.y) {
@@ -731,24 +717,15 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
                                                                 (float)(ty * 16), 16.0f, skipped, budget, quarter, unused, 0u, &ref_slots, qraw, idx0);
         const int kind = kind_all & kBatchKindMask;
         cost += nb + kBatchCost;
-#ifdef GSX_TEST_HOOKS
-        probe_staged += nb;
-        if (checked && probe_checked_at == 0xFFFFFFu) probe_checked_at = probe_batch;
-        ++probe_batch;
-#endif
         // (kBatchHasRef, not the batch's kind: a batch that also holds a monomial record is kBatchMono whatever else it holds)
         if (REF && (kind_all & kBatchHasRef)) saw_ref = true;
-        // (the plain instance also leaves a batch with a MONOMIAL record -- stage-2 entry, degenerate conics -- to the other one:
-        // such a batch may hold a reference-order record as well, and its kind does not say)
+        // (a batch that holds a reference-order record is reported as kBatchRefOrder to the plain instance even when it also
+        // holds a monomial one -- stage_records --; a batch that is only monomial, kBatchMono < kBatchRefOrder, is composited here)
         if (!REF && kind >= kBatchRefOrder) {       // (wave-uniform) not here: the quarter stays undone (GSX_FLAG_PLAIN_FOOTPRINTS)
             if (lane == 0) atomicAdd(redo, 1u);
             return;
         }
         tile_sync<REF>();
-#ifdef GSX_TEST_HOOKS
-        unsigned long long probe_q1 = __builtin_readcyclecounter();
-        probe_qc[0] += (uint32_t)(probe_q1 - probe_q0);
-#endif
         // Whole trips of eight records (the batch is padded with null records, see kPad).  The alphas of a trip
         // are computed independently of each other and of T -- no branch between them --; then either the plain
         // chain T -> T - T alpha with ONE wave-level saturation test per trip, or -- from the first trip in which any
@@ -819,14 +796,6 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
                     c2 = __builtin_fmaf(ta[u], cb, c2);
                 }
                 T = Tt;
-#ifdef GSX_TEST_HOOKS
-                {
-                    const unsigned long long now = __builtin_readcyclecounter();
-                    probe_qc[1] += (uint32_t)(now - probe_q1);
-                    probe_q1 = now;
-                    ++probe_qtrips;
-                }
-#endif
             }
         }
         tile_sync<REF>();
@@ -835,17 +804,6 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
     // (the largest of the four quarters' costs = the records one wave would have walked until all 256 pixels are done)
     if (cost_out && lane == 0) atomicMax(cost_out, cost | 0x80000000u);
     if (REF && saw_ref && lane == 0 && redo) atomicAdd(redo, 1u);      // (GsxFrameStats.n_redo)
-#ifdef GSX_TEST_HOOKS
-    if (g_blend_probe && lane == 0)
-        g_blend_probe[blockIdx.x] = make_uint4((uint32_t)(__builtin_readcyclecounter() - probe_t0), t | 0x40000000u, rg.y - rg.x,
-                                               probe_staged | (checked ? 0x80000000u : 0u));
-    if (g_blend_probe && lane == 2 && blockDim.x == 64u)
-        g_blend_probe[3 * kProbeSecond + 65536u + blockIdx.x] = make_uint4(probe_qc[0], probe_qc[1], probe_qc[2], probe_qref | (probe_qtrips << 12));
-    if (g_blend_probe && lane == 1)
-        g_blend_probe[kProbeSecond + blockIdx.x] =
-            make_uint4(probe_checked_at, (uint32_t)wall_clock64(),
-                       (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu) | (__builtin_amdgcn_s_getreg((3 << 11) | 20) << 16), probe_w0h);
-#endif
     float *o = out.ptr + (int64_t)(px - out.x0) * out.stride_x + (int64_t)(py - out.y0) * out.stride_y;
     o[0] = c0;
     o[1] = c1;
@@ -854,20 +812,14 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
 
 // One 16x16 tile on one wave, 4 pixels per lane (the body of blend_tile16_kernel; see there).  REF as in
 // blend_long_tile_quarter: false -- a batch that holds a reference-order record ends the tile, counted in *lt.redo.
-template <int VARIANT, bool REF>
+template <bool REF>
 __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, const float4 *__restrict__ qraw,
                                              const uint32_t *__restrict__ vals,
                                              const uint2 *__restrict__ ranges, const TileGrid &g, const OutDesc &out,
                                              const LongTiles &lt, uint32_t budget, const BlendHints &hints, const TileSpan &span,
                                              uint32_t t, Staged &sh) {
-    const int lane = REF ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;      // (REF: four independent waves per workgroup)
-#ifdef GSX_TEST_HOOKS
-    const unsigned long long probe_t0 = __builtin_readcyclecounter();
-    const uint32_t probe_w0 = (uint32_t)wall_clock64();
-    uint32_t probe_staged = 0, probe_batches = 0, probe_after = 0;
-    uint32_t probe_first_ref = 0xFFFu, probe_ref_batches = 0, probe_ref_records = 0;      // (REF: tools/attic/ref_probe.py)
-    uint32_t probe_cyc[4] = {0u, 0u, 0u, 0u}, probe_ent[3] = {0u, 0u, 0u};      // cycles: staging, compositing regular / wild / ref-order batches; entries walked
-#endif
+    // (one wave per workgroup in both instances: the mask changes no value, but without it the REF instance compiles to other instructions)
+    const int lane = REF ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
     const int tx = g.wx0 + (int)(t / (uint32_t)g.nwy()), ty = g.wy0 + (int)(t % (uint32_t)g.nwy());
     if ((span.axis ? ty : tx) < span.lo || (span.axis ? ty : tx) >= span.hi) return;      // another part's tile
     // WH3: lanes 4q..4q+3 cover one x (contiguous 192 B); HW3: lanes 16q..16q+15 cover one y-quad
@@ -931,45 +883,21 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
         if (base + 64u + (uint32_t)lane < rg.y) idx = vals[base + 64u + lane];
         uint32_t count[kBlocks];
         unsigned long long ref_slots = 0ull;     // (wave-uniform) the slots of this batch that hold a reference-order record
-#ifdef GSX_TEST_HOOKS
-        const unsigned long long probe_b0 = __builtin_readcyclecounter();
-#endif
-        const int kind_all = stage_batch<kStageBlocks, (REF || VARIANT == 0)>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16),
-                                                                              (float)(ty * 16), 16.0f, skipped, count, budget, &idx_now, 0,
-                                                                              dead, &ref_slots);
+        const int kind_all = stage_batch<kStageBlocks, REF>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16), (float)(ty * 16),
+                                                            16.0f, skipped, count, budget, &idx_now, 0, dead, &ref_slots);
         const int kind = kind_all & kBatchKindMask;
         const bool wild = kind != kBatchRegular;     // wave-uniform
         // (kBatchHasRef, not the batch's kind: a batch that also holds a monomial record is kBatchMono whatever else it holds)
         if (REF && (kind_all & kBatchHasRef)) saw_ref = true;
-#ifdef GSX_TEST_HOOKS
-        if (REF && kind >= kBatchRefOrder) {
-            if (probe_first_ref == 0xFFFu) probe_first_ref = probe_batches;
-            ++probe_ref_batches;
-            probe_ref_records += (uint32_t)__popcll(ref_slots);
-        }
-#endif
         // the wave walks as far as its LONGEST block list; the other blocks' lists are padded with a null record
         const uint32_t nl = max(max(count[0], count[1]), max(count[2], count[3]));
         cost += nl + kBatchCost;
-#ifdef GSX_TEST_HOOKS
-        probe_staged += nl;
-        probe_batches = min(0xFFFu, probe_batches + 1u);
-        if (checked) probe_after += nl;           // (entries walked under the exact rule, whole batches)
-#endif
         tile_sync<REF>();
-#ifdef GSX_TEST_HOOKS
-        const unsigned long long probe_b1 = __builtin_readcyclecounter();
-        probe_cyc[0] += (uint32_t)(probe_b1 - probe_b0);
-#endif
-        if (VARIANT == 0) {
-            for (uint32_t k = 0; k < nb; ++k) {
-                const Splat s = read_splat(sh, k);
-                composite<4, (REF || VARIANT == 0)>(cx, cy, s, T, c0, c1, c2, blk, (float)(tx * 16), (float)(ty * 16));
-            }
-        } else if (!REF && kind >= kBatchRefOrder) {
-            // (wave-uniform) an ill-conditioned footprint -- or a record in the monomial fallback (stage-2 entry, degenerate
-            // conics), whose batch may hold one without its kind saying so: not here -- the tile stays undone
-            // (GSX_FLAG_PLAIN_FOOTPRINTS; the instance that evaluates both composites it when the frame is rendered again)
+        if (!REF && kind >= kBatchRefOrder) {
+            // (wave-uniform) an ill-conditioned footprint: not here -- the tile stays undone (GSX_FLAG_PLAIN_FOOTPRINTS; the
+            // other instance composites it when the frame is rendered again).  A batch that holds such a record is reported
+            // as kBatchRefOrder to this instance even when it also holds a monomial one (stage_records); a batch that is only
+            // monomial, kBatchMono < kBatchRefOrder, is composited here (below)
             if (lane == 0) atomicAdd(lt.redo, 1u);
             return;
         } else if (kind == kBatchMono) {
@@ -989,7 +917,7 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
             // Same operations per pixel and record in both forms, same order: same bits.
             // Entry k of the lane's list names the slot of ITS block's k-th record: the four blocks read four different
             // records per instruction (four LDS addresses; a 16-lane group shares one).
-            constexpr int kTrip = VARIANT == 2 ? 6 : 4;
+            constexpr int kTrip = 4;
             uint32_t k = 0;
             // one trip of N list entries from k; false: some pixel saturates inside it (nothing is committed)
             auto trip = [&](auto n_tag) __attribute__((always_inline)) -> bool {
@@ -1101,26 +1029,14 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
             }
         }
         tile_sync<REF>();
-#ifdef GSX_TEST_HOOKS
-        {
-            const int pk = kind == kBatchRegular ? 0 : (kind >= kBatchRefOrder ? 2 : 1);
-            probe_cyc[1 + pk] += (uint32_t)(__builtin_readcyclecounter() - probe_b1);
-            probe_ent[pk] += nl;
-        }
-#endif
-        bool live;
-        if (VARIANT == 0)
-            live = (T[0] > 0.0f) | (T[1] > 0.0f) | (T[2] > 0.0f) | (T[3] > 0.0f);
-        else
-            live = (Ta.x > 0.0f) | (Ta.y > 0.0f) | (Tb.x > 0.0f) | (Tb.y > 0.0f);
-        const unsigned long long alive = __ballot(live);
+        const unsigned long long alive = __ballot((Ta.x > 0.0f) | (Ta.y > 0.0f) | (Tb.x > 0.0f) | (Tb.y > 0.0f));
         if (alive == 0ull) break;
-        if (checked || VARIANT == 0) {
+        if (checked) {
 #pragma unroll
             for (int gb = 0; gb < kBlocks; ++gb) dead |= (alive & lanes_of[gb]) == 0ull ? (1u << gb) : 0u;
         }
     }
-    if (VARIANT != 0 && restart_scalar) {
+    if (restart_scalar) {
         // the whole tile again, one record at a time on the scalar form (composite<4>: same bits as the packed loops)
         tile_sync<REF>();
 #pragma unroll
@@ -1133,8 +1049,8 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
         for (uint32_t base = rg.x; base < rg.y; base += 64) {
             uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - base));
             uint32_t count[kBlocks];
-            const int later = stage_batch<kStageBlocks, (REF || VARIANT == 0)>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16),
-                                                                               (float)(ty * 16), 16.0f, skipped, count, budget);
+            const int later = stage_batch<kStageBlocks, REF>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16), (float)(ty * 16),
+                                                             16.0f, skipped, count, budget);
             if (REF && (later & kBatchHasRef)) saw_ref = true;
             if (!REF && (later & kBatchKindMask) >= kBatchRefOrder) {   // (wave-uniform) a later batch holds one: the tile stays undone
                 if (lane == 0) atomicAdd(lt.redo, 1u);
@@ -1144,12 +1060,12 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
             tile_sync<REF>();
             for (uint32_t k = 0; k < nb; ++k) {         // every staged record, in order; a lane's block takes what it keeps
                 const Splat s = read_splat(sh, k);
-                composite<4, (REF || VARIANT == 0)>(cx, cy, s, T, c0, c1, c2, blk, (float)(tx * 16), (float)(ty * 16));
+                composite<4, REF>(cx, cy, s, T, c0, c1, c2, blk, (float)(tx * 16), (float)(ty * 16));
             }
             tile_sync<REF>();
             if (__ballot((T[0] > 0.0f) | (T[1] > 0.0f) | (T[2] > 0.0f) | (T[3] > 0.0f)) == 0ull) break;
         }
-    } else if (VARIANT != 0) {
+    } else {
         c0[0] = c0a.x; c0[1] = c0a.y; c0[2] = c0b.x; c0[3] = c0b.y;
         c1[0] = c1a.x; c1[1] = c1a.y; c1[2] = c1b.x; c1[3] = c1b.y;
         c2[0] = c2a.x; c2[1] = c2a.y; c2[2] = c2b.x; c2[3] = c2b.y;
@@ -1157,26 +1073,6 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
 
     if (hints.lens && lane == 0) hints.lens[t] = cost;
     if (REF && saw_ref && lane == 0 && lt.redo) atomicAdd(lt.redo, 1u);        // (GsxFrameStats.n_redo)
-#ifdef GSX_TEST_HOOKS
-    // REF (several waves per workgroup): by tile, behind the two records of the first launch's workgroups
-    if (REF && g_blend_probe && lane == 0)
-        g_blend_probe[2 * kProbeSecond + t] = make_uint4((uint32_t)(__builtin_readcyclecounter() - probe_t0),
-                                                         probe_batches | (probe_first_ref << 12) | (checked ? 0x80000000u : 0u),
-                                                         probe_ref_batches | (probe_ref_records << 12), rg.y - rg.x);
-    if (REF && g_blend_probe && lane == 1) {
-        g_blend_probe[2 * kProbeSecond + 65536u + t] = make_uint4(probe_cyc[0], probe_cyc[1], probe_cyc[2], probe_cyc[3]);
-        g_blend_probe[3 * kProbeSecond + t] = make_uint4(probe_ent[0], probe_ent[1], probe_ent[2], 0u);
-    }
-    if ((!REF || blockDim.x == 64u) && g_blend_probe && lane == 0)
-        g_blend_probe[blockIdx.x] = make_uint4((uint32_t)(__builtin_readcyclecounter() - probe_t0), t, rg.y - rg.x,
-                                               probe_staged | (checked ? 0x80000000u : 0u));
-    // (where and when: HW_ID = register 4, XCC_ID = register 20; wall_clock64 ticks at 100 MHz on every XCD alike)
-    if ((!REF || blockDim.x == 64u) && g_blend_probe && lane == 1)
-        g_blend_probe[kProbeSecond + blockIdx.x] =
-            make_uint4(probe_batches | (probe_after << 12), (uint32_t)wall_clock64(),
-                       (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu) | (__builtin_amdgcn_s_getreg((3 << 11) | 20) << 16),
-                       probe_w0);
-#endif
     float *o = out.ptr + (int64_t)(px - out.x0) * out.stride_x + (int64_t)(py0 - out.y0) * out.stride_y;
     if (y_contig && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
         float4 *o4 = reinterpret_cast<float4 *>(o);
@@ -1201,15 +1097,13 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
 //   GSX_LAYOUT_WH3  out[x][y][c]: the lane's 4 pixels are 48 contiguous bytes (3 x dwordx4);
 //   GSX_LAYOUT_HW3  out[y][x][c]: 4 stores of 12 B; the 16 lanes that share a y write 192
 //                   contiguous bytes per store instruction.
-// VARIANT 0: scalar-form composite<4>; VARIANT 1: packed form, four (then two) records per saturation test;
-// VARIANT 2 (test library only): six per test.
-template <int VARIANT, bool REF>
+template <bool REF>
 __device__ __forceinline__ void blend_tile16_grid(const Record *__restrict__ rec, const float4 *__restrict__ qraw,
                                                   const uint32_t *__restrict__ vals, const uint2 *__restrict__ ranges,
                                                   const TileGrid &g, const OutDesc &out, const ClearPlan &cp, const LongTiles &lt,
                                                   uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget,
-                                                  uint32_t quarters, const BlendHints &hints, uint32_t tile_blocks,
-                                                  uint32_t sched_cap_, const TileSpan &span, Staged &sh) {
+                                                  const BlendHints &hints, uint32_t tile_blocks, uint32_t sched_cap_,
+                                                  const TileSpan &span, Staged &sh) {
     // block order: [spare workgroups: the next frame's splitters] [helpers of long tiles (dispatched first: they have
     // the most to do)] [tiles] [clears]
     // (hints.rank_last -- gsx_api.hip: a window whose tiles just about fill the chip once -- : the spare workgroups come
@@ -1225,26 +1119,6 @@ __device__ __forceinline__ void blend_tile16_grid(const Record *__restrict__ rec
         return;
     }
     const uint32_t block = hints.rank_last ? blockIdx.x : blockIdx.x - nrank;
-    if (quarters) {
-        // A window of few tiles (a rank's strip): EVERY tile on four waves, a quarter of its pixels each.  One wave per
-        // tile would leave the SIMDs with one to four waves, and a wave with few neighbours needs up to 3.3x its own
-        // issue time per trip (tools/attic/occupancy_probe.py); the quarter form -- one pixel per lane, eight independent
-        // alphas per trip, the gather running ahead -- is built for exactly that situation.  Same arithmetic, same
-        // pixels.  32 consecutive blocks serve 8 tiles; the 4 quarters of a tile share b % 8, i.e. an XCD, and XCD x
-        // gets the x-th eighth of the window's tiles (neighbouring tiles share most of their Gaussians).
-        const uint32_t b = block, nt = (uint32_t)g.count(), groups = (nt + 7u) >> 3;
-        if (b >= groups * 32u) {
-            clear_block(b - groups * 32u, cp, out.ptr);
-            return;
-        }
-        const uint32_t u = ((b >> 5) << 3) | (b & 7u);          // (XCD = b & 7, index inside it = b >> 5)
-        const uint32_t per = nt >> 3, extra = nt & 7u, xcd = b & 7u, i = b >> 5;
-        if (i >= per + (xcd < extra ? 1u : 0u)) return;
-        (void)u;
-        blend_long_tile_quarter<REF>(rec, qraw, vals, ranges, g, out, xcd_remap((i << 3) | xcd, nt), (int)((b >> 3) & 3u), sh, budget,
-                                     nullptr, lt.redo);
-        return;
-    }
     if (block < nhelpers) {
         // 32 consecutive blocks serve 8 long tiles; the 4 quarters of a tile share b % 8, i.e. an XCD
         const uint32_t b = block, slot = (b >> 5) * 8u + (b & 7u);
@@ -1267,40 +1141,34 @@ __device__ __forceinline__ void blend_tile16_grid(const Record *__restrict__ rec
     const uint32_t t = hints.xcd_sched ? xcd_scheduled_tile(bid, (uint32_t)g.count(), sched_cap_, sched, hints.header)
                                        : scheduled_tile(bid, (uint32_t)g.count(), sched);
     if (t >= (uint32_t)g.count()) return;
-    blend_tile16<VARIANT, REF>(rec, qraw, vals, ranges, g, out, lt, budget, hints, span, t, sh);
+    blend_tile16<REF>(rec, qraw, vals, ranges, g, out, lt, budget, hints, span, t, sh);
 }
 
-template <int VARIANT>
 #ifndef GSX_PLAIN_WAVES
 #define GSX_PLAIN_WAVES 8    // (build-time knob for A/B runs: tools/ab_bench.sh)
 #endif
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_PLAIN_WAVES, 8)))   // 64 VGPRs: every lost wave costs
     blend_tile16_kernel(const Record *__restrict__ rec, const float4 *__restrict__ qraw, const uint32_t *__restrict__ vals,
                         const uint2 *__restrict__ ranges, TileGrid g, OutDesc out, ClearPlan cp, LongTiles lt,
-                        uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget, uint32_t quarters, BlendHints hints,
+                        uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget, BlendHints hints,
                         uint32_t tile_blocks, uint32_t sched_cap_, TileSpan span) {
     __shared__ Staged sh;
-    blend_tile16_grid<VARIANT, false>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, quarters, hints, tile_blocks,
-                                      sched_cap_, span, sh);
+    blend_tile16_grid<false>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, hints, tile_blocks, sched_cap_, span, sh);
 }
 
 // The same grid with reference-order records evaluated where they turn up (REF, see above): what a frame runs.  128 VGPRs,
 // 4 waves per SIMD.  (5 and 6 waves -- 96 and 80 VGPRs, 130 and 206 of them spilled -- measured 1 .. 6 % slower on the
 // uniform and the heavy-tailed 1M-Gaussian frames alike, 8 waves -- 314 spilled -- 15 .. 20 %.)
 #ifndef GSX_REF_WAVES
-#define GSX_REF_WAVES 4      // (build-time knobs for A/B runs: tools/ab_bench.sh)
-#endif
-#ifndef GSX_REF_VARIANT
-#define GSX_REF_VARIANT 1    // (2: trips of six records)
+#define GSX_REF_WAVES 4      // (build-time knob for A/B runs: tools/ab_bench.sh)
 #endif
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_REF_WAVES, 8)))
     blend_tile16_ref_kernel(const Record *__restrict__ rec, const float4 *__restrict__ qraw, const uint32_t *__restrict__ vals,
                             const uint2 *__restrict__ ranges, TileGrid g, OutDesc out, ClearPlan cp, LongTiles lt,
-                            uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget, uint32_t quarters,
-                            BlendHints hints, uint32_t tile_blocks, uint32_t sched_cap_, TileSpan span) {
+                            uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget, BlendHints hints,
+                            uint32_t tile_blocks, uint32_t sched_cap_, TileSpan span) {
     __shared__ Staged sh;
-    blend_tile16_grid<GSX_REF_VARIANT, true>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, quarters, hints,
-                                             tile_blocks, sched_cap_, span, sh);
+    blend_tile16_grid<true>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, hints, tile_blocks, sched_cap_, span, sh);
 }
 
 // Any tile size: one wave per tile, one pixel per lane, tile*tile/64 sweeps over the list.
@@ -1639,21 +1507,6 @@ hipError_t launch_clear(const ClearPlan &cp, float *base, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Up to this many tiles in the window every tile is composited by four waves (blend_tile16_kernel, `quarters`).
-// Measured (round 3, tools/attic/strip_probe.py with GSX_QUARTERS_BELOW): it does NOT pay -- a 1/8 strip of the 5M / 4K frame
-// composites in 0.192 ms on one wave per tile and in 0.314 ms on four, 1M / 1080p: 0.073 vs 0.090 ms; the quarter form
-// issues 14 operations per pixel and record where the 4-pixel form shares the x terms (11.25) and stages every
-// record four times.  The mode stays in the kernel (default off) as the strongest test of the quarter path: a frame
-// rendered with it must equal the normal frame bit for bit.
-constexpr int kQuartersBelow = 0;
-
-#ifdef GSX_TEST_HOOKS
-hipError_t set_blend_probe(void *device_buffer) {
-    uint4 *p = (uint4 *)device_buffer;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_blend_probe), &p, sizeof p);
-}
-#endif
-
 bool blend_splits_long_tiles(const TileGrid &grid, int semantics, bool generic) {
     if (knob("GSX_LONG_SPLIT", 1) == 0) return false;     // test library only
     return semantics == GSX_SEM_REF_CPU && grid.tile == 16 && !generic;
@@ -1664,8 +1517,6 @@ bool blend_splits_long_tiles(const TileGrid &grid, int semantics, bool generic) 
 bool blend_uses_schedule(const TileGrid &grid, int semantics, bool generic, int64_t n, int asked) {
     const int forced = knob("GSX_TILE_SCHEDULE", -1);   // test library only: 0 never, 1 always
     if ((semantics != GSX_SEM_REF_CPU && semantics != GSX_SEM_STD_3DGS) || grid.tile != 16 || generic) return false;
-    // a window whose tiles all go on four waves (launch_blend) is not handed out by list length
-    if (semantics == GSX_SEM_REF_CPU && grid.count() <= (int64_t)knob("GSX_QUARTERS_BELOW", kQuartersBelow)) return false;
     if (asked >= 0) return asked != 0;          // GSX_FLAG_TILE_SCHEDULE / GSX_FLAG_NO_TILE_SCHEDULE
     if (forced >= 0) return forced != 0;
     // a window of up to 2048 tiles (a rank's strip of a 1080p frame) puts at most two tiles on a SIMD: the
@@ -1674,7 +1525,7 @@ bool blend_uses_schedule(const TileGrid &grid, int semantics, bool generic, int6
 }
 
 bool blend_in_parts(const TileGrid &grid, int semantics, bool generic) {
-    return semantics == GSX_SEM_REF_CPU && grid.tile == 16 && !generic && grid.count() > (int64_t)knob("GSX_QUARTERS_BELOW", kQuartersBelow);
+    return semantics == GSX_SEM_REF_CPU && grid.tile == 16 && !generic;
 }
 
 hipError_t launch_blend(const Record *rec, const float4 *bbox, const uint32_t *sorted_vals, const uint2 *ranges,
@@ -1701,36 +1552,20 @@ hipError_t launch_blend(const Record *rec, const float4 *bbox, const uint32_t *s
     }
     if (semantics != GSX_SEM_REF_CPU) return hipErrorNotSupported;
     if (grid.tile == 16 && !generic) {
-        const int variant = knob("GSX_BLEND_VARIANT", 1);   // test library only: A/B runs of the compositing loop
         // test library only: GSX_SKIP_BUDGET_LOG2 = -9 hardly ever refuses a skip (round 2's behaviour); default 2^-17
         const uint32_t budget = 1u << (40 + knob("GSX_SKIP_BUDGET_LOG2", -17));
-        // a window of up to kQuartersBelow tiles puts every tile on four waves (see the kernel)
-        const bool quarters = nt <= (int64_t)knob("GSX_QUARTERS_BELOW", kQuartersBelow);
-        BlendHints bh = hints;
-        if (quarters) bh.lens = nullptr;
         // GSX_FLAG_PLAIN_FOOTPRINTS: the instance that does not evaluate reference-order records (see tile_sync)
-        const bool plain = bh.plain != 0u && lt.redo != nullptr;
+        const bool plain = hints.plain != 0u && lt.redo != nullptr;
         // tile workgroups: one per tile, or -- per-XCD schedule from GsxParams.hints -- 8 x cap (gsx_schedule_device.h)
-        const uint32_t cap = bh.xcd_sched ? sched_cap((uint32_t)nt, (uint32_t)grid.nwy()) : 0u;
-        const unsigned tile_blocks = bh.xcd_sched ? kSchedXcds * cap : (unsigned)nt;
+        const uint32_t cap = hints.xcd_sched ? sched_cap((uint32_t)nt, (uint32_t)grid.nwy()) : 0u;
+        const unsigned tile_blocks = hints.xcd_sched ? kSchedXcds * cap : (unsigned)nt;
         const unsigned clear_blocks = (unsigned)(cp.n > 0 ? cp.first[cp.n] : 0);
-        unsigned nh = lt.max ? 4u * lt.max : 0u, grid_blocks = tile_blocks + clear_blocks + nh;
-        if (quarters) {
-            nh = 0;
-            grid_blocks = (unsigned)((nt + 7) / 8) * 32u + clear_blocks;
-        }
-        grid_blocks += bh.samples ? kRankGroups : 0u;
-        const uint32_t q = quarters ? 1u : 0u;
-        if (variant == 1 && !plain)
-            blend_tile16_ref_kernel<<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, q, bh, tile_blocks, cap, span);
-        else if (variant == 0)
-            blend_tile16_kernel<0><<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, q, bh, tile_blocks, cap, span);
-        else if (variant == 2)
-            blend_tile16_kernel<2><<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, q, bh, tile_blocks, cap, span);
-        else if (variant == 3)
-            blend_tile16_kernel<3><<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, q, bh, tile_blocks, cap, span);
+        const unsigned nh = lt.max ? 4u * lt.max : 0u;
+        const unsigned grid_blocks = tile_blocks + clear_blocks + nh + (hints.samples ? kRankGroups : 0u);
+        if (plain)
+            blend_tile16_kernel<<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, hints, tile_blocks, cap, span);
         else
-            blend_tile16_kernel<1><<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, q, bh, tile_blocks, cap, span);
+            blend_tile16_ref_kernel<<<grid_blocks, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp, lt, nh, sched, budget, hints, tile_blocks, cap, span);
     } else {
         blend_generic_kernel<<<nb, 64, 0, s>>>(rec, bbox, sorted_vals, ranges, grid, out, cp);
     }

@@ -52,7 +52,7 @@ def test_shipping_library_exports_exactly_the_header():
 
 
 def test_shipping_library_reads_no_environment_variable():
-    """The measurement knobs (GSX_DEPTH_SORT, GSX_TILE_SCHEDULE, GSX_BLEND_VARIANT, ...) exist only under
+    """The measurement knobs (GSX_DEPTH_SORT, GSX_TILE_SCHEDULE, GSX_LONG_SPLIT, ...) exist only under
     -DGSX_TEST_HOOKS: the product library does not import getenv at all."""
     if shutil.which("nm") is None:
         pytest.skip("needs binutils nm")
