@@ -384,7 +384,8 @@ GSX_API int gsx_render_forward(const GsxCamera *camera, const float *means3d, co
  * produced from the same inputs and params (its pixels enter every gradient).  Projection, depth order and binning are
  * run again (deterministic: the same lists as the forward's); GsxParams.hints is neither read nor written.  Every row
  * of both outputs is written (0 for a Gaussian on no tile list).  Same inputs, same bits: no float atomics.
- * Refused with GSX_ERR_INVALID_ARGUMENT: other semantics, GsxParams.sh, a tile window, an output window, substrips,
+ * Refused with GSX_ERR_INVALID_ARGUMENT: other semantics, GsxParams.sh (an SH scene passes the colours gsx_sh_to_rgb evaluated
+ * and carries grad_colors on to its coefficients with gsx_sh_backward), a tile window, an output window, substrips,
  * GSX_FLAG_NO_SYNC, camera_device.  workspace: gsx_backward_workspace_bytes(n, width, height, tile, pairs) with at
  * least the frame's pair count (GsxFrameStats.n_instances of the forward); fewer: GSX_ERR_WORKSPACE_TOO_SMALL.
  * Synchronises `stream`.
@@ -452,6 +453,22 @@ GSX_API int gsx_project_points(const GsxCamera *camera, const float *means3d, in
  */
 GSX_API int gsx_sh_to_rgb(const float *means3d, const float *sh, int32_t degree, int64_t n,
                   const float *camera_center_host, float *colors_out, void *stream);
+
+/*
+ * Backward of gsx_sh_to_rgb (build extension), the last link of an SH scene's gradient chain: from grad_colors (n,3) =
+ * dL/d(view-dependent colour) -- what gsx_render_backward / gsx_render_backward_geometry write when they are handed the
+ * colours gsx_sh_to_rgb evaluated -- to grad_sh (n, (degree+1)^2, 3) = dL/dsh and, when grad_means3d is not NULL, to
+ * grad_means3d (n,3), the gradient that reaches the mean through the view direction d = v / |v|, v = mean - camera centre:
+ *   m_c = 1 where 0.5 + sum_k Y_k(d) sh[k][c] > 0 (the forward's own operations and order), else 0;
+ *   grad_sh[i][k][c] = Y_k(d) m_c grad_colors[i][c];
+ *   grad_means3d[i]  = (g - d (d . g)) / |v|,  g = sum_k sum_c m_c grad_colors[i][c] sh[k][c] dY_k/dd.
+ * Every entry of both outputs is written (exact zeros for a clamped channel, and for grad_means3d at degree 0); grad_means3d
+ * is written, not accumulated: a caller that also has gsx_render_backward_geometry's dL/dmeans3d adds the two.  No atomics:
+ * same inputs, same bits.  Does not synchronise.  n == 0 is GSX_OK.
+ */
+GSX_API int gsx_sh_backward(const float *means3d, const float *sh, int32_t degree, int64_t n,
+                            const float *camera_center_host, const float *grad_colors,
+                            float *grad_sh, float *grad_means3d /* may be NULL */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,7 @@ SIGNATURES = {
     "gsx_covariance_2d": (ctypes.c_int, [POINTER(GsxCamera), _FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_project_points": (ctypes.c_int, [POINTER(GsxCamera), _FP, c_int64, _FP, c_void_p, c_void_p]),
     "gsx_sh_to_rgb": (ctypes.c_int, [_FP, _FP, c_int32, c_int64, POINTER(c_float), _FP, c_void_p]),
+    "gsx_sh_backward": (ctypes.c_int, [_FP, _FP, c_int32, c_int64, POINTER(c_float), _FP, _FP, _FP, c_void_p]),
 }
 
 # csrc/gsx_debug.h

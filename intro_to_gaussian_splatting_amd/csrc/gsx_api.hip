@@ -668,6 +668,17 @@ int gsx_sh_to_rgb(const float *means3d, const float *sh, int32_t degree, int64_t
     return GSX_OK;
 }
 
+int gsx_sh_backward(const float *means3d, const float *sh, int32_t degree, int64_t n, const float *camera_center_host,
+                    const float *grad_colors, float *grad_sh, float *grad_means3d, void *stream) {
+    if (degree < 0 || degree > 3) return fail(GSX_ERR_INVALID_ARGUMENT, "SH degree %d outside [0,3]", degree);
+    if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n is negative");
+    if (!camera_center_host) return fail(GSX_ERR_INVALID_ARGUMENT, "camera_center_host is NULL");
+    if (n > 0 && (!means3d || !sh || !grad_colors || !grad_sh)) return fail(GSX_ERR_INVALID_ARGUMENT, "an array is NULL");
+    GSX_HIP(gsx::launch_sh_backward(means3d, sh, degree, n, camera_center_host, grad_colors, grad_sh, grad_means3d,
+                                    (hipStream_t)stream));
+    return GSX_OK;
+}
+
 int gsx_covariance_3d(const float *scales, const float *quats, int64_t n, float *covariance_out, void *stream) {
     if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n is negative");
     if (n > 0 && (!scales || !quats || !covariance_out)) return fail(GSX_ERR_INVALID_ARGUMENT, "an array is NULL");

@@ -276,6 +276,10 @@ uint64_t *emit_chunk_sums(void *temp, int64_t n, int64_t cap);
 // ---- gsx_sh.hip
 hipError_t launch_sh_to_rgb(const float *means3d, const float *sh, int degree, int64_t n, const float *center,
                             float *colors, hipStream_t s);
+// dL/dcolors (n,3) -> dL/dsh (n,K,3), every entry written, and (grad_means3d may be NULL) dL/dmeans3d (n,3) through the view
+// direction, written, not accumulated.  A degree outside 0..3: hipErrorInvalidValue.
+hipError_t launch_sh_backward(const float *means3d, const float *sh, int degree, int64_t n, const float *center,
+                              const float *grad_colors, float *grad_sh, float *grad_means3d, hipStream_t s);
 
 // ---- gsx_blend.hip
 // background: 3 floats, read on the host (GSX_SEM_STD_3DGS only); generic: GSX_FLAG_GENERIC_KERNELS.

@@ -8,11 +8,12 @@
 // centre), with the constants of gsx_sh_device.h.  Degree 0 with sh0 = (rgb - 0.5) / 0.28209479
 // reproduces the reference's RGB path, which is how it is tested against the pinned pipeline.
 //
-// This file is the standalone entry (gsx_sh_to_rgb: colours for the stage-1 API).  The whole-path render
+// This file is the standalone entry (gsx_sh_to_rgb: colours for the stage-1 API) and its backward
+// (gsx_sh_backward: the last link of the gradient chain of an SH scene).  The whole-path render
 // evaluates the same code inside the projection kernel (GsxParams.sh), so a frame has no colour launch
 // and no colour array at all.
 //
-// HBM-bound elementwise op: 12 B (mean) + 12 (deg+1)^2 B (coefficients) read, 12 B written.
+// HBM-bound elementwise ops: 12 B (mean) + 12 (deg+1)^2 B (coefficients) read, 12 B written by the forward.
 #include "gsx_internal.h"
 #include "gsx_sh_device.h"
 
@@ -36,7 +37,75 @@ __global__ void __launch_bounds__(sh::kBlock)
     colors[3 * i + 2] = b;
 }
 
+// gsx_sh_backward: dL/dcolour -> dL/dsh and, through the view direction, dL/dmean.  The forward kernel's memory path
+// mirrored: the workgroup's coefficient block comes in through LDS (sh::stage), every thread recomputes its Gaussian's
+// pre-clamp colour with the forward's own operations (the mask: channels the forward did not clamp), takes what the mean
+// gradient needs from its row, overwrites the row with Y_k * masked dL/dcolour, and the block goes out through the same
+// LDS buffer as coalesced 16-byte stores (sh::unstage).  One row per thread, no atomics.
+// HBM: 24 B + 24 K B per Gaussian (mean, dL/dcolour, coefficients in; coefficient gradients out), + 12 B for dL/dmean.
+template <int DEG>
+__global__ void __launch_bounds__(sh::kBlock)
+    sh_backward_kernel(const float *__restrict__ means3d, const float *__restrict__ coeffs, int64_t n, float cx, float cy,
+                       float cz, const float *__restrict__ grad_colors, float *__restrict__ grad_sh,
+                       float *__restrict__ grad_means3d, bool vec_in, bool vec_out) {
+    constexpr int K = sh::Layout<DEG>::K;
+    __shared__ float lds[sh::Layout<DEG>::kLdsFloats];
+    const int64_t g0 = (int64_t)blockIdx.x * sh::kBlock;
+    sh::stage<DEG>(coeffs, n, g0, lds, vec_in);
+    const int64_t i = g0 + threadIdx.x;
+    if (i < n) {
+        float *row = lds + threadIdx.x * sh::Layout<DEG>::STRIDE;
+        float basis[K], x, y, z, inv, pre[3];
+        sh::basis_at<DEG>(means3d[3 * i] - cx, means3d[3 * i + 1] - cy, means3d[3 * i + 2] - cz, basis, x, y, z, inv);
+        sh::pre_clamp<DEG>(basis, row, pre[0], pre[1], pre[2]);
+        float gm[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gm[c] = pre[c] > 0.0f ? grad_colors[3 * i + c] : 0.0f;
+        if (grad_means3d) {
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            if (DEG > 0) {
+                float t[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) t[k] = gm[0] * row[3 * k] + gm[1] * row[3 * k + 1] + gm[2] * row[3 * k + 2];
+                float dgx, dgy, dgz;
+                sh::basis_gradient<DEG>(t, x, y, z, dgx, dgy, dgz);
+                const float radial = x * dgx + y * dgy + z * dgz;      // the part along d moves nothing: d stays a unit vector
+                gx = (dgx - x * radial) * inv;
+                gy = (dgy - y * radial) * inv;
+                gz = (dgz - z * radial) * inv;
+            }
+            grad_means3d[3 * i] = gx;
+            grad_means3d[3 * i + 1] = gy;
+            grad_means3d[3 * i + 2] = gz;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) row[3 * k + c] = pre[c] > 0.0f ? basis[k] * gm[c] : 0.0f;
+    }
+    sh::unstage<DEG>(grad_sh, n, g0, lds, vec_out);
+}
+
 }  // namespace
+
+hipError_t launch_sh_backward(const float *means3d, const float *sh, int degree, int64_t n, const float *center,
+                              const float *grad_colors, float *grad_sh, float *grad_means3d, hipStream_t s) {
+    if (degree < 0 || degree > 3) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const unsigned nb = (unsigned)((n + gsx::sh::kBlock - 1) / gsx::sh::kBlock);
+    const float cx = center[0], cy = center[1], cz = center[2];
+    const bool vi = (reinterpret_cast<uintptr_t>(sh) & 15u) == 0, vo = (reinterpret_cast<uintptr_t>(grad_sh) & 15u) == 0;
+#define GSX_SH_BACKWARD(D) \
+    sh_backward_kernel<D><<<nb, gsx::sh::kBlock, 0, s>>>(means3d, sh, n, cx, cy, cz, grad_colors, grad_sh, grad_means3d, vi, vo)
+    switch (degree) {
+        case 0: GSX_SH_BACKWARD(0); break;
+        case 1: GSX_SH_BACKWARD(1); break;
+        case 2: GSX_SH_BACKWARD(2); break;
+        default: GSX_SH_BACKWARD(3); break;
+    }
+#undef GSX_SH_BACKWARD
+    return hipGetLastError();
+}
 
 hipError_t launch_sh_to_rgb(const float *means3d, const float *sh, int degree, int64_t n, const float *center,
                             float *colors, hipStream_t s) {

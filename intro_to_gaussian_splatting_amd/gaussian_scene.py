@@ -226,28 +226,48 @@ class CapturedFrame:
 
 def _wants_grad(g, geometry: bool = False) -> bool:
     """Gradients are recorded for this render: grad mode is on and the colours or the opacity logits require grad --
-    or, with ``geometry`` (``geometry_gradients=True``), the points, scales or quaternions."""
-    names = ("colors", "opacity") + (("points", "scales", "quaternions") if geometry else ())
+    or, with ``geometry`` (``geometry_gradients=True``), the points, scales or quaternions -- or, on an SH scene, the
+    coefficients ``gaussians.sh`` (what makes an SH scene differentiable: ``_sh_wants_grad``)."""
+    names = ("colors", "opacity", "sh") + (("points", "scales", "quaternions") if geometry else ())
     return torch.is_grad_enabled() and any(getattr(getattr(g, name, None), "requires_grad", False) for name in names)
 
 
+def _sh_wants_grad(g) -> bool:
+    """An SH scene is differentiable when its coefficients require grad (gsx_sh_backward carries dL/dcolour on to them)."""
+    return bool(getattr(getattr(g, "sh", None), "requires_grad", False))
+
+
+def _refusals(g, semantics="ref_cpu", tile_window=None, out=None, substrips=None, no_sync=False, camera_buffer=None):
+    """What ``render_image_hip`` was asked for that has no gradient: (what, asked for it) in the order it is refused."""
+    return [("semantics=%r" % semantics, semantics != "ref_cpu"),
+            ("an SH scene (gaussians.sh) whose coefficients do not require grad (call gaussians.sh.requires_grad_(True) to "
+             "differentiate it)", getattr(g, "sh", None) is not None and not _sh_wants_grad(g)),
+            ("tile_window", tile_window is not None), ("out", out is not None),
+            ("substrips", substrips is not None), ("no_sync", bool(no_sync)),
+            ("camera_buffer", camera_buffer is not None)]
+
+
 def _refuse_with_grad(what: str) -> None:
-    raise ValueError("gradients of the frame (gaussians.colors / gaussians.opacity require grad) are not available with %s: "
-                     "only the whole ref_cpu frame of RGB colours is differentiable (gsx_render_backward, and with "
-                     "geometry_gradients=True gsx_render_backward_geometry); call it under torch.no_grad() or without "
+    raise ValueError("gradients of the frame (gaussians.colors / gaussians.opacity / gaussians.sh require grad) are not "
+                     "available with %s: only the whole ref_cpu frame is differentiable, of RGB colours or of SH "
+                     "coefficients that require grad (gsx_render_backward, with geometry_gradients=True "
+                     "gsx_render_backward_geometry, gsx_sh_backward); call it under torch.no_grad() or without "
                      "requires_grad" % what)
 
 
 class _RenderImageFunction(torch.autograd.Function):
-    """The ref_cpu frame as a function of (points, scales, quaternions, opacity, colors).  Forward: the frame
-    ``render_image_hip`` returns without gradients, bit for bit.  Backward: gsx_render_backward -- dL/dcolors and
-    dL/dopacity (logits); points, scales and quaternions get None, as in the reference.  With
-    ``geometry_gradients=True``: gsx_render_backward_geometry -- also dL/dpoints, dL/dscales (linear scales) and
-    dL/dquaternions, each for the tensors that require grad; the colour and opacity gradients are the same bits.  The
-    five tensors are saved, so autograd's version counters catch an in-place edit between forward and backward."""
+    """The ref_cpu frame as a function of (points, scales, quaternions, opacity, colors, sh); ``sh`` is None for an RGB
+    scene.  Forward: the frame ``render_image_hip`` returns without gradients, bit for bit.  Backward:
+    gsx_render_backward -- dL/dcolors and dL/dopacity (logits); points, scales and quaternions get None, as in the
+    reference.  With ``geometry_gradients=True``: gsx_render_backward_geometry -- also dL/dpoints, dL/dscales (linear
+    scales) and dL/dquaternions, each for the tensors that require grad; the colour and opacity gradients are the same
+    bits.  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
+    colour), and gsx_sh_backward carries that on to dL/dsh and -- with geometry gradients -- adds the view direction's
+    share to dL/dpoints; ``colors`` gets None (the frame does not read it).  The tensors are saved, so autograd's version
+    counters catch an in-place edit between forward and backward."""
 
     @staticmethod
-    def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors):
+    def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh):
         kw = dict(kw)
         ctx.geometry = bool(kw.pop("geometry_gradients", False))
         user_stats, st = kw.pop("stats", None), {}
@@ -256,12 +276,13 @@ class _RenderImageFunction(torch.autograd.Function):
             user_stats.update(st)
         ctx.scene, ctx.image_idx, ctx.tile_size, ctx.layout = scene, image_idx, tile_size, layout
         ctx.n_instances, ctx.n_visible = int(st["n_instances"]), int(st["n_visible"])
-        ctx.save_for_backward(points, scales, quaternions, opacity, colors, frame)
+        ctx.has_sh = sh is not None
+        ctx.save_for_backward(points, scales, quaternions, opacity, colors, frame, *((sh,) if ctx.has_sh else ()))
         return frame
 
     @staticmethod
     def backward(ctx, grad_frame):
-        points, scales, quaternions, opacity, colors, frame = ctx.saved_tensors
+        points, scales, quaternions, opacity, colors, frame = ctx.saved_tensors[:6]
         scene = ctx.scene
         want = ctx.needs_input_grad
         geometry = ctx.geometry and any(want[5:8])      # the colour-only call gives the same colour and opacity bits
@@ -269,11 +290,20 @@ class _RenderImageFunction(torch.autograd.Function):
                                        ctx.n_instances, ctx.n_visible, geometry=geometry)
         gc, go = grads[:2]
         gp, gs, gq = grads[2:] if geometry else (None, None, None)
+        gsh = None
+        if ctx.has_sh:      # gc is dL/d(view-dependent colour): on to the coefficients, and through the direction to the mean
+            sh = ctx.saved_tensors[6]
+            gsh, gview = scene._sh_backward(ctx.image_idx, gc, with_points=geometry and want[5])
+            gsh, gc = gsh.view(sh.shape), None
+            if gview is not None:
+                gp = gp + gview
         return (None, None, None, None, None,
                 gp.view(points.shape) if gp is not None and want[5] else None,
                 gs.view(scales.shape) if gs is not None and want[6] else None,
                 gq.view(quaternions.shape) if gq is not None and want[7] else None,
-                go.view(opacity.shape) if want[8] else None, gc.view(colors.shape) if want[9] else None)
+                go.view(opacity.shape) if want[8] else None,
+                gc.view(colors.shape) if gc is not None and want[9] else None,
+                gsh if want[10] else None)
 
 
 class GaussianScene:
@@ -458,15 +488,13 @@ class GaussianScene:
         under the reference's autograd).  ``geometry_gradients=True`` also records gradients when only ``points``,
         ``scales`` or ``quaternions`` require grad, and delivers dL/dpoints, dL/dscales and dL/dquaternions
         (gsx_render_backward_geometry) to those of the three that do.  The frame is the same bits either way.
+        An SH scene is differentiable when ``gaussians.sh`` requires grad: dL/dsh (gsx_sh_backward) and dL/dopacity, and
+        with ``geometry_gradients=True`` the geometry too, dL/dpoints including the share that reaches the mean through the
+        view direction; an SH scene whose ``sh`` does not require grad is refused when gradients are asked for.
         """
         if _private is None and _wants_grad(self.gaussians, bool(geometry_gradients)):
-            # gradients (gsx_render_backward, gsx_render_backward_geometry): the whole ref_cpu frame of RGB colours only
-            refused = [("semantics=%r" % semantics, semantics != "ref_cpu"),
-                       ("an SH scene (gaussians.sh)", getattr(self.gaussians, "sh", None) is not None),
-                       ("tile_window", tile_window is not None), ("out", out is not None),
-                       ("substrips", substrips is not None), ("no_sync", bool(no_sync)),
-                       ("camera_buffer", camera_buffer is not None)]
-            for what, bad in refused:
+            # gradients (gsx_render_backward, gsx_render_backward_geometry, gsx_sh_backward): the whole ref_cpu frame only
+            for what, bad in _refusals(self.gaussians, semantics, tile_window, out, substrips, no_sync, camera_buffer):
                 if bad:
                     _refuse_with_grad(what)
             g = self.gaussians
@@ -474,7 +502,7 @@ class GaussianScene:
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
                       geometry_gradients=bool(geometry_gradients))
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
-                                              g.opacity, g.colors)
+                                              g.opacity, g.colors, getattr(g, "sh", None))
         lib = _ffi.load()
         dev, n, tensors = self._inputs(image_idx, inline_sh=True)
         g_ = self.gaussians
@@ -712,6 +740,29 @@ class GaussianScene:
                            *[_ptr(t) for t in outs], ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
             _ffi.check(rc)
         return tuple(outs)
+
+    def _sh_backward(self, image_idx: int, grad_colors: torch.Tensor,
+                     with_points: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """gsx_sh_backward: (dL/dsh (N,K,3), dL/dpoints (N,3) through the view direction, or None without ``with_points``)
+        of this camera's view-dependent colours for dL/dcolour = ``grad_colors`` (N,3)."""
+        lib = _ffi.load()
+        g = self.gaussians
+        with torch.no_grad():
+            dev = g.points.device
+            _require_gpu(dev)
+            n = int(g.points.shape[0])
+            k = (int(g.sh_degree) + 1) ** 2
+            pts = _check_f32("points", g.points.detach().reshape(n, 3), dev)
+            sh = _check_f32("sh", g.sh.detach().reshape(n, k, 3), dev)
+            gc = _check_f32("grad_colors", grad_colors.detach().reshape(n, 3), dev)
+            gsh = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+            gview = torch.empty((n, 3), dtype=torch.float32, device=dev) if with_points else None
+            center = (ctypes.c_float * 3)(*self.images[image_idx].camera_center_host)
+            with torch.cuda.device(dev):
+                rc = lib.gsx_sh_backward(_ptr(pts), _ptr(sh), int(g.sh_degree), n, center, _ptr(gc), _ptr(gsh), _ptr(gview),
+                                         _stream_handle(dev))
+            _ffi.check(rc)
+        return gsh, gview
 
     def _note_count(self, cap_key, n_instances: int, n_kept: int = 0, n_redo: Optional[int] = None) -> None:
         self._instances_hint = max(self._instances_hint, int(n_instances * 1.1))

@@ -9,7 +9,9 @@ Gaussian weight is a Python float (splat/utils.py:357-365, ``.item()``), which c
 through the means and the covariances.  Here gradients are opt-in: ``g.colors.requires_grad_(True)``
 and / or ``g.opacity.requires_grad_(True)``, and ``GaussianScene.render_image`` /
 ``render_image_hip`` then return a frame with a ``grad_fn`` whose backward runs in libgsx
-(gsx_render_backward); points, scales and quaternions get no gradient, like the reference's.
+(gsx_render_backward); points, scales and quaternions get no gradient, like the reference's
+(``geometry_gradients=True`` delivers them).  An SH scene (``sh`` set) is differentiable when
+``g.sh.requires_grad_(True)``: dL/dsh comes from gsx_sh_backward.
 """
 from __future__ import annotations
 

@@ -1,0 +1,290 @@
+"""Differentiable SH scenes on the GPU: gsx_sh_backward against the float64 restatement (tests/sh_backward_restatement.py)
+at every block edge the staging branches on, and the whole chain through ``render_image_hip`` -- an SH scene's gradients
+are the RGB scene's (same camera's evaluated colours) carried one link further, bit for bit.
+
+Bound: 12 E_REF per output, E_REF the float32 reference's own error (tests/test_sh_backward_host.py, measured on the CPU:
+sh 6.921e-07, points 3.838e-07).  What the kernel measured on an MI355X over the seven cases below, same unit:
+    sh      6.769e-07  (n 70001, degree 3)
+    points  4.419e-07  (n 70001, degree 3)
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+
+import sh_backward_restatement as shr
+from test_hip_backward import DEV, _golden_scene
+from test_sh_backward_host import BOUND
+
+pytestmark = pytest.mark.gpu
+
+# worst error / scale of gsx_sh_backward against the restatement, measured on an MI355X (bounds: 8.31e-06, 4.61e-06)
+KERNEL_MEASURED = {"sh": 6.769e-7, "points": 4.419e-7}
+GUARD = 64          # floats on both sides of every output buffer that the kernel must leave alone
+SENTINEL = 12345.0
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _guarded(n_floats, lead):
+    """(whole buffer, the n_floats view that starts `lead` floats behind the front guard) filled with the sentinel."""
+    whole = torch.full((GUARD + lead + n_floats + GUARD,), SENTINEL, dtype=torch.float32, device=DEV)
+    return whole, whole[GUARD + lead:GUARD + lead + n_floats]
+
+
+def _call(pts, sh, degree, gc, grad_sh, grad_means, center=shr.CENTER):
+    from intro_to_gaussian_splatting_amd import _ffi
+
+    lib = _ffi.load()
+    n = int(pts.shape[0])
+    c = (ctypes.c_float * 3)(*[float(v) for v in center])
+    p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+    _ffi.check(lib.gsx_sh_backward(p(pts), p(sh), degree, n, c, p(gc), p(grad_sh), p(grad_means), _stream()))
+
+
+@pytest.mark.parametrize("n,degree,skip", shr.CASES)
+def test_kernel_matches_restatement_at_block_edges_and_unaligned_bases(n, degree, skip):
+    k = (degree + 1) ** 2
+    pts, sh, gc = shr.case_inputs(n, degree, skip)
+    d_pts = torch.from_numpy(pts).to(DEV)[skip:].contiguous()
+    d_gc = torch.from_numpy(gc).to(DEV)[skip:].contiguous()
+    d_sh = torch.from_numpy(sh).to(DEV)[skip:]                  # a view: base pointer + skip * 12 K bytes
+    assert d_sh.is_contiguous() and (skip == 0 or d_sh.data_ptr() % 16 != 0)
+    pts, sh, gc = pts[skip:], sh[skip:], gc[skip:]
+    whole_sh, out_sh = _guarded(n * 3 * k, skip * 3 * k)
+    whole_mean, out_mean = _guarded(n * 3, 0)
+    assert (out_sh.data_ptr() % 16 != 0) == (skip != 0) and out_mean.data_ptr() % 16 == 0
+    _call(d_pts, d_sh, degree, d_gc, out_sh, out_mean)
+    torch.cuda.synchronize()
+    got_sh, got_mean = out_sh.cpu().numpy().reshape(n, k, 3), out_mean.cpu().numpy().reshape(n, 3)
+    # every entry written, nothing outside
+    lead = GUARD + skip * 3 * k
+    w = whole_sh.cpu().numpy()
+    assert (w[:lead] == SENTINEL).all() and (w[lead + n * 3 * k:] == SENTINEL).all() and w.size == lead + n * 3 * k + GUARD
+    w = whole_mean.cpu().numpy()
+    assert (w[:GUARD] == SENTINEL).all() and (w[GUARD + n * 3:] == SENTINEL).all()
+    assert np.isfinite(got_sh).all() and np.isfinite(got_mean).all()
+    assert not (got_sh == SENTINEL).any() and not (got_mean == SENTINEL).any()
+
+    pre, mask = shr.forward(pts, sh, degree, shr.CENTER)[:2]
+    clamped = float((~mask).mean())
+    sure = np.abs(pre) >= shr.NEAR_ZERO
+    print("n %d degree %d: %.1f %% of channels clamped, %d of %d left out near zero" % (
+        n, degree, 100 * clamped, int((~sure).sum()), sure.size))
+    if n >= 200:
+        assert 0.03 <= clamped <= 0.5, clamped
+    assert (~sure).mean() <= 0.01
+    # mask: away from the edge the kernel's zero pattern IS the restatement's mask (grad_colors has no zero entry;
+    # basis 0 is a constant, so column 0 of a live channel is never zero)
+    assert np.array_equal((got_sh[:, 0, :] != 0)[sure], mask[sure])
+    assert not got_sh[np.broadcast_to((~mask & sure)[:, None, :], got_sh.shape)].any()       # exact zeros, every k
+    ref_sh, ref_mean, scale_sh, scale_mean = shr.backward(pts, sh, degree, shr.CENTER, gc)
+    e_sh = shr.scaled_error(got_sh, ref_sh, scale_sh, keep=sure[:, None, :])
+    e_mean = shr.scaled_error(got_mean, ref_mean, scale_mean, keep=sure.all(1)[:, None])
+    print("n %d degree %d: kernel vs restatement, max error / scale: sh %.4g (bound %.3g), points %.4g (bound %.3g)" % (
+        n, degree, e_sh, BOUND["sh"], e_mean, BOUND["points"]))
+    assert e_sh <= BOUND["sh"], e_sh
+    assert e_mean <= BOUND["points"], e_mean
+    if degree == 0:
+        assert not got_mean.any()
+    else:
+        assert np.abs(got_mean).max() > 0
+
+    # grad_means3d = NULL: the same grad_sh bits; a second call: identical bits
+    _, again_sh = _guarded(n * 3 * k, skip * 3 * k)
+    _call(d_pts, d_sh, degree, d_gc, again_sh, None)
+    assert torch.equal(again_sh, out_sh)
+    _, twice_sh = _guarded(n * 3 * k, skip * 3 * k)
+    _, twice_mean = _guarded(n * 3, 0)
+    _call(d_pts, d_sh, degree, d_gc, twice_sh, twice_mean)
+    assert torch.equal(twice_sh, out_sh) and torch.equal(twice_mean, out_mean)
+
+
+def test_abi_accepts_nothing_and_refuses_a_degree_outside_0_to_3():
+    from intro_to_gaussian_splatting_amd import _ffi
+
+    lib = _ffi.load()
+    c = (ctypes.c_float * 3)(0.0, 0.0, 0.0)
+    null = ctypes.c_void_p(0)
+    assert lib.gsx_sh_backward(null, null, 3, 0, c, null, null, null, _stream()) == _ffi.GSX_OK
+    t = torch.zeros(48, device=DEV)
+    p = ctypes.c_void_p(t.data_ptr())
+    for degree in (-1, 4):
+        assert lib.gsx_sh_backward(p, p, degree, 1, c, p, p, null, _stream()) == _ffi.GSX_ERR_INVALID_ARGUMENT
+
+
+# ---- end to end
+def _sh_for(colors, degree, seed):
+    """Coefficients whose degree-0 colour is `colors` (n,3), the higher orders strong enough to clamp some channels."""
+    rs = np.random.RandomState(seed)
+    n, k = colors.shape[0], (degree + 1) ** 2
+    sh = np.zeros((n, k, 3), np.float32)
+    sh[:, 0, :] = (colors - 0.5) / shr.C0
+    sh[:, 0, :] -= (rs.uniform(size=(n, 1)) < 0.2) * 2.0        # a fifth of the Gaussians: dark enough to clamp at degree 0
+    sh[:, 1:, :] = rs.normal(0, 0.4, size=(n, k - 1, 3))
+    return sh
+
+
+def _sh_scene(tmp_path, degree, seed=11):
+    gg = load_golden("grad_trainedlike_128x128_n3000")
+    scene = _golden_scene(tmp_path, gg)
+    g = scene.gaussians
+    g.sh = torch.from_numpy(_sh_for(np.asarray(gg["colors"], np.float32), degree, seed)).to(DEV).contiguous()
+    g.sh_degree = degree
+    return scene, torch.from_numpy(gg["W"]).to(DEV)
+
+
+NAMES = ("points", "scales", "quaternions", "opacity", "colors", "sh")
+
+
+def _grads(scene, W, want, geometry):
+    g = scene.gaussians
+    for name in NAMES:
+        t = getattr(g, name)
+        if t is not None:
+            t.requires_grad_(name in want)
+            t.grad = None
+    frame = scene.render_image_hip(1, geometry_gradients=geometry)
+    (frame * W).sum().backward()
+    out = {name: (None if getattr(g, name) is None or getattr(g, name).grad is None else getattr(g, name).grad.detach().clone())
+           for name in NAMES}
+    for name in NAMES:
+        t = getattr(g, name)
+        if t is not None:
+            t.requires_grad_(False)
+            t.grad = None
+    return frame.detach(), out
+
+
+@pytest.mark.parametrize("degree", [0, 1, 2, 3])
+def test_sh_scene_gradients_are_the_rgb_scene_s_carried_one_link_further(tmp_path, degree):
+    from intro_to_gaussian_splatting_amd import GaussianScene
+
+    scene, W = _sh_scene(tmp_path, degree)
+    g = scene.gaussians
+    n, k = g.points.shape[0], (degree + 1) ** 2
+    with torch.no_grad():
+        plain = scene.render_image_hip(1).clone()
+        colors = scene._colors(1).clone()
+    clamped = float((colors == 0).float().mean())
+    print("degree %d: %.1f %% of channels clamped" % (degree, 100 * clamped))
+    assert 0.01 <= clamped <= 0.5
+    frame, sh_grads = _grads(scene, W, ("points", "scales", "quaternions", "opacity", "sh"), geometry=True)
+    assert torch.equal(frame, plain)
+    frame2, sh_only = _grads(scene, W, ("points", "scales", "quaternions", "opacity", "sh"), geometry=False)
+    assert torch.equal(frame2, plain)
+
+    # the RGB scene of this camera's colours
+    rgb = GaussianScene(str(tmp_path), _rgb_copy(g, colors))
+    rgb_frame, rgb_grads = _grads(rgb, W, ("points", "scales", "quaternions", "opacity", "colors"), geometry=True)
+    assert torch.equal(rgb_frame, plain)
+    for name in ("opacity", "scales", "quaternions"):
+        assert sh_grads[name].abs().max() > 0 and torch.equal(sh_grads[name], rgb_grads[name]), name
+    want_sh = torch.empty((n, k, 3), device=DEV)
+    want_view = torch.empty((n, 3), device=DEV)
+    _call(g.points, g.sh, degree, rgb_grads["colors"].contiguous(), want_sh, want_view,
+          center=scene.images[1].camera_center_host)
+    assert sh_grads["sh"].shape == g.sh.shape and sh_grads["sh"].abs().max() > 0
+    assert torch.equal(sh_grads["sh"], want_sh)
+    assert torch.equal(sh_grads["points"], rgb_grads["points"] + want_view)
+    assert (want_view.abs().max() > 0) == (degree > 0)
+    assert sh_grads["colors"] is None
+    # without geometry_gradients: no gradient for the geometry, the same dL/dsh and dL/dopacity bits
+    assert sh_only["points"] is None and sh_only["scales"] is None and sh_only["quaternions"] is None
+    assert torch.equal(sh_only["sh"], want_sh) and torch.equal(sh_only["opacity"], rgb_grads["opacity"])
+
+
+def _rgb_copy(g, colors):
+    from intro_to_gaussian_splatting_amd import Gaussians
+
+    out = Gaussians.from_arrays(g.points.detach().cpu(), torch.zeros_like(colors).cpu(), g.scales.detach().cpu(),
+                                g.quaternions.detach().cpu(), g.opacity.detach().cpu(), device=DEV)
+    out.colors = colors.detach().clone().contiguous()
+    return out
+
+
+def test_spatially_ordered_sh_scene_gives_the_permuted_rows(tmp_path):
+    from intro_to_gaussian_splatting_amd import GaussianScene
+
+    scene, W = _sh_scene(tmp_path, 3)
+    want = ("points", "opacity", "sh")
+    frame, a = _grads(scene, W, want, geometry=True)
+    with torch.no_grad():
+        ordered = scene.gaussians.spatially_ordered()
+    assert ordered.sh is not None and ordered.original_index is not None
+    scene2 = GaussianScene(str(tmp_path), ordered)
+    frame2, b = _grads(scene2, W, want, geometry=True)
+    oi = ordered.original_index.long()
+    assert torch.equal(frame, frame2)
+    for name in want:
+        assert torch.equal(b[name], a[name][oi]), name
+
+
+def test_refused_modes_raise_with_sh_requiring_grad_and_run_without(tmp_path):
+    scene, W = _sh_scene(tmp_path, 2)
+    g = scene.gaussians
+    out = torch.empty((128, 128, 3), device=DEV)
+    cam_bytes = ctypes.sizeof(scene.images[1].gsx_camera())
+    cam_buf = torch.frombuffer(bytearray(bytes(scene.images[1].gsx_camera())), dtype=torch.uint8).to(DEV)
+    assert cam_buf.numel() == cam_bytes
+    calls = {
+        "semantics": lambda: scene.render_image_hip(1, semantics="ref_cuda"),
+        "tile_window": lambda: scene.render_image_hip(1, tile_window=(0, 1, 0, 1)),
+        "out": lambda: scene.render_image_hip(1, out=out),
+        "substrips": lambda: scene.render_image_hip(1, substrips=[0, 3, 7]),
+        "no_sync": lambda: scene.render_image_hip(1, no_sync=True),
+        "camera_buffer": lambda: scene.render_image_hip(1, camera_buffer=cam_buf),
+        "capture_frame": lambda: scene.capture_frame(1),
+        "render_images": lambda: next(iter(scene.render_images([1]))),
+    }
+    g.sh.requires_grad_(True)
+    for what, call in calls.items():
+        with pytest.raises(ValueError, match=what):
+            call()
+    with torch.no_grad():
+        for what, call in calls.items():
+            call()
+        scene.confirm_frames()
+    # coefficients that do not require grad: refused as ever, and the message says what to do
+    g.sh.requires_grad_(False)
+    g.opacity.requires_grad_(True)
+    with pytest.raises(ValueError, match="SH") as err:
+        scene.render_image_hip(1)
+    assert "gaussians.sh.requires_grad_(True)" in str(err.value)
+    g.opacity.requires_grad_(False)
+    # an in-place edit of the coefficients between forward and backward
+    g.sh.requires_grad_(True)
+    frame = scene.render_image_hip(1)
+    with torch.no_grad():
+        g.sh.mul_(1.0)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        (frame * W).sum().backward()
+    g.sh.requires_grad_(False)
+
+
+def test_thirty_adam_steps_on_the_coefficients_lower_the_loss(tmp_path):
+    scene, _ = _sh_scene(tmp_path, 3)
+    g = scene.gaussians
+    rs = np.random.RandomState(5)
+    with torch.no_grad():
+        start = g.sh.clone()
+        g.sh.add_(torch.from_numpy(rs.normal(0, 0.2, size=tuple(g.sh.shape)).astype(np.float32)).to(DEV))
+        target = scene.render_image_hip(1).clone()
+        g.sh.copy_(start)
+    g.sh.requires_grad_(True)
+    opt = torch.optim.Adam([g.sh], lr=0.02)
+    losses = []
+    for _ in range(30):
+        opt.zero_grad()
+        loss = ((scene.render_image_hip(1) - target) ** 2).sum()
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+    print("L2 loss: first %.6g, last %.6g" % (losses[0], losses[-1]))
+    assert losses[-1] < losses[0]
+    g.sh.requires_grad_(False)

@@ -1,6 +1,6 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--sh]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
 gradients, median of HIP-event-bracketed frames), the whole backward call (median, host-synchronised as the call is) and
@@ -8,6 +8,13 @@ its stages from GSX_FLAG_TIMING (test library: gsx_debug_backward_stage_ms) -- t
 compositing backward (+ raw records and emission prefix), the per-Gaussian sums --, and the bytes stored into the
 per-pair slots (16 per pair).  --geometry adds the same figures for gsx_render_backward_geometry (key "geometry": the
 points, scales and quaternions too; 48 slot bytes per pair, the per-Gaussian chain counted with the sums).
+
+--sh times the differentiable SH scene INSTEAD: the trained-like 1M scene with degree-3 coefficients (bench.py's
+c3_trainedlike).  Its backward is gsx_render_backward on this camera's evaluated colours (gsx_sh_to_rgb runs again) and
+then gsx_sh_backward: the whole backward, the share of gsx_sh_backward in it, and the kernel alone -- time per launch
+over batches of back-to-back launches, bytes = n (24 + 24 K) (+ 12 n with the mean gradient), GB/s -- beside the forward
+kernel gsx_sh_to_rgb (n (24 + 12 K) bytes) timed the same way in the same run as the yardstick.  Both kernels alternate
+between two copies of the coefficients, so that no launch finds its 192 MB in the 256 MB last-level cache.
 """
 from __future__ import annotations
 
@@ -83,14 +90,81 @@ def run(name, n, steps, warmup, geometry=False):
     return out
 
 
+def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10):
+    import torch
+
+    from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
+    from intro_to_gaussian_splatting_amd.synthetic import make_trained_like_scene, write_colmap_text
+
+    sc = make_trained_like_scene(n, 1920, 1080, seed=0)
+    with tempfile.TemporaryDirectory() as tmp:
+        write_colmap_text(tmp, sc)
+        g = Gaussians.from_arrays(sc["points"], sc["colors_0_255"], sc["scales"], sc["quaternions"], sc["opacity"],
+                                  device="cuda:0")
+        g.sh, g.sh_degree = torch.from_numpy(sc["sh"]).to(g.device).contiguous(), int(sc["sh_degree"])
+        scene = GaussianScene(tmp, g)
+    lib = _ffi.load()
+    deg, k = g.sh_degree, (g.sh_degree + 1) ** 2
+    with torch.no_grad():
+        st = {}
+        frame = scene.render_image_hip(1, stats=st).clone()
+        fwd_ms = _median_ms(lambda: scene.render_image_hip(1), steps, warmup)
+        W = torch.randn(frame.shape, device=frame.device, generator=torch.Generator(device=frame.device).manual_seed(0))
+
+        def whole(geo):
+            def call():
+                grads = scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"], geometry=geo)
+                return scene._sh_backward(1, grads[0], with_points=geo)
+            return _median_ms(call, steps, warmup)
+
+        # the two kernels alone, on the gradient the frame really produces
+        gc = scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"])[0]
+        pts = g.points.reshape(n, 3).contiguous()
+        shs = [g.sh.reshape(n, k, 3).contiguous(), g.sh.reshape(n, k, 3).clone()]
+        gsh, gview, cols = torch.empty((n, k, 3), device=pts.device), torch.empty((n, 3), device=pts.device), \
+            torch.empty((n, 3), device=pts.device)
+        center = (ctypes.c_float * 3)(*scene.images[1].camera_center_host)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+
+        def kernel_ms(launch):
+            def burst():
+                for i in range(batch):
+                    _ffi.check(launch(shs[i & 1]))
+            return _median_ms(burst, steps, warmup) / batch
+
+        bwd = kernel_ms(lambda sh: lib.gsx_sh_backward(p(pts), p(sh), deg, n, center, p(gc), p(gsh), None, stream))
+        bwd_pts = kernel_ms(lambda sh: lib.gsx_sh_backward(p(pts), p(sh), deg, n, center, p(gc), p(gsh), p(gview), stream))
+        fwd = kernel_ms(lambda sh: lib.gsx_sh_to_rgb(p(pts), p(sh), deg, n, center, p(cols), stream))
+        rate = lambda nbytes, ms: round(nbytes / ms / 1e6, 1)  # noqa: E731  (GB/s)
+        b_bwd, b_fwd = n * (24 + 24 * k), n * (24 + 12 * k)
+        whole_ms = whole(False)
+        out = dict(workload="c3_trainedlike", n=n, sh_degree=deg, n_instances=int(st["n_instances"]),
+                   forward_frame_ms=round(fwd_ms, 4), backward_ms=round(whole_ms, 4),
+                   backward_over_forward=round(whole_ms / fwd_ms, 3),
+                   sh_backward_ms=round(bwd, 4), sh_backward_share=round(bwd / whole_ms, 4), sh_backward_bytes=b_bwd,
+                   sh_backward_gbps=rate(b_bwd, bwd),
+                   sh_backward_with_points_ms=round(bwd_pts, 4), sh_backward_with_points_bytes=b_bwd + 12 * n,
+                   sh_backward_with_points_gbps=rate(b_bwd + 12 * n, bwd_pts),
+                   sh_to_rgb_ms=round(fwd, 4), sh_to_rgb_bytes=b_fwd, sh_to_rgb_gbps=rate(b_fwd, fwd))
+        if geometry:
+            geo_ms = whole(True)
+            out["geometry"] = dict(backward_ms=round(geo_ms, 4), sh_backward_share=round(bwd_pts / geo_ms, 4))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--geometry", action="store_true", help="also time gsx_render_backward_geometry")
+    ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     args = ap.parse_args()
     from intro_to_gaussian_splatting_amd import _ffi
 
+    if args.sh:
+        print(json.dumps(dict(metric="sh_backward_ms", results=run_sh(args.steps, args.warmup, args.geometry))))
+        return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
     out = {name: run(name, n, args.steps, args.warmup, args.geometry) for name, n in WORKLOADS.items()}
     print(json.dumps(dict(metric="backward_ms", results=out)))
