@@ -470,6 +470,40 @@ GSX_API int gsx_sh_backward(const float *means3d, const float *sh, int32_t degre
                             const float *camera_center_host, const float *grad_colors,
                             float *grad_sh, float *grad_means3d /* may be NULL */, void *stream);
 
+/*
+ * Build extension (the reference renders and stops): the photometric loss every splat fit minimises (Kerbl et al. 2023),
+ * value and gradient in one call.  image (the frame, x) and target (y) are channel-interleaved (.., .., 3) float32; only
+ * the region [0, rows) x [0, cols) of the two leading axes takes part, exactly as if both had been cropped to it -- a row of
+ * each starts every *_row_stride floats (>= 3 cols: the caller crops by passing the full image's stride).  The window is
+ * symmetric, so GSX_LAYOUT_WH3 and GSX_LAYOUT_HW3 frames are the same problem.
+ *   g[i] = exp(-(i - 5)^2 / (2 1.5^2)) / sum, i = 0..10;  G* = the separable 11 x 11 filter per channel, zero padding 5
+ *   mu1 = G*x, mu2 = G*y, p = G*(x x), q = G*(x y), r = G*(y y);  s1 = p - mu1^2, s2 = r - mu2^2, s12 = q - mu1 mu2
+ *   A1 = 2 mu1 mu2 + C1, A2 = 2 s12 + C2, B1 = mu1^2 + mu2^2 + C1, B2 = s1 + s2 + C2,  C1 = 0.01^2, C2 = 0.03^2
+ *   ssim = mean(A1 A2 / (B1 B2)) and l1 = mean|x - y| over the n = 3 rows cols elements
+ *   loss = (1 - lambda_dssim) l1 + lambda_dssim (1 - ssim)
+ * loss_out (DEVICE, 3 floats) receives loss, l1, ssim.  grad_image (DEVICE, or NULL for the value alone) receives
+ * dloss/dimage: with w = -lambda_dssim / n,
+ *   Dmu = 2 mu2 (A2 - A1) / (B1 B2) - 2 mu1 A1 A2 (B2 - B1) / (B1 B2)^2,  Dp = -A1 A2 / (B1 B2^2),  Dq = 2 A1 / (B1 B2)
+ *   grad = (1 - lambda_dssim) sign(x - y) / n + G*(w Dmu) + 2 x G*(w Dp) + y G*(w Dq),  sign(0) = 0
+ * Exactly the rows x cols x 3 region elements are written (a row every grad_row_stride floats, nothing behind a row's
+ * 3 cols floats), written, not accumulated, and scaled by nothing but the formula.  Vector accesses are used wherever a
+ * base pointer is 16-byte aligned and its stride a multiple of 4 floats; any float-aligned base and stride is accepted.
+ * No atomics: same inputs, same bits, and loss_out holds the same bits with and without grad_image.
+ * Refused with GSX_ERR_INVALID_ARGUMENT (gsx_last_error names the argument), before any HIP call: NULL image, target,
+ * loss_out or workspace; rows or cols <= 0; a stride < 3 cols; lambda_dssim outside [0, 1] or not finite; a region of more
+ * than 2^31 - 1 tiles of 32 x 32; a workspace that is not 256-byte aligned.  workspace:
+ * gsx_photometric_loss_workspace_bytes(rows, cols, grad_image != NULL); fewer bytes: GSX_ERR_WORKSPACE_TOO_SMALL.
+ * Does not synchronise, does not allocate, reads no hints: stream-ordered, may be captured into a hipGraph.
+ */
+GSX_API int gsx_photometric_loss(const float *image, int64_t image_row_stride, const float *target, int64_t target_row_stride,
+                                 int32_t rows, int32_t cols, float lambda_dssim, float *loss_out /* 3 floats */,
+                                 float *grad_image /* may be NULL */, int64_t grad_row_stride,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_photometric_loss needs: one partial-sum pair per tile and, with_grad != 0, the three
+ * gradient maps (0 on invalid arguments). */
+GSX_API size_t gsx_photometric_loss_workspace_bytes(int32_t rows, int32_t cols, int32_t with_grad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ Gaussians, hand-written HIP kernels (libgsx.so, C ABI in include/gsx.h) do the w
 from .gaussians import Gaussians
 from .gaussian_scene import GaussianScene, NativeExtension, render_preprocessed
 from .image import GaussianImage
+from .loss import photometric_loss
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension"]
+           "NativeExtension", "photometric_loss"]

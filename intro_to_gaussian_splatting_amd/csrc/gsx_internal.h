@@ -281,6 +281,18 @@ hipError_t launch_sh_to_rgb(const float *means3d, const float *sh, int degree, i
 hipError_t launch_sh_backward(const float *means3d, const float *sh, int degree, int64_t n, const float *center,
                               const float *grad_colors, float *grad_sh, float *grad_means3d, hipStream_t s);
 
+// ---- gsx_loss.hip
+// gsx_photometric_loss behind its argument checks: loss_out = (loss, l1, ssim) over the rows x cols region and, when
+// grad_image is not NULL, dloss/dimage into it.  `ws` is carved by `c` (plan::loss_carve with with_grad = grad_image != NULL).
+struct LossImages {
+    const float *image, *target;
+    float *grad;                       // or NULL
+    int64_t image_stride, target_stride, grad_stride;   // floats per row
+    int32_t rows, cols;
+};
+hipError_t launch_photometric_loss(const LossImages &im, float lambda, float *loss_out, char *ws, const plan::LossCarve &c,
+                                   hipStream_t s);
+
 // ---- gsx_blend.hip
 // background: 3 floats, read on the host (GSX_SEM_STD_3DGS only); generic: GSX_FLAG_GENERIC_KERNELS.
 // cp: what the launch zeroes besides compositing its tiles (extra workgroups of the same kernel).

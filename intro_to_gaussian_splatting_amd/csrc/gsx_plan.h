@@ -252,6 +252,39 @@ inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes,
     return c;
 }
 
+// ---- gsx_photometric_loss (gsx_loss.hip): the region is cut into kLossTile x kLossTile tiles, one workgroup each.
+//   partials  one (sum m, sum |x - y|) float pair per tile, summed by one workgroup in a fixed order
+//   maps[3]   with_grad only: w Dmu, w Dp, w Dq, each rows x cols x 3 interleaved like the images, a row every map_stride
+//             floats (3 cols rounded up to 4, so that every row starts 16-byte aligned whatever the caller's strides are)
+constexpr int kLossTile = 32;
+constexpr int kLossHalo = 5;           // the 11-tap window reaches this far
+struct LossCarve {
+    int64_t tiles_r, tiles_c, tiles, map_stride;
+    size_t partials, maps[3], total;   // byte offsets
+};
+// false: sizes no call accepts (not positive, more than 2^31 - 1 tiles).  With at most 2^31 - 1 tiles the region has fewer
+// than 2^41 pixels and a map fewer than 2^45 bytes: nothing below overflows 64 bits.
+inline bool loss_carve(int32_t rows, int32_t cols, bool with_grad, LossCarve &c) {
+    c = LossCarve{};
+    if (rows <= 0 || cols <= 0) return false;
+    c.tiles_r = ((int64_t)rows + kLossTile - 1) / kLossTile;
+    c.tiles_c = ((int64_t)cols + kLossTile - 1) / kLossTile;
+    c.tiles = c.tiles_r * c.tiles_c;       // < 2^52
+    if (c.tiles > kMaxPairs) return false;
+    c.map_stride = ((int64_t)cols * 3 + 3) & ~(int64_t)3;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t at = off;
+        off = align_up(off + bytes);
+        return at;
+    };
+    c.partials = take((size_t)c.tiles * 2 * sizeof(float));
+    if (with_grad)
+        for (int k = 0; k < 3; ++k) c.maps[k] = take((size_t)rows * (size_t)c.map_stride * sizeof(float));
+    c.total = off;
+    return true;
+}
+
 inline int64_t max_tiles_of(int32_t width, int32_t height, int32_t tile) {
     return (int64_t)((width + tile - 1) / tile) * ((height + tile - 1) / tile);
 }

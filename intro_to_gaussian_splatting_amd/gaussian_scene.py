@@ -880,6 +880,31 @@ class GaussianScene:
 
     render = render_image  # the name BASELINE.json's north star uses
 
+    def rendered_region(self, image_idx: int, tile_size: int = 16, layout: str = "wh3") -> Tuple[int, int]:
+        """Extent (a, b) of what a ``ref_cpu`` frame of this camera renders, in the order of the frame's two leading axes:
+        whole tiles from the origin, the last tile row and column left out (``strips.tiles_along``).  Everything outside is
+        the zeros the frame was cleared to -- not a rendering of black."""
+        from .strips import tiles_along
+
+        if layout not in ("wh3", "hw3"):
+            raise ValueError("layout must be 'wh3' or 'hw3', got %r" % (layout,))
+        cam = self.images[image_idx].gsx_camera()
+        w = tiles_along(int(cam.width), int(tile_size)) * int(tile_size)
+        h = tiles_along(int(cam.height), int(tile_size)) * int(tile_size)
+        return (w, h) if layout == "wh3" else (h, w)
+
+    def photometric_loss(self, image_idx: int, frame: torch.Tensor, target: torch.Tensor, tile_size: int = 16,
+                         lambda_dssim: float = 0.2, layout: str = "wh3", terms: Optional[dict] = None) -> torch.Tensor:
+        """``loss.photometric_loss`` of a ``ref_cpu`` frame of this camera against ``target`` over ``rendered_region``: the
+        rim no tile covers takes no part and receives an exact zero gradient."""
+        from .loss import photometric_loss
+
+        region = self.rendered_region(image_idx, tile_size, layout)
+        if region[0] <= 0 or region[1] <= 0:
+            raise ValueError("a %s frame of camera %r has no rendered tile at tile_size %d (extent <= tile)" % (
+                layout, image_idx, tile_size))
+        return photometric_loss(frame, target, lambda_dssim=lambda_dssim, region=region, terms=terms)
+
     def render_images(self, image_indices, tile_size: int = 16):
         """``render_image`` for a sequence of cameras -- the reference's own loop renders one image index after another
         (splat/gaussian_scene.py:200-203) --, as a generator of (W,H,3) HOST tensors with the device-to-host copy of

@@ -1,0 +1,102 @@
+"""The photometric loss of a splat fit on the GPU: ``photometric_loss`` (gsx_photometric_loss, include/gsx.h).
+
+``L = (1 - lambda) mean|frame - target| + lambda (1 - mean SSIM(frame, target))`` with the 11 x 11 Gaussian window of
+sigma 1.5, over a region at the origin of the two images -- under ``ref_cpu`` rules the last tile row and column of a frame
+are never rendered, and a loss over the whole frame would pull every Gaussian near the border toward black
+(``GaussianScene.rendered_region`` / ``GaussianScene.photometric_loss``).  Value and dL/dframe come out of ONE library call;
+there is no torch composition behind it and no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _ffi
+from .gaussian_scene import _WORKSPACE, _ptr, _stream_handle
+
+
+def _check_image(name: str, t: torch.Tensor, device: Optional[torch.device] = None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("%s must have shape (A, B, 3), got %s" % (name, tuple(t.shape)))
+    if device is not None and t.device != device:
+        raise ValueError("%s is on %s, expected %s" % (name, t.device, device))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return t
+
+
+def _call(frame: torch.Tensor, target: torch.Tensor, lam: float, region: Tuple[int, int], with_grad: bool):
+    """(loss_out (3,) = loss, l1, ssim; dL/dframe of the frame's shape with zeros outside the region, or None)."""
+    lib = _ffi.load()
+    dev = frame.device
+    a, b = region
+    stride = int(frame.shape[1]) * 3
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    grad = None
+    if with_grad:
+        whole = (a, b) == (int(frame.shape[0]), int(frame.shape[1]))
+        grad = (torch.empty if whole else torch.zeros)(frame.shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = lib.gsx_photometric_loss_workspace_bytes(a, b, 1 if with_grad else 0)
+        if nbytes == 0:
+            raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_photometric_loss_workspace_bytes rejected the region %s" % (region,))
+        ws = _WORKSPACE.get(dev, nbytes)
+        rc = lib.gsx_photometric_loss(_ptr(frame), stride, _ptr(target), stride, a, b, lam, _ptr(out), _ptr(grad), stride,
+                                      _ptr(ws), nbytes, _stream_handle(dev))
+    _ffi.check(rc)
+    return out, grad
+
+
+class _PhotometricLossFunction(torch.autograd.Function):
+    """Forward: value and dL/dframe in the one library call, the gradient saved; backward: grad_output times it."""
+
+    @staticmethod
+    def forward(ctx, frame, target, lam, region):
+        out, grad = _call(frame.detach(), target, lam, region, True)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        (grad,) = ctx.saved_tensors
+        return grad_loss * grad, None, None, None
+
+
+def photometric_loss(frame: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2,
+                     region: Optional[Tuple[int, int]] = None, terms: Optional[dict] = None) -> torch.Tensor:
+    """The loss above as a 0-d float32 tensor on the GPU.  ``frame`` and ``target``: contiguous float32 (A, B, 3) tensors on
+    the same GPU; ``region=(a, b)`` crops the two leading axes (None: the whole tensor); ``terms``: a dict that receives
+    ``l1`` and ``ssim`` as 0-d tensors.  Nothing waits for the device.  When ``frame`` requires grad (and grad mode is on)
+    the result carries dL/dframe -- computed in the same call, zero outside the region; ``target`` never gets one."""
+    _check_image("frame", frame)
+    if frame.device.type != "cuda":
+        raise ValueError("frame is on %s: the loss runs only as HIP kernels on an AMD GPU (torch device 'cuda'); "
+                         "there is no CPU fallback" % frame.device)
+    _check_image("target", target, frame.device)
+    if tuple(target.shape) != tuple(frame.shape):
+        raise ValueError("target has shape %s, the frame %s" % (tuple(target.shape), tuple(frame.shape)))
+    if target.requires_grad:
+        raise ValueError("target requires grad: photometric_loss differentiates the frame alone (pass target.detach())")
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lambda_dssim = %r is outside [0, 1]" % (lambda_dssim,))
+    if region is None:
+        region = (int(frame.shape[0]), int(frame.shape[1]))
+    else:
+        region = (int(region[0]), int(region[1]))
+        if not (1 <= region[0] <= frame.shape[0] and 1 <= region[1] <= frame.shape[1]):
+            raise ValueError("region %s does not fit the leading axes %s" % (region, tuple(frame.shape[:2])))
+    if frame.requires_grad and torch.is_grad_enabled():
+        loss, out = _PhotometricLossFunction.apply(frame, target, lam, region)
+    else:
+        out, _ = _call(frame.detach(), target, lam, region, False)
+        loss = out[0]
+    if terms is not None:
+        terms["l1"], terms["ssim"] = out[1], out[2]
+    return loss
