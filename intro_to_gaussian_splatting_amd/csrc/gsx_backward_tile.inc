@@ -90,7 +90,9 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                         d2 = __builtin_fmaf(ta, G2[j], d2);
                         du = __builtin_fmaf(da, alpha, du);
                         if constexpr (GEO) {
-                            const float u = da * alpha, e0 = A.x - fx[j], e1 = A.y - fy[j];
+                            // (alpha_ref_tail: where v_exp_f32 flushed alpha to zero the moments still get their terms)
+                            const float ag = alpha_ref_tail(A.x, A.y, A.z, A.w, B.x, B.y, B.z, fx[j], fy[j], alpha);
+                            const float u = da * ag, e0 = A.x - fx[j], e1 = A.y - fy[j];
                             const float u0 = u * e0, u1 = u * e1;
                             m1 += u0;
                             m2 += u1;

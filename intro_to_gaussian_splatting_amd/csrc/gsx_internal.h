@@ -83,6 +83,22 @@ __device__ __forceinline__ float alpha_ref(float x, float y, float q00, float q0
     return __builtin_amdgcn_exp2f(power * 1.44269504088896340736f) * op;
 }
 
+// alpha_ref for the geometry moments.  v_exp_f32 returns zero where its result would be below 2^-126, so alpha_ref is
+// exactly 0 for a pixel in the far tail of a footprint, where the reference's expf still returns 1e-38 .. 1e-45.  The
+// frame and the colour sums cannot see the difference (T - T alpha == T, and T alpha c is below every sum's last bit
+// unless the sum is itself that small); the moments of a Gaussian that is graded on such pixels ONLY consist of nothing
+// else.  Below 2^-100 the exponential is taken 2^64 higher and scaled back after the opacity factor, one rounding into
+// the subnormal range; elsewhere this is `alpha`, alpha_ref's own value.
+__device__ __forceinline__ float alpha_ref_tail(float x, float y, float q00, float q01, float q10, float q11, float op,
+                                                float px, float py, float alpha) {
+    const float e0 = x - px, e1 = y - py;
+    const float d0 = -0.5f * e0, d1 = -0.5f * e1;
+    const float t0 = __builtin_fmaf(d1, q10, d0 * q00);
+    const float t1 = __builtin_fmaf(d1, q11, d0 * q01);
+    const float p2 = (t0 * e0 + t1 * e1) * 1.44269504088896340736f;
+    return p2 < -100.0f ? (__builtin_amdgcn_exp2f(p2 + 64.0f) * op) * 0x1p-64f : alpha;
+}
+
 // Tiles whose list is much longer than the frame's average are composited by FOUR waves (a quarter of the
 // tile's pixels each, one pixel per lane, eight records per trip) instead of one: a lone wave walks its list
 // at ~430 cycles per record, so one 20 000-entry tile would outlast the rest of the frame several times over.

@@ -10,7 +10,10 @@ reference's own render_image.
 Before anything is written the tool ASSERTS that the rebinding changed nothing else: the image, grad_colors and
 grad_opacity must equal the committed tests/golden/grad_<scene>.npz bit for bit.  The scenes of STANDALONE have no
 grad_ fixture; their image is asserted against the committed forward fixture tests/golden/<scene>.npz instead, and
-their file also holds the scene arguments, W, the image, grad_colors and grad_opacity.
+their file also holds the scene arguments, W, the image, grad_colors and grad_opacity.  The scenes of OWN_STAGE1 (one to
+three visible Gaussians, each on a rendered tile) have no forward fixture either: the reference renders them a second
+time with its ORIGINAL compute_gaussian_weight under no_grad, the two images must be equal bit for bit, and their file
+also holds the reference's camera constants and PreprocessedScene arrays under the keys of oracle/capture_golden.py.
 
     python tools/capture_geometry_grad_golden.py            # all scenes
     python tools/capture_geometry_grad_golden.py tile2      # only those whose name contains "tile2"
@@ -41,6 +44,16 @@ SCENES = ["tile2_40x32_n80", "small_64x48_n300", "small_80x64_n120_tile8", "tile
 # 110 Gaussians: over 21 GB); name it on the command line on a machine with the memory and an hour to spare.
 EXTRA = ["trainedlike_128x128_n3000"]
 STANDALONE = ("wide_64x64_n400", "cull_96x80_n400")     # no grad_ fixture: the file carries its own inputs
+# No forward fixture and no grad_ fixture: name -> generator arguments (the table of oracle/capture_golden.py's FIXTURES).
+# The row classes of one to three visible Gaussians (GSX_FLAG_ONE_VISIBLE / GSX_FLAG_SMALL_BATCH), every visible Gaussian
+# on a rendered tile; the forward fixtures single_48x48_n1 and onevisible_48x48_n7 have theirs on no rendered pixel.
+OWN_STAGE1 = {
+    "rows1_48x48_n1": dict(n=1, width=48, height=48, seed=40, tile=16),
+    "rows3_48x48_n3": dict(n=3, width=48, height=48, seed=40, tile=16),
+    "rows1_48x48_n500": dict(n=500, width=48, height=48, seed=41, tile=16, generator="few", visible=1),
+    "rows3_48x48_n500": dict(n=500, width=48, height=48, seed=43, tile=16, generator="few", visible=3),
+}
+SCENES += list(OWN_STAGE1)
 BRANCHES = ("n_floored_det", "n_clamped", "n_culled")
 
 
@@ -69,12 +82,38 @@ def branch_counts(scene, g) -> dict:
                     n_culled=np.int64((~in_view).sum().item()))
 
 
-def capture(name: str, GaussianScene, Gaussians) -> None:
+def own_stage1(scene, g) -> dict:
+    """The reference's camera constants and PreprocessedScene arrays (no gradient), keyed as oracle/capture_golden.py
+    keys them: what conftest.oracle_camera and conftest.golden_preprocessed read."""
+    import torch
+    from splat.utils import in_view_frustum
+
+    with torch.no_grad():
+        cam = scene.images[1]
+        in_view = in_view_frustum(points=g.points, view_matrix=cam.world2view)
+        pre = scene.preprocess(1)
+        hom = torch.cat([g.points[in_view], torch.ones(int(in_view.sum()), 1)], dim=1)
+        depth_unsorted = (hom @ cam.world2view)[:, 2]
+        perm = torch.argsort(depth_unsorted)
+        assert torch.equal(depth_unsorted[perm], pre.depths), "argsort is not reproducible"
+    num = lambda t: t.detach().numpy()  # noqa: E731
+    return dict(
+        world2view=num(cam.world2view), full_proj_transform=num(cam.full_proj_transform), tan_fovX=num(cam.tan_fovX),
+        tan_fovY=num(cam.tan_fovY), f_x=num(cam.f_x), f_y=num(cam.f_y), in_view=num(in_view),
+        order=np.nonzero(num(in_view))[0][num(perm)].astype(np.int64),
+        pre_points=num(pre.points), pre_colors=num(pre.colors), pre_covariance_2d=num(pre.covariance_2d),
+        pre_depths=num(pre.depths), pre_inverse_covariance_2d=num(pre.inverse_covariance_2d), pre_radius=num(pre.radius),
+        pre_points_xy=num(pre.points_xy), pre_min_x=num(pre.min_x), pre_min_y=num(pre.min_y), pre_max_x=num(pre.max_x),
+        pre_max_y=num(pre.max_y), pre_sigmoid_opacity=num(pre.sigmoid_opacity))
+
+
+def capture(name: str, GaussianScene, Gaussians, original_weight=None) -> None:
     import torch
 
     from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
 
-    spec = dict(FIXTURES[name])
+    own = name in OWN_STAGE1
+    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
     tile = spec.pop("tile")
     assert not spec.pop("defaults", False)
     sc = _generate(spec)
@@ -89,6 +128,17 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
         g.points, g.scales, g.quaternions, g.colors, g.opacity = points, scales, quats, colors, opacity
         scene = GaussianScene(os.path.join(tmp, "colmap"), g)
         counts = branch_counts(scene, g)
+        stage1 = {}
+        if own:     # the reference as it is, once: its `.item()` weight, no graph
+            import splat.gaussian_scene as ref_scene
+
+            stage1 = own_stage1(scene, g)
+            ref_scene.compute_gaussian_weight = original_weight
+            try:
+                with torch.no_grad():
+                    untouched = scene.render_image(1, tile_size=tile).numpy().copy()
+            finally:
+                ref_scene.compute_gaussian_weight = _weight
         t0 = time.time()
         image = scene.render_image(1, tile_size=tile)
         t_fwd = time.time() - t0
@@ -103,9 +153,15 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
     image = image.detach().numpy()
     out = dict(grad_points=gp, grad_scales=gs, grad_quaternions=gq, reference_forward_seconds=np.float64(t_fwd),
                reference_backward_seconds=np.float64(t_bwd), **counts)
-    if name in STANDALONE:
-        fwd = np.load(os.path.join(OUT_DIR, name + ".npz"))
-        assert np.array_equal(image, fwd["image"]), name + ": the rebinding changed the reference's image"
+    if name in STANDALONE or own:
+        if own:
+            assert loss.grad_fn is not None and untouched.any(), name + ": no visible Gaussian on a rendered pixel"
+            assert np.array_equal(image.view(np.uint32), untouched.view(np.uint32)), \
+                name + ": the rebinding changed the reference's image"
+            out.update(stage1)
+        else:
+            fwd = np.load(os.path.join(OUT_DIR, name + ".npz"))
+            assert np.array_equal(image, fwd["image"]), name + ": the rebinding changed the reference's image"
         out.update(sc)
         out.update(opacity=np.asarray(sc["opacity"], np.float32), colors=colors.detach().numpy(), tile=np.int64(tile),
                    W=W.numpy(), image=image, grad_colors=gc, grad_opacity=go)
@@ -147,10 +203,11 @@ def main() -> None:
         GaussianScene, Gaussians = _import_reference()
         import splat.gaussian_scene as ref_scene
 
+        original_weight = ref_scene.compute_gaussian_weight
         ref_scene.compute_gaussian_weight = _weight
         for name in SCENES + [e for e in EXTRA if only and only in e]:
             if only in name:
-                capture(name, GaussianScene, Gaussians)
+                capture(name, GaussianScene, Gaussians, original_weight)
     if only in ("", "--check"):
         check_branches()
 
