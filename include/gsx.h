@@ -504,6 +504,55 @@ GSX_API int gsx_photometric_loss(const float *image, int64_t image_row_stride, c
  * gradient maps (0 on invalid arguments). */
 GSX_API size_t gsx_photometric_loss_workspace_bytes(int32_t rows, int32_t cols, int32_t with_grad);
 
+/*
+ * Build extension (the reference has no training loop): one Adam step (Kingma & Ba 2015) over up to GSX_ADAM_MAX_GROUPS
+ * parameter arrays of the same n rows -- the arrays of a Gaussian container -- in ONE kernel launch, in place.  What it
+ * steps along are the gradients the calls above wrote.  Those are exact zeros for every Gaussian that is culled or on no
+ * tile list (gsx_render_backward*: "0 for a Gaussian on no tile list"; gsx_sh_backward multiplies by them), which is what
+ * makes GSX_ADAM_SKIP_ZERO_ROWS a visibility test -- as long as the caller adds nothing to them: for an SH scene the
+ * Python surface adds gsx_sh_backward's view-direction term to dL/dmeans3d before it sets .grad, and that term is itself
+ * zero where dL/dcolour is.
+ *
+ * Each group g is four DEVICE arrays of (n, width) float32 with contiguous rows: param, grad (read only), exp_avg and
+ * exp_avg_sq (the moments, zero before step 1).  Host scalars, computed once per call in double and rounded to float:
+ *   c1 = 1 - beta1,  c2 = 1 - beta2,  a_g = lr_g / (1 - beta1^step),  s2 = sqrt(1 - beta2^step)
+ * Per element, every float32 operation rounded on its own (no fused multiply-add; divide and sqrt correctly rounded):
+ *   g' = g (GSX_ADAM_LINEAR)  or  g p (GSX_ADAM_LOG: the gradient with respect to theta = log p)
+ *   m' = beta1 m + c1 g';   v' = beta2 v + (c2 g') g';   d = sqrt(v') / s2 + eps;   u = a_g (m' / d)
+ *   p' = p - u (GSX_ADAM_LINEAR)  or  p expf(-u) (GSX_ADAM_LOG)
+ * A LOG group is Adam on theta with p = exp(theta), the parametrisation the published method gives the scales, without
+ * storing theta: its moments are those of dL/dtheta, a positive parameter stays positive for any finite step, and, as no
+ * logarithm is ever taken, a non-positive one keeps its sign (it must be positive to mean anything).
+ *
+ * GSX_ADAM_SKIP_ZERO_ROWS (the published trainer's sparse Adam): row r is skipped iff every gradient element of row r in
+ * every group of the call is +0 or -0 (a NaN is not zero).  A skipped row's param, exp_avg and exp_avg_sq are neither read
+ * nor written in any group; a row that is not skipped is updated in all groups, also where its gradient is zero.  The
+ * bias corrections use the caller's global `step` for every row.
+ *
+ * No workspace, no allocation, no synchronisation, no hints, no atomics: same inputs, same bits.  16-byte accesses are used
+ * in a group whose four base pointers are 16-byte aligned; any float-aligned base is accepted.  `step` (>= 1, the number
+ * of this step) enters through host scalars: a hipGraph that captured the call has it baked in.  n == 0 is GSX_OK.
+ * Refused with GSX_ERR_INVALID_ARGUMENT (gsx_last_error names the argument) before any HIP call: groups NULL; n_groups
+ * outside 1 .. GSX_ADAM_MAX_GROUPS; n < 0; step < 1; beta1 or beta2 outside [0, 1) or not finite; eps negative or not finite;
+ * unknown flags; in a group: width outside 1 .. 2^20, an unknown transform, reserved != 0, lr negative or not finite, and,
+ * when n > 0, a NULL pointer.
+ */
+#define GSX_ADAM_MAX_GROUPS 8
+enum { GSX_ADAM_LINEAR = 0, GSX_ADAM_LOG = 1 };
+#define GSX_ADAM_SKIP_ZERO_ROWS 1u
+typedef struct GsxAdamGroup {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq; /* each (n, width) float32, rows contiguous */
+    int32_t width;
+    int32_t transform; /* GSX_ADAM_LINEAR / GSX_ADAM_LOG */
+    float lr;
+    float reserved;    /* must be 0 */
+} GsxAdamGroup;
+GSX_API int gsx_adam_step(const GsxAdamGroup *groups /* host */, int32_t n_groups, int64_t n, int64_t step /* >= 1 */,
+                          float beta1, float beta2, float eps, uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ from .gaussians import Gaussians
 from .gaussian_scene import GaussianScene, NativeExtension, render_preprocessed
 from .image import GaussianImage
 from .loss import photometric_loss
+from .optim import GaussianAdam, expon_lr
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension", "photometric_loss"]
+           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr"]

@@ -39,6 +39,10 @@ GSX_FLAG_SMALL_BATCH = 256
 GSX_FLAG_ONE_VISIBLE = 512
 GSX_FLAG_PLAIN_FOOTPRINTS = 1024
 GSX_BOUNDS_ROWS = 256
+GSX_ADAM_MAX_GROUPS = 8
+GSX_ADAM_LINEAR = 0
+GSX_ADAM_LOG = 1
+GSX_ADAM_SKIP_ZERO_ROWS = 1
 
 
 def visible_rows_flag(n: int, n_visible: int, flags: int) -> int:
@@ -90,6 +94,11 @@ class GsxFrameStats(ctypes.Structure):
                 ("stage_ms", c_float * 6), ("n_kept", c_int64), ("n_redo", c_int64)]
 
 
+class GsxAdamGroup(ctypes.Structure):
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("width", c_int32), ("transform", c_int32), ("lr", c_float), ("reserved", c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/gsx.h declares.
 _FP = c_void_p  # device float*
 SIGNATURES = {
@@ -119,6 +128,8 @@ SIGNATURES = {
     "gsx_photometric_loss": (ctypes.c_int, [_FP, c_int64, _FP, c_int64, c_int32, c_int32, c_float, _FP, _FP, c_int64,
                                             c_void_p, c_size_t, c_void_p]),
     "gsx_photometric_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "gsx_adam_step": (ctypes.c_int, [POINTER(GsxAdamGroup), c_int32, c_int64, c_int64, c_float, c_float, c_float,
+                                     ctypes.c_uint32, c_void_p]),
 }
 
 # csrc/gsx_debug.h

@@ -1,6 +1,8 @@
 // C ABI of libgsx.so (see include/gsx.h): argument validation, workspace carving and the
 // stream-ordered launch sequence.  No device memory is allocated here and nothing is retained
 // between calls; errors are returned as codes with a thread-local message.
+#include <float.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -711,6 +713,53 @@ int gsx_photometric_loss(const float *image, int64_t image_row_stride, const flo
                     workspace_bytes, rows, cols, grad_image ? 1 : 0, c.total);
     const gsx::LossImages im{image, target, grad_image, image_row_stride, target_row_stride, grad_row_stride, rows, cols};
     GSX_HIP(gsx::launch_photometric_loss(im, lambda_dssim, loss_out, (char *)workspace, c, (hipStream_t)stream));
+    return GSX_OK;
+}
+
+int gsx_adam_step(const GsxAdamGroup *groups, int32_t n_groups, int64_t n, int64_t step, float beta1, float beta2, float eps,
+                  uint32_t flags, void *stream) {
+    if (!groups) return fail(GSX_ERR_INVALID_ARGUMENT, "groups is NULL");
+    if (n_groups < 1 || n_groups > GSX_ADAM_MAX_GROUPS)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n_groups = %d is outside 1 .. %d", n_groups, GSX_ADAM_MAX_GROUPS);
+    if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is negative", (long long)n);
+    if (n > (int64_t)0x7fffffff * kAdamRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is more than 2^31 - 1 blocks of %d rows", (long long)n, kAdamRows);
+    if (step < 1) return fail(GSX_ERR_INVALID_ARGUMENT, "step = %lld is below 1", (long long)step);
+    if (!(beta1 >= 0.0f && beta1 < 1.0f)) return fail(GSX_ERR_INVALID_ARGUMENT, "beta1 %g is outside [0, 1)", (double)beta1);   // (a NaN fails both)
+    if (!(beta2 >= 0.0f && beta2 < 1.0f)) return fail(GSX_ERR_INVALID_ARGUMENT, "beta2 %g is outside [0, 1)", (double)beta2);
+    if (!(eps >= 0.0f && eps <= FLT_MAX)) return fail(GSX_ERR_INVALID_ARGUMENT, "eps %g is negative or not finite", (double)eps);
+    if (flags & ~GSX_ADAM_SKIP_ZERO_ROWS) return fail(GSX_ERR_INVALID_ARGUMENT, "flags 0x%x has unknown bits", flags);
+    AdamArgs a;
+    memset(&a, 0, sizeof a);
+    for (int i = 0; i < n_groups; ++i) {
+        const GsxAdamGroup &g = groups[i];
+        if (g.width <= 0 || g.width > kAdamMaxWidth)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].width = %d is outside 1 .. %d", i, g.width, kAdamMaxWidth);
+        if (g.transform != GSX_ADAM_LINEAR && g.transform != GSX_ADAM_LOG)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].transform = %d is unknown", i, g.transform);
+        if (g.reserved != 0.0f) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].reserved is not 0", i);
+        if (!(g.lr >= 0.0f && g.lr <= FLT_MAX)) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].lr %g is negative or not finite", i, (double)g.lr);
+        if (n > 0) {
+            if (!g.param) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].param is NULL", i);
+            if (!g.grad) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].grad is NULL", i);
+            if (!g.exp_avg) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].exp_avg is NULL", i);
+            if (!g.exp_avg_sq) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].exp_avg_sq is NULL", i);
+        }
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(g.param) | reinterpret_cast<uintptr_t>(g.grad) |
+                               reinterpret_cast<uintptr_t>(g.exp_avg) | reinterpret_cast<uintptr_t>(g.exp_avg_sq);
+        // the host scalars: once per call, in double, rounded to float (include/gsx.h)
+        a.group[i] = AdamGroupArgs{g.param, g.grad, g.exp_avg, g.exp_avg_sq, g.width, g.transform == GSX_ADAM_LOG,
+                                   (float)((double)g.lr / (1.0 - pow((double)beta1, (double)step))), (bits & 15u) == 0};
+    }
+    if (n == 0) return GSX_OK;
+    a.n = n;
+    a.n_groups = n_groups;
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.c1 = (float)(1.0 - (double)beta1);
+    a.c2 = (float)(1.0 - (double)beta2);
+    a.s2 = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    a.eps = eps;
+    GSX_HIP(gsx::launch_adam(a, (flags & GSX_ADAM_SKIP_ZERO_ROWS) != 0, (hipStream_t)stream));
     return GSX_OK;
 }
 

@@ -309,6 +309,27 @@ struct LossImages {
 hipError_t launch_photometric_loss(const LossImages &im, float lambda, float *loss_out, char *ws, const plan::LossCarve &c,
                                    hipStream_t s);
 
+// ---- gsx_adam.hip
+// gsx_adam_step behind its argument checks.  One workgroup per kAdamRows rows; the whole struct is the kernel's argument.
+constexpr int kAdamRows = 256;
+constexpr int kAdamMaxWidth = 1 << 20;      // a block's run of a group, kAdamRows * width floats, is indexed with 32 bits
+struct AdamGroupArgs {
+    float *param;
+    const float *grad;
+    float *exp_avg, *exp_avg_sq;
+    int32_t width;
+    int32_t log_space;      // GSX_ADAM_LOG
+    float a;                // lr / (1 - beta1^step)
+    int32_t vec;            // all four bases are 16-byte aligned
+};
+struct AdamArgs {
+    AdamGroupArgs group[8];
+    int64_t n;
+    int32_t n_groups;
+    float beta1, beta2, c1, c2, s2, eps;    // c1 = 1 - beta1, c2 = 1 - beta2, s2 = sqrt(1 - beta2^step)
+};
+hipError_t launch_adam(const AdamArgs &args, bool skip_zero_rows, hipStream_t s);
+
 // ---- gsx_blend.hip
 // background: 3 floats, read on the host (GSX_SEM_STD_3DGS only); generic: GSX_FLAG_GENERIC_KERNELS.
 // cp: what the launch zeroes besides compositing its tiles (extra workgroups of the same kernel).
