@@ -24,6 +24,10 @@
 //     tile is saturated" is one __ballot over the wave;
 //   - each lane gathers one 48-B record per batch of 64 (3 x dwordx4) into LDS; the k-loop then
 //     reads record k with uniform-address (broadcast) ds_reads;
+//   - the instance a frame runs (blend_tile16<true>) stages TWO such sub-batches per synchronisation wherever both are
+//     regular and no pixel of the tile has saturated yet: six gathers in flight per lane, one trip to memory, one pair
+//     of syncs and one ballot per 128 list entries, and a walk as long as the longest 128-entry block list (StagedT,
+//     blend_tile16; same pixels bit for bit, same cost word: docs/lab_notes/blend_pairs.md);
 //   - the saturation test of the reference (stop when T(1-alpha) < 1e-6, before accumulating)
 //     is kept exact but off the common path: one v_min3 + v_min + v_cmp per record decides, for
 //     the whole wave, whether any of its 256 pixels stops at this record; only then are the
@@ -78,7 +82,7 @@ constexpr uint32_t kBatchCost = 5;        // staging a batch of 64 costs about a
 // (a branch between the records of a trip keeps the compiler from interleaving their dependent chains, and a wave
 // that has its SIMD to itself -- the long, saturated tiles of a heavy-tailed frame -- then pays every chain in full).
 // A null record changes nothing under either form of the rule: T alpha = 0, T - 0 = T, fma(0, 0, C) = C.
-constexpr int kPad = 8, kSlots = 64 + kPad;
+constexpr int kPad = 8;
 // Round 4: a 16x16 tile is composited as FOUR 8x8 BLOCKS, each with its own list.  The reference lists a Gaussian for a
 // tile when its bounding box touches the tile (plus a tile of slack), and under its rules every listed Gaussian is
 // evaluated at every pixel -- but a record whose alpha stays below 2^-26 on a whole 8x8 block changes nothing there
@@ -89,11 +93,22 @@ constexpr int kPad = 8, kSlots = 64 + kPad;
 // benchmark scene) instead of all of it, at ~10 % more per trip (tools/microbench_trip.hip, V5).
 // Block g covers x offsets [8 (g & 1), +8) and y offsets [8 (g >> 1), +8) of the tile.
 constexpr int kBlocks = 4;
-struct __attribute__((aligned(16))) Staged {
+// BATCH = 64: what every kernel but the REF tile-16 instance stages.  BATCH = 128 (blend_tile16<true>): TWO consecutive
+// 64-record sub-batches per synchronisation, staged one after the other into slots [0, nb1) and [nb1, nb1 + nb2); a block's
+// list is the entries it keeps of the first followed by those of the second (see blend_tile16).  There the one null record
+// the lists are padded with sits in the fixed slot kNull = BATCH, behind every record, and is written once per tile.
+template <int BATCH>
+struct __attribute__((aligned(16))) StagedT {
+    static constexpr int kBatch = BATCH, kSlots = BATCH + kPad, kNull = BATCH;
+    static constexpr bool kWide = BATCH > 64;
     float4 rec[3][kSlots];            // the staged records, by slot (see read_splat)
     uint16_t list[kBlocks][kSlots];   // per block: the records it keeps, in list order, as BYTE OFFSETS of their slots in rec[0]
                                       // (16 x slot: one shift less per record and lane), padded with a null record's
 };
+using Staged = StagedT<64>;
+using StagedWide = StagedT<128>;
+static_assert(sizeof(StagedWide) >= sizeof(Staged) && alignof(StagedWide) == alignof(Staged), "the REF kernel's helpers stage 64 records in the same LDS");
+static_assert((StagedWide::kSlots - 1) * 16 <= 0xFFFF, "list entries are 16-bit byte offsets");
 
 // Contiguous-chunk remap: hardware places block b on XCD b % 8; give XCD x the x-th eighth of
 // the tile list.  Bijective for every n_tiles.
@@ -327,12 +342,18 @@ __device__ __forceinline__ float skip_threshold(float bound, uint32_t &skipped, 
 // record is staged as (x, y, Q00, Q01) (Q10, op, r, g) (b, Q11, flag, bits) in FRAME coordinates; without it the record
 // keeps its completed-square form -- all the caller needs is the batch's kind: it leaves the tile undone and counts it.
 // Either way the skip bound is the completed square's, computed like any other record's.
-template <int MODE, bool WITH_REF = true>
-__device__ __forceinline__ int stage_records(float4 a, float4 b, float4 c, bool have, uint32_t &nb, Staged &sh, int lane,
+// SH::kWide (StagedT<128>, kStageBlocks only): this is one 64-record SUB-BATCH of a batch of two.  Every decision is made
+// exactly as for a batch of 64 -- same running totals, same order --; what changes is where the results go: its records
+// into the slots from slot0 on (the records the first sub-batch staged lie in front), its list entries behind the
+// list0[g] entries block g already has, *ref_slots counted from slot0.  The caller has filled the lists with the null
+// record's slot (kNull) beforehand; nothing is padded here.
+template <int MODE, bool WITH_REF = true, class SH = Staged>
+__device__ __forceinline__ int stage_records(float4 a, float4 b, float4 c, bool have, uint32_t &nb, SH &sh, int lane,
                                              float tile_x0, float tile_y0, float tile_side, uint32_t (&skipped)[kBlocks],
                                              uint32_t budget, int blk, uint32_t (&count)[kBlocks], uint32_t dead = 0u,
                                              unsigned long long *ref_slots = nullptr, const float4 *__restrict__ qraw = nullptr,
-                                             uint32_t gi = 0u) {
+                                             uint32_t gi = 0u, uint32_t slot0 = 0u, const uint32_t *list0 = nullptr) {
+    static_assert(!SH::kWide || MODE == kStageBlocks, "two sub-batches per synchronisation: the four-lists form only");
     bool irregular = false, mono = false, refo = false;
     float bound[kBlocks] = {0.0f, 0.0f, 0.0f, 0.0f};   // < -26: a candidate, alpha < 2^bound on the whole block
     float x_abs = 0.0f, y_abs = 0.0f;
@@ -424,8 +445,9 @@ __device__ __forceinline__ int stage_records(float4 a, float4 b, float4 c, bool 
     if (WITH_REF && refo && keep) q4 = qraw[gi];
     const unsigned long long mask = __ballot(keep);
     nb = (uint32_t)__popcll(mask);
-    const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));   // kept lanes below this one
-    if (MODE == kStageBlocks) {
+    uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));   // kept lanes below this one
+    if (SH::kWide) slot += slot0;
+    if (MODE == kStageBlocks && !SH::kWide) {
         // every block's list starts out as nothing but the first null record's slot (the loops take whole trips) ...
         const uint16_t null_slot = (uint16_t)(nb * 16u);
 #pragma unroll
@@ -454,14 +476,14 @@ __device__ __forceinline__ int stage_records(float4 a, float4 b, float4 c, bool 
 #pragma unroll
             for (int g = 0; g < kBlocks; ++g)
                 if ((bits >> g) & 1u)
-                    sh.list[g][__builtin_amdgcn_mbcnt_hi((uint32_t)(kept_by[g] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kept_by[g], 0u))] = (uint16_t)(slot * 16u);
+                    sh.list[g][(SH::kWide ? list0[g] : 0u) + __builtin_amdgcn_mbcnt_hi((uint32_t)(kept_by[g] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kept_by[g], 0u))] = (uint16_t)(slot * 16u);
         }
     }
     if (MODE == kStageBlocks) {
 #pragma unroll
         for (int g = 0; g < kBlocks; ++g) count[g] = (uint32_t)__popcll(kept_by[g]);
     }
-    if (lane < kPad) {                  // the null records behind the batch (see kPad)
+    if (!SH::kWide && lane < kPad) {    // the null records behind the batch (see kPad)
         sh.rec[0][nb + lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         sh.rec[1][nb + lane] = make_float4(0.0f, -__builtin_inff(), 0.0f, 0.0f);
         sh.rec[2][nb + lane] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFu));
@@ -633,7 +655,7 @@ __device__ __forceinline__ void rank_samples(uint32_t group, int lane, const Ble
 }
 
 // ---- two instances of every tile-16 loop.  REF = true (blend_tile16_ref_kernel, what a frame runs): reference-order
-// records are evaluated where they turn up; 128 VGPRs, 4 waves per SIMD, nothing spilled.  REF = false
+// records are evaluated where they turn up; 95 VGPRs, 7 616 bytes of LDS, nothing spilled.  REF = false
 // (blend_tile16_kernel, GSX_FLAG_PLAIN_FOOTPRINTS: the caller knows from an earlier frame of the view that no tile holds
 // such a record): the completed square only, 64 VGPRs, 8 waves per SIMD -- 6 % faster on a 4K frame of 5M Gaussians, no
 // faster at 1080p --; a tile or long tile's quarter that does meet a flagged record stops there, writes nothing and adds
@@ -812,12 +834,34 @@ __device__ __forceinline__ void blend_long_tile_quarter(const Record *__restrict
 
 // One 16x16 tile on one wave, 4 pixels per lane (the body of blend_tile16_kernel; see there).  REF as in
 // blend_long_tile_quarter: false -- a batch that holds a reference-order record ends the tile, counted in *lt.redo.
-template <bool REF>
+//
+// SH = StagedWide (the REF instance): where nothing stands against it a batch is TWO consecutive 64-record sub-batches.
+// A lane issues the gathers of its record of both back to back -- one trip to memory where there were two --, stages the
+// first, then the second (stage_records: every keep / skip / demote decision per sub-batch, in list order, against the
+// same running totals as a batch of 64 would make it), and the wave walks the CONCATENATED block lists between one pair
+// of synchronisations: half the exposed gathers, syncs and ballots, and the walk is as long as the longest of the four
+// 128-entry lists, not the sum of the longest of each half.  Pixels: bit for bit those of batches of 64 -- every pixel
+// meets the same records with the same alphas in the same order; where the null padding sits changes nothing
+// (fma(0, 0, C) = C, T - 0 = T).
+//   - Only REGULAR sub-batches are paired, and only while no pixel of the tile has saturated.  If one of the 128 gathered
+//     records is a monomial, flagged or D1 < 0 one (looked at as gathered, before any of them is dropped), the first 64
+//     are staged and composited as the batch of 64 they are, the second 64 are gathered again with the next batch, and
+//     that one is a batch of 64 as well; a regular batch of 64 switches back.  A heavy-tailed frame, with such a record in
+//     nearly every batch and most of its tiles saturating, so runs as it did (paired all the same -- exact rule for 128
+//     entries if either half is wild, `dead` noticed every 128 -- it lost 2 .. 4 %); the uniform frame runs paired.
+//   - `dead` is therefore noticed late only in the pair in which the tile's FIRST pixel saturates: a block that dies in
+//     its first half still stages and walks what it keeps of the second.  All its pixels have T = 0 there, every record
+//     adds exactly 0 and T stays 0.
+//   - the cost word stays the sum over the SUB-batches of (longest of its four counts + kBatchCost): the schedule and the
+//     choice of long tiles do not move -- EXCEPT in that one pair: a block that has died still counts for the second half's
+//     term, and the second half is staged (and its term added) even if the whole tile died in the first, where a batch of
+//     64 would have left the loop: up to 64 + kBatchCost more in the word of a tile that saturates.
+template <bool REF, class SH>
 __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, const float4 *__restrict__ qraw,
                                              const uint32_t *__restrict__ vals,
                                              const uint2 *__restrict__ ranges, const TileGrid &g, const OutDesc &out,
                                              const LongTiles &lt, uint32_t budget, const BlendHints &hints, const TileSpan &span,
-                                             uint32_t t, Staged &sh) {
+                                             uint32_t t, SH &sh) {
     // (one wave per workgroup in both instances: the mask changes no value, but without it the REF instance compiles to other instructions)
     const int lane = REF ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
     const int tx = g.wx0 + (int)(t / (uint32_t)g.nwy()), ty = g.wy0 + (int)(t % (uint32_t)g.nwy());
@@ -877,21 +921,94 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
     // the list entries of the next batch are requested while this one is composited (one register): one of the two
     // dependent trips to memory per batch leaves the path of a wave that has its SIMD to itself
     uint32_t idx = rg.x + (uint32_t)lane < rg.y ? vals[rg.x + lane] : 0u;
-    for (uint32_t base = rg.x; base < rg.y; base += 64) {
-        uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - base));
-        const uint32_t idx_now = idx;
-        if (base + 64u + (uint32_t)lane < rg.y) idx = vals[base + 64u + lane];
+    // SH::kWide: TWO registers.  INVARIANT at the head of every iteration: idx = vals[base + lane], idx_b = vals[base + 64 + lane]
+    // (0 beyond the list's end), whether the iteration before was a pair (base moved by 128) or a batch of 64 (by 64).
+    uint32_t idx_b = 0u;
+    if constexpr (SH::kWide) {
+        if (rg.x + 64u + (uint32_t)lane < rg.y) idx_b = vals[rg.x + 64u + lane];
+        if (lane == 0) {             // the null record the lists are padded with: once per tile, no record is staged over it
+            sh.rec[0][SH::kNull] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            sh.rec[1][SH::kNull] = make_float4(0.0f, -__builtin_inff(), 0.0f, 0.0f);
+            sh.rec[2][SH::kNull] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFu));
+        }
+    }
+    bool single = false;             // (SH::kWide, wave-uniform) the next batch is one of 64
+    for (uint32_t base = rg.x; base < rg.y; base += 64u) {
         uint32_t count[kBlocks];
         unsigned long long ref_slots = 0ull;     // (wave-uniform) the slots of this batch that hold a reference-order record
-        const int kind_all = stage_batch<kStageBlocks, REF>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16), (float)(ty * 16),
-                                                            16.0f, skipped, count, budget, &idx_now, 0, dead, &ref_slots);
+        int kind_all;
+        if constexpr (!SH::kWide) {
+            uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - base));
+            const uint32_t idx_now = idx;
+            if (base + 64u + (uint32_t)lane < rg.y) idx = vals[base + 64u + lane];
+            kind_all = stage_batch<kStageBlocks, REF>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16), (float)(ty * 16),
+                                                      16.0f, skipped, count, budget, &idx_now, 0, dead, &ref_slots);
+            // the wave walks as far as its LONGEST block list; the other blocks' lists are padded with a null record
+            cost += max(max(count[0], count[1]), max(count[2], count[3])) + kBatchCost;
+        } else {
+            // Three ways through one iteration (all wave-uniform):
+            //   pair      n2 != 0 and all 128 gathered records regular: both sub-batches staged, base moves by 128;
+            //   rejected  n2 != 0 but an irregular record among the 128: the first 64 alone, base moves by 64, the next
+            //             iteration is `single` (its first half is this one's second, gathered again);
+            //   single    n2 == 0 (asked for by the iteration before, or a pixel has saturated, or the list ends inside the
+            //             first half): the first 64 alone, base moves by 64; a regular one lets the next iteration pair again.
+            const uint32_t n1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - base));
+            const uint32_t n2 = (single || checked) ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - min(rg.y, base + 64u)));
+            const bool have1 = (uint32_t)lane < n1, have2 = (uint32_t)lane < n2;
+            const uint32_t gi1 = idx, gi2 = idx_b;
+            // both sub-batches' records in flight together: 6 x dwordx4 per lane, ONE trip to memory per 128 entries
+            float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = a1, c1 = a1, a2 = a1, b2 = a1, c2_ = a1;
+            if (have1) {
+                const Record *q = rec + gi1;
+                a1 = q->a; b1 = q->b; c1 = q->c;
+            }
+            if (have2) {
+                const Record *q = rec + gi2;
+                a2 = q->a; b2 = q->b; c2_ = q->c;
+            }
+            // (wave-uniform) paired only if all 128 are plain completed squares as gathered (see above)
+            const bool pair = n2 && !__any((have1 && (c1.z != 0.0f || !(a1.z >= 0.0f))) || (have2 && (c2_.z != 0.0f || !(a2.z >= 0.0f))));
+            {   // every list starts out as nothing but the null record's slot: 4 x 136 entries = 68 x 16 bytes
+                typedef uint32_t fill4 __attribute__((ext_vector_type(4), may_alias));
+                static_assert(sizeof(sh.list) % 16 == 0 && sizeof(sh.list) / 16 <= 128 && offsetof(SH, list) % 16 == 0, "one or two 16-byte stores per lane");
+                fill4 *fill = reinterpret_cast<fill4 *>(&sh.list[0][0]);
+                const uint32_t two = (uint32_t)(SH::kNull * 16) * 0x10001u;
+                fill[lane] = fill4{two, two, two, two};
+                if (lane < (int)(sizeof(sh.list) / 16) - 64) fill[64 + lane] = fill4{two, two, two, two};
+            }
+            const uint32_t none[kBlocks] = {0u, 0u, 0u, 0u};
+            uint32_t nb1 = n1;
+            kind_all = stage_records<kStageBlocks, REF, SH>(a1, b1, c1, have1, nb1, sh, lane, (float)(tx * 16), (float)(ty * 16), 16.0f,
+                                                            skipped, budget, 0, count, dead, &ref_slots, qraw, gi1, 0u, none);
+            cost += max(max(count[0], count[1]), max(count[2], count[3])) + kBatchCost;
+            if (pair) {
+                uint32_t nb2 = n2, count2[kBlocks];
+                unsigned long long no_ref = 0ull;
+                // (both halves are regular: neither holds a record that could make it anything else)
+                kind_all |= stage_records<kStageBlocks, REF, SH>(a2, b2, c2_, have2, nb2, sh, lane, (float)(tx * 16), (float)(ty * 16), 16.0f,
+                                                                 skipped, budget, 0, count2, dead, &no_ref, qraw, gi2, nb1, count);
+                cost += max(max(count2[0], count2[1]), max(count2[2], count2[3])) + kBatchCost;
+#pragma unroll
+                for (int gb = 0; gb < kBlocks; ++gb) count[gb] += count2[gb];
+                base += 64u;                     // (and 64 more at the head of the loop: the next iteration starts at base + 64)
+                // invariant: idx = vals[next base + lane] -- not requested yet, a pair consumed both registers
+                idx = base + 64u + (uint32_t)lane < rg.y ? vals[base + 64u + lane] : 0u;
+            } else {
+                // a batch of 64 (the second half, if gathered, comes again as the next batch's first)
+                // invariant: the next iteration starts at base + 64, whose entries idx_b already holds
+                idx = idx_b;
+                single = n2 != 0u || (kind_all & kBatchKindMask) != kBatchRegular;
+            }
+            // invariant: idx_b = vals[next base + 64 + lane]; the next iteration starts at base + 64 on either path (a pair
+            // has moved base already), so that is entry base + 128.  Requested after the staging, which has no register to
+            // spare for it, and in flight while this batch is composited.
+            idx_b = base + 128u + (uint32_t)lane < rg.y ? vals[base + 128u + lane] : 0u;
+        }
         const int kind = kind_all & kBatchKindMask;
         const bool wild = kind != kBatchRegular;     // wave-uniform
         // (kBatchHasRef, not the batch's kind: a batch that also holds a monomial record is kBatchMono whatever else it holds)
         if (REF && (kind_all & kBatchHasRef)) saw_ref = true;
-        // the wave walks as far as its LONGEST block list; the other blocks' lists are padded with a null record
         const uint32_t nl = max(max(count[0], count[1]), max(count[2], count[3]));
-        cost += nl + kBatchCost;
         tile_sync<REF>();
         if (!REF && kind >= kBatchRefOrder) {
             // (wave-uniform) an ill-conditioned footprint: not here -- the tile stays undone (GSX_FLAG_PLAIN_FOOTPRINTS; the
@@ -908,9 +1025,9 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
             restart_scalar = true;
             break;
         } else {
-            // Common path: whole trips of four list entries (the lists are padded with a null record's slot, see
-            // stage_records), ONE wave-level saturation test per trip, no per-pixel selects: twice the independent work
-            // of two records between two tests hides more of the wave's own LDS reads and exponentials -- 264 -> 254 us
+            // Common path: whole trips of four list entries (the lists are padded with a null record's slot: by
+            // stage_records for a batch of 64, by the fill above -- the fixed slot SH::kNull -- for SH::kWide), ONE wave-level
+            // saturation test per trip, no per-pixel selects: twice the independent work of two records between two tests hides more of the wave's own LDS reads and exponentials -- 264 -> 254 us
             // at 1M Gaussians in round 2, more where a SIMD holds fewer than 8 waves (a rank's strip).  From the first
             // trip in which any pixel of the tile saturates -- that trip is done again -- the reference's exact rule
             // per pixel and record (checked_pair) on trips of two; a saturated pixel has T = 0, adds 0 and stays 0.
@@ -1006,7 +1123,7 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
                         }
                     }
                     const uint32_t s0_ = my_list[k], s1_ = my_list[k + 1];
-                    // (a list's padding names the null record's slot, which may be slot 64: no bit of the mask)
+                    // (a list's padding names the null record's slot, which may be slot 64 -- SH::kWide: is slot 128 --: no bit of the mask; only a batch of 64 gets here)
                     const bool r0 = is_ref(s0_), r1 = is_ref(s1_);
                     if (!__any(r0 | r1)) {
                         exact_pair();
@@ -1039,6 +1156,7 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
     if (restart_scalar) {
         // the whole tile again, one record at a time on the scalar form (composite<4>: same bits as the packed loops)
         tile_sync<REF>();
+        Staged &sh64 = reinterpret_cast<Staged &>(sh);       // (this loop stages 64 at a time in either instance)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             T[j] = 1.0f;
@@ -1049,7 +1167,7 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
         for (uint32_t base = rg.x; base < rg.y; base += 64) {
             uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(64u, rg.y - base));
             uint32_t count[kBlocks];
-            const int later = stage_batch<kStageBlocks, REF>(rec, qraw, vals, base, nb, sh, lane, (float)(tx * 16), (float)(ty * 16),
+            const int later = stage_batch<kStageBlocks, REF>(rec, qraw, vals, base, nb, sh64, lane, (float)(tx * 16), (float)(ty * 16),
                                                              16.0f, skipped, count, budget);
             if (REF && (later & kBatchHasRef)) saw_ref = true;
             if (!REF && (later & kBatchKindMask) >= kBatchRefOrder) {   // (wave-uniform) a later batch holds one: the tile stays undone
@@ -1059,7 +1177,7 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
             cost += 4u * nb;
             tile_sync<REF>();
             for (uint32_t k = 0; k < nb; ++k) {         // every staged record, in order; a lane's block takes what it keeps
-                const Splat s = read_splat(sh, k);
+                const Splat s = read_splat(sh64, k);
                 composite<4, REF>(cx, cy, s, T, c0, c1, c2, blk, (float)(tx * 16), (float)(ty * 16));
             }
             tile_sync<REF>();
@@ -1097,13 +1215,13 @@ __device__ __forceinline__ void blend_tile16(const Record *__restrict__ rec, con
 //   GSX_LAYOUT_WH3  out[x][y][c]: the lane's 4 pixels are 48 contiguous bytes (3 x dwordx4);
 //   GSX_LAYOUT_HW3  out[y][x][c]: 4 stores of 12 B; the 16 lanes that share a y write 192
 //                   contiguous bytes per store instruction.
-template <bool REF>
+template <bool REF, class SH>
 __device__ __forceinline__ void blend_tile16_grid(const Record *__restrict__ rec, const float4 *__restrict__ qraw,
                                                   const uint32_t *__restrict__ vals, const uint2 *__restrict__ ranges,
                                                   const TileGrid &g, const OutDesc &out, const ClearPlan &cp, const LongTiles &lt,
                                                   uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget,
                                                   const BlendHints &hints, uint32_t tile_blocks, uint32_t sched_cap_,
-                                                  const TileSpan &span, Staged &sh) {
+                                                  const TileSpan &span, SH &sh) {
     // block order: [spare workgroups: the next frame's splitters] [helpers of long tiles (dispatched first: they have
     // the most to do)] [tiles] [clears]
     // (hints.rank_last -- gsx_api.hip: a window whose tiles just about fill the chip once -- : the spare workgroups come
@@ -1129,7 +1247,8 @@ __device__ __forceinline__ void blend_tile16_grid(const Record *__restrict__ rec
             const int lead = span.axis ? g.wy0 + (int)(lt_tile % (uint32_t)g.nwy()) : g.wx0 + (int)(lt_tile / (uint32_t)g.nwy());
             if (lead < span.lo || lead >= span.hi) return;
         }
-        blend_long_tile_quarter<REF>(rec, qraw, vals, ranges, g, out, lt_tile, quarter, sh, budget,
+        // (a helper stages 64 records at a time, in the same LDS)
+        blend_long_tile_quarter<REF>(rec, qraw, vals, ranges, g, out, lt_tile, quarter, reinterpret_cast<Staged &>(sh), budget,
                                      hints.lens ? hints.lens + lt_tile : nullptr, lt.redo);
         return;
     }
@@ -1141,7 +1260,7 @@ __device__ __forceinline__ void blend_tile16_grid(const Record *__restrict__ rec
     const uint32_t t = hints.xcd_sched ? xcd_scheduled_tile(bid, (uint32_t)g.count(), sched_cap_, sched, hints.header)
                                        : scheduled_tile(bid, (uint32_t)g.count(), sched);
     if (t >= (uint32_t)g.count()) return;
-    blend_tile16<REF>(rec, qraw, vals, ranges, g, out, lt, budget, hints, span, t, sh);
+    blend_tile16<REF, SH>(rec, qraw, vals, ranges, g, out, lt, budget, hints, span, t, sh);
 }
 
 #ifndef GSX_PLAIN_WAVES
@@ -1153,12 +1272,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_PLA
                         uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget, BlendHints hints,
                         uint32_t tile_blocks, uint32_t sched_cap_, TileSpan span) {
     __shared__ Staged sh;
-    blend_tile16_grid<false>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, hints, tile_blocks, sched_cap_, span, sh);
+    blend_tile16_grid<false, Staged>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, hints, tile_blocks, sched_cap_, span, sh);
 }
 
-// The same grid with reference-order records evaluated where they turn up (REF, see above): what a frame runs.  128 VGPRs,
-// 4 waves per SIMD.  (5 and 6 waves -- 96 and 80 VGPRs, 130 and 206 of them spilled -- measured 1 .. 6 % slower on the
-// uniform and the heavy-tailed 1M-Gaussian frames alike, 8 waves -- 314 spilled -- 15 .. 20 %.)
+// The same grid with reference-order records evaluated where they turn up (REF, see above): what a frame runs.  At least
+// 4 waves per SIMD asked for; with two sub-batches per synchronisation (StagedWide) the kernel needs 95 VGPRs, which lets a
+// fifth wave in without a spill, and 20 waves x 7 616 bytes fit a CU's 160 KB.  (FORCED to 5 and 6 waves -- 96 and 80 VGPRs,
+// 130 and 206 of them spilled -- the batch-of-64 kernel measured 1 .. 6 % slower on the uniform and the heavy-tailed
+// 1M-Gaussian frames alike, 8 waves -- 314 spilled -- 15 .. 20 %.)
 #ifndef GSX_REF_WAVES
 #define GSX_REF_WAVES 4      // (build-time knob for A/B runs: tools/ab_bench.sh)
 #endif
@@ -1167,8 +1288,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_REF
                             const uint2 *__restrict__ ranges, TileGrid g, OutDesc out, ClearPlan cp, LongTiles lt,
                             uint32_t nhelpers, const uint32_t *__restrict__ sched, uint32_t budget, BlendHints hints,
                             uint32_t tile_blocks, uint32_t sched_cap_, TileSpan span) {
-    __shared__ Staged sh;
-    blend_tile16_grid<true>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, hints, tile_blocks, sched_cap_, span, sh);
+    __shared__ StagedWide sh;     // 7 616 bytes: 16 waves per CU keep 122 KB of its 160 KB
+    blend_tile16_grid<true, StagedWide>(rec, qraw, vals, ranges, g, out, cp, lt, nhelpers, sched, budget, hints, tile_blocks, sched_cap_, span, sh);
 }
 
 // Any tile size: one wave per tile, one pixel per lane, tile*tile/64 sweeps over the list.
