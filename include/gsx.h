@@ -553,6 +553,91 @@ typedef struct GsxAdamGroup {
 GSX_API int gsx_adam_step(const GsxAdamGroup *groups /* host */, int32_t n_groups, int64_t n, int64_t step /* >= 1 */,
                           float beta1, float beta2, float eps, uint32_t flags, void *stream);
 
+/*
+ * Build extension (the reference has no training loop): adaptive density control, the part of the published 3D Gaussian
+ * Splatting trainer (Kerbl et al. 2023) that prunes, clones and splits Gaussians every few hundred steps, in three calls:
+ * a statistic that is accumulated after every backward pass, a plan that gives every row one action and every output row
+ * its place, and one out-of-place rewrite of every array of the container AND of the optimiser's moments along that plan.
+ * Device pointers only, the caller owns all memory, nothing is allocated, no atomics: same inputs, same bits.  Every float32
+ * operation below is rounded on its own (no fused multiply-add; divide and sqrt correctly rounded).
+ *
+ * Three differences from the published method, on purpose:
+ *  (1) the statistic is the norm of the gradient array the caller names (the Python surface passes dL/dpoints), not of the
+ *      screen-space mean gradient, which gsx_render_backward_geometry keeps internal;
+ *  (2) pruning wins over densifying and a split's children are not examined until the next round (the published order
+ *      densifies first and prunes the children in the same round);
+ *  (3) rows stay in source order with the new rows BESIDE their parent (the published order appends them at the end):
+ *      spatial locality is kept, the order is stable, and one scan places every row.
+ *
+ * gsx_density_accumulate: grad (n, width) float32, read only; grad_sum (n) float32; seen (n) uint32.  Per row
+ *   norm = sqrt(((g0 g0 + g1 g1) + g2 g2) + ...), left to right;
+ * if any element of the row is not +0 or -0 (a NaN is not zero): grad_sum[i] += norm and seen[i] += 1.  A row of zeros touches
+ * neither array.  Does not synchronise.  n == 0 is GSX_OK.  Refused (GSX_ERR_INVALID_ARGUMENT, gsx_last_error names the
+ * argument, before any HIP call): n < 0 or n > 2^30; width outside 1 .. 2^20; when n > 0, grad, grad_sum or seen NULL.
+ *
+ * gsx_density_plan: one action per row i, the comparisons exactly as written, in float32 (a NaN fails every comparison, so a
+ * row whose statistic, scales or opacity are NaN where they are compared is KEEP unless another comparison decides), with
+ * smax = max(max(s0, s1), s2), which is NaN when one of the three is:
+ *   PRUNE (0 output rows): opacity_logit[i] < prune_logit, or smax > prune_scale;                         otherwise
+ *   SPLIT (2 rows): seen[i] > 0 and grad_sum[i] / (float)seen[i] >= grad_threshold and smax > dense_scale;  otherwise
+ *   CLONE (2 rows): seen[i] > 0 and grad_sum[i] / (float)seen[i] >= grad_threshold and smax <= dense_scale; otherwise
+ *   KEEP  (1 row).
+ * scales is (n,3), opacity_logit (n): the LOGIT (under GSX_SEM_REF_CPU the effective opacity is sigmoid(sigmoid(logit)), so a
+ * probability threshold would mean different things under different rule sets).  The plan -- the action of every row and
+ * the exclusive prefix sum of the output counts: the output rows of row i are [prefix[i], prefix[i] + count[i]) -- is left
+ * in `workspace` (gsx_density_workspace_bytes(n) bytes, 256-byte aligned) for gsx_density_apply, with n and the counts in
+ * its header.  counts_host (HOST, 4 x int64) receives n_out, n_pruned, n_cloned, n_split; the call synchronises `stream`
+ * once, after its last launch.  n == 0 is GSX_OK with four zeros.  Refused: grad_sum, seen, scales, opacity_logit (n > 0),
+ * rules, counts_host or workspace NULL; n < 0 or n > 2^30; rules->flags != 0; rules->split_shrink not a positive finite
+ * number; a workspace that is not 256-byte aligned; fewer bytes than asked for: GSX_ERR_WORKSPACE_TOO_SMALL.
+ *
+ * gsx_density_apply: every group g is rewritten from src (n, width) into dst (n_out, width), all groups in one launch:
+ *   KEEP:  the row is copied, whatever the role.
+ *   CLONE: two rows.  The first continues the source row: copied, whatever the role.  The second is the new Gaussian:
+ *          copied, except in a GSX_DENSITY_ZERO_NEW group, where every element is +0.
+ *   SPLIT: two new rows, child c = 0, 1.  ZERO_NEW: +0.  COPY and QUATS: copied.  SCALES: s_k / split_shrink.
+ *          POINTS: p_k + ((R[k][0] (s0 e0) + R[k][1] (s1 e1)) + R[k][2] (s2 e2)),  e = noise[i][c][0..2],
+ *          s the PARENT's scales and R the rotation of the parent's quaternion (w, x, y, z) = q / nrm (four divides),
+ *          nrm = sqrt(((qw qw + qx qx) + qy qy) + qz qz); (w, x, y, z) = (1, 0, 0, 0) when !(nrm > 0):
+ *            R[0][0] = 1 - 2 (y y + z z)   R[0][1] = 2 (x y - w z)       R[0][2] = 2 (x z + w y)
+ *            R[1][0] = 2 (x y + w z)       R[1][1] = 1 - 2 (x x + z z)   R[1][2] = 2 (y z - w x)
+ *            R[2][0] = 2 (x z - w y)       R[2][1] = 2 (y z + w x)       R[2][2] = 1 - 2 (x x + y y)
+ * noise is DEVICE (n, 2, 3) float32 (standard normal draws; the caller's generator is the caller's determinism) and is read
+ * for SPLIT rows only.  ZERO_NEW is for Adam's exp_avg / exp_avg_sq: a survivor keeps its moments' bits, a new Gaussian
+ * starts at zero.  source_row (DEVICE, int32 (n_out), may be NULL): i for an output row that continues source row i,
+ * -(i + 1) for a new row made from i.  Nothing is read of a pruned row.  16-byte accesses are used where the addresses allow;
+ * any float-aligned base is accepted, with the same bits.
+ * The call compares n and n_out with the plan's header: it reads 16 bytes back on `stream` and so waits for what was queued
+ * there before it (nothing, straight after gsx_density_plan); it does not wait for its own launch.  n_out == 0 or n == 0 is
+ * GSX_OK with nothing launched.  Refused, before any HIP call: groups or workspace NULL; n_groups outside
+ * 1 .. GSX_DENSITY_MAX_GROUPS; n < 0 or n > 2^30; n_out < 0 or n_out > 2 n; a workspace that is not 256-byte aligned or too
+ * small (GSX_ERR_WORKSPACE_TOO_SMALL); in a group: width outside 1 .. 2^20, an unknown role, src or dst NULL (n, n_out > 0),
+ * dst == src; more than one POINTS, SCALES or QUATS group; POINTS or SCALES of a width other than 3, QUATS other than 4; a
+ * POINTS group without both a SCALES and a QUATS group; noise NULL with a POINTS group.  Refused after the read: n or n_out
+ * different from the plan's.
+ */
+#define GSX_DENSITY_MAX_GROUPS 24
+enum { GSX_DENSITY_COPY = 0, GSX_DENSITY_ZERO_NEW = 1, GSX_DENSITY_POINTS = 2, GSX_DENSITY_SCALES = 3, GSX_DENSITY_QUATS = 4 };
+typedef struct GsxDensityGroup {
+    const float *src; /* (n, width) float32, rows contiguous */
+    float *dst;       /* (n_out, width) */
+    int32_t width;
+    int32_t role;     /* GSX_DENSITY_COPY .. GSX_DENSITY_QUATS */
+} GsxDensityGroup;    /* 24 bytes */
+typedef struct GsxDensityRules {
+    float grad_threshold, dense_scale, prune_logit, prune_scale, split_shrink;
+    uint32_t flags;   /* must be 0 */
+} GsxDensityRules;
+GSX_API int gsx_density_accumulate(const float *grad, int32_t width, int64_t n, float *grad_sum, uint32_t *seen, void *stream);
+GSX_API size_t gsx_density_workspace_bytes(int64_t n);   /* 0 on invalid arguments (n < 0 or n > 2^30) */
+GSX_API int gsx_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
+                             int64_t n, const GsxDensityRules *rules, void *workspace, size_t workspace_bytes,
+                             int64_t *counts_host /* 4 */, void *stream);
+GSX_API int gsx_density_apply(const GsxDensityGroup *groups /* host */, int32_t n_groups, int64_t n, int64_t n_out,
+                              const float *noise /* (n,2,3), may be NULL without a POINTS group */,
+                              int32_t *source_row /* (n_out), may be NULL */, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ from .gaussian_scene import GaussianScene, NativeExtension, render_preprocessed
 from .image import GaussianImage
 from .loss import photometric_loss
 from .optim import GaussianAdam, expon_lr
+from .density import DensityControl
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr"]
+           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl"]

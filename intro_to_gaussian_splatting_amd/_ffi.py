@@ -43,6 +43,12 @@ GSX_ADAM_MAX_GROUPS = 8
 GSX_ADAM_LINEAR = 0
 GSX_ADAM_LOG = 1
 GSX_ADAM_SKIP_ZERO_ROWS = 1
+GSX_DENSITY_MAX_GROUPS = 24
+GSX_DENSITY_COPY = 0
+GSX_DENSITY_ZERO_NEW = 1
+GSX_DENSITY_POINTS = 2
+GSX_DENSITY_SCALES = 3
+GSX_DENSITY_QUATS = 4
 
 
 def visible_rows_flag(n: int, n_visible: int, flags: int) -> int:
@@ -99,6 +105,15 @@ class GsxAdamGroup(ctypes.Structure):
                 ("width", c_int32), ("transform", c_int32), ("lr", c_float), ("reserved", c_float)]
 
 
+class GsxDensityGroup(ctypes.Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("width", c_int32), ("role", c_int32)]
+
+
+class GsxDensityRules(ctypes.Structure):
+    _fields_ = [("grad_threshold", c_float), ("dense_scale", c_float), ("prune_logit", c_float), ("prune_scale", c_float),
+                ("split_shrink", c_float), ("flags", ctypes.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/gsx.h declares.
 _FP = c_void_p  # device float*
 SIGNATURES = {
@@ -130,6 +145,12 @@ SIGNATURES = {
     "gsx_photometric_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "gsx_adam_step": (ctypes.c_int, [POINTER(GsxAdamGroup), c_int32, c_int64, c_int64, c_float, c_float, c_float,
                                      ctypes.c_uint32, c_void_p]),
+    "gsx_density_accumulate": (ctypes.c_int, [_FP, c_int32, c_int64, _FP, c_void_p, c_void_p]),
+    "gsx_density_workspace_bytes": (c_size_t, [c_int64]),
+    "gsx_density_plan": (ctypes.c_int, [_FP, c_void_p, _FP, _FP, c_int64, POINTER(GsxDensityRules), c_void_p, c_size_t,
+                                        POINTER(c_int64), c_void_p]),
+    "gsx_density_apply": (ctypes.c_int, [POINTER(GsxDensityGroup), c_int32, c_int64, c_int64, _FP, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
 }
 
 # csrc/gsx_debug.h

@@ -763,6 +763,121 @@ int gsx_adam_step(const GsxAdamGroup *groups, int32_t n_groups, int64_t n, int64
     return GSX_OK;
 }
 
+int gsx_density_accumulate(const float *grad, int32_t width, int64_t n, float *grad_sum, uint32_t *seen, void *stream) {
+    if (n < 0 || n > kDensityMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (width < 1 || width > kDensityMaxWidth)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "width = %d is outside 1 .. %d", width, kDensityMaxWidth);
+    if (n > 0) {
+        if (!grad) return fail(GSX_ERR_INVALID_ARGUMENT, "grad is NULL");
+        if (!grad_sum) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_sum is NULL");
+        if (!seen) return fail(GSX_ERR_INVALID_ARGUMENT, "seen is NULL");
+    }
+    GSX_HIP(gsx::launch_density_accumulate(grad, width, n, grad_sum, seen, (hipStream_t)stream));
+    return GSX_OK;
+}
+
+size_t gsx_density_workspace_bytes(int64_t n) {
+    DensityCarve c;
+    return density_carve(n, c) ? c.total : 0;
+}
+
+namespace {
+// n and the workspace of gsx_density_plan / gsx_density_apply
+int check_density_workspace(int64_t n, const void *workspace, size_t workspace_bytes, DensityCarve &c) {
+    if (!density_carve(n, c)) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    if (workspace_bytes < c.total)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_density_workspace_bytes(%lld) = %zu", workspace_bytes,
+                    (long long)n, c.total);
+    return GSX_OK;
+}
+}  // namespace
+
+int gsx_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit, int64_t n,
+                     const GsxDensityRules *rules, void *workspace, size_t workspace_bytes, int64_t *counts_host, void *stream) {
+    if (!rules) return fail(GSX_ERR_INVALID_ARGUMENT, "rules is NULL");
+    if (!counts_host) return fail(GSX_ERR_INVALID_ARGUMENT, "counts_host is NULL");
+    if (rules->flags != 0u) return fail(GSX_ERR_INVALID_ARGUMENT, "rules->flags 0x%x has unknown bits", rules->flags);
+    if (!(rules->split_shrink > 0.0f && rules->split_shrink <= FLT_MAX))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "rules->split_shrink %g is not a positive finite number", (double)rules->split_shrink);
+    DensityCarve c;
+    const int rc = check_density_workspace(n, workspace, workspace_bytes, c);
+    if (rc != GSX_OK) return rc;
+    if (n > 0) {
+        if (!grad_sum) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_sum is NULL");
+        if (!seen) return fail(GSX_ERR_INVALID_ARGUMENT, "seen is NULL");
+        if (!scales) return fail(GSX_ERR_INVALID_ARGUMENT, "scales is NULL");
+        if (!opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "opacity_logit is NULL");
+    }
+    for (int i = 0; i < 4; ++i) counts_host[i] = 0;
+    if (n == 0) return GSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GSX_HIP(gsx::launch_density_plan(grad_sum, seen, scales, opacity_logit, n, *rules, (char *)workspace, c, s));
+    GSX_HIP(hipMemcpyAsync(counts_host, (const char *)workspace + 8, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
+}
+
+int gsx_density_apply(const GsxDensityGroup *groups, int32_t n_groups, int64_t n, int64_t n_out, const float *noise,
+                      int32_t *source_row, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!groups) return fail(GSX_ERR_INVALID_ARGUMENT, "groups is NULL");
+    if (n_groups < 1 || n_groups > GSX_DENSITY_MAX_GROUPS)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n_groups = %d is outside 1 .. %d", n_groups, GSX_DENSITY_MAX_GROUPS);
+    DensityCarve c;
+    const int rc = check_density_workspace(n, workspace, workspace_bytes, c);
+    if (rc != GSX_OK) return rc;
+    if (n_out < 0 || n_out > 2 * n) return fail(GSX_ERR_INVALID_ARGUMENT, "n_out = %lld is outside 0 .. 2 n = %lld", (long long)n_out, (long long)(2 * n));
+    DensityArgs a;
+    memset(&a, 0, sizeof a);
+    int at[5] = {-1, -1, -1, -1, -1};       // by role: the group that has it
+    for (int i = 0; i < n_groups; ++i) {
+        const GsxDensityGroup &g = groups[i];
+        if (g.width < 1 || g.width > kDensityMaxWidth)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].width = %d is outside 1 .. %d", i, g.width, kDensityMaxWidth);
+        if (g.role < GSX_DENSITY_COPY || g.role > GSX_DENSITY_QUATS)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].role = %d is unknown", i, g.role);
+        if (g.role >= GSX_DENSITY_POINTS) {
+            static const char *const names[] = {"", "", "POINTS", "SCALES", "QUATS"};
+            if (at[g.role] >= 0)
+                return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].role: a second %s group (groups[%d] is one)", i, names[g.role], at[g.role]);
+            const int want = g.role == GSX_DENSITY_QUATS ? 4 : 3;
+            if (g.width != want)
+                return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].width = %d: a %s group has width %d", i, g.width, names[g.role], want);
+            at[g.role] = i;
+        }
+        if (n > 0 && !g.src) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].src is NULL", i);
+        if (n_out > 0 && !g.dst) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].dst is NULL", i);
+        if (g.dst && g.dst == g.src) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].dst equals src: the rewrite is out of place", i);
+        a.group[i] = DensityGroupArgs{g.src, g.dst, g.width, g.role};
+    }
+    if (at[GSX_DENSITY_POINTS] >= 0) {
+        if (at[GSX_DENSITY_SCALES] < 0 || at[GSX_DENSITY_QUATS] < 0)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].role: a POINTS group needs a SCALES and a QUATS group in the same call",
+                        at[GSX_DENSITY_POINTS]);
+        if (!noise) return fail(GSX_ERR_INVALID_ARGUMENT, "noise is NULL with a POINTS group");
+        a.scales = groups[at[GSX_DENSITY_SCALES]].src;
+        a.quats = groups[at[GSX_DENSITY_QUATS]].src;
+        a.noise = noise;
+    }
+    if (n == 0 || n_out == 0) return GSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t planned[2] = {-1, -1};          // the header's n and n_out
+    GSX_HIP(hipMemcpyAsync(planned, workspace, sizeof planned, hipMemcpyDeviceToHost, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    if (planned[0] != n) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld, the plan in workspace is of %lld rows", (long long)n, (long long)planned[0]);
+    if (planned[1] != n_out)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n_out = %lld, the plan in workspace gives %lld rows", (long long)n_out, (long long)planned[1]);
+    a.action = reinterpret_cast<const uint8_t *>((const char *)workspace + c.action);
+    a.prefix = reinterpret_cast<const uint32_t *>((const char *)workspace + c.prefix);
+    a.shrink = reinterpret_cast<const float *>((const char *)workspace + kDensityShrinkAt);
+    a.source_row = source_row;
+    a.n = n;
+    a.n_groups = n_groups;
+    GSX_HIP(gsx::launch_density_apply(a, n_out, s));
+    return GSX_OK;
+}
+
 int gsx_covariance_3d(const float *scales, const float *quats, int64_t n, float *covariance_out, void *stream) {
     if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n is negative");
     if (n > 0 && (!scales || !quats || !covariance_out)) return fail(GSX_ERR_INVALID_ARGUMENT, "an array is NULL");

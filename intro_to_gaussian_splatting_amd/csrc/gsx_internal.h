@@ -330,6 +330,54 @@ struct AdamArgs {
 };
 hipError_t launch_adam(const AdamArgs &args, bool skip_zero_rows, hipStream_t s);
 
+// ---- gsx_density.hip
+// gsx_density_accumulate / _plan / _apply behind their argument checks.  The workspace of n rows (DensityCarve):
+//   header  kDensityHeader bytes: int64 n, n_out, n_pruned, n_cloned, n_split; float split_shrink at kDensityShrinkAt
+//   action  one byte per row (kDensityKeep ..), padded to whole scan blocks of kDensityScanRows rows
+//   prefix  uint32 per row: the row's first output row
+//   bsum    per scan block (+1): the output rows of the blocks before it; then the blocks' pruned and split counts
+constexpr int kDensityRows = 256;               // source rows of one workgroup of the apply kernel (kAdamRows, block_bounds)
+constexpr int kDensityScanRows = 1024;          // rows of one workgroup of the plan's scan
+constexpr int kDensityScanPass = 256 * kDensityScanRows;    // rows one pass of the block-level scan covers
+constexpr int64_t kDensityMaxRows = (int64_t)1 << 30;
+constexpr int kDensityMaxWidth = 1 << 20;       // a block's run of a group, at most 512 * width floats, is indexed with 32 bits
+constexpr size_t kDensityHeader = 256, kDensityShrinkAt = 40;
+enum : uint8_t { kDensityKeep = 0, kDensityPrune = 1, kDensityClone = 2, kDensitySplit = 3 };
+struct DensityCarve {
+    size_t action, prefix, bsum, total;
+    uint32_t scan_blocks;
+};
+inline bool density_carve(int64_t n, DensityCarve &c) {
+    if (n < 0 || n > kDensityMaxRows) return false;
+    const size_t nsb = (size_t)((n + kDensityScanRows - 1) / kDensityScanRows);
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    c.scan_blocks = (uint32_t)nsb;
+    c.action = kDensityHeader;
+    c.prefix = c.action + up(nsb * kDensityScanRows);
+    c.bsum = c.prefix + up((size_t)n * 4);
+    c.total = c.bsum + up((3 * nsb + 1) * 4);
+    return true;
+}
+struct DensityGroupArgs {
+    const float *src;
+    float *dst;
+    int32_t width, role;
+};
+struct DensityArgs {
+    DensityGroupArgs group[24];
+    const float *scales, *quats, *noise;    // the POINTS group's companions (null without one)
+    const uint8_t *action;
+    const uint32_t *prefix;
+    int32_t *source_row;                    // or null
+    const float *shrink;                    // rules.split_shrink, where the plan left it in the header
+    int64_t n;
+    int32_t n_groups;
+};
+hipError_t launch_density_accumulate(const float *grad, int32_t width, int64_t n, float *grad_sum, uint32_t *seen, hipStream_t s);
+hipError_t launch_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
+                               int64_t n, const GsxDensityRules &rules, char *ws, const DensityCarve &c, hipStream_t s);
+hipError_t launch_density_apply(const DensityArgs &args, int64_t n_out, hipStream_t s);
+
 // ---- gsx_blend.hip
 // background: 3 floats, read on the host (GSX_SEM_STD_3DGS only); generic: GSX_FLAG_GENERIC_KERNELS.
 // cp: what the launch zeroes besides compositing its tiles (extra workgroups of the same kernel).

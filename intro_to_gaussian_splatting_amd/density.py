@@ -1,0 +1,193 @@
+"""Adaptive density control of a splat fit on the GPU: ``DensityControl`` (gsx_density_accumulate / gsx_density_plan /
+gsx_density_apply, include/gsx.h).
+
+After every ``backward()`` ``accumulate()`` adds the norm of each Gaussian's ``points.grad`` to a running statistic; every few
+hundred steps ``densify_and_prune()`` gives every Gaussian one action -- prune, clone, split or keep -- and rewrites every
+array of the container and both moment arrays of the optimiser in ONE library call: a survivor keeps the bits of its
+parameters and of its Adam moments, a new Gaussian starts with zero moments, and rows stay in source order with the children
+beside their parent.  There is no torch composition behind it and no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Dict, Optional
+
+import torch
+
+from . import _ffi
+from .gaussian_scene import _stream_handle
+from .optim import GROUP_NAMES
+
+_ROLES = {"points": _ffi.GSX_DENSITY_POINTS, "scales": _ffi.GSX_DENSITY_SCALES, "quaternions": _ffi.GSX_DENSITY_QUATS}
+COUNT_NAMES = ("n_out", "n_pruned", "n_cloned", "n_split")
+
+
+class DensityControl:
+    """Prune / clone / split over ``gaussians`` (and ``optimizer``'s moments, and ``scene``'s per-view caches).
+
+    The rules (include/gsx.h, gsx_density_plan), in this order: PRUNE where the opacity LOGIT is below ``prune_logit`` or the
+    largest scale above ``prune_scale``; otherwise, where the mean accumulated gradient norm is at least ``grad_threshold``,
+    SPLIT in two (scales divided by ``split_shrink``, positions drawn from the parent's own Gaussian) when the largest scale
+    is above ``dense_scale`` and CLONE when it is not; KEEP everything else.  ``max_gaussians``: when a round would leave
+    more rows than this, it prunes only.  The statistic is the norm of dL/dpoints (world units), not the published
+    screen-space gradient, so the published 2e-4 is only a default to start from: set ``grad_threshold`` and ``dense_scale``
+    for the scene (the attributes may be changed between rounds)."""
+
+    def __init__(self, gaussians, optimizer=None, scene=None, grad_threshold: float = 2e-4, dense_scale: float = 0.01,
+                 prune_logit: float = -5.3, prune_scale: float = math.inf, split_shrink: float = 1.6,
+                 max_gaussians: Optional[int] = None) -> None:
+        if getattr(gaussians, "original_index", None) is not None:
+            raise ValueError("the container is spatially ordered: its permutation and block boxes would be stale after a "
+                             "round.  Densify the plain container and call spatially_ordered() again")
+        if optimizer is not None and optimizer.gaussians is not gaussians:
+            raise ValueError("optimizer belongs to another container than gaussians")
+        if scene is not None and scene.gaussians is not gaussians:
+            raise ValueError("scene renders another container than gaussians")
+        if not (float(split_shrink) > 0.0 and math.isfinite(float(split_shrink))):
+            raise ValueError("split_shrink = %r is not a positive finite number" % (split_shrink,))
+        if max_gaussians is not None and int(max_gaussians) < 0:
+            raise ValueError("max_gaussians = %r is negative" % (max_gaussians,))
+        self.gaussians, self.optimizer, self.scene = gaussians, optimizer, scene
+        self.grad_threshold, self.dense_scale = float(grad_threshold), float(dense_scale)
+        self.prune_logit, self.prune_scale = float(prune_logit), float(prune_scale)
+        self.split_shrink = float(split_shrink)
+        self.max_gaussians = None if max_gaussians is None else int(max_gaussians)
+        self._check_arrays()
+        dev = gaussians.points.device
+        n = len(gaussians)
+        self.grad_sum = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.seen = torch.zeros(n, dtype=torch.int32, device=dev)        # (the library's uint32)
+        self._workspace: Optional[torch.Tensor] = None
+        self._groups = (_ffi.GsxDensityGroup * _ffi.GSX_DENSITY_MAX_GROUPS)()
+
+    # ------------------------------------------------------------------ helpers
+    def _names(self):
+        return tuple(name for name in GROUP_NAMES if getattr(self.gaussians, name, None) is not None)
+
+    def _check_arrays(self) -> None:
+        g = self.gaussians
+        if getattr(g, "original_index", None) is not None:
+            raise ValueError("the container is spatially ordered: densify the plain container and call spatially_ordered() again")
+        n = len(g)
+        dev = g.points.device
+        for name in self._names():
+            t = getattr(g, name)
+            if t.device.type != "cuda":
+                raise ValueError("%s is on %s: density control runs only as HIP kernels on an AMD GPU (torch device 'cuda'); "
+                                 "there is no CPU fallback" % (name, t.device))
+            if t.device != dev:
+                raise ValueError("%s is on %s, points on %s" % (name, t.device, dev))
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != n:
+                raise ValueError("%s must be a contiguous float32 tensor of %d rows" % (name, n))
+
+    def _rules(self, grad_threshold: float) -> _ffi.GsxDensityRules:
+        return _ffi.GsxDensityRules(grad_threshold, self.dense_scale, self.prune_logit, self.prune_scale, self.split_shrink, 0)
+
+    def _plan(self, n: int, grad_threshold: float, dev) -> Dict[str, int]:
+        g = self.gaussians
+        need = int(_ffi.load().gsx_density_workspace_bytes(n))
+        if need == 0:
+            raise ValueError("%d Gaussians are more than density control takes (2^30)" % n)
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        counts = (ctypes.c_int64 * 4)()
+        rules = self._rules(grad_threshold)
+        with torch.cuda.device(dev):
+            rc = _ffi.load().gsx_density_plan(self.grad_sum.data_ptr(), self.seen.data_ptr(), g.scales.data_ptr(),
+                                              g.opacity.data_ptr(), n, ctypes.byref(rules), self._workspace.data_ptr(),
+                                              self._workspace.numel(), counts, _stream_handle(dev))
+        _ffi.check(rc)
+        return dict(zip(COUNT_NAMES, (int(c) for c in counts)))
+
+    # ------------------------------------------------------------------ the surface
+    def accumulate(self) -> None:
+        """After ``backward()``: adds |points.grad| of every Gaussian with a non-zero gradient row to the statistic and counts
+        it as seen (gsx_density_accumulate).  Allocates nothing after the first call."""
+        g = self.gaussians
+        grad = g.points.grad
+        if grad is None:
+            raise ValueError("points has no .grad: call backward() (with geometry_gradients=True) before accumulate()")
+        n = len(g)
+        if grad.dtype != torch.float32 or not grad.is_contiguous() or tuple(grad.shape) != tuple(g.points.shape):
+            raise ValueError("points.grad must be contiguous float32 and of the shape of points")
+        if grad.device.type != "cuda" or grad.device != self.grad_sum.device:
+            raise ValueError("points.grad is on %s, the statistic on %s; there is no CPU fallback" % (grad.device, self.grad_sum.device))
+        if self.grad_sum.shape[0] != n:
+            raise ValueError("the container has %d rows, the statistic %d: rows changed outside densify_and_prune()"
+                             % (n, self.grad_sum.shape[0]))
+        dev = grad.device
+        with torch.cuda.device(dev):
+            rc = _ffi.load().gsx_density_accumulate(grad.data_ptr(), grad.numel() // n if n else 3, n, self.grad_sum.data_ptr(),
+                                                    self.seen.data_ptr(), _stream_handle(dev))
+        _ffi.check(rc)
+
+    def densify_and_prune(self, generator: Optional[torch.Generator] = None) -> Dict[str, int]:
+        """One round: plan, rewrite every array and moment, install, reset the statistic and the scene's caches.  Returns
+        ``n_out``, ``n_pruned``, ``n_cloned``, ``n_split``.  The split positions draw ``torch.randn((n, 2, 3))`` from
+        ``generator`` (a generator of the container's device): the same seed gives the same container."""
+        self._check_arrays()
+        g, opt = self.gaussians, self.optimizer
+        n = len(g)
+        dev = g.points.device
+        if self.grad_sum.shape[0] != n:
+            raise ValueError("the container has %d rows, the statistic %d: rows changed outside densify_and_prune()"
+                             % (n, self.grad_sum.shape[0]))
+        if opt is not None:
+            if opt.gaussians is not g:
+                raise ValueError("optimizer belongs to another container than gaussians")
+            for name in opt.names:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    m = getattr(opt, key)[name]
+                    if tuple(m.shape) != tuple(getattr(g, name).shape) or m.device != dev or not m.is_contiguous():
+                        raise ValueError("optimizer.%s[%r] is not of the shape and device of %s" % (key, name, name))
+        counts = self._plan(n, self.grad_threshold, dev)
+        if self.max_gaussians is not None and counts["n_out"] > self.max_gaussians:
+            counts = self._plan(n, math.inf, dev)           # prune only
+        n_out = counts["n_out"]
+        noise = torch.randn((n, 2, 3), generator=generator, device=dev, dtype=torch.float32)
+
+        names = self._names()
+        jobs = [(name, getattr(g, name), _ROLES.get(name, _ffi.GSX_DENSITY_COPY)) for name in names]
+        if opt is not None:
+            jobs += [((key, name), getattr(opt, key)[name], _ffi.GSX_DENSITY_ZERO_NEW)
+                     for name in opt.names for key in ("exp_avg", "exp_avg_sq")]
+        if len(jobs) > _ffi.GSX_DENSITY_MAX_GROUPS:
+            raise ValueError("%d arrays are more than one call rewrites (%d)" % (len(jobs), _ffi.GSX_DENSITY_MAX_GROUPS))
+        new = {}
+        for i, (key, src, role) in enumerate(jobs):
+            dst = torch.empty((n_out,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
+            new[key] = dst
+            grp = self._groups[i]
+            grp.src, grp.dst = src.data_ptr(), dst.data_ptr()
+            grp.width = src.numel() // n if n else max(1, math.prod(src.shape[1:]))
+            grp.role = role
+        with torch.cuda.device(dev):
+            rc = _ffi.load().gsx_density_apply(self._groups, len(jobs), n, n_out, noise.data_ptr(), None,
+                                               self._workspace.data_ptr(), self._workspace.numel(), _stream_handle(dev))
+        _ffi.check(rc)
+
+        for name in names:
+            old = getattr(g, name)
+            setattr(g, name, new[name].requires_grad_(old.requires_grad))        # a leaf again, .grad None
+        if opt is not None:
+            opt.exp_avg = {name: new[("exp_avg", name)] for name in opt.names}
+            opt.exp_avg_sq = {name: new[("exp_avg_sq", name)] for name in opt.names}
+        self.grad_sum = torch.zeros(n_out, dtype=torch.float32, device=dev)
+        self.seen = torch.zeros(n_out, dtype=torch.int32, device=dev)
+        if self.scene is not None:
+            self.scene.gaussians_changed()
+        return counts
+
+    def reset_opacity(self, cap_logit: float) -> None:
+        """The published trainer's opacity reset, on the logit: ``opacity.clamp_(max=cap_logit)`` in place and zeros in the
+        optimiser's two opacity moment arrays.  Plain torch -- it runs once in thousands of steps."""
+        g = self.gaussians
+        if g.opacity.device.type != "cuda":
+            raise ValueError("opacity is on %s; there is no CPU fallback" % g.opacity.device)
+        with torch.no_grad():
+            g.opacity.clamp_(max=float(cap_logit))
+            opt = self.optimizer
+            if opt is not None and "opacity" in opt.exp_avg:
+                opt.exp_avg["opacity"].zero_()
+                opt.exp_avg_sq["opacity"].zero_()

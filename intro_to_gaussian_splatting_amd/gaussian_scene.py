@@ -773,6 +773,19 @@ class GaussianScene:
         if cap_key[2] is None and cap_key[3] == "ref_cpu":
             self._last_instances = n_instances
 
+    def gaussians_changed(self) -> None:
+        """Tell the scene that the ROWS of ``gaussians`` changed -- their number or which Gaussian a row holds
+        (``DensityControl.densify_and_prune`` calls it; so does a user who replaces the arrays).  Everything the scene keeps
+        per view from earlier frames was measured on the old rows: the pair capacities, the kept counts, the n_redo counts,
+        the per-row hints buffers and the workspace sizing.  All of it is dropped, so the next frame of every view is a first
+        frame."""
+        self._cap_hints.clear()
+        self._kept_hints.clear()
+        self._n_redo_seen.clear()
+        self._hints.clear()
+        self._instances_hint = 0
+        self._last_instances = 0
+
     def _ensure_pinned_pool(self) -> None:
         if self._pinned_pool is None:
             self._pinned_pool = torch.zeros((_PINNED_SLOTS, ctypes.sizeof(_ffi.GsxFrameStats)),
