@@ -638,6 +638,42 @@ GSX_API int gsx_density_apply(const GsxDensityGroup *groups /* host */, int32_t 
                               int32_t *source_row /* (n_out), may be NULL */, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/*
+ * Build extension: scale initialisation.  The reference's Gaussians.initialize_scale (splat/gaussians.py:35-52: the mean of
+ * the three smallest neighbour distances; switched off there, its n x n x 3 difference tensor does not fit) as one call that
+ * is exact: for every one of n points the distances to its three nearest OTHER points.  Device pointers only, the caller owns
+ * all memory, no float atomics: a pure function of `points`, the same bits on every run.  Every float32 operation below is
+ * rounded on its own (no fused multiply-add; sqrt and divide correctly rounded).
+ *
+ * For row i, over all rows j != i (exclusion is by ROW, not by value: a duplicate point counts, at distance 0):
+ *   dx = xj - xi, dy = yj - yi, dz = zj - zi;   q = (dx dx + dy dy) + dz dz;
+ * the three smallest q, ascending: q0 <= q1 <= q2, and d_k = sqrtf(q_k).  A neighbour that does not exist (n < 4) is +inf.
+ * Only the VALUES of the three smallest q enter, so ties need no rule and the result does not depend on the order in which
+ * candidates are met.
+ *   dist3 (n, 3) float32, may be NULL: d0, d1, d2.
+ *   scale (n) float32, may be NULL:
+ *     GSX_KNN_RULE_REFERENCE   max(((d0 + d1) + d2) / 3.0f, 1e-5f)          (splat/gaussians.py:46-48)
+ *     GSX_KNN_RULE_PUBLISHED   sqrtf(max(((q0 + q1) + q2) / 3.0f, 1e-7f))   (the linear scale of the published 3D Gaussian
+ *                              Splatting initialisation: the root of the mean squared distance)
+ * points is (n, 3) float32 and is only read.  FINITE coordinates are a precondition: with a NaN or an infinity the values of
+ * the rows are unspecified, but the call still ends and stays inside its arrays.
+ * order (DEVICE, int32 (n), may be NULL: rows as given): a permutation of 0 .. n-1, the sequence in which rows are grouped
+ * into blocks of 256 for the search.  It changes the speed -- blocks of a space-filling curve are compact, and whole blocks
+ * are skipped by an exact lower bound of their distances -- and never a bit of the result.  (An entry that is not a row is
+ * replaced by its own position; with an `order` that is not a permutation the rows' values are unspecified.)
+ * candidates (HOST, may be NULL): the number of (query, candidate) pairs whose q was evaluated; n (n - 1) without pruning.
+ * The call synchronises `stream` only when candidates is asked for.  workspace: gsx_knn3_workspace_bytes(n) bytes, 256-byte
+ * aligned (16 n bytes of gathered points, 32 bytes per block, a header).
+ * n == 0 is GSX_OK, nothing is written or looked at.  Refused (GSX_ERR_INVALID_ARGUMENT, gsx_last_error names the argument,
+ * before any HIP call): n < 0 or n > 2^30; an unknown rule; dist3 and scale both NULL; when n > 0: points NULL, workspace NULL
+ * or not 256-byte aligned; fewer workspace bytes than asked for: GSX_ERR_WORKSPACE_TOO_SMALL.
+ */
+enum { GSX_KNN_RULE_REFERENCE = 0, GSX_KNN_RULE_PUBLISHED = 1 };
+GSX_API size_t gsx_knn3_workspace_bytes(int64_t n);   /* 0 on invalid arguments (n < 0 or n > 2^30) */
+GSX_API int gsx_knn3(const float *points /* (n,3) */, int64_t n, const int32_t *order /* (n), may be NULL */, int32_t rule,
+                     float *dist3 /* (n,3), may be NULL */, float *scale /* (n), may be NULL */,
+                     int64_t *candidates /* host, may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

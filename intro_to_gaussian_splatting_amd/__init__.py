@@ -7,7 +7,8 @@ from .image import GaussianImage
 from .loss import photometric_loss
 from .optim import GaussianAdam, expon_lr
 from .density import DensityControl
+from .knn import nearest3
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl"]
+           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3"]

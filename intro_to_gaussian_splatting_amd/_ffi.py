@@ -49,6 +49,8 @@ GSX_DENSITY_ZERO_NEW = 1
 GSX_DENSITY_POINTS = 2
 GSX_DENSITY_SCALES = 3
 GSX_DENSITY_QUATS = 4
+GSX_KNN_RULE_REFERENCE = 0
+GSX_KNN_RULE_PUBLISHED = 1
 
 
 def visible_rows_flag(n: int, n_visible: int, flags: int) -> int:
@@ -151,6 +153,8 @@ SIGNATURES = {
                                         POINTER(c_int64), c_void_p]),
     "gsx_density_apply": (ctypes.c_int, [POINTER(GsxDensityGroup), c_int32, c_int64, c_int64, _FP, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    "gsx_knn3_workspace_bytes": (c_size_t, [c_int64]),
+    "gsx_knn3": (ctypes.c_int, [_FP, c_int64, c_void_p, c_int32, _FP, _FP, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
 }
 
 # csrc/gsx_debug.h

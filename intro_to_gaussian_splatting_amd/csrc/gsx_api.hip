@@ -878,6 +878,38 @@ int gsx_density_apply(const GsxDensityGroup *groups, int32_t n_groups, int64_t n
     return GSX_OK;
 }
 
+size_t gsx_knn3_workspace_bytes(int64_t n) {
+    KnnCarve c;
+    return knn_carve(n, c) ? c.total : 0;
+}
+
+int gsx_knn3(const float *points, int64_t n, const int32_t *order, int32_t rule, float *dist3, float *scale, int64_t *candidates,
+             void *workspace, size_t workspace_bytes, void *stream) {
+    KnnCarve c;
+    if (!knn_carve(n, c)) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (rule != GSX_KNN_RULE_REFERENCE && rule != GSX_KNN_RULE_PUBLISHED)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "rule = %d is neither GSX_KNN_RULE_REFERENCE nor GSX_KNN_RULE_PUBLISHED", rule);
+    if (!dist3 && !scale) return fail(GSX_ERR_INVALID_ARGUMENT, "dist3 and scale are both NULL");
+    if (n == 0) {
+        if (candidates) *candidates = 0;
+        return GSX_OK;
+    }
+    if (!points) return fail(GSX_ERR_INVALID_ARGUMENT, "points is NULL");
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    if (workspace_bytes < c.total)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_knn3_workspace_bytes(%lld) = %zu", workspace_bytes,
+                    (long long)n, c.total);
+    hipStream_t s = (hipStream_t)stream;
+    if (candidates) GSX_HIP(hipMemsetAsync(workspace, 0, sizeof(uint64_t), s));
+    GSX_HIP(gsx::launch_knn3(points, n, order, rule, dist3, scale, (char *)workspace, c, candidates != nullptr, s));
+    if (candidates) {
+        GSX_HIP(hipMemcpyAsync(candidates, workspace, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        GSX_HIP(hipStreamSynchronize(s));
+    }
+    return GSX_OK;
+}
+
 int gsx_covariance_3d(const float *scales, const float *quats, int64_t n, float *covariance_out, void *stream) {
     if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n is negative");
     if (n > 0 && (!scales || !quats || !covariance_out)) return fail(GSX_ERR_INVALID_ARGUMENT, "an array is NULL");

@@ -378,6 +378,32 @@ hipError_t launch_density_plan(const float *grad_sum, const uint32_t *seen, cons
                                int64_t n, const GsxDensityRules &rules, char *ws, const DensityCarve &c, hipStream_t s);
 hipError_t launch_density_apply(const DensityArgs &args, int64_t n_out, hipStream_t s);
 
+// ---- gsx_knn.hip
+// gsx_knn3 behind its argument checks.  The workspace of n rows (KnnCarve):
+//   header  kKnnHeader bytes: uint64 (query, candidate) pairs evaluated (zeroed and read only when the caller asks)
+//   boxes   two float4 per block of kKnnRows consecutive entries: (min xyz, 0), (max xyz, 0)
+//   pts     float4 per entry: (x, y, z, the bits of the entry's row), in the caller's `order`
+constexpr int kKnnRows = 256;                   // entries of one workgroup (kAdamRows, kDensityRows, block_bounds)
+constexpr int64_t kKnnMaxRows = (int64_t)1 << 30;
+constexpr size_t kKnnHeader = 256;
+struct KnnCarve {
+    size_t boxes, pts, total;
+    uint32_t blocks;
+};
+inline bool knn_carve(int64_t n, KnnCarve &c) {
+    if (n < 0 || n > kKnnMaxRows) return false;
+    const size_t nb = (size_t)((n + kKnnRows - 1) / kKnnRows);
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    c.blocks = (uint32_t)nb;
+    c.boxes = kKnnHeader;
+    c.pts = c.boxes + up(nb * 32);
+    c.total = c.pts + up((size_t)n * 16);
+    return true;
+}
+// counter: the header's uint64, or nullptr when nobody asked
+hipError_t launch_knn3(const float *points, int64_t n, const int32_t *order, int32_t rule, float *dist3, float *scale,
+                       char *ws, const KnnCarve &c, bool count, hipStream_t s);
+
 // ---- gsx_blend.hip
 // background: 3 floats, read on the host (GSX_SEM_STD_3DGS only); generic: GSX_FLAG_GENERIC_KERNELS.
 // cp: what the launch zeroes besides compositing its tiles (extra workgroups of the same kernel).

@@ -126,16 +126,9 @@ class Gaussians:
         if n == 0:
             perm = torch.zeros(0, dtype=torch.int64, device=p.device)
         else:
-            lo, hi = p.min(dim=0).values, p.max(dim=0).values
-            span = torch.clamp(hi - lo, min=1e-30)
-            cells = float(1 << bits)
-            q = torch.clamp(((p - lo) / span * cells).to(torch.int64), 0, (1 << bits) - 1)
-            q = torch.where(torch.isfinite(p), q, torch.zeros_like(q))         # (NaN / inf means: cell 0)
-            code = torch.zeros(n, dtype=torch.int64, device=p.device)
-            for b in range(bits):
-                for axis in range(3):
-                    code |= ((q[:, axis] >> b) & 1) << (3 * b + axis)
-            perm = torch.argsort(code, stable=True)
+            from .knn import morton_permutation
+
+            perm = morton_permutation(p, bits)
         for name in ("points", "colors", "scales", "quaternions", "opacity"):
             setattr(g, name, getattr(self, name)[perm].contiguous())
         g.sh = None if self.sh is None else self.sh[perm].contiguous()
@@ -145,6 +138,30 @@ class Gaussians:
         g.block_bounds = None
         g.refresh_block_bounds()
         return g
+
+    def initialize_scale(self, rule: str = "reference") -> None:
+        """The reference's ``initialize_scale`` (splat/gaussians.py:35-52), which it leaves switched off because its
+        n x n x 3 difference tensor does not fit: the scale of every Gaussian from the distances to its three nearest other
+        points, exact, in one library call (gsx_knn3; ``knn.nearest3``).
+        ``rule="reference"`` does what the reference does, quirk included: ``scales *= max(mean(d0, d1, d2), 1e-5)`` in
+        place, so the constructor's 0.001 gives 0.001 x the mean distance, and fewer than four points give inf.
+        ``rule="published"`` assigns sqrt(max(mean(d0^2, d1^2, d2^2), 1e-7)), the initial scale of the published 3D Gaussian
+        Splatting trainer, to all three axes.  The rows are visited along a 21-bit Morton curve (10 bits leave the clusters
+        of a trained scene unordered inside one cell); a spatially ordered container is visited as it is.  The in-place
+        write is what ``current_block_bounds()`` watches."""
+        from .knn import morton_permutation, nearest3
+
+        n = len(self)
+        p = self.points.detach().reshape(n, 3)
+        order = None
+        if self.original_index is None and n > 0 and p.device.type == "cuda":
+            order = morton_permutation(p, 21).to(torch.int32).contiguous()
+        _, scale = nearest3(p, order=order, rule=rule)
+        with torch.no_grad():
+            if rule == "reference":
+                self.scales *= scale
+            else:
+                self.scales.copy_(scale.expand(n, 3))
 
     def get_3d_covariance_matrix(self) -> torch.Tensor:
         """(N,3,3) Sigma = (R S)(R S)^T, computed on the GPU (gsx_covariance_3d); same result as the
