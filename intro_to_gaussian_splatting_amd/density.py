@@ -16,7 +16,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
-from .gaussian_scene import _stream_handle
+from ._device import _stream_handle
 from .optim import GROUP_NAMES
 
 _ROLES = {"points": _ffi.GSX_DENSITY_POINTS, "scales": _ffi.GSX_DENSITY_SCALES, "quaternions": _ffi.GSX_DENSITY_QUATS}

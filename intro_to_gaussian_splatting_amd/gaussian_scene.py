@@ -16,70 +16,21 @@ Added: ``.render_image_hip`` (explicit layout / tile window / stats), ``.render_
 from __future__ import annotations
 
 import ctypes
-from collections import OrderedDict
+from collections import namedtuple
+from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import _ffi
+from . import _ffi, _hip
+from ._device import _WORKSPACE, _Lru, _Workspace, _check_f32, _ptr, _require_gpu, _stream_handle  # noqa: F401
 from .colmap import read_camera_file, read_image_file
 from .gaussians import Gaussians
 from .image import GaussianImage
+from .loss import photometric_loss
 from .schema import PreprocessedScene
+from .strips import tiles_along
 
-
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _check_f32(name: str, t: torch.Tensor, device: torch.device) -> torch.Tensor:
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32, got %s" % (name, t.dtype))
-    if t.device != device:
-        raise ValueError("%s is on %s, expected %s" % (name, t.device, device))
-    return t if t.is_contiguous() else t.contiguous()
-
-
-class _Lru(OrderedDict):
-    """A dict that forgets its least recently used entry beyond ``limit`` (device buffers keyed by stream handles or
-    by views: a viewer that keeps creating streams, a sweep over hundreds of cameras or a strip plan that moves with
-    every rebalance would otherwise grow them for the life of the process)."""
-
-    def __init__(self, limit: int) -> None:
-        super().__init__()
-        self.limit = int(limit)
-
-    def lookup(self, key):
-        val = self.get(key)
-        if val is not None:
-            self.move_to_end(key)
-        return val
-
-    def store(self, key, val):
-        self[key] = val
-        self.move_to_end(key)
-        while len(self) > self.limit:
-            self.popitem(last=False)      # (freed on its own stream: torch's allocator orders the reuse behind its last kernel)
-        return val
-
-
-class _Workspace:
-    """Caller-owned device scratch for libgsx (the library never allocates)."""
-
-    def __init__(self, limit: int = 8) -> None:
-        self.buffers = _Lru(limit)
-
-    def get(self, device: torch.device, nbytes: int) -> torch.Tensor:
-        # one buffer per (device, stream): frames in flight on different streams must not share scratch; the
-        # buffers of the `limit` most recently used streams are kept (a C3 frame's is ~130 MB)
-        key = (device, torch.cuda.current_stream(device).cuda_stream)
-        buf = self.buffers.lookup(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = self.buffers.store(key, torch.empty(nbytes, dtype=torch.uint8, device=device))
-        return buf
-
-
-_WORKSPACE = _Workspace()
 _PINNED_SLOTS = 256
 _PLAIN_MIN_TILES = 16384  # windows from this many tiles take GSX_FLAG_PLAIN_FOOTPRINTS when the view allows it (render_image_hip)
 _HINT_VIEWS = 64          # GsxParams.hints buffers a scene keeps (83 KB each at 1080p, 300 KB at 4K): the most recent views
@@ -87,15 +38,83 @@ _SEMANTICS = {"ref_cpu": _ffi.GSX_SEM_REF_CPU, "ref_cuda": _ffi.GSX_SEM_REF_CUDA
               "std_3dgs": _ffi.GSX_SEM_STD_3DGS}
 
 
-def _stream_handle(device: torch.device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def _frame_stats(pinned: torch.Tensor) -> _ffi.GsxFrameStats:
+    """The GsxFrameStats a frame's counts arrive in, as a view of its pinned slot (no copy: read it after a synchronise)."""
+    return ctypes.cast(ctypes.c_void_p(pinned.data_ptr()), ctypes.POINTER(_ffi.GsxFrameStats)).contents
 
 
-def _require_gpu(device: torch.device) -> None:
-    if device.type != "cuda":
-        raise RuntimeError(
-            "the Gaussian tensors are on %s: this renderer runs only as HIP kernels on an AMD GPU "
-            "(torch device 'cuda'); there is no CPU fallback" % device)
+@dataclass
+class _OwnedFrame:
+    """``render_image_hip(_private=...)``: what ONE frame owns instead of taking it from the scene (capture_frame: its graph
+    bakes the addresses in, so they must not be shared with or recycled by any other frame).  Such a call neither reads nor
+    updates the scene's hints and pending list; a field left at its default comes from the scene as in any other call."""
+    cap: Optional[int] = None                   # pair capacity; fixed: a frame that needs more is an error, not a retry
+    workspace: Optional[torch.Tensor] = None
+    kept: Optional[int] = None                  # GsxParams.kept_hint
+    rows_flag: int = 0                          # GSX_FLAG_SMALL_BATCH / _ONE_VISIBLE: an owned call is not issued again
+    plain: Optional[bool] = None                # GSX_FLAG_PLAIN_FOOTPRINTS where the call allows it
+    pinned: Optional[torch.Tensor] = None       # GsxFrameStats slot of a no_sync frame
+    inputs: Optional[list] = None               # receives the tensors whose addresses the call handed to the library
+    hints: Optional[list] = None                # [GsxParams.hints buffer, a frame has run with it?]
+
+    @classmethod
+    def of(cls, private) -> Optional["_OwnedFrame"]:
+        """None and the empty dict: not owned.  A dict: its record (an unknown key is a TypeError).  A record: itself."""
+        if private is None or isinstance(private, cls):
+            return private
+        return cls(**private) if private else None
+
+
+_UNOWNED = _OwnedFrame()        # every field at its default: all of it from the scene
+# a ``no_sync`` frame whose counts are still in flight (GaussianScene._settle).  pinned: the slot its GsxFrameStats arrive
+# in; ran_plain: issued with GSX_FLAG_PLAIN_FOOTPRINTS; call: render_image_hip(**call) renders it again, synchronously
+_PendingFrame = namedtuple("_PendingFrame", "pinned cap_key ran_plain call")
+# one gsx_render_forward call, all but the per-view state (GaussianScene._plan_frame).  tensors: the five parameter tensors
+# (colours: None on an SH scene); owned_inputs: every tensor the call hands over besides out; keep_alive: host arrays
+_FramePlan = namedtuple("_FramePlan", "dev n cam tensors params out cap_key owned_inputs keep_alive")
+
+
+def _next_attempt(rc: int, n_visible: int, n_instances: int, n_redo: int, flags: int, n: int, speculative: bool,
+                  owned: bool, fixed_cap: bool, semantics: str) -> Tuple[str, Optional[int]]:
+    """What follows a gsx_render_forward over ``n`` Gaussians, issued with ``flags``, that returned ``rc`` and these counts:
+    ("done", None) -- ``rc`` is the outcome --, or once more with ("flags", other flags) or ("cap", another pair capacity):
+    1. the plain compositing instance ran and the view does hold ill-conditioned footprints: the one that evaluates them;
+    2. at most three Gaussians pass the cull, fewer than the call assumed: the reference's BLAS then sums its products over
+       the visible ones in another order (GSX_FLAG_SMALL_BATCH / _ONE_VISIBLE, include/gsx.h) -- in that order; an owned
+       call is told its row class, std_3dgs has none;
+    3. the workspace was too small: room for 1.25 x the pairs counted, unless the capacity is fixed.
+    A speculative (no_sync) call has no counts yet: 1 and 2 are left to ``confirm_frames``."""
+    if rc == _ffi.GSX_OK and not speculative:
+        if flags & _ffi.GSX_FLAG_PLAIN_FOOTPRINTS and n_redo > 0:
+            return "flags", flags & ~_ffi.GSX_FLAG_PLAIN_FOOTPRINTS
+        again = 0 if owned or semantics == "std_3dgs" else _ffi.visible_rows_flag(n, n_visible, flags)
+        if again:
+            return "flags", _ffi.with_rows_flag(flags, again)
+    if rc == _ffi.GSX_ERR_WORKSPACE_TOO_SMALL and not fixed_cap:
+        return "cap", int(n_instances * 1.25) + 4096
+    return "done", None
+
+
+def _report(stats: dict, st: _ffi.GsxFrameStats, ran_plain: bool, owned: bool, speculative: bool, timing: bool) -> None:
+    """``render_image_hip(stats=...)``; plain_footprints: the frame ran the compositing instance of GSX_FLAG_PLAIN_FOOTPRINTS."""
+    if speculative:
+        if not owned:
+            stats.update(n_visible=None, n_instances=None, n_tiles=st.n_tiles, speculative=True, plain_footprints=ran_plain)
+        return
+    stats.update(n_visible=st.n_visible, n_instances=st.n_instances, n_tiles=st.n_tiles, n_kept=st.n_kept,
+                 n_redo=int(st.n_redo))
+    if not owned:
+        stats["plain_footprints"] = ran_plain
+        if timing:
+            stats["stage_ms"] = {k: float(st.stage_ms[i]) for i, k in enumerate(_ffi.STAGE_NAMES)}
+
+
+def _window_tiles(width: int, height: int, tile_size: int, semantics: str, tile_window) -> Tuple[int, int]:
+    """Tiles along x and y of what a frame renders: ``tile_window`` with its upper bounds clamped (negative: "to the end")."""
+    ntx, nty = tiles_along(width, tile_size, semantics), tiles_along(height, tile_size, semantics)
+    wx0, wx1, wy0, wy1 = (0, ntx, 0, nty) if tile_window is None else [int(v) for v in tile_window]
+    wx1, wy1 = (ntx if wx1 < 0 else min(wx1, ntx)), (nty if wy1 < 0 else min(wy1, nty))
+    return max(0, wx1 - wx0), max(0, wy1 - wy0)
 
 
 def render_preprocessed(height: int, width: int, tile_size: int, point_means: torch.Tensor,
@@ -207,12 +226,12 @@ class CapturedFrame:
         synchronises.  More pairs than room: pairs were dropped, the frame has to be rendered again (``confirm()``
         raises for exactly that)."""
         torch.cuda.synchronize(self.out.device)
-        st = ctypes.cast(ctypes.c_void_p(self._pinned.data_ptr()), ctypes.POINTER(_ffi.GsxFrameStats)).contents
+        st = _frame_stats(self._pinned)
         return int(st.n_visible), int(st.n_instances), int(st.reserved)
 
     def confirm(self) -> torch.Tensor:
         torch.cuda.synchronize(self.out.device)
-        st = ctypes.cast(ctypes.c_void_p(self._pinned.data_ptr()), ctypes.POINTER(_ffi.GsxFrameStats)).contents
+        st = _frame_stats(self._pinned)
         if st.n_instances > st.reserved:
             raise _ffi.GsxError(_ffi.GSX_ERR_WORKSPACE_TOO_SMALL,
                                 "the captured frame holds %d pairs but the scene now produces %d: capture it again"
@@ -337,15 +356,20 @@ class GaussianScene:
         dev = g.points.device
         _require_gpu(dev)
         n = int(g.points.shape[0])
-        k = (int(g.sh_degree) + 1) ** 2
         pts = _check_f32("points", g.points.reshape(n, 3), dev)
-        sh = _check_f32("sh", g.sh.reshape(n, k, 3), dev)
+        sh, degree = self._sh_flat(n, dev)
         out = torch.empty((n, 3), dtype=torch.float32, device=dev)
         center = (ctypes.c_float * 3)(*self.images[image_idx].camera_center_host)   # no device read per frame
         with torch.cuda.device(dev):
-            rc = lib.gsx_sh_to_rgb(_ptr(pts), _ptr(sh), int(g.sh_degree), n, center, _ptr(out), _stream_handle(dev))
+            rc = lib.gsx_sh_to_rgb(_ptr(pts), _ptr(sh), degree, n, center, _ptr(out), _stream_handle(dev))
         _ffi.check(rc)
         return out
+
+    def _sh_flat(self, n: int, dev) -> Tuple[torch.Tensor, int]:
+        """(``gaussians.sh`` as the library reads it: contiguous float32 (n, K, 3) on ``dev``; its degree, K = (degree + 1)^2)."""
+        g = self.gaussians
+        degree = int(g.sh_degree)
+        return _check_f32("sh", g.sh.reshape(n, (degree + 1) ** 2, 3), dev), degree
 
     def _inputs(self, image_idx: Optional[int] = None, inline_sh: bool = False):
         """The five parameter tensors the library reads.  With ``inline_sh`` and an SH scene the last one is
@@ -492,39 +516,63 @@ class GaussianScene:
         with ``geometry_gradients=True`` the geometry too, dL/dpoints including the share that reaches the mean through the
         view direction; an SH scene whose ``sh`` does not require grad is refused when gradients are asked for.
         """
-        if _private is None and _wants_grad(self.gaussians, bool(geometry_gradients)):
+        g = self.gaussians
+        if _private is None and _wants_grad(g, bool(geometry_gradients)):
             # gradients (gsx_render_backward, gsx_render_backward_geometry, gsx_sh_backward): the whole ref_cpu frame only
-            for what, bad in _refusals(self.gaussians, semantics, tile_window, out, substrips, no_sync, camera_buffer):
+            for what, bad in _refusals(g, semantics, tile_window, out, substrips, no_sync, camera_buffer):
                 if bad:
                     _refuse_with_grad(what)
-            g = self.gaussians
             kw = dict(stats=stats, timing=timing, generic_kernels=generic_kernels, tile_counts=tile_counts,
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
                       geometry_gradients=bool(geometry_gradients))
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
                                               g.opacity, g.colors, getattr(g, "sh", None))
-        lib = _ffi.load()
+        own = _OwnedFrame.of(_private)
+        speculative = bool(no_sync and not timing)
+        plan = self._plan_frame(image_idx, tile_size, layout, tile_window, out, out_origin, timing, semantics, background,
+                                generic_kernels, published_rects, camera_buffer, tile_counts, split_long_tiles,
+                                tile_schedule, substrips, substrip_events)
+        cap, hint_slot = self._view_state(plan, own, tile_size, tile_window, semantics, generic_kernels, use_hints)
+        pinned, st = self._issue(plan, own, cap, tile_size, semantics, speculative)
+        if hint_slot is not None:
+            # (stream order: the next frame on this stream finds what this one left -- or, where the library took a
+            # path that does not use the buffer, the zeros it was created with: its header then says "nothing here")
+            hint_slot[1] = True
+        ran_plain = bool(plan.params.flags & _ffi.GSX_FLAG_PLAIN_FOOTPRINTS)
+        if own is None and speculative:
+            # counts are still in flight: remember what has to be confirmed
+            self._pending.append(_PendingFrame(pinned, plan.cap_key, ran_plain, dict(
+                image_idx=image_idx, tile_size=tile_size, layout=layout, tile_window=tile_window, out=plan.out,
+                out_origin=out_origin, semantics=semantics, background=background,
+                generic_kernels=generic_kernels, published_rects=published_rects, camera_buffer=camera_buffer,
+                tile_counts=tile_counts, split_long_tiles=split_long_tiles, tile_schedule=tile_schedule,
+                use_hints=use_hints)))
+        elif own is None:
+            self._note_count(plan.cap_key, int(st.n_instances), int(st.n_kept), int(st.n_redo))
+        if stats is not None:
+            _report(stats, st, ran_plain, own is not None, speculative, timing)
+        return plan.out
+
+    def _plan_frame(self, image_idx, tile_size, layout, tile_window, out, out_origin, timing, semantics, background,
+                    generic_kernels, published_rects, camera_buffer, tile_counts, split_long_tiles, tile_schedule,
+                    substrips, substrip_events):
+        """Validates the arguments of ``render_image_hip`` and fills GsxParams: all but the per-view state (``_view_state``)."""
+        _ffi.load()         # (a missing library is reported before anything about the arguments)
         dev, n, tensors = self._inputs(image_idx, inline_sh=True)
-        g_ = self.gaussians
         cam = self.images[image_idx].gsx_camera()
         width, height = cam.width, cam.height
         params, oi = self._frame_params(dev, n, layout, semantics)
-        sh_flat = None
+        owned_inputs = [t for t in tensors if t is not None]
         if tensors[4] is None:      # SH scene: the projection kernel evaluates the view-dependent colour itself
-            g = self.gaussians
-            k = (int(g.sh_degree) + 1) ** 2
-            sh_flat = _check_f32("sh", g.sh.reshape(n, k, 3), dev)
-            params.sh, params.sh_degree = sh_flat.data_ptr(), int(g.sh_degree)
+            sh_flat, params.sh_degree = self._sh_flat(n, dev)
+            params.sh = sh_flat.data_ptr()
+            owned_inputs.append(sh_flat)
         if oi is not None:
-            # a strip's projection drops whole blocks of 256 rows of a spatially ordered scene after reading their box
-            # (recomputed here when points / scales were modified since: Gaussians.current_block_bounds)
-            bb = g_.current_block_bounds() if hasattr(g_, "current_block_bounds") else getattr(g_, "block_bounds", None)
+            owned_inputs += [oi, self.gaussians.row_of_index]
+            bb = self._block_bounds(dev, n)
             if bb is not None:
-                if bb.device != dev or bb.dtype != torch.float32 or not bb.is_contiguous() or \
-                        tuple(bb.shape) != (-(-n // _ffi.GSX_BOUNDS_ROWS), 8):
-                    raise ValueError("gaussians.block_bounds must be a contiguous float32 (%d, 8) tensor on %s "
-                                     "(Gaussians.refresh_block_bounds)" % (-(-n // _ffi.GSX_BOUNDS_ROWS), dev))
                 params.block_bounds = bb.data_ptr()
+                owned_inputs.append(bb)
         params.background[0], params.background[1], params.background[2] = [float(v) for v in background]
         if timing:
             params.flags |= _ffi.GSX_FLAG_TIMING
@@ -543,32 +591,15 @@ class GaussianScene:
             params.camera_device = camera_buffer.data_ptr()
         if tile_window is not None:
             params.tile_x0, params.tile_x1, params.tile_y0, params.tile_y1 = [int(v) for v in tile_window]
-        keep_alive = []
-        if substrips is not None and len(substrips) > 2:
-            from . import _hip
-
-            k_parts = len(substrips) - 1
-            bounds = (ctypes.c_int32 * (k_parts + 1))(*[int(v) for v in substrips])
-            evs = self._part_events.setdefault((torch.cuda.current_stream(dev).cuda_stream, k_parts),
-                                               [_hip.Event() for _ in range(k_parts)])
-            handles = (ctypes.c_void_p * k_parts)(*[e.handle for e in evs])
-            params.n_substrips, params.substrip_axis = k_parts, 0 if layout == "wh3" else 1
-            params.substrip_bounds = ctypes.cast(bounds, ctypes.POINTER(ctypes.c_int32))
-            params.substrip_events = ctypes.cast(handles, ctypes.POINTER(ctypes.c_void_p))
-            keep_alive += [bounds, handles]
-            if substrip_events is not None:
-                substrip_events[:] = evs
+        cut = substrips is not None and len(substrips) > 2
+        keep_alive = self._plan_substrips(params, dev, layout, substrips, substrip_events) if cut else []
         if tile_counts is not None:
             if tile_counts.device != dev or tile_counts.dtype not in (torch.int32, torch.uint32) or \
                     not tile_counts.is_contiguous():
                 raise ValueError("tile_counts must be a contiguous int32 tensor on %s" % dev)
-            from .strips import tiles_along
-            ntx, nty = tiles_along(width, tile_size, semantics), tiles_along(height, tile_size, semantics)
-            wx0, wx1, wy0, wy1 = (0, ntx, 0, nty) if tile_window is None else [int(v) for v in tile_window]
-            wx1, wy1 = (ntx if wx1 < 0 else min(wx1, ntx)), (nty if wy1 < 0 else min(wy1, nty))
-            if tile_counts.numel() < max(0, wx1 - wx0) * max(0, wy1 - wy0):
-                raise ValueError("tile_counts holds %d entries, the window has %d tiles"
-                                 % (tile_counts.numel(), max(0, wx1 - wx0) * max(0, wy1 - wy0)))
+            tx, ty = _window_tiles(width, height, tile_size, semantics, tile_window)
+            if tile_counts.numel() < tx * ty:
+                raise ValueError("tile_counts holds %d entries, the window has %d tiles" % (tile_counts.numel(), tx * ty))
             params.tile_counts = tile_counts.data_ptr()
         if out is None:
             shape = (width, height, 3) if layout == "wh3" else (height, width, 3)
@@ -579,131 +610,119 @@ class GaussianScene:
                 raise ValueError("out must be contiguous")
             ow, oh = (out.shape[0], out.shape[1]) if layout == "wh3" else (out.shape[1], out.shape[0])
             params.out_x0, params.out_y0, params.out_w, params.out_h = int(out_origin[0]), int(out_origin[1]), int(ow), int(oh)
-        # pair capacity: 1.1 x the count this (camera, tile size, window, semantics) produced last time
-        # -- the binning kernels' grids are sized by it -- or a generous guess for a first frame
         cap_key = (image_idx, tile_size, None if tile_window is None else tuple(int(v) for v in tile_window),
                    semantics + ("/published" if published_rects else ""))
-        cap = self._cap_hints.get(cap_key, 0) or max(self._instances_hint, 8 * n + 4096)
-        # _private (capture_frame): a pair capacity, scratch buffer and count slot owned by ONE captured
-        # frame -- its graph bakes their addresses in, so they must not be shared with or recycled by
-        # any other frame; such a call neither reads nor updates the scene's hints and pending list
-        own = _private or {}
-        if "cap" in own:
-            cap = int(own["cap"])
-        if "inputs" in own:         # capture_frame: the tensors whose addresses the graph bakes in stay alive with it
-            passed = [t for t in tensors if t is not None] + ([sh_flat] if sh_flat is not None else [])
-            scene_own = [g_.points, g_.scales, g_.quaternions, g_.opacity] + \
-                ([g_.sh] if sh_flat is not None else [g_.colors])
-            if any(t.data_ptr() != a.data_ptr() for t, a in zip(passed, scene_own)):
+        return _FramePlan(dev, n, cam, tensors, params, out, cap_key, owned_inputs, keep_alive)
+
+    def _block_bounds(self, dev, n: int) -> Optional[torch.Tensor]:
+        """``gaussians.block_bounds``, checked, or None: a strip's projection drops whole blocks of 256 rows of a spatially
+        ordered scene after reading their box (recomputed here when points / scales were modified since)."""
+        g = self.gaussians
+        bb = g.current_block_bounds() if hasattr(g, "current_block_bounds") else getattr(g, "block_bounds", None)
+        if bb is not None and (bb.device != dev or bb.dtype != torch.float32 or not bb.is_contiguous() or
+                               tuple(bb.shape) != (-(-n // _ffi.GSX_BOUNDS_ROWS), 8)):
+            raise ValueError("gaussians.block_bounds must be a contiguous float32 (%d, 8) tensor on %s "
+                             "(Gaussians.refresh_block_bounds)" % (-(-n // _ffi.GSX_BOUNDS_ROWS), dev))
+        return bb
+
+    def _plan_substrips(self, params, dev, layout: str, substrips, substrip_events) -> list:
+        """GsxParams.n_substrips, the bounds and one event per part; returns the host arrays ``params`` now points to."""
+        k_parts = len(substrips) - 1
+        bounds = (ctypes.c_int32 * (k_parts + 1))(*[int(v) for v in substrips])
+        evs = self._part_events.setdefault((torch.cuda.current_stream(dev).cuda_stream, k_parts),
+                                           [_hip.Event() for _ in range(k_parts)])
+        handles = (ctypes.c_void_p * k_parts)(*[e.handle for e in evs])
+        params.n_substrips, params.substrip_axis = k_parts, 0 if layout == "wh3" else 1
+        params.substrip_bounds = ctypes.cast(bounds, ctypes.POINTER(ctypes.c_int32))
+        params.substrip_events = ctypes.cast(handles, ctypes.POINTER(ctypes.c_void_p))
+        if substrip_events is not None:
+            substrip_events[:] = evs
+        return [bounds, handles]
+
+    def _view_state(self, plan, own: Optional[_OwnedFrame], tile_size, tile_window, semantics, generic_kernels, use_hints):
+        """What earlier frames of this view left for the call, from the scene's dictionaries or from the frame's own record,
+        into ``plan.params`` (kept_hint, the plain-footprints and row-class flags, hints).  Returns (pair capacity, hints slot)."""
+        params, cap_key, dev, rec = plan.params, plan.cap_key, plan.dev, own if own is not None else _UNOWNED
+        # pair capacity: 1.1 x the count this (camera, tile size, window, semantics) produced last time
+        # -- the binning kernels' grids are sized by it -- or a generous guess for a first frame
+        cap = int(rec.cap) if rec.cap is not None else \
+            self._cap_hints.get(cap_key, 0) or max(self._instances_hint, 8 * plan.n + 4096)
+        if rec.inputs is not None:  # capture_frame: the tensors whose addresses the graph bakes in stay alive with it
+            g = self.gaussians
+            scene_own = [g.points, g.scales, g.quaternions, g.opacity, g.sh if plan.tensors[4] is None else g.colors]
+            if any(t.data_ptr() != a.data_ptr() for t, a in zip(plan.owned_inputs, scene_own)):
                 raise ValueError("capture_frame needs contiguous float32 Gaussian tensors: a captured frame replays "
                                  "from the scene's own memory, and a non-contiguous attribute would be copied once, "
                                  "at capture time")
-            own["inputs"][:] = passed + ([oi, g_.row_of_index] if oi is not None else []) + \
-                ([bb] if oi is not None and bb is not None else [])
+            rec.inputs[:] = plan.owned_inputs
         # how many Gaussians reached a tile of this window last time: picks the depth-sort route (a hint)
-        params.kept_hint = int(own.get("kept", self._kept_hints.get(cap_key, 0)))
+        params.kept_hint = int(rec.kept if rec.kept is not None else self._kept_hints.get(cap_key, 0))
         # GSX_FLAG_PLAIN_FOOTPRINTS: no tile of the last frame of this view held an ill-conditioned footprint, so this one runs
         # the compositing instance that cannot evaluate them -- where that pays: from _PLAIN_MIN_TILES tiles (measured: 6 %
-        # of a 4K frame of 5M Gaussians, nothing at 1080p); its own n_redo says whether that held (checked below / by
-        # confirm_frames / by CapturedFrame.confirm: a frame that was wrong about it is rendered again without the flag)
+        # of a 4K frame of 5M Gaussians, nothing at 1080p); its own n_redo says whether that held (_next_attempt /
+        # confirm_frames / CapturedFrame.confirm: a frame that was wrong about it is rendered again without the flag)
+        # (not _window_tiles: the threshold was measured against THIS count, the window as given or the frame's ceil-division)
         n_window_tiles = (tile_window[1] - tile_window[0]) * (tile_window[3] - tile_window[2]) if tile_window is not None \
-            else (-(-width // tile_size) * -(-height // tile_size) if tile_size > 0 else 0)
-        plain = bool(own["plain"]) if "plain" in own else \
+            else (-(-plan.cam.width // tile_size) * -(-plan.cam.height // tile_size) if tile_size > 0 else 0)
+        plain = bool(rec.plain) if rec.plain is not None else \
             (self._n_redo_seen.get(cap_key) == 0 and n_window_tiles >= _PLAIN_MIN_TILES)
         if plain and semantics == "ref_cpu" and tile_size == 16 and not generic_kernels:
             params.flags |= _ffi.GSX_FLAG_PLAIN_FOOTPRINTS
         # capture_frame: the row class (GSX_FLAG_SMALL_BATCH / _ONE_VISIBLE) the view's uncaptured frame ended up with is
         # baked into the graph -- a captured call cannot be issued again when n_visible says it assumed wrongly
-        params.flags |= int(own.get("rows_flag", 0))
+        params.flags |= int(rec.rows_flag)
+        if not use_hints:
+            return cap, None
         # GsxParams.hints: one buffer per view and stream (a captured frame owns its own), valid once a frame has filled it
-        hint_slot = None
-        if use_hints:
-            if "hints" in own:
-                hint_slot = own["hints"]
-            else:
-                hkey = (cap_key, torch.cuda.current_stream(dev).cuda_stream)
-                hint_slot = self._hints.lookup(hkey)
-                hbytes = lib.gsx_hints_bytes(width, height, tile_size)
-                if hint_slot is None or hint_slot[0].numel() != hbytes or hint_slot[0].device != dev:
-                    hint_slot = self._hints.store(hkey, [torch.zeros(hbytes, dtype=torch.uint8, device=dev), False])
-            params.hints = hint_slot[0].data_ptr()
-            if hint_slot[1]:
-                params.flags |= _ffi.GSX_FLAG_HINTS_VALID
-        speculative = bool(no_sync and not timing)
+        hint_slot = rec.hints
+        if hint_slot is None:
+            hkey = (cap_key, torch.cuda.current_stream(dev).cuda_stream)
+            hint_slot = self._hints.lookup(hkey)
+            hbytes = _ffi.load().gsx_hints_bytes(plan.cam.width, plan.cam.height, tile_size)
+            if hint_slot is None or hint_slot[0].numel() != hbytes or hint_slot[0].device != dev:
+                hint_slot = self._hints.store(hkey, [torch.zeros(hbytes, dtype=torch.uint8, device=dev), False])
+        params.hints = hint_slot[0].data_ptr()
+        if hint_slot[1]:
+            params.flags |= _ffi.GSX_FLAG_HINTS_VALID
+        return cap, hint_slot
+
+    def _issue(self, plan, own: Optional[_OwnedFrame], cap: int, tile_size: int, semantics: str, speculative: bool):
+        """gsx_render_forward until ``_next_attempt`` says done (each of its reasons at most once or twice); raises for what it
+        ended with.  Returns (pinned slot or None, GsxFrameStats): a speculative frame's counts arrive later, in pinned memory."""
+        lib = _ffi.load()
+        dev, n, cam, params = plan.dev, plan.n, plan.cam, plan.params
+        own_ws, pinned = (None, None) if own is None else (own.workspace, own.pinned)
         if speculative:
             params.flags |= _ffi.GSX_FLAG_NO_SYNC
-            if "pinned" in own:
-                pinned = own["pinned"]
-            else:
+            if pinned is None:
                 if len(self._pending) >= _PINNED_SLOTS:
                     self.confirm_frames()
                 pinned = self._pinned_slot()
-            st_ref = ctypes.cast(ctypes.c_void_p(pinned.data_ptr()), ctypes.POINTER(_ffi.GsxFrameStats))
-            st = st_ref.contents
+            st = _frame_stats(pinned)
         else:
-            st = _ffi.GsxFrameStats()
-            st_ref = ctypes.byref(st)
+            pinned, st = None, _ffi.GsxFrameStats()
         with torch.cuda.device(dev):
-            for _ in range(6):      # (a larger workspace, the second compositing launch after all, another row class: each at most once or twice)
-                nbytes = lib.gsx_workspace_bytes(n, width, height, tile_size, cap)
+            for _ in range(6):
+                nbytes = lib.gsx_workspace_bytes(n, cam.width, cam.height, tile_size, cap)
                 if nbytes == 0:
                     raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_workspace_bytes rejected the sizes")
-                ws = own.get("workspace")
-                if ws is None:
-                    ws = _WORKSPACE.get(dev, nbytes)
-                elif ws.numel() < nbytes:
+                ws = _WORKSPACE.get(dev, nbytes) if own_ws is None else own_ws
+                if ws.numel() < nbytes:
                     raise ValueError("private workspace holds %d bytes, the frame needs %d" % (ws.numel(), nbytes))
                 # hand over exactly the bytes of `cap` pairs (the buffer may be larger): the library
                 # derives its pair capacity -- and the binning grids -- from the size it is given
-                rc = lib.gsx_render_forward(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(out),
-                                            ctypes.byref(params), st_ref, _ptr(ws), nbytes,
-                                            _stream_handle(dev))
-                if rc == _ffi.GSX_OK and not speculative and params.flags & _ffi.GSX_FLAG_PLAIN_FOOTPRINTS and int(st.n_redo) > 0:
-                    # the view does hold ill-conditioned footprints after all: once more, with the instance that evaluates them
-                    params.flags &= ~_ffi.GSX_FLAG_PLAIN_FOOTPRINTS
-                    continue
-                again = 0
-                if rc == _ffi.GSX_OK and not speculative and not own and semantics != "std_3dgs":
-                    again = _ffi.visible_rows_flag(n, int(st.n_visible), params.flags)
-                if again:
-                    # at most three Gaussians pass the cull, fewer than the call assumed: the reference's BLAS then sums
-                    # its products over the visible ones in another order (GSX_FLAG_SMALL_BATCH / _ONE_VISIBLE,
-                    # include/gsx.h) -- once more, in that order
-                    params.flags = _ffi.with_rows_flag(params.flags, again)
-                    continue
-                if rc != _ffi.GSX_ERR_WORKSPACE_TOO_SMALL or "cap" in own:
+                rc = lib.gsx_render_forward(ctypes.byref(cam), *[_ptr(t) for t in plan.tensors], n, tile_size, _ptr(plan.out),
+                                            ctypes.byref(params), ctypes.byref(st), _ptr(ws), nbytes, _stream_handle(dev))
+                what, value = _next_attempt(rc, int(st.n_visible), int(st.n_instances), int(st.n_redo), params.flags, n,
+                                            speculative, own is not None, own is not None and own.cap is not None, semantics)
+                if what == "done":
                     break
-                cap = int(st.n_instances * 1.25) + 4096
+                if what == "flags":
+                    params.flags = value
+                else:
+                    cap = value
         _ffi.check(rc)
-        if hint_slot is not None:
-            # (stream order: the next frame on this stream finds what this one left -- or, where the library took a
-            # path that does not use the buffer, the zeros it was created with: its header then says "nothing here")
-            hint_slot[1] = True
-        if own:
-            if stats is not None and not speculative:
-                stats.update(n_visible=st.n_visible, n_instances=st.n_instances, n_tiles=st.n_tiles, n_kept=st.n_kept,
-                             n_redo=int(st.n_redo))
-            return out
-        if speculative:
-            # counts are still in flight: remember what has to be confirmed
-            self._pending.append((pinned, cap_key, bool(params.flags & _ffi.GSX_FLAG_PLAIN_FOOTPRINTS), dict(
-                image_idx=image_idx, tile_size=tile_size, layout=layout, tile_window=tile_window, out=out,
-                out_origin=out_origin, semantics=semantics, background=background,
-                generic_kernels=generic_kernels, published_rects=published_rects, camera_buffer=camera_buffer,
-                tile_counts=tile_counts, split_long_tiles=split_long_tiles, tile_schedule=tile_schedule,
-                use_hints=use_hints)))
-            if stats is not None:
-                stats.update(n_visible=None, n_instances=None, n_tiles=st.n_tiles, speculative=True,
-                             plain_footprints=bool(params.flags & _ffi.GSX_FLAG_PLAIN_FOOTPRINTS))
-            return out
-        self._note_count(cap_key, int(st.n_instances), int(st.n_kept), int(st.n_redo))
-        if stats is not None:
-            # (plain_footprints: the frame ran the compositing instance of GSX_FLAG_PLAIN_FOOTPRINTS)
-            stats.update(n_visible=st.n_visible, n_instances=st.n_instances, n_tiles=st.n_tiles, n_kept=st.n_kept,
-                         n_redo=int(st.n_redo), plain_footprints=bool(params.flags & _ffi.GSX_FLAG_PLAIN_FOOTPRINTS))
-            if timing:
-                stats["stage_ms"] = {k: float(st.stage_ms[i]) for i, k in enumerate(_ffi.STAGE_NAMES)}
-        return out
+        return pinned, st
 
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
                          n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False) -> Tuple[torch.Tensor, ...]:
@@ -751,15 +770,14 @@ class GaussianScene:
             dev = g.points.device
             _require_gpu(dev)
             n = int(g.points.shape[0])
-            k = (int(g.sh_degree) + 1) ** 2
             pts = _check_f32("points", g.points.detach().reshape(n, 3), dev)
-            sh = _check_f32("sh", g.sh.detach().reshape(n, k, 3), dev)
+            sh, degree = self._sh_flat(n, dev)      # (under no_grad: nothing is recorded)
             gc = _check_f32("grad_colors", grad_colors.detach().reshape(n, 3), dev)
-            gsh = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+            gsh = torch.empty(sh.shape, dtype=torch.float32, device=dev)
             gview = torch.empty((n, 3), dtype=torch.float32, device=dev) if with_points else None
             center = (ctypes.c_float * 3)(*self.images[image_idx].camera_center_host)
             with torch.cuda.device(dev):
-                rc = lib.gsx_sh_backward(_ptr(pts), _ptr(sh), int(g.sh_degree), n, center, _ptr(gc), _ptr(gsh), _ptr(gview),
+                rc = lib.gsx_sh_backward(_ptr(pts), _ptr(sh), degree, n, center, _ptr(gc), _ptr(gsh), _ptr(gview),
                                          _stream_handle(dev))
             _ffi.check(rc)
         return gsh, gview
@@ -786,14 +804,11 @@ class GaussianScene:
         self._instances_hint = 0
         self._last_instances = 0
 
-    def _ensure_pinned_pool(self) -> None:
+    def _pinned_slot(self) -> torch.Tensor:
+        """One 64-byte slot of a pinned ring (pinning memory per frame would dominate the frame)."""
         if self._pinned_pool is None:
             self._pinned_pool = torch.zeros((_PINNED_SLOTS, ctypes.sizeof(_ffi.GsxFrameStats)),
                                             dtype=torch.uint8).pin_memory()
-
-    def _pinned_slot(self) -> torch.Tensor:
-        """One 64-byte slot of a pinned ring (pinning memory per frame would dominate the frame)."""
-        self._ensure_pinned_pool()
         slot = self._pinned_pool[self._pinned_next % _PINNED_SLOTS]
         self._pinned_next += 1
         slot.zero_()
@@ -807,16 +822,19 @@ class GaussianScene:
         if not self._pending:
             return 0
         torch.cuda.synchronize(self.gaussians.points.device)
-        redone = 0
         pending, self._pending = self._pending, []
-        for pinned, cap_key, ran_plain, call in pending:
-            st = ctypes.cast(ctypes.c_void_p(pinned.data_ptr()), ctypes.POINTER(_ffi.GsxFrameStats)).contents
-            self._note_count(cap_key, int(st.n_instances), int(st.n_kept), int(st.n_redo))
-            # more pairs than the workspace held (dropped), or tiles left to a second compositing launch that was not issued
-            if st.n_instances > st.reserved or (ran_plain and st.n_redo > 0):
-                redone += 1
-                self.render_image_hip(**call)          # synchronising path, same output tensor
-        return redone
+        return sum(self._settle(frame) for frame in pending)
+
+    def _settle(self, frame) -> bool:
+        """The counts a ``no_sync`` frame left in its pinned slot (the caller has synchronised): filed for the view's next
+        frame; pairs dropped or tiles left undone: rendered again, synchronously, into the same tensor.  Returns whether."""
+        st = _frame_stats(frame.pinned)
+        self._note_count(frame.cap_key, int(st.n_instances), int(st.n_kept), int(st.n_redo))
+        # more pairs than the workspace held (dropped), or tiles left to a second compositing launch that was not issued
+        again = bool(st.n_instances > st.reserved or (frame.ran_plain and st.n_redo > 0))
+        if again:
+            self.render_image_hip(**frame.call)
+        return again
 
     def capture_frame(self, image_idx: int, tile_size: int = 16, layout: str = "wh3",
                       semantics: str = "ref_cpu", movable_camera: bool = False,
@@ -856,25 +874,24 @@ class GaussianScene:
         # the graph bakes in which compositing instance runs: the plain one (GSX_FLAG_PLAIN_FOOTPRINTS) only for a fixed camera
         # whose frame held no ill-conditioned footprint, where it pays (confirm() checks every replay's n_redo); a movable
         # camera may turn to such footprints
-        private = dict(cap=cap, workspace=torch.empty(nbytes, dtype=torch.uint8, device=dev), kept=int(st["n_kept"]),
-                       rows_flag=0 if semantics == "std_3dgs" else _ffi.rows_flag(n, int(st["n_visible"])),
-                       plain=(not movable_camera) and int(st.get("n_redo", 1)) == 0 and
-                       int(st.get("n_tiles", 0)) >= _PLAIN_MIN_TILES,
-                       pinned=torch.zeros(ctypes.sizeof(_ffi.GsxFrameStats), dtype=torch.uint8).pin_memory(), inputs=[],
-                       hints=[torch.zeros(lib.gsx_hints_bytes(cam.width, cam.height, tile_size), dtype=torch.uint8,
-                                          device=dev), False])
+        own = _OwnedFrame(
+            cap=cap, workspace=torch.empty(nbytes, dtype=torch.uint8, device=dev), kept=int(st["n_kept"]),
+            rows_flag=0 if semantics == "std_3dgs" else _ffi.rows_flag(n, int(st["n_visible"])),
+            plain=(not movable_camera) and int(st.get("n_redo", 1)) == 0 and int(st.get("n_tiles", 0)) >= _PLAIN_MIN_TILES,
+            pinned=torch.zeros(ctypes.sizeof(_ffi.GsxFrameStats), dtype=torch.uint8).pin_memory(), inputs=[],
+            hints=[torch.zeros(lib.gsx_hints_bytes(cam.width, cam.height, tile_size), dtype=torch.uint8, device=dev), False])
         stream = torch.cuda.Stream(dev)
         with torch.cuda.stream(stream):   # the same call once on the capture stream, outside the capture
-            self.render_image_hip(image_idx, _private=private, **kw)
+            self.render_image_hip(image_idx, _private=own, **kw)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=stream):
-            self.render_image_hip(image_idx, no_sync=True, _private=private, **kw)
+            self.render_image_hip(image_idx, no_sync=True, _private=own, **kw)
         call = dict(image_idx=image_idx, **kw)
-        frame = CapturedFrame(self, graph, out, private["pinned"], call, camera_buffer=cam_buf,
-                              workspace=private["workspace"], capacity=cap, inputs=private["inputs"])
-        frame._hints = private["hints"][0]     # the recorded kernels read and refresh this buffer on every replay
-        frame._plain_footprints = bool(private["plain"])
+        frame = CapturedFrame(self, graph, out, own.pinned, call, camera_buffer=cam_buf, workspace=own.workspace,
+                              capacity=cap, inputs=own.inputs)
+        frame._hints = own.hints[0]     # the recorded kernels read and refresh this buffer on every replay
+        frame._plain_footprints = bool(own.plain)
         return frame
 
     def render_image(self, image_idx: int, tile_size: int = 16, geometry_gradients: bool = False) -> torch.Tensor:
@@ -897,8 +914,6 @@ class GaussianScene:
         """Extent (a, b) of what a ``ref_cpu`` frame of this camera renders, in the order of the frame's two leading axes:
         whole tiles from the origin, the last tile row and column left out (``strips.tiles_along``).  Everything outside is
         the zeros the frame was cleared to -- not a rendering of black."""
-        from .strips import tiles_along
-
         if layout not in ("wh3", "hw3"):
             raise ValueError("layout must be 'wh3' or 'hw3', got %r" % (layout,))
         cam = self.images[image_idx].gsx_camera()
@@ -910,8 +925,6 @@ class GaussianScene:
                          lambda_dssim: float = 0.2, layout: str = "wh3", terms: Optional[dict] = None) -> torch.Tensor:
         """``loss.photometric_loss`` of a ``ref_cpu`` frame of this camera against ``target`` over ``rendered_region``: the
         rim no tile covers takes no part and receives an exact zero gradient."""
-        from .loss import photometric_loss
-
         region = self.rendered_region(image_idx, tile_size, layout)
         if region[0] <= 0 or region[1] <= 0:
             raise ValueError("a %s frame of camera %r has no rendered tile at tile_size %d (extent <= tile)" % (
@@ -935,13 +948,8 @@ class GaussianScene:
 
         def finish(k: int) -> torch.Tensor:
             copied[k].synchronize()
-            if checks[k] is not None:
-                pinned, cap_key, ran_plain, call = checks[k]
-                st = ctypes.cast(ctypes.c_void_p(pinned.data_ptr()), ctypes.POINTER(_ffi.GsxFrameStats)).contents
-                self._note_count(cap_key, int(st.n_instances), int(st.n_kept), int(st.n_redo))
-                if st.n_instances > st.reserved or (ran_plain and st.n_redo > 0):    # dropped pairs / tiles left undone: once more, synchronously
-                    self.render_image_hip(**call)
-                    hosts[k].copy_(frames[k])
+            if checks[k] is not None and self._settle(checks[k]):    # dropped pairs / tiles left undone: rendered once more
+                hosts[k].copy_(frames[k])
             return hosts[k]
 
         for n, idx in enumerate(image_indices):

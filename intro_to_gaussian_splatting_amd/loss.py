@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _ffi
-from .gaussian_scene import _WORKSPACE, _ptr, _stream_handle
+from ._device import _WORKSPACE, _ptr, _stream_handle
 
 
 def _check_image(name: str, t: torch.Tensor, device: Optional[torch.device] = None) -> torch.Tensor:

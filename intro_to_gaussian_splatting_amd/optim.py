@@ -14,7 +14,7 @@ from typing import Callable, Dict, Iterable, Tuple, Union
 import torch
 
 from . import _ffi
-from .gaussian_scene import _stream_handle
+from ._device import _stream_handle
 
 GROUP_NAMES = ("points", "scales", "quaternions", "opacity", "colors", "sh")
 LearningRate = Union[float, Callable[[int], float]]

@@ -387,3 +387,133 @@ def test_block_bounds_follow_points_and_scales():
     assert float(g.current_block_bounds()[0, 3]) == float(g.scales[:256].abs().max()) and g.block_bounds.data_ptr() == addr
     plain = Gaussians(torch.rand(10, 3), torch.rand(10, 3), device="cpu")
     assert plain.current_block_bounds() is None
+
+
+def test_owned_frame_record_converts_dicts_and_rejects_unknown_keys():
+    """render_image_hip(_private=...): a dict becomes the typed record once, a misspelt key is a TypeError instead of being
+    ignored, and the empty dict keeps meaning what None means: a frame that owns nothing."""
+    from intro_to_gaussian_splatting_amd.gaussian_scene import _OwnedFrame
+
+    ws, pinned, hints, inputs = torch.zeros(8, dtype=torch.uint8), torch.zeros(64, dtype=torch.uint8), [torch.zeros(4), False], []
+    d = dict(cap=77, workspace=ws, kept=5, rows_flag=4, plain=True, pinned=pinned, inputs=inputs, hints=hints)
+    own = _OwnedFrame.of(d)
+    assert isinstance(own, _OwnedFrame) and _OwnedFrame.of(own) is own
+    assert (own.cap, own.kept, own.rows_flag, own.plain) == (77, 5, 4, True)
+    assert own.workspace is ws and own.pinned is pinned and own.inputs is inputs and own.hints is hints
+    some = _OwnedFrame.of(dict(cap=3, workspace=ws, hints=hints))          # what the guarded-buffer test passes
+    assert some.cap == 3 and some.kept is None and some.rows_flag == 0 and some.plain is None and some.pinned is None
+    assert some.inputs is None
+    with pytest.raises(TypeError):
+        _OwnedFrame.of(dict(cap=3, workspce=ws))
+    assert _OwnedFrame.of({}) is None and _OwnedFrame.of(None) is None
+
+
+def test_next_attempt_follows_the_rules_of_the_frame_loop():
+    """gaussian_scene._next_attempt, case by case: the plain fallback first, then the row class -- not for a speculative or
+    owned call or under std_3dgs --, then a larger workspace unless the capacity is fixed; anything else is the outcome."""
+    from intro_to_gaussian_splatting_amd import _ffi
+    from intro_to_gaussian_splatting_amd.gaussian_scene import _next_attempt
+
+    ok, small = _ffi.GSX_OK, _ffi.GSX_ERR_WORKSPACE_TOO_SMALL
+    plain, few, one = _ffi.GSX_FLAG_PLAIN_FOOTPRINTS, _ffi.GSX_FLAG_SMALL_BATCH, _ffi.GSX_FLAG_ONE_VISIBLE
+    other = _ffi.GSX_FLAG_HINTS_VALID | _ffi.GSX_FLAG_TIMING
+    assert len({plain, few, one, _ffi.GSX_FLAG_HINTS_VALID, _ffi.GSX_FLAG_TIMING}) == 5 and not other & (plain | few | one)
+    done = ("done", None)
+
+    def f(rc, n_visible, n_instances, n_redo, flags, n=9, speculative=False, owned=False, fixed_cap=False, semantics="ref_cpu"):
+        return _next_attempt(rc, n_visible, n_instances, n_redo, flags, n, speculative, owned, fixed_cap, semantics)
+
+    # 1. the plain instance ran and tiles were left undone: the flag goes, nothing else changes -- also before a row class
+    assert f(ok, 9, 500, 1, plain | other) == ("flags", other)
+    assert f(ok, 2, 500, 3, plain | other) == ("flags", other)
+    assert f(ok, 9, 500, 1, plain | other, owned=True, fixed_cap=True) == ("flags", other)
+    assert f(ok, 9, 500, 1, plain | other, speculative=True) == done
+    assert f(ok, 9, 500, 0, plain | other) == done and f(ok, 9, 500, 1, other) == done
+    # 2. the row class
+    cases = [((2, other), other | few), ((1, other), other | one), ((4, other | few), other), ((9, other | one), other),
+             ((1, other | few), other | one)]
+    for (n_visible, flags), want in cases:
+        assert f(ok, n_visible, 500, 0, flags) == ("flags", want), (n_visible, flags)
+        assert f(ok, n_visible, 500, 0, flags, owned=True) == done
+        assert f(ok, n_visible, 500, 0, flags, speculative=True) == done
+        assert f(ok, n_visible, 500, 0, flags, semantics="std_3dgs") == done
+        assert f(ok, n_visible, 500, 0, flags, semantics="ref_cuda") == ("flags", want)
+    assert f(ok, 2, 500, 0, other | few) == done and f(ok, 3, 3, 0, 0, n=3) == done and f(ok, 0, 0, 0, 0) == done
+    # 3. the workspace
+    assert f(small, 9, 1000, 0, other) == ("cap", 5346) == ("cap", int(1000 * 1.25) + 4096)
+    assert f(small, 9, 1000, 0, other, speculative=True) == ("cap", 5346)
+    assert f(small, 9, 1000, 0, other, owned=True) == ("cap", 5346)          # owned, but no capacity of its own
+    assert f(small, 9, 1000, 0, other, owned=True, fixed_cap=True) == done   # the error is what the caller sees
+    assert f(small, 2, 1000, 1, plain) == ("cap", 5346)                      # counts of a failed call decide nothing else
+    for rc in (_ffi.GSX_ERR_INVALID_ARGUMENT, _ffi.GSX_ERR_UNSUPPORTED):
+        assert f(rc, 2, 1000, 1, plain) == done and f(rc, 9, 1000, 0, 0, fixed_cap=True) == done
+    # the worst sequence ends within the six rounds of the loop: plain wrong, row class wrong, too small twice
+    replies = [(ok, 9, 500, 3), (ok, 2, 500, 0), (small, 2, 1000, 0), (small, 2, 6000, 0), (ok, 2, 6000, 0)]
+    flags, cap, seen = plain | other, 16, []
+    for rounds in range(1, 7):
+        rc, n_visible, n_instances, n_redo = replies[rounds - 1]
+        what, value = f(rc, n_visible, n_instances, n_redo, flags)
+        seen.append((what, value))
+        if what == "done":
+            break
+        flags, cap = (value, cap) if what == "flags" else (flags, value)
+    assert seen == [("flags", other), ("flags", other | few), ("cap", 5346), ("cap", 11596), done]
+    assert rounds == 5 and rc == ok and (flags, cap) == (other | few, 11596)
+
+
+def test_a_pending_frame_is_rendered_again_for_dropped_pairs_or_undone_tiles(tmp_path):
+    """GaussianScene._settle on hand-built GsxFrameStats in a frame's slot: the counts are filed for the view's next frame
+    either way, the frame is issued again -- with its own arguments -- only for dropped pairs or tiles left undone."""
+    import ctypes
+
+    from intro_to_gaussian_splatting_amd import _ffi
+    from intro_to_gaussian_splatting_amd.gaussian_scene import _frame_stats, _PendingFrame
+
+    sc = make_scene(50, 64, 48, seed=2)
+    write_colmap_text(str(tmp_path), sc)
+    g = Gaussians.from_arrays(sc["points"], sc["colors_0_255"], sc["scales"], sc["quaternions"], sc["opacity"], device="cpu")
+    scene = GaussianScene(str(tmp_path), g)
+    calls = []
+    scene.render_image_hip = lambda **kw: calls.append(kw)
+    key = (1, 16, None, "ref_cpu")
+    for n_instances, n_redo, ran_plain, again in ((100, 0, True, False), (101, 0, False, True), (101, 0, True, True),
+                                                  (100, 1, True, True), (100, 1, False, False)):
+        pinned = torch.zeros(ctypes.sizeof(_ffi.GsxFrameStats), dtype=torch.uint8)
+        st = _frame_stats(pinned)                   # a view of the slot, not a copy
+        st.n_instances, st.reserved, st.n_kept, st.n_redo = n_instances, 100, 40, n_redo
+        assert int(pinned.view(torch.int64)[1]) == n_instances
+        del calls[:]
+        assert scene._settle(_PendingFrame(pinned, key, ran_plain, dict(image_idx=1, tile_size=16))) is again
+        assert calls == ([dict(image_idx=1, tile_size=16)] if again else [])
+        assert scene._cap_hints[key] == int(n_instances * 1.1) + 4096 and scene._kept_hints[key] == 40
+        assert scene._n_redo_seen[key] == n_redo and scene._last_instances == n_instances
+
+
+def test_device_helpers_are_a_leaf_module():
+    """_device.py (pointers, stream handles, the scratch buffers) imports nothing of the package, and the loss, the
+    optimiser and the density control reach it without the scene class and its COLMAP readers.  The package's own
+    __init__ imports the scene for its public names, so the fresh interpreter is given the bare package instead."""
+    import subprocess
+    import sys
+
+    from intro_to_gaussian_splatting_amd import _device, density, gaussian_scene, loss, optim
+
+    code = ("import sys, types\n"
+            "name = 'intro_to_gaussian_splatting_amd'\n"
+            "pkg = types.ModuleType(name)\n"
+            "pkg.__path__ = [sys.argv[1]]\n"
+            "sys.modules[name] = pkg\n"
+            "import intro_to_gaussian_splatting_amd._device\n"
+            "print(sorted(m for m in sys.modules if m.startswith(name + '.')))\n"
+            "from intro_to_gaussian_splatting_amd import loss, optim, density\n"
+            "print(sorted(m for m in sys.modules if m.startswith(name + '.')))\n")
+    r = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "intro_to_gaussian_splatting_amd")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    alone, with_users = [eval(line) for line in r.stdout.strip().splitlines()]
+    p = "intro_to_gaussian_splatting_amd."
+    assert alone == [p + "_device"]
+    assert with_users == [p + m for m in ("_device", "_ffi", "density", "loss", "optim")]
+    assert loss._WORKSPACE is gaussian_scene._WORKSPACE is _device._WORKSPACE
+    assert gaussian_scene._Lru is _device._Lru and gaussian_scene._Workspace is _device._Workspace
+    assert optim._stream_handle is density._stream_handle is gaussian_scene._stream_handle is _device._stream_handle
