@@ -419,6 +419,33 @@ GSX_API int gsx_render_backward_geometry(const GsxCamera *camera, const float *m
 GSX_API size_t gsx_backward_geometry_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
 
 /*
+ * gsx_render_backward_geometry plus what screen-space density control reads (gsx_density_accumulate_screen): the same
+ * arguments with two more outputs behind grad_quats, the same refusals (and grad_means2d NULL), the same synchronisation, the
+ * same workspace (gsx_backward_geometry_workspace_bytes), no float atomics: same inputs, same bits.  The five older outputs
+ * hold the bits gsx_render_backward_geometry writes.
+ *   grad_means2d (n,2), required: dL/d(NDC mean), the published trainer's viewspace_points.grad[:, :2]:
+ *       (dL/dmean_x (width - 1) / 2,  dL/dmean_y (height - 1) / 2),   dL/dmean = -1/2 (Q + Q^T) sum u d
+ *     over every composited (Gaussian, pixel), with d = mean - pixel in pixels and u = dL/dpower -- the very values the chain
+ *     to dL/dmeans3d starts from.  In float32, from the Gaussian's moment sums S1 = sum u d0, S2 = sum u d1 and the conic Q as
+ *     the frame's record stores it:
+ *       gmx = -0.5f * (2.0f * q00 * S1 + (q01 + q10) * S2)        gmy = -0.5f * ((q01 + q10) * S1 + 2.0f * q11 * S2)
+ *       grad_means2d = (gmx * sx, gmy * sy),   sx = ((float)width - 1.0f) * 0.5f,   sy = ((float)height - 1.0f) * 0.5f
+ *     every operation rounded on its own, the products and sums left to right as written.  It is the rasteriser's share
+ *     only: for an SH scene the view direction's share of dL/dmeans3d (gsx_sh_backward) is not in it, as published.
+ *   screen_radius (n), may be NULL: for a Gaussian on at least one tile list of the frame the forward's radius in pixels,
+ *     ceilf(3 sqrtf(lam)) -- the bits gsx_preprocess reports in `radius`, in the row class the call runs with
+ *     (GSX_FLAG_ONE_VISIBLE / GSX_FLAG_SMALL_BATCH).
+ * Both are written for every row: exact +0 for a Gaussian that is culled or on no tile list, so screen_radius > 0 says
+ * "this frame listed the Gaussian", whatever its gradient.
+ */
+GSX_API int gsx_render_backward_screen(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                               const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                               const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                               float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                               float *screen_radius /* may be NULL */, const GsxParams *params, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =
  * (R S)(R S)^T from linear scales (n,3) and quaternions (n,4) (w,x,y,z), the quaternion
  * normalised twice as the reference does.  The render entry points compute this inline; the
@@ -561,12 +588,13 @@ GSX_API int gsx_adam_step(const GsxAdamGroup *groups /* host */, int32_t n_group
  * Device pointers only, the caller owns all memory, nothing is allocated, no atomics: same inputs, same bits.  Every float32
  * operation below is rounded on its own (no fused multiply-add; divide and sqrt correctly rounded).
  *
- * Three differences from the published method, on purpose:
- *  (1) the statistic is the norm of the gradient array the caller names (the Python surface passes dL/dpoints), not of the
- *      screen-space mean gradient, which gsx_render_backward_geometry keeps internal;
- *  (2) pruning wins over densifying and a split's children are not examined until the next round (the published order
+ * Two statistics.  gsx_density_accumulate takes the norm of any gradient array the caller names (the Python surface's default
+ * passes dL/dpoints, in world units); gsx_density_accumulate_screen takes the published one, the norm of the screen-space mean
+ * gradient that gsx_render_backward_screen exports, and gsx_density_plan_screen adds the published prune on the screen radius.
+ * Two differences from the published method remain, on purpose:
+ *  (1) pruning wins over densifying and a split's children are not examined until the next round (the published order
  *      densifies first and prunes the children in the same round);
- *  (3) rows stay in source order with the new rows BESIDE their parent (the published order appends them at the end):
+ *  (2) rows stay in source order with the new rows BESIDE their parent (the published order appends them at the end):
  *      spatial locality is kept, the order is stable, and one scan places every row.
  *
  * gsx_density_accumulate: grad (n, width) float32, read only; grad_sum (n) float32; seen (n) uint32.  Per row
@@ -574,6 +602,16 @@ GSX_API int gsx_adam_step(const GsxAdamGroup *groups /* host */, int32_t n_group
  * if any element of the row is not +0 or -0 (a NaN is not zero): grad_sum[i] += norm and seen[i] += 1.  A row of zeros touches
  * neither array.  Does not synchronise.  n == 0 is GSX_OK.  Refused (GSX_ERR_INVALID_ARGUMENT, gsx_last_error names the
  * argument, before any HIP call): n < 0 or n > 2^30; width outside 1 .. 2^20; when n > 0, grad, grad_sum or seen NULL.
+ *
+ * gsx_density_accumulate_screen: grad_means2d (n,2) and screen_radius (n) float32 as gsx_render_backward_screen wrote them, read
+ * only; grad_sum (n) float32; seen (n) uint32; radius_max (n) float32.  Per row, if screen_radius[i] > 0 (a NaN fails the
+ * comparison):
+ *   norm = sqrtf(g0 g0 + g1 g1);   grad_sum[i] += norm;   seen[i] += 1;
+ *   radius_max[i] = r > radius_max[i] ? r : radius_max[i]          (r = screen_radius[i]; a NaN radius_max[i] stays)
+ * otherwise the row touches none of the three.  This differs from gsx_density_accumulate on purpose: a row counts as seen when
+ * the frame LISTED it, zero gradient or not (and a NaN gradient is added as it is), because the published denominator counts
+ * visibility, not non-zero gradients.  Does not synchronise.  n == 0 is GSX_OK.  Refused, before any HIP call: n < 0 or
+ * n > 2^30; when n > 0, grad_means2d, screen_radius, grad_sum, seen or radius_max NULL.
  *
  * gsx_density_plan: one action per row i, the comparisons exactly as written, in float32 (a NaN fails every comparison, so a
  * row whose statistic, scales or opacity are NaN where they are compared is KEEP unless another comparison decides), with
@@ -590,6 +628,12 @@ GSX_API int gsx_adam_step(const GsxAdamGroup *groups /* host */, int32_t n_group
  * once, after its last launch.  n == 0 is GSX_OK with four zeros.  Refused: grad_sum, seen, scales, opacity_logit (n > 0),
  * rules, counts_host or workspace NULL; n < 0 or n > 2^30; rules->flags != 0; rules->split_shrink not a positive finite
  * number; a workspace that is not 256-byte aligned; fewer bytes than asked for: GSX_ERR_WORKSPACE_TOO_SMALL.
+ *
+ * gsx_density_plan_screen: gsx_density_plan with one more way to PRUNE, the published prune of Gaussians that grew too large
+ * on screen:   PRUNE: ... or radius_max[i] > prune_radius   (float32; a NaN radius_max[i] fails the comparison, exactly
+ * equal is not pruned, prune_radius = +inf never prunes).  radius_max (n) may be NULL: the rule is off, and the workspace and the
+ * four counts are gsx_density_plan's byte for byte.  Everything else -- the other rules, the workspace, counts_host, the one
+ * synchronisation, the refusals -- is gsx_density_plan's; also refused: a prune_radius that is NaN.  The plan feeds gsx_density_apply.
  *
  * gsx_density_apply: every group g is rewritten from src (n, width) into dst (n_out, width), all groups in one launch:
  *   KEEP:  the row is copied, whatever the role.
@@ -633,6 +677,12 @@ GSX_API size_t gsx_density_workspace_bytes(int64_t n);   /* 0 on invalid argumen
 GSX_API int gsx_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
                              int64_t n, const GsxDensityRules *rules, void *workspace, size_t workspace_bytes,
                              int64_t *counts_host /* 4 */, void *stream);
+GSX_API int gsx_density_accumulate_screen(const float *grad_means2d, const float *screen_radius, int64_t n, float *grad_sum,
+                                          uint32_t *seen, float *radius_max, void *stream);
+GSX_API int gsx_density_plan_screen(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
+                                    const float *radius_max /* may be NULL */, float prune_radius, int64_t n,
+                                    const GsxDensityRules *rules, void *workspace, size_t workspace_bytes,
+                                    int64_t *counts_host /* 4 */, void *stream);
 GSX_API int gsx_density_apply(const GsxDensityGroup *groups /* host */, int32_t n_groups, int64_t n, int64_t n_out,
                               const float *noise /* (n,2,3), may be NULL without a POINTS group */,
                               int32_t *source_row /* (n_out), may be NULL */, void *workspace, size_t workspace_bytes,

@@ -380,9 +380,11 @@ int bin_and_blend(const Plan &p, const Carve &c, char *ws, int64_t n, int64_t ca
 thread_local float g_backward_ms[3] = {0.0f, 0.0f, 0.0f};
 #endif
 
-// The three outputs gsx_render_backward_geometry adds.
+// The three outputs gsx_render_backward_geometry adds, and the two gsx_render_backward_screen adds to those (null / null:
+// the geometry entry; radius may be null on its own).
 struct GeometryGrads {
     float *means3d, *scales, *quats;
+    float *means2d = nullptr, *radius = nullptr;
 };
 
 // gsx_render_backward (geo == nullptr) and gsx_render_backward_geometry: one body.  The geometry call carves the third
@@ -424,6 +426,8 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means3d, (size_t)n * 3, s));
         GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->scales, (size_t)n * 3, s));
         GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->quats, (size_t)n * 4, s));
+        if (geo->means2d) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means2d, (size_t)n * 2, s));
+        if (geo->radius) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->radius, (size_t)n, s));
     }
     if (n == 0 || p.grid.count() == 0) {
         GSX_HIP(hipStreamSynchronize(s));
@@ -462,7 +466,7 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
     if (geo)
         GSX_HIP(gsx::launch_backward_geometry(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
-                                              geo->scales, geo->quats, s));
+                                              geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s));
     tm.mark();  // 3: sums (and the geometry chain)
     GSX_HIP(hipStreamSynchronize(s));
 #ifdef GSX_TEST_HOOKS
@@ -652,6 +656,20 @@ int gsx_render_backward_geometry(const GsxCamera *camera, const float *means3d, 
                            grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
 }
 
+int gsx_render_backward_screen(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                               const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                               const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                               float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                               float *screen_radius, const GsxParams *params, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+    if (!grad_means3d || !grad_scales || !grad_quats)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
+    if (!grad_means2d) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d is NULL");
+    const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
+    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+}
+
 #ifdef GSX_TEST_HOOKS
 int gsx_debug_backward_stage_ms(float *out3) {
     if (!out3) return fail(GSX_ERR_INVALID_ARGUMENT, "out3 is NULL");
@@ -776,6 +794,20 @@ int gsx_density_accumulate(const float *grad, int32_t width, int64_t n, float *g
     return GSX_OK;
 }
 
+int gsx_density_accumulate_screen(const float *grad_means2d, const float *screen_radius, int64_t n, float *grad_sum,
+                                  uint32_t *seen, float *radius_max, void *stream) {
+    if (n < 0 || n > kDensityMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (n > 0) {
+        if (!grad_means2d) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d is NULL");
+        if (!screen_radius) return fail(GSX_ERR_INVALID_ARGUMENT, "screen_radius is NULL");
+        if (!grad_sum) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_sum is NULL");
+        if (!seen) return fail(GSX_ERR_INVALID_ARGUMENT, "seen is NULL");
+        if (!radius_max) return fail(GSX_ERR_INVALID_ARGUMENT, "radius_max is NULL");
+    }
+    GSX_HIP(gsx::launch_density_accumulate_screen(grad_means2d, screen_radius, n, grad_sum, seen, radius_max, (hipStream_t)stream));
+    return GSX_OK;
+}
+
 size_t gsx_density_workspace_bytes(int64_t n) {
     DensityCarve c;
     return density_carve(n, c) ? c.total : 0;
@@ -792,15 +824,17 @@ int check_density_workspace(int64_t n, const void *workspace, size_t workspace_b
                     (long long)n, c.total);
     return GSX_OK;
 }
-}  // namespace
 
-int gsx_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit, int64_t n,
-                     const GsxDensityRules *rules, void *workspace, size_t workspace_bytes, int64_t *counts_host, void *stream) {
+// gsx_density_plan (radius_max == nullptr, prune_radius = +inf) and gsx_density_plan_screen: one body
+int density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
+                 const float *radius_max, float prune_radius, bool screen, int64_t n, const GsxDensityRules *rules, void *workspace,
+                 size_t workspace_bytes, int64_t *counts_host, void *stream) {
     if (!rules) return fail(GSX_ERR_INVALID_ARGUMENT, "rules is NULL");
     if (!counts_host) return fail(GSX_ERR_INVALID_ARGUMENT, "counts_host is NULL");
     if (rules->flags != 0u) return fail(GSX_ERR_INVALID_ARGUMENT, "rules->flags 0x%x has unknown bits", rules->flags);
     if (!(rules->split_shrink > 0.0f && rules->split_shrink <= FLT_MAX))
         return fail(GSX_ERR_INVALID_ARGUMENT, "rules->split_shrink %g is not a positive finite number", (double)rules->split_shrink);
+    if (prune_radius != prune_radius) return fail(GSX_ERR_INVALID_ARGUMENT, "prune_radius is NaN");
     DensityCarve c;
     const int rc = check_density_workspace(n, workspace, workspace_bytes, c);
     if (rc != GSX_OK) return rc;
@@ -813,10 +847,28 @@ int gsx_density_plan(const float *grad_sum, const uint32_t *seen, const float *s
     for (int i = 0; i < 4; ++i) counts_host[i] = 0;
     if (n == 0) return GSX_OK;
     hipStream_t s = (hipStream_t)stream;
-    GSX_HIP(gsx::launch_density_plan(grad_sum, seen, scales, opacity_logit, n, *rules, (char *)workspace, c, s));
+    if (screen)
+        GSX_HIP(gsx::launch_density_plan_screen(grad_sum, seen, scales, opacity_logit, radius_max, prune_radius, n, *rules,
+                                                (char *)workspace, c, s));
+    else
+        GSX_HIP(gsx::launch_density_plan(grad_sum, seen, scales, opacity_logit, n, *rules, (char *)workspace, c, s));
     GSX_HIP(hipMemcpyAsync(counts_host, (const char *)workspace + 8, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     GSX_HIP(hipStreamSynchronize(s));
     return GSX_OK;
+}
+}  // namespace
+
+int gsx_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit, int64_t n,
+                     const GsxDensityRules *rules, void *workspace, size_t workspace_bytes, int64_t *counts_host, void *stream) {
+    return density_plan(grad_sum, seen, scales, opacity_logit, nullptr, INFINITY, false, n, rules, workspace, workspace_bytes,
+                        counts_host, stream);
+}
+
+int gsx_density_plan_screen(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
+                            const float *radius_max, float prune_radius, int64_t n, const GsxDensityRules *rules, void *workspace,
+                            size_t workspace_bytes, int64_t *counts_host, void *stream) {
+    return density_plan(grad_sum, seen, scales, opacity_logit, radius_max, prune_radius, true, n, rules, workspace,
+                        workspace_bytes, counts_host, stream);
 }
 
 int gsx_density_apply(const GsxDensityGroup *groups, int32_t n_groups, int64_t n, int64_t n_out, const float *noise,

@@ -27,6 +27,8 @@
 // (gsx_backward_tile.inc), also sums five moments of u = dL/dalpha alpha per record into a second slot array;
 // (2') backward_geometry_sum_kernel sums them per Gaussian and backward_geometry_chain_kernel carries them through stage 1's
 // derivative (geometry_chain, below).  The colour-only kernels and their slots are the same code and layout either way.
+// gsx_render_backward_screen is the geometry call with two more per-Gaussian stores in the chain kernel: dL/d(NDC mean), which
+// the chain forms anyway on its way to dL/dpoint, and the radius project_raw_kernel left in the raw record's last word.
 //
 // alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
@@ -202,7 +204,7 @@ struct GeoCamera {
 __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float *__restrict__ p, const float *__restrict__ sc,
                                                const float *__restrict__ qin, const float4 QA, const float4 QB,
                                                float S1, float S2, float S3, float S4, float S5, float *__restrict__ gp,
-                                               float *__restrict__ gs, float *__restrict__ gq) {
+                                               float *__restrict__ gs, float *__restrict__ gq, float *__restrict__ gn) {
     const float *V = cam.V, *F = cam.F;
     const float p0 = p[0], p1 = p[1], p2 = p[2];
     // ---- forward values
@@ -345,7 +347,9 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
     const float h0 = __builtin_fmaf(p2, F[8], __builtin_fmaf(p1, F[4], p0 * F[0])) + F[12];
     const float h1 = __builtin_fmaf(p2, F[9], __builtin_fmaf(p1, F[5], p0 * F[1])) + F[13];
     const float h3 = __builtin_fmaf(p2, F[11], __builtin_fmaf(p1, F[7], p0 * F[3])) + F[15];
-    const float gn0 = gmx * cam.sx, gn1 = gmy * cam.sy;
+    const float gn0 = gmx * cam.sx, gn1 = gmy * cam.sy;     // dL/d(NDC mean): gsx_render_backward_screen's grad_means2d
+    gn[0] = gn0;
+    gn[1] = gn1;
     const float gh0 = gn0 / h3, gh1 = gn1 / h3;
     const float gh3 = -(gn0 * h0 + gn1 * h1) / (h3 * h3);
 #pragma unroll
@@ -379,12 +383,15 @@ __global__ void __launch_bounds__(256)
 }
 
 // One thread per depth rank: the chain on the sums backward_geometry_sum_kernel left, the Gaussian's three rows written.
+// gsx_render_backward_screen (grad_means2d not null) also gets the chain's dL/d(NDC mean) and (screen_radius, or null) the
+// radius project_raw_kernel left in the record's last word; the launch has zeroed both for the rows this kernel skips.
 __global__ void __launch_bounds__(256)
     backward_geometry_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
                                    const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m, GeoCamera cam,
                                    const float *__restrict__ means3d, const float *__restrict__ scales,
                                    const float *__restrict__ quats, float *__restrict__ grad_means3d,
-                                   float *__restrict__ grad_scales, float *__restrict__ grad_quats) {
+                                   float *__restrict__ grad_scales, float *__restrict__ grad_quats,
+                                   float *__restrict__ grad_means2d, float *__restrict__ screen_radius) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= m) return;
     const uint32_t b = prefix[r];
@@ -392,8 +399,8 @@ __global__ void __launch_bounds__(256)
     const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
     const int64_t row = order[r];
     const Record rec = raw[row];
-    float gp[3], gs[3], gq[4];
-    geometry_chain(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq);
+    float gp[3], gs[3], gq[4], gn[2];
+    geometry_chain(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq, gn);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         grad_means3d[3 * row + k] = gp[k];
@@ -401,6 +408,11 @@ __global__ void __launch_bounds__(256)
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
+    if (grad_means2d) {
+        grad_means2d[2 * row] = gn[0];
+        grad_means2d[2 * row + 1] = gn[1];
+        if (screen_radius) screen_radius[row] = rec.c.w;
+    }
 }
 
 }  // namespace
@@ -435,7 +447,7 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
 hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
                                     const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, hipStream_t s) {
+                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s) {
     if (m == 0) return hipSuccess;
     GeoCamera cam;
     for (int i = 0; i < 16; ++i) {
@@ -450,7 +462,8 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
     cam.sy = ((float)camera.height - 1.0f) * 0.5f;
     backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
     backward_geometry_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
-        geo_slots, prefix, order, raw, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats);
+        geo_slots, prefix, order, raw, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
+        screen_radius);
     return hipGetLastError();
 }
 

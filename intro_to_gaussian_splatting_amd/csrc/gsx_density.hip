@@ -21,38 +21,12 @@
 // of four floats and both runs are 16-byte aligned, a quad is one 16-byte load as well.  The group index is uniform,
 // so the descriptors are read from the kernel-argument segment with scalar loads.  Each element of a surviving row is read
 // once and written once; nothing is read of a pruned row but its action.
-#include "gsx_internal.h"
+#include "gsx_density_device.h"
 
 namespace gsx {
 namespace {
 
-constexpr int kThreads = 256, kScanPer = kDensityScanRows / kThreads;
-static_assert(kScanPer == 4, "a thread packs its four action bytes into one word");
-
-__device__ __forceinline__ uint32_t rows_of(uint32_t action) {
-    return action == kDensityPrune ? 0u : (action == kDensityKeep ? 1u : 2u);
-}
-
-// max(a, b) that is NaN when either is
-__device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-
-// Exclusive scan of one value per thread over the 256 threads of the workgroup; total = the sum.
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t *lds, uint32_t &total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 1; s < kThreads; s <<= 1) {
-        const uint32_t add = t >= s ? lds[t - s] : 0u;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    total = lds[kThreads - 1];
-    const uint32_t incl = lds[t];
-    __syncthreads();
-    return incl - v;
-}
+using namespace density;    // kThreads, kScanPer, rows_of, max_nan, block_exclusive, classify, leave_block
 
 __global__ void __launch_bounds__(kThreads)
     density_accumulate_kernel(const float *__restrict__ grad, uint32_t width, int64_t n, float *__restrict__ grad_sum,
@@ -70,19 +44,6 @@ __global__ void __launch_bounds__(kThreads)
     if (!any) return;
     grad_sum[i] = grad_sum[i] + sqrtf(sum);
     seen[i] = seen[i] + 1u;
-}
-
-__device__ __forceinline__ uint32_t classify(const float *__restrict__ grad_sum, const uint32_t *__restrict__ seen,
-                                             const float *__restrict__ scales, const float *__restrict__ opacity_logit,
-                                             int64_t i, const GsxDensityRules &r) {
-    const float smax = max_nan(max_nan(scales[3 * i], scales[3 * i + 1]), scales[3 * i + 2]);
-    if (opacity_logit[i] < r.prune_logit || smax > r.prune_scale) return kDensityPrune;
-    const uint32_t c = seen[i];
-    if (c > 0u && grad_sum[i] / (float)c >= r.grad_threshold) {
-        if (smax > r.dense_scale) return kDensitySplit;
-        if (smax <= r.dense_scale) return kDensityClone;
-    }
-    return kDensityKeep;
 }
 
 // Per 1024 rows: the action bytes (rows behind n: PRUNE, counted nowhere), and the block's output rows, pruned and split rows.
@@ -104,15 +65,7 @@ __global__ void __launch_bounds__(kThreads)
         }
         word |= a << (8 * k);
     }
-    action4[(size_t)blockIdx.x * kThreads + threadIdx.x] = word;
-    uint32_t total, total2;
-    (void)block_exclusive(out, lds, total);
-    (void)block_exclusive(tally, lds, total2);
-    if (threadIdx.x == 0) {
-        bsum[blockIdx.x] = total;
-        bpruned[blockIdx.x] = total2 & 0xffffu;
-        bsplit[blockIdx.x] = total2 >> 16;
-    }
+    leave_block(word, out, tally, lds, action4, bsum, bpruned, bsplit);
 }
 
 // One workgroup: exclusive scan of the nb block sums in place (bsum[nb] = n_out), the pruned and split totals, the header.
@@ -298,10 +251,19 @@ hipError_t launch_density_plan(const float *grad_sum, const uint32_t *seen, cons
                                int64_t n, const GsxDensityRules &rules, char *ws, const DensityCarve &c, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const uint32_t nb = c.scan_blocks;
-    uint32_t *action4 = reinterpret_cast<uint32_t *>(ws + c.action), *prefix = reinterpret_cast<uint32_t *>(ws + c.prefix);
+    uint32_t *action4 = reinterpret_cast<uint32_t *>(ws + c.action);
     uint32_t *bsum = reinterpret_cast<uint32_t *>(ws + c.bsum), *bpruned = bsum + nb + 1, *bsplit = bpruned + nb;
     density_classify_kernel<<<nb, kThreads, 0, s>>>(grad_sum, seen, scales, opacity_logit, n, rules, action4, bsum, bpruned, bsplit);
-    density_blocks_kernel<<<1, kThreads, 0, s>>>(bsum, bpruned, bsplit, nb, n, rules.split_shrink, ws);
+    return launch_density_plan_finish(n, rules.split_shrink, ws, c, s);
+}
+
+// The plan behind its classify launch (this file's or gsx_density_screen.hip's): block sums scanned, header, every row's place.
+hipError_t launch_density_plan_finish(int64_t n, float split_shrink, char *ws, const DensityCarve &c, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const uint32_t nb = c.scan_blocks;
+    uint32_t *action4 = reinterpret_cast<uint32_t *>(ws + c.action), *prefix = reinterpret_cast<uint32_t *>(ws + c.prefix);
+    uint32_t *bsum = reinterpret_cast<uint32_t *>(ws + c.bsum), *bpruned = bsum + nb + 1, *bsplit = bpruned + nb;
+    density_blocks_kernel<<<1, kThreads, 0, s>>>(bsum, bpruned, bsplit, nb, n, split_shrink, ws);
     density_final_kernel<<<nb, kThreads, 0, s>>>(action4, bsum, n, prefix);
     return hipGetLastError();
 }

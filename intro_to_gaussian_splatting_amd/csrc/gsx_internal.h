@@ -192,7 +192,7 @@ hipError_t launch_project_full(const Record *stage, const uint32_t *order, const
                                const StageOneOut &out, hipStream_t s);
 hipError_t launch_pack_preprocessed(const PreprocessedIn &in, int64_t n, const TileGrid &grid, int semantics,
                                     Record *rec, TileRect *rect, float4 *bbox, hipStream_t s);
-// The backward pass: per row, (x, y, Q00, Q01), (Q10, Q11, op, sigmoid(logit)), (r, g, b, 0) -- project_raw_kernel.
+// The backward pass: per row, (x, y, Q00, Q01), (Q10, Q11, op, sigmoid(logit)), (r, g, b, radius) -- project_raw_kernel.
 hipError_t launch_project_raw(const GsxCamera &cam, const GaussiansIn &in, int64_t n, int visible_rows, Record *raw, hipStream_t s);
 hipError_t launch_covariance3d(const float *scales, const float *quats, int64_t n, float *out, hipStream_t s);
 hipError_t launch_covariance2d(const GsxCamera &cam, const float *points, const float *cov3d, int64_t n, float *out,
@@ -377,6 +377,18 @@ hipError_t launch_density_accumulate(const float *grad, int32_t width, int64_t n
 hipError_t launch_density_plan(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
                                int64_t n, const GsxDensityRules &rules, char *ws, const DensityCarve &c, hipStream_t s);
 hipError_t launch_density_apply(const DensityArgs &args, int64_t n_out, hipStream_t s);
+// what launch_density_plan runs behind its classify kernel: the scan of the block sums with the header, then every row's
+// first output row (the action bytes and the three per-block counts are in `ws` by then)
+hipError_t launch_density_plan_finish(int64_t n, float split_shrink, char *ws, const DensityCarve &c, hipStream_t s);
+
+// ---- gsx_density_screen.hip
+// gsx_density_accumulate_screen / gsx_density_plan_screen behind their argument checks.  The plan's workspace is
+// gsx_density_plan's (radius_max may be null: the same bytes).
+hipError_t launch_density_accumulate_screen(const float *grad_means2d, const float *screen_radius, int64_t n, float *grad_sum,
+                                            uint32_t *seen, float *radius_max, hipStream_t s);
+hipError_t launch_density_plan_screen(const float *grad_sum, const uint32_t *seen, const float *scales, const float *opacity_logit,
+                                      const float *radius_max, float prune_radius, int64_t n, const GsxDensityRules &rules,
+                                      char *ws, const DensityCarve &c, hipStream_t s);
 
 // ---- gsx_knn.hip
 // gsx_knn3 behind its argument checks.  The workspace of n rows (KnnCarve):
@@ -454,10 +466,11 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
                                 uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
 // gsx_render_backward_geometry: geometry slots of each rank summed in emission order (one wave per rank; the sums are
 // left in the rank's first slot), then one thread per rank runs the chain from dL/dQ and dL/dmean to the inputs
-// (gsx_backward.hip: geometry_chain) and scatters to rows (order[r])
+// (gsx_backward.hip: geometry_chain) and scatters to rows (order[r]).  gsx_render_backward_screen: grad_means2d (n,2) gets
+// the chain's dL/d(NDC mean) and screen_radius (n, or null) the record's radius; null for gsx_render_backward_geometry
 hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
                                     const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, hipStream_t s);
+                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s);
 
 }  // namespace gsx

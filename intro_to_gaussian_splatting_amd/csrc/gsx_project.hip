@@ -996,8 +996,9 @@ namespace {
 // The backward pass (gsx_backward.hip): per ROW, the reference's own float32 stage-1 values of every Gaussian -- pixel mean,
 // raw conic, the opacity factor sigmoid(sigmoid(logit)) and sigmoid(logit) itself, the RGB colour -- by the operations the
 // whole-path projection runs (project, sigmoid_torch, sigmoidf: same bits), for the backward compositing kernel's
-// alpha_ref.  a = (x, y, Q00, Q01)  b = (Q10, Q11, op, s)  c = (r, g, b, 0).  Rows behind the cull plane get whatever the
-// arithmetic gives: no tile list names them.
+// alpha_ref.  a = (x, y, Q00, Q01)  b = (Q10, Q11, op, s)  c = (r, g, b, radius).  Rows behind the cull plane get whatever the
+// arithmetic gives: no tile list names them.  radius is finish_projection's ceilf(3 sqrtf(lam)), the bits gsx_preprocess reports:
+// the compositing kernels copy c and never look at its last word; gsx_render_backward_screen's chain kernel delivers it.
 __global__ void __launch_bounds__(kBlock)
     project_raw_kernel(GsxCamera cam, GaussiansIn in, int64_t n, int vis, Record *__restrict__ raw) {
     const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -1011,7 +1012,7 @@ __global__ void __launch_bounds__(kBlock)
     Record r;
     r.a = make_float4(o.x, o.y, o.q00, o.q01);
     r.b = make_float4(o.q10, o.q11, sigmoidf(s), s);
-    r.c = make_float4(c[0], c[1], c[2], 0.0f);
+    r.c = make_float4(c[0], c[1], c[2], o.radius);
     raw[g] = r;
 }
 }  // namespace

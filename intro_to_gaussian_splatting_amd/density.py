@@ -1,7 +1,8 @@
 """Adaptive density control of a splat fit on the GPU: ``DensityControl`` (gsx_density_accumulate / gsx_density_plan /
-gsx_density_apply, include/gsx.h).
+gsx_density_apply and, with ``statistic="screen"``, gsx_density_accumulate_screen / gsx_density_plan_screen, include/gsx.h).
 
-After every ``backward()`` ``accumulate()`` adds the norm of each Gaussian's ``points.grad`` to a running statistic; every few
+After every ``backward()`` ``accumulate()`` adds the norm of each Gaussian's ``points.grad`` -- or, with
+``statistic="screen"``, of its screen-space mean gradient, the published statistic -- to a running statistic; every few
 hundred steps ``densify_and_prune()`` gives every Gaussian one action -- prune, clone, split or keep -- and rewrites every
 array of the container and both moment arrays of the optimiser in ONE library call: a survivor keeps the bits of its
 parameters and of its Adam moments, a new Gaussian starts with zero moments, and rows stay in source order with the children
@@ -30,13 +31,30 @@ class DensityControl:
     largest scale above ``prune_scale``; otherwise, where the mean accumulated gradient norm is at least ``grad_threshold``,
     SPLIT in two (scales divided by ``split_shrink``, positions drawn from the parent's own Gaussian) when the largest scale
     is above ``dense_scale`` and CLONE when it is not; KEEP everything else.  ``max_gaussians``: when a round would leave
-    more rows than this, it prunes only.  The statistic is the norm of dL/dpoints (world units), not the published
-    screen-space gradient, so the published 2e-4 is only a default to start from: set ``grad_threshold`` and ``dense_scale``
-    for the scene (the attributes may be changed between rounds)."""
+    more rows than this, it prunes only.
+
+    ``statistic``: what ``accumulate()`` adds up.
+    ``"points"`` (default): the norm of dL/dpoints, in world units, over the backward passes that gave the Gaussian a non-zero
+    gradient.  That is not the published statistic, so the published 2e-4 is only a default to start from: set
+    ``grad_threshold`` and ``dense_scale`` for the scene (the attributes may be changed between rounds).
+    ``"screen"`` (needs ``scene``): the published one.  Render with ``geometry_gradients=True, screen_statistics=True``;
+    ``accumulate()`` then consumes ``scene.screen_statistics`` -- the norm of dL/d(NDC mean), so ``grad_threshold`` is in
+    loss per NDC unit, the published convention, and the published 2e-4 means what it means there -- and counts a Gaussian as
+    seen whenever the frame listed it on a tile, zero gradient or not (gsx_density_accumulate_screen).  It also keeps the
+    largest screen radius seen, ``radius_max``, and a round PRUNES, besides the rules above, where that is above
+    ``prune_radius`` pixels (``math.inf``: never; gsx_density_plan_screen)."""
+
+    STATISTICS = ("points", "screen")
 
     def __init__(self, gaussians, optimizer=None, scene=None, grad_threshold: float = 2e-4, dense_scale: float = 0.01,
                  prune_logit: float = -5.3, prune_scale: float = math.inf, split_shrink: float = 1.6,
-                 max_gaussians: Optional[int] = None) -> None:
+                 max_gaussians: Optional[int] = None, statistic: str = "points", prune_radius: float = math.inf) -> None:
+        if statistic not in self.STATISTICS:
+            raise ValueError("statistic = %r is neither 'points' nor 'screen'" % (statistic,))
+        if statistic == "screen" and scene is None:
+            raise ValueError("statistic='screen' needs scene: accumulate() reads scene.screen_statistics")
+        if math.isnan(float(prune_radius)):
+            raise ValueError("prune_radius is NaN")
         if getattr(gaussians, "original_index", None) is not None:
             raise ValueError("the container is spatially ordered: its permutation and block boxes would be stale after a "
                              "round.  Densify the plain container and call spatially_ordered() again")
@@ -53,11 +71,13 @@ class DensityControl:
         self.prune_logit, self.prune_scale = float(prune_logit), float(prune_scale)
         self.split_shrink = float(split_shrink)
         self.max_gaussians = None if max_gaussians is None else int(max_gaussians)
+        self.statistic, self.prune_radius = statistic, float(prune_radius)
         self._check_arrays()
         dev = gaussians.points.device
         n = len(gaussians)
         self.grad_sum = torch.zeros(n, dtype=torch.float32, device=dev)
         self.seen = torch.zeros(n, dtype=torch.int32, device=dev)        # (the library's uint32)
+        self.radius_max = torch.zeros(n, dtype=torch.float32, device=dev) if statistic == "screen" else None
         self._workspace: Optional[torch.Tensor] = None
         self._groups = (_ffi.GsxDensityGroup * _ffi.GSX_DENSITY_MAX_GROUPS)()
 
@@ -94,16 +114,25 @@ class DensityControl:
         counts = (ctypes.c_int64 * 4)()
         rules = self._rules(grad_threshold)
         with torch.cuda.device(dev):
-            rc = _ffi.load().gsx_density_plan(self.grad_sum.data_ptr(), self.seen.data_ptr(), g.scales.data_ptr(),
-                                              g.opacity.data_ptr(), n, ctypes.byref(rules), self._workspace.data_ptr(),
-                                              self._workspace.numel(), counts, _stream_handle(dev))
+            if self.statistic == "screen":
+                rc = _ffi.load().gsx_density_plan_screen(self.grad_sum.data_ptr(), self.seen.data_ptr(), g.scales.data_ptr(),
+                                                         g.opacity.data_ptr(), self.radius_max.data_ptr(), self.prune_radius, n,
+                                                         ctypes.byref(rules), self._workspace.data_ptr(),
+                                                         self._workspace.numel(), counts, _stream_handle(dev))
+            else:
+                rc = _ffi.load().gsx_density_plan(self.grad_sum.data_ptr(), self.seen.data_ptr(), g.scales.data_ptr(),
+                                                  g.opacity.data_ptr(), n, ctypes.byref(rules), self._workspace.data_ptr(),
+                                                  self._workspace.numel(), counts, _stream_handle(dev))
         _ffi.check(rc)
         return dict(zip(COUNT_NAMES, (int(c) for c in counts)))
 
     # ------------------------------------------------------------------ the surface
     def accumulate(self) -> None:
         """After ``backward()``: adds |points.grad| of every Gaussian with a non-zero gradient row to the statistic and counts
-        it as seen (gsx_density_accumulate).  Allocates nothing after the first call."""
+        it as seen (gsx_density_accumulate).  Allocates nothing after the first call.  ``statistic="screen"``: consumes
+        ``scene.screen_statistics`` instead (``_accumulate_screen``)."""
+        if self.statistic == "screen":
+            return self._accumulate_screen()
         g = self.gaussians
         grad = g.points.grad
         if grad is None:
@@ -121,6 +150,31 @@ class DensityControl:
             rc = _ffi.load().gsx_density_accumulate(grad.data_ptr(), grad.numel() // n if n else 3, n, self.grad_sum.data_ptr(),
                                                     self.seen.data_ptr(), _stream_handle(dev))
         _ffi.check(rc)
+
+    def _accumulate_screen(self) -> None:
+        """After a ``backward()`` of a frame rendered with ``screen_statistics=True``: adds the norm of dL/d(NDC mean) of
+        every Gaussian the frame listed to the statistic, counts it as seen and keeps its largest radius
+        (gsx_density_accumulate_screen), then sets ``scene.screen_statistics`` to None: one backward is counted once."""
+        stat = self.scene.screen_statistics
+        if stat is None:
+            raise ValueError("scene.screen_statistics is None: render with geometry_gradients=True, screen_statistics=True and "
+                             "call backward() before every accumulate()")
+        _, grad, radius = stat
+        n = len(self.gaussians)
+        if grad.shape[0] != n or radius.shape[0] != n or self.grad_sum.shape[0] != n:
+            raise ValueError("the container has %d rows, scene.screen_statistics %d and the statistic %d: rows changed "
+                             "outside densify_and_prune()" % (n, grad.shape[0], self.grad_sum.shape[0]))
+        dev = self.grad_sum.device
+        for name, t, shape in (("grad_means2d", grad, (n, 2)), ("screen_radius", radius, (n,))):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != dev:
+                raise ValueError("scene.screen_statistics: %s must be contiguous float32 of shape %s on %s; there is no CPU "
+                                 "fallback" % (name, shape, dev))
+        with torch.cuda.device(dev):
+            rc = _ffi.load().gsx_density_accumulate_screen(grad.data_ptr(), radius.data_ptr(), n, self.grad_sum.data_ptr(),
+                                                           self.seen.data_ptr(), self.radius_max.data_ptr(),
+                                                           _stream_handle(dev))
+        _ffi.check(rc)
+        self.scene.screen_statistics = None
 
     def densify_and_prune(self, generator: Optional[torch.Generator] = None) -> Dict[str, int]:
         """One round: plan, rewrite every array and moment, install, reset the statistic and the scene's caches.  Returns
@@ -175,6 +229,8 @@ class DensityControl:
             opt.exp_avg_sq = {name: new[("exp_avg_sq", name)] for name in opt.names}
         self.grad_sum = torch.zeros(n_out, dtype=torch.float32, device=dev)
         self.seen = torch.zeros(n_out, dtype=torch.int32, device=dev)
+        if self.radius_max is not None:
+            self.radius_max = torch.zeros(n_out, dtype=torch.float32, device=dev)
         if self.scene is not None:
             self.scene.gaussians_changed()
         return counts

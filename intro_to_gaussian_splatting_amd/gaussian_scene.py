@@ -280,7 +280,8 @@ class _RenderImageFunction(torch.autograd.Function):
     gsx_render_backward -- dL/dcolors and dL/dopacity (logits); points, scales and quaternions get None, as in the
     reference.  With ``geometry_gradients=True``: gsx_render_backward_geometry -- also dL/dpoints, dL/dscales (linear
     scales) and dL/dquaternions, each for the tensors that require grad; the colour and opacity gradients are the same
-    bits.  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
+    bits.  With ``screen_statistics=True`` besides: gsx_render_backward_screen, the same five gradients, and
+    ``scene.screen_statistics`` = (image_idx, dL/d(NDC mean) (N,2), screen radius (N,)) left for ``DensityControl``.  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
     colour), and gsx_sh_backward carries that on to dL/dsh and -- with geometry gradients -- adds the view direction's
     share to dL/dpoints; ``colors`` gets None (the frame does not read it).  The tensors are saved, so autograd's version
     counters catch an in-place edit between forward and backward."""
@@ -289,6 +290,7 @@ class _RenderImageFunction(torch.autograd.Function):
     def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh):
         kw = dict(kw)
         ctx.geometry = bool(kw.pop("geometry_gradients", False))
+        ctx.screen = bool(kw.pop("screen_statistics", False))
         user_stats, st = kw.pop("stats", None), {}
         frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
         if user_stats is not None:
@@ -304,11 +306,14 @@ class _RenderImageFunction(torch.autograd.Function):
         points, scales, quaternions, opacity, colors, frame = ctx.saved_tensors[:6]
         scene = ctx.scene
         want = ctx.needs_input_grad
-        geometry = ctx.geometry and any(want[5:8])      # the colour-only call gives the same colour and opacity bits
+        # the colour-only call gives the same colour and opacity bits; the screen entry runs whoever requires grad
+        geometry = ctx.geometry and (ctx.screen or any(want[5:8]))
         grads = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
-                                       ctx.n_instances, ctx.n_visible, geometry=geometry)
+                                       ctx.n_instances, ctx.n_visible, geometry=geometry, screen=ctx.screen)
         gc, go = grads[:2]
-        gp, gs, gq = grads[2:] if geometry else (None, None, None)
+        gp, gs, gq = grads[2:5] if geometry else (None, None, None)
+        if ctx.screen:
+            scene.screen_statistics = (ctx.image_idx, grads[5], grads[6].view(-1))
         gsh = None
         if ctx.has_sh:      # gc is dL/d(view-dependent colour): on to the coefficients, and through the direction to the mean
             sh = ctx.saved_tensors[6]
@@ -344,6 +349,7 @@ class GaussianScene:
         self._part_events = {}        # (stream, K) -> K HIP events the library records behind the parts of a frame
         self._pinned_pool = None
         self._pinned_next = 0
+        self.screen_statistics = None   # (image_idx, dL/d(NDC mean) (N,2), radius (N,)) of the latest screen_statistics backward
 
     # ------------------------------------------------------------------ helpers
     def _colors(self, image_idx: int) -> torch.Tensor:
@@ -478,7 +484,8 @@ class GaussianScene:
                          tile_counts: Optional[torch.Tensor] = None, split_long_tiles: bool = True,
                          tile_schedule: Optional[bool] = None, use_hints: bool = True,
                          substrips: Optional[Sequence[int]] = None, substrip_events: Optional[list] = None,
-                         _private: Optional[dict] = None, geometry_gradients: bool = False) -> torch.Tensor:
+                         _private: Optional[dict] = None, geometry_gradients: bool = False,
+                         screen_statistics: bool = False) -> torch.Tensor:
         """Full forward render in libgsx (gsx_render_forward).
 
         semantics: "ref_cpu" (the reference's ``render_image``), "ref_cuda" (its CUDA kernel's rules
@@ -515,7 +522,16 @@ class GaussianScene:
         An SH scene is differentiable when ``gaussians.sh`` requires grad: dL/dsh (gsx_sh_backward) and dL/dopacity, and
         with ``geometry_gradients=True`` the geometry too, dL/dpoints including the share that reaches the mean through the
         view direction; an SH scene whose ``sh`` does not require grad is refused when gradients are asked for.
+        ``screen_statistics`` (needs ``geometry_gradients=True``): when the frame is differentiable its ``backward()`` runs
+        gsx_render_backward_screen -- whichever tensors require grad -- and leaves ``scene.screen_statistics`` =
+        (image_idx, dL/d(NDC mean) (N,2), screen radius in pixels (N,)), one row per row of the container, zeros for a
+        Gaussian the frame listed on no tile; every such backward replaces it, ``DensityControl(statistic="screen")``
+        consumes it.  It is the rasteriser's share, the published ``viewspace_points.grad[:, :2]``: an SH scene's
+        view-direction term (gsx_sh_backward) reaches ``points.grad`` only.  Gradients and frame are the same bits either way.
         """
+        if screen_statistics and not geometry_gradients:
+            raise ValueError("screen_statistics=True needs geometry_gradients=True: the statistic comes out of the geometry "
+                             "backward (gsx_render_backward_screen)")
         g = self.gaussians
         if _private is None and _wants_grad(g, bool(geometry_gradients)):
             # gradients (gsx_render_backward, gsx_render_backward_geometry, gsx_sh_backward): the whole ref_cpu frame only
@@ -524,7 +540,7 @@ class GaussianScene:
                     _refuse_with_grad(what)
             kw = dict(stats=stats, timing=timing, generic_kernels=generic_kernels, tile_counts=tile_counts,
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
-                      geometry_gradients=bool(geometry_gradients))
+                      geometry_gradients=bool(geometry_gradients), screen_statistics=bool(screen_statistics))
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
                                               g.opacity, g.colors, getattr(g, "sh", None))
         own = _OwnedFrame.of(_private)
@@ -725,10 +741,12 @@ class GaussianScene:
         return pinned, st
 
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
-                         n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False) -> Tuple[torch.Tensor, ...]:
+                         n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False,
+                         screen: bool = False) -> Tuple[torch.Tensor, ...]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
         ``grad_frame``; with ``geometry`` gsx_render_backward_geometry: those two and (dL/dpoints (N,3), dL/dscales (N,3),
-        dL/dquaternions (N,4)).  The projection, depth order and binning run again in the library (the same lists as the
+        dL/dquaternions (N,4)); with ``screen`` besides gsx_render_backward_screen: those five and (dL/d(NDC mean) (N,2),
+        screen radius (N,1)).  The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
         lib = _ffi.load()
@@ -746,10 +764,13 @@ class GaussianScene:
             go = torch.empty((n, 1), dtype=torch.float32, device=dev)
             outs = [gc, go]
             if geometry:
-                outs += [torch.empty((n, k), dtype=torch.float32, device=dev) for k in (3, 3, 4)]
+                outs += [torch.empty((n, k), dtype=torch.float32, device=dev) for k in (3, 3, 4) + ((2, 1) if screen else ())]
+            elif screen:
+                raise ValueError("screen needs geometry: the statistic comes out of the geometry backward")
             cap = int(n_instances) + 4096
             size_fn = lib.gsx_backward_geometry_workspace_bytes if geometry else lib.gsx_backward_workspace_bytes
-            entry = lib.gsx_render_backward_geometry if geometry else lib.gsx_render_backward
+            entry = (lib.gsx_render_backward_screen if screen else lib.gsx_render_backward_geometry) if geometry \
+                else lib.gsx_render_backward
             with torch.cuda.device(dev):
                 nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
                 if nbytes == 0:
@@ -803,6 +824,7 @@ class GaussianScene:
         self._hints.clear()
         self._instances_hint = 0
         self._last_instances = 0
+        self.screen_statistics = None       # its rows were the old rows
 
     def _pinned_slot(self) -> torch.Tensor:
         """One 64-byte slot of a pinned ring (pinning memory per frame would dominate the frame)."""
@@ -894,13 +916,15 @@ class GaussianScene:
         frame._plain_footprints = bool(own.plain)
         return frame
 
-    def render_image(self, image_idx: int, tile_size: int = 16, geometry_gradients: bool = False) -> torch.Tensor:
+    def render_image(self, image_idx: int, tile_size: int = 16, geometry_gradients: bool = False,
+                     screen_statistics: bool = False) -> torch.Tensor:
         """(W,H,3) float32 indexed [x,y]; same result as the reference's pure-Python
         ``render_image`` (gaussian_scene.py:200-238), computed on the GPU and -- like the reference,
         whose image is a CPU tensor (gaussian_scene.py:206) -- returned in host memory, so that
         ``plt.imshow(scene.render_image(i))`` keeps working.  ``render_image_hip`` is the same frame
-        left on the device.  ``geometry_gradients``: as in ``render_image_hip``."""
-        frame = self.render_image_hip(image_idx, tile_size=tile_size, layout="wh3", geometry_gradients=geometry_gradients)
+        left on the device.  ``geometry_gradients``, ``screen_statistics``: as in ``render_image_hip``."""
+        frame = self.render_image_hip(image_idx, tile_size=tile_size, layout="wh3", geometry_gradients=geometry_gradients,
+                                      screen_statistics=screen_statistics)
         # page-locked destination (torch's caching host allocator keeps the pages registered between
         # calls): the copy runs at PCIe rate instead of through a pageable staging loop
         host = torch.empty(frame.shape, dtype=frame.dtype, pin_memory=True)

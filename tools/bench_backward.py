@@ -1,13 +1,15 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--sh]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--sh]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
 gradients, median of HIP-event-bracketed frames), the whole backward call (median, host-synchronised as the call is) and
 its stages from GSX_FLAG_TIMING (test library: gsx_debug_backward_stage_ms) -- the forward's stages run again, the
 compositing backward (+ raw records and emission prefix), the per-Gaussian sums --, and the bytes stored into the
 per-pair slots (16 per pair).  --geometry adds the same figures for gsx_render_backward_geometry (key "geometry": the
-points, scales and quaternions too; 48 slot bytes per pair, the per-Gaussian chain counted with the sums).
+points, scales and quaternions too; 48 slot bytes per pair, the per-Gaussian chain counted with the sums).  --screen adds
+them for gsx_render_backward_screen (key "screen": the same work plus 12 bytes stored per Gaussian, dL/d(NDC mean) and the
+radius), its steps taking turns with the geometry entry's so that both see the same clocks ("screen_over_geometry").
 
 --sh times the differentiable SH scene INSTEAD: the trained-like 1M scene with degree-3 coefficients (bench.py's
 c3_trainedlike).  Its backward is gsx_render_backward on this camera's evaluated colours (gsx_sh_to_rgb runs again) and
@@ -49,7 +51,7 @@ def _median_ms(fn, steps, warmup):
     return statistics.median(out)
 
 
-def run(name, n, steps, warmup, geometry=False):
+def run(name, n, steps, warmup, geometry=False, screen=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -68,9 +70,9 @@ def run(name, n, steps, warmup, geometry=False):
         W = torch.randn(frame.shape, device=frame.device, generator=torch.Generator(device=frame.device).manual_seed(0))
         lib = _ffi.load()
 
-        def leg(geo, slot_bytes):
+        def leg(geo, slot_bytes, scr=False):
             call = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
-                                                       geometry=geo, **kw)
+                                                       geometry=geo, screen=scr, **kw)
             bwd_ms = _median_ms(call, steps, warmup)
             stages = []         # once per step, under GSX_FLAG_TIMING
             for _ in range(steps):
@@ -87,6 +89,21 @@ def run(name, n, steps, warmup, geometry=False):
         if geometry:
             out["geometry"] = leg(True, 48)
             out["geometry_over_colour_only"] = round(out["geometry"]["backward_ms"] / out["backward_ms"], 3)
+        if screen:
+            out["screen"] = leg(True, 48, scr=True)
+            # the two entries step by step in turn: whatever the clocks do, they do to both
+            calls = [lambda scr=scr: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],
+                                                            geometry=True, screen=scr) for scr in (False, True)]
+            turns = [[], []]
+            for i in range(2 * (warmup + steps)):
+                ms = _median_ms(calls[i & 1], 1, 0)
+                if i >= 2 * warmup:
+                    turns[i & 1].append(ms)
+            geo_ms, scr_ms = statistics.median(turns[0]), statistics.median(turns[1])
+            out["alternating"] = dict(geometry_ms=round(geo_ms, 4), screen_ms=round(scr_ms, 4),
+                                      geometry_min_max=[round(min(turns[0]), 4), round(max(turns[0]), 4)],
+                                      screen_min_max=[round(min(turns[1]), 4), round(max(turns[1]), 4)])
+            out["screen_over_geometry"] = round(scr_ms / geo_ms, 4)
     return out
 
 
@@ -158,6 +175,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--geometry", action="store_true", help="also time gsx_render_backward_geometry")
+    ap.add_argument("--screen", action="store_true", help="also time gsx_render_backward_screen, in turns with the geometry entry")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     args = ap.parse_args()
     from intro_to_gaussian_splatting_amd import _ffi
@@ -166,7 +184,7 @@ def main():
         print(json.dumps(dict(metric="sh_backward_ms", results=run_sh(args.steps, args.warmup, args.geometry))))
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
-    out = {name: run(name, n, args.steps, args.warmup, args.geometry) for name, n in WORKLOADS.items()}
+    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen) for name, n in WORKLOADS.items()}
     print(json.dumps(dict(metric="backward_ms", results=out)))
 
 

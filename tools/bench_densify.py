@@ -1,6 +1,6 @@
 """Density control timing (gsx_density_* through DensityControl) on the trained-like 1M scene at SH degree 3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_densify.py [--steps 20] [--warmup 3]
+    timeout -k 10 600 python tools/bench_densify.py [--steps 20] [--warmup 3] [--screen]
 
 bench.py's c3_trainedlike scene (1M Gaussians, seed 0, 1920x1080, degree-3 coefficients) with points, scales, quaternions,
 opacity and sh trained and two Adam steps taken: 59 floats per Gaussian x 3 arrays (parameter, exp_avg, exp_avg_sq), plus the
@@ -12,6 +12,10 @@ synchronisation, its noise draw and its allocations):
   accumulate_ms / torch_accumulate_ms   DensityControl.accumulate() | grad_sum += grad.norm(dim=1) where the row is non-zero
   round_ms / torch_round_ms             DensityControl.densify_and_prune() | the same rules as boolean masks, and per array
                                         mask indexing plus cat (survivors, clones, split children), moments zero-filled
+--screen adds a third contender to the first line, taking its turn inside the same steps:
+  screen_accumulate_ms                  DensityControl(statistic="screen").accumulate() on the statistic one real
+                                        backward with screen_statistics=True left (gsx_density_accumulate_screen: 12 B read
+                                        per row, 12 B more read and 12 B written per LISTED row)
 Both rounds start from the same container every time (the rewrite is out of place: the sources are re-installed).
 Bytes: 4 B read and 4 B written per element of an output row (a new row's moments are not read), 28 B per row for the plan
 (statistic, scales, opacity in; action and prefix out and in again); the same model for both contenders.
@@ -91,7 +95,7 @@ def torch_round(g, opt, grad_sum, seen, knobs, generator):
     return out, moments, int(out["points"].shape[0])
 
 
-def run(steps, warmup, prune_share, densify_share, n=1_000_000):
+def run(steps, warmup, prune_share, densify_share, n=1_000_000, screen=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import DensityControl, GaussianAdam, GaussianScene, Gaussians
@@ -123,6 +127,12 @@ def run(steps, warmup, prune_share, densify_share, n=1_000_000):
         scene.photometric_loss(1, scene.render_image_hip(1, geometry_gradients=True), target).backward()
         dc.accumulate()
         opt.step()
+    screen_stat, dcs = None, None
+    if screen:      # one more backward, through gsx_render_backward_screen: the statistic the third contender consumes every step
+        opt.zero_grad()
+        scene.photometric_loss(1, scene.render_image_hip(1, geometry_gradients=True, screen_statistics=True), target).backward()
+        screen_stat = scene.screen_statistics
+        dcs = DensityControl(g, scene=scene, statistic="screen")
     mean = dc.grad_sum / dc.seen.clamp(min=1).float()
     n_seen = max(1, int((dc.seen > 0).sum()))
     dc.grad_threshold = float(torch.quantile(mean[dc.seen > 0], max(0.0, 1.0 - densify_share * n / n_seen)))
@@ -151,11 +161,18 @@ def run(steps, warmup, prune_share, densify_share, n=1_000_000):
         t_sum.add_(torch.where(live, grad.norm(dim=1), torch.zeros_like(t_sum)))
         t_seen.add_(live.to(t_seen.dtype))
 
-    samples = {k: [] for k in ("accumulate_ms", "torch_accumulate_ms", "round_ms", "torch_round_ms")}
+    def screen_accumulate():
+        scene.screen_statistics = screen_stat       # (accumulate() consumes it)
+        dcs.accumulate()
+
+    samples = {k: [] for k in ("accumulate_ms", "torch_accumulate_ms", "round_ms", "torch_round_ms") +
+               (("screen_accumulate_ms",) if screen else ())}
     counts, torch_n_out = None, None
     for step in range(warmup + steps):
         restore()
         took = {"accumulate_ms": _timed(dc.accumulate)[0], "torch_accumulate_ms": _timed(torch_accumulate)[0]}
+        if screen:
+            took["screen_accumulate_ms"] = _timed(screen_accumulate)[0]
         restore()
         took["round_ms"], counts = _timed(lambda: dc.densify_and_prune(generator=torch.Generator(device=dev).manual_seed(step)))
         restore()
@@ -182,6 +199,11 @@ def run(steps, warmup, prune_share, densify_share, n=1_000_000):
                accumulate_gbps=rate(acc_bytes, med["accumulate_ms"]), torch_accumulate_gbps=rate(acc_bytes, med["torch_accumulate_ms"]),
                torch_round_over_hip=round(med["torch_round_ms"] / med["round_ms"], 2),
                torch_accumulate_over_hip=round(med["torch_accumulate_ms"] / med["accumulate_ms"], 2))
+    if screen:
+        listed = int((screen_stat[2] > 0).sum())
+        sbytes = 12 * n + 24 * listed
+        res.update(screen_listed=listed, screen_accumulate_bytes=sbytes, screen_accumulate_gbps=rate(sbytes, med["screen_accumulate_ms"]),
+                   screen_accumulate_over_points=round(med["screen_accumulate_ms"] / med["accumulate_ms"], 3))
     return res
 
 
@@ -192,8 +214,10 @@ def main():
     ap.add_argument("--prune", type=float, default=0.05)
     ap.add_argument("--densify", type=float, default=0.10)
     ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--screen", action="store_true", help="also time accumulate() under statistic='screen'")
     args = ap.parse_args()
-    print(json.dumps(dict(metric="densify_round_ms", results=run(args.steps, args.warmup, args.prune, args.densify, args.n))))
+    print(json.dumps(dict(metric="densify_round_ms",
+                          results=run(args.steps, args.warmup, args.prune, args.densify, args.n, args.screen))))
 
 
 if __name__ == "__main__":
