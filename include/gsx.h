@@ -498,6 +498,24 @@ GSX_API int gsx_sh_backward(const float *means3d, const float *sh, int32_t degre
                             float *grad_sh, float *grad_means3d /* may be NULL */, void *stream);
 
 /*
+ * The SH degree schedule of a fit (build extension): the two entries above on the first (active_degree + 1)^2 coefficients of
+ * rows STORED at stored_degree.  sh and grad_sh are (n, K_S, 3), K_S = (stored_degree + 1)^2; of each row only the
+ * coefficients k < K_A = (active_degree + 1)^2 are read -- what the others hold, NaN included, reaches no output.  With
+ * P = sh[:, :K_A] made contiguous, bit for bit:
+ *   colors_out        = what gsx_sh_to_rgb(P, active_degree) writes;
+ *   grad_sh[:, :K_A]  = what gsx_sh_backward(P, active_degree) writes, grad_sh[:, K_A:] = +0 -- every entry is written;
+ *   grad_means3d      = what gsx_sh_backward(P, active_degree) writes (may be NULL).
+ * active_degree == stored_degree runs the kernels of the two entries above.  Any float-aligned base.  No atomics, does not
+ * synchronise, n == 0 is GSX_OK.  A degree outside 0..3 or active_degree > stored_degree: GSX_ERR_INVALID_ARGUMENT before
+ * any HIP call, gsx_last_error names the argument.
+ */
+GSX_API int gsx_sh_to_rgb_active(const float *means3d, const float *sh, int32_t stored_degree, int32_t active_degree,
+                                 int64_t n, const float *camera_center_host, float *colors_out, void *stream);
+GSX_API int gsx_sh_backward_active(const float *means3d, const float *sh, int32_t stored_degree, int32_t active_degree,
+                                   int64_t n, const float *camera_center_host, const float *grad_colors,
+                                   float *grad_sh, float *grad_means3d /* may be NULL */, void *stream);
+
+/*
  * Build extension (the reference renders and stops): the photometric loss every splat fit minimises (Kerbl et al. 2023),
  * value and gradient in one call.  image (the frame, x) and target (y) are channel-interleaved (.., .., 3) float32; only
  * the region [0, rows) x [0, cols) of the two leading axes takes part, exactly as if both had been cropped to it -- a row of

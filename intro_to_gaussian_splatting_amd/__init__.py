@@ -8,7 +8,9 @@ from .loss import photometric_loss
 from .optim import GaussianAdam, expon_lr
 from .density import DensityControl
 from .knn import nearest3
+from .fit import Trainer, events_at
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3"]
+           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3",
+           "Trainer", "events_at"]

@@ -144,6 +144,9 @@ SIGNATURES = {
     "gsx_project_points": (ctypes.c_int, [POINTER(GsxCamera), _FP, c_int64, _FP, c_void_p, c_void_p]),
     "gsx_sh_to_rgb": (ctypes.c_int, [_FP, _FP, c_int32, c_int64, POINTER(c_float), _FP, c_void_p]),
     "gsx_sh_backward": (ctypes.c_int, [_FP, _FP, c_int32, c_int64, POINTER(c_float), _FP, _FP, _FP, c_void_p]),
+    "gsx_sh_to_rgb_active": (ctypes.c_int, [_FP, _FP, c_int32, c_int32, c_int64, POINTER(c_float), _FP, c_void_p]),
+    "gsx_sh_backward_active": (ctypes.c_int, [_FP, _FP, c_int32, c_int32, c_int64, POINTER(c_float), _FP, _FP, _FP,
+                                              c_void_p]),
     "gsx_photometric_loss": (ctypes.c_int, [_FP, c_int64, _FP, c_int64, c_int32, c_int32, c_float, _FP, _FP, c_int64,
                                             c_void_p, c_size_t, c_void_p]),
     "gsx_photometric_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),

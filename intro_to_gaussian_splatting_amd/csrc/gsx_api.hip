@@ -699,6 +699,40 @@ int gsx_sh_backward(const float *means3d, const float *sh, int32_t degree, int64
     return GSX_OK;
 }
 
+// stored_degree / active_degree of the two _active entries: 0 when both are in range, else the failure already filed
+static int check_sh_degrees(int32_t stored_degree, int32_t active_degree) {
+    if (stored_degree < 0 || stored_degree > 3)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "stored_degree %d outside [0,3]", stored_degree);
+    if (active_degree < 0 || active_degree > 3)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "active_degree %d outside [0,3]", active_degree);
+    if (active_degree > stored_degree)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "active_degree %d above stored_degree %d", active_degree, stored_degree);
+    return GSX_OK;
+}
+
+int gsx_sh_to_rgb_active(const float *means3d, const float *sh, int32_t stored_degree, int32_t active_degree, int64_t n,
+                         const float *camera_center_host, float *colors_out, void *stream) {
+    if (int rc = check_sh_degrees(stored_degree, active_degree)) return rc;
+    if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n is negative");
+    if (!camera_center_host) return fail(GSX_ERR_INVALID_ARGUMENT, "camera_center_host is NULL");
+    if (n > 0 && (!means3d || !sh || !colors_out)) return fail(GSX_ERR_INVALID_ARGUMENT, "an array is NULL");
+    GSX_HIP(gsx::launch_sh_to_rgb_active(means3d, sh, stored_degree, active_degree, n, camera_center_host, colors_out,
+                                         (hipStream_t)stream));
+    return GSX_OK;
+}
+
+int gsx_sh_backward_active(const float *means3d, const float *sh, int32_t stored_degree, int32_t active_degree, int64_t n,
+                           const float *camera_center_host, const float *grad_colors, float *grad_sh, float *grad_means3d,
+                           void *stream) {
+    if (int rc = check_sh_degrees(stored_degree, active_degree)) return rc;
+    if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n is negative");
+    if (!camera_center_host) return fail(GSX_ERR_INVALID_ARGUMENT, "camera_center_host is NULL");
+    if (n > 0 && (!means3d || !sh || !grad_colors || !grad_sh)) return fail(GSX_ERR_INVALID_ARGUMENT, "an array is NULL");
+    GSX_HIP(gsx::launch_sh_backward_active(means3d, sh, stored_degree, active_degree, n, camera_center_host, grad_colors,
+                                           grad_sh, grad_means3d, (hipStream_t)stream));
+    return GSX_OK;
+}
+
 size_t gsx_photometric_loss_workspace_bytes(int32_t rows, int32_t cols, int32_t with_grad) {
     LossCarve c;
     return loss_carve(rows, cols, with_grad != 0, c) ? c.total : 0;

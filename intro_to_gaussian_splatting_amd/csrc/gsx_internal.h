@@ -297,6 +297,16 @@ hipError_t launch_sh_to_rgb(const float *means3d, const float *sh, int degree, i
 hipError_t launch_sh_backward(const float *means3d, const float *sh, int degree, int64_t n, const float *center,
                               const float *grad_colors, float *grad_sh, float *grad_means3d, hipStream_t s);
 
+// ---- gsx_sh_active.hip
+// The two above on the first (active+1)^2 coefficients of rows stored at degree `stored` (sh, grad_sh: (n, (stored+1)^2, 3)):
+// the bits of the packed degree-`active` call; the tail of every grad_sh row is written +0.  active == stored: the two above.
+// Degrees outside 0..3 or active > stored: hipErrorInvalidValue.
+hipError_t launch_sh_to_rgb_active(const float *means3d, const float *sh, int stored, int active, int64_t n,
+                                   const float *center, float *colors, hipStream_t s);
+hipError_t launch_sh_backward_active(const float *means3d, const float *sh, int stored, int active, int64_t n,
+                                     const float *center, const float *grad_colors, float *grad_sh, float *grad_means3d,
+                                     hipStream_t s);
+
 // ---- gsx_loss.hip
 // gsx_photometric_loss behind its argument checks: loss_out = (loss, l1, ssim) over the rows x cols region and, when
 // grad_image is not NULL, dloss/dimage into it.  `ws` is carved by `c` (plan::loss_carve with with_grad = grad_image != NULL).

@@ -1,0 +1,164 @@
+"""A fit loop over the parts the library has: ``Trainer``.
+
+Every part of a splat fit is a HIP call behind a Python surface -- the differentiable frame (``render_image_hip``), the
+photometric loss, ``GaussianAdam``, ``DensityControl`` and the SH degree schedule (``Gaussians.active_sh_degree``).  This
+module adds no kernel and no arithmetic of its own: it fixes the ORDER of those calls, once, so that nobody has to re-derive
+it.  One step, numbered from 1:
+
+1. the view: the next index of a seeded CPU ``torch.randperm`` over ``targets``, drawn afresh for every epoch;
+2. ``frame = scene.render_image_hip(idx, tile_size, geometry_gradients=True, screen_statistics=statistic == "screen")``;
+3. ``loss = scene.photometric_loss(idx, frame, targets[idx], tile_size, lambda_dssim, terms=...)``;
+4. ``loss.backward()``;
+5. ``density.accumulate()``;
+6. ``opt.step()``, then ``opt.zero_grad()``;
+7. the events ``events_at`` names for this step, in this order: ``density.densify_and_prune(generator)``,
+   ``density.reset_opacity(opacity_reset_logit)``, ``gaussians.oneup_sh_degree()``.
+
+The coefficients keep ONE learning rate: a second rate for the higher bands, as published, needs an Adam group over a strided
+part of ``sh`` and is not built.
+"""
+from __future__ import annotations
+
+import math
+from typing import Callable, Dict, Iterable, Optional, Tuple
+
+import torch
+
+from .density import DensityControl
+from .optim import GROUP_NAMES, GaussianAdam
+
+EVENT_NAMES = ("densify", "opacity_reset", "sh_oneup")
+# the published rates (Kerbl et al. 2023); the position rate is per unit of scene extent there: scale it for the scene
+DEFAULT_LR = {"points": 1.6e-4, "scales": 5e-3, "quaternions": 1e-3, "opacity": 5e-2, "colors": 2.5e-3, "sh": 2.5e-3}
+DEFAULT_OPACITY_RESET_LOGIT = math.log(0.01 / 0.99)         # the published reset: opacity at most 0.01
+
+
+def _period(name: str, value) -> int:
+    if value is None:
+        return 0
+    if isinstance(value, bool) or int(value) != value or int(value) < 0:
+        raise ValueError("%s = %r is not a non-negative integer (0 or None: never)" % (name, value))
+    return int(value)
+
+
+def events_at(step: int, sh_degree_every: Optional[int] = 1000, densify_from: int = 500, densify_every: Optional[int] = 100,
+              densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000) -> Tuple[str, ...]:
+    """The events due after the optimiser step of ``step`` (1 for the first), in the order they run -- a pure function:
+    "densify"        ``densify_from < step <= densify_until`` and ``step`` a multiple of ``densify_every``;
+    "opacity_reset"  ``step <= densify_until`` and ``step`` a multiple of ``opacity_reset_every``;
+    "sh_oneup"       ``step`` a multiple of ``sh_degree_every``.
+    A period of 0 or None switches its event off."""
+    if isinstance(step, bool) or int(step) != step or int(step) < 1:
+        raise ValueError("step = %r is not a positive integer (the first step is 1)" % (step,))
+    step = int(step)
+    sh_every, d_every, o_every = (_period("sh_degree_every", sh_degree_every), _period("densify_every", densify_every),
+                                  _period("opacity_reset_every", opacity_reset_every))
+    due = []
+    if d_every and int(densify_from) < step <= int(densify_until) and step % d_every == 0:
+        due.append("densify")
+    if o_every and step <= int(densify_until) and step % o_every == 0:
+        due.append("opacity_reset")
+    if sh_every and step % sh_every == 0:
+        due.append("sh_oneup")
+    return tuple(due)
+
+
+class Trainer:
+    """Fits ``scene.gaussians`` to ``targets`` (image index -> (W,H,3) float32 tensor on the scene's GPU, the layout of
+    ``render_image_hip``) with the composition of this module's docstring.
+
+    ``lr``: name -> rate or callable of the step, as ``GaussianAdam`` takes it; the arrays it names that the container holds
+    are set to require grad (an SH container trains ``sh``, never ``colors``).  ``statistic`` and ``density`` (keyword
+    arguments) go to ``DensityControl``.  ``seed`` seeds both the view order (CPU) and the split positions (device).
+    The schedule arguments are ``events_at``'s.  ``opt`` and ``density`` are public: their knobs may be changed between steps."""
+
+    def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
+                 tile_size: int = 16, statistic: str = "screen", density: Optional[dict] = None,
+                 sh_degree_every: Optional[int] = 1000, densify_from: int = 500, densify_every: Optional[int] = 100,
+                 densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000,
+                 opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0) -> None:
+        g = scene.gaussians
+        if not targets:
+            raise ValueError("targets is empty: nothing to fit")
+        for idx in targets:
+            if idx not in scene.images:
+                raise ValueError("targets names image %r, which the scene does not have" % (idx,))
+        lr = dict(DEFAULT_LR if lr is None else lr)
+        for name in lr:
+            if name not in GROUP_NAMES:
+                raise ValueError("lr names %r, which is no array of a Gaussians container %s" % (name, GROUP_NAMES))
+        has_sh = getattr(g, "sh", None) is not None
+        lr.pop("colors" if has_sh else "sh", None)              # the frame reads one of the two
+        if not 0.0 <= float(lambda_dssim) <= 1.0:
+            raise ValueError("lambda_dssim = %r is outside [0, 1]" % (lambda_dssim,))
+        self._schedule = dict(sh_degree_every=sh_degree_every, densify_from=int(densify_from), densify_every=densify_every,
+                              densify_until=int(densify_until), opacity_reset_every=opacity_reset_every)
+        events_at(1, **self._schedule)                          # refuses a bad period here, not at step 1000
+        for name in lr:
+            if getattr(g, name, None) is not None:
+                getattr(g, name).requires_grad_(True)
+        self.scene, self.gaussians, self.targets = scene, g, dict(targets)
+        self.lambda_dssim, self.tile_size, self.statistic = float(lambda_dssim), int(tile_size), statistic
+        self.opacity_reset_logit = float(opacity_reset_logit)
+        self.opt = GaussianAdam(g, lr=lr)
+        self.density = DensityControl(g, optimizer=self.opt, scene=scene, statistic=statistic, **(density or {}))
+        self.step_count = 0
+        self._views = sorted(self.targets)
+        self._order: list = []
+        self._view_generator = torch.Generator(device="cpu").manual_seed(int(seed))
+        self._split_generator = torch.Generator(device=g.points.device).manual_seed(int(seed))
+
+    def events_at(self, step: int) -> Tuple[str, ...]:
+        return events_at(step, **self._schedule)
+
+    def _next_view(self) -> int:
+        if not self._order:     # a new epoch: every view once, in a fresh order
+            self._order = [self._views[i] for i in torch.randperm(len(self._views), generator=self._view_generator).tolist()]
+        return self._order.pop(0)
+
+    def step(self) -> Tuple[torch.Tensor, int]:
+        """One step.  Returns ((3,) device tensor: loss, l1, ssim; the view): nothing is read back to the host here."""
+        scene, g = self.scene, self.gaussians
+        idx = self._next_view()
+        frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
+                                       screen_statistics=self.statistic == "screen")
+        terms: dict = {}
+        loss = scene.photometric_loss(idx, frame, self.targets[idx], tile_size=self.tile_size,
+                                      lambda_dssim=self.lambda_dssim, terms=terms)
+        loss.backward()
+        self.density.accumulate()
+        self.opt.step()
+        self.opt.zero_grad()
+        self.step_count += 1
+        for event in self.events_at(self.step_count):
+            if event == "densify":
+                self.density.densify_and_prune(generator=self._split_generator)
+            elif event == "opacity_reset":
+                self.density.reset_opacity(self.opacity_reset_logit)
+            else:
+                g.oneup_sh_degree()
+        return torch.stack((loss.detach(), terms["l1"], terms["ssim"])), idx
+
+    def fit(self, steps: int, callback: Optional[Callable] = None) -> None:
+        """``steps`` steps; ``callback(trainer, losses, view)`` after each, with what ``step()`` returned."""
+        for _ in range(int(steps)):
+            losses, idx = self.step()
+            if callback is not None:
+                callback(self, losses, idx)
+
+    def evaluate(self, indices: Optional[Iterable[int]] = None) -> Dict[int, Dict[str, float]]:
+        """image index -> ``l1``, ``ssim`` (the loss's own terms) and ``psnr`` (dB, peak 1) of the current frame against its
+        target over ``rendered_region``, under ``no_grad``; one host read per view."""
+        out = {}
+        with torch.no_grad():
+            for idx in (self._views if indices is None else indices):
+                target = self.targets[idx]
+                frame = self.scene.render_image_hip(idx, tile_size=self.tile_size)
+                terms: dict = {}
+                self.scene.photometric_loss(idx, frame, target, tile_size=self.tile_size, lambda_dssim=self.lambda_dssim,
+                                            terms=terms)
+                a, b = self.scene.rendered_region(idx, self.tile_size)
+                mse = ((frame[:a, :b] - target[:a, :b]) ** 2).mean()
+                l1, ssim, mse = (float(v) for v in torch.stack((terms["l1"], terms["ssim"], mse)).tolist())
+                out[idx] = dict(l1=l1, ssim=ssim, psnr=math.inf if mse == 0.0 else -10.0 * math.log10(mse))
+        return out

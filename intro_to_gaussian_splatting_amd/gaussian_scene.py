@@ -216,6 +216,9 @@ class CapturedFrame:
         # (spatially ordered rows: the boxes a strip's projection trusts follow points / scales -- refreshed IN PLACE, at the
         # address the graph holds, when those were modified since; a comparison of six integers otherwise)
         g = self.scene.gaussians
+        if getattr(g, "sh", None) is not None and self.scene._sh_truncated():
+            raise ValueError("gaussians.active_sh_degree = %d is below sh_degree = %d: the captured frame evaluates every "
+                             "stored band" % (self.scene._active_sh_degree(), int(g.sh_degree)))
         if getattr(g, "original_index", None) is not None:
             g.current_block_bounds()
         self.graph.replay()
@@ -354,7 +357,8 @@ class GaussianScene:
     # ------------------------------------------------------------------ helpers
     def _colors(self, image_idx: int) -> torch.Tensor:
         """``gaussians.colors`` like the reference, or -- build extension -- the view-dependent colour
-        of this camera evaluated on the GPU from ``gaussians.sh`` (gsx_sh_to_rgb)."""
+        of this camera evaluated on the GPU from the active bands of ``gaussians.sh`` (gsx_sh_to_rgb_active: with every
+        stored band active, gsx_sh_to_rgb's kernels)."""
         g = self.gaussians
         if getattr(g, "sh", None) is None:
             return g.colors
@@ -367,7 +371,8 @@ class GaussianScene:
         out = torch.empty((n, 3), dtype=torch.float32, device=dev)
         center = (ctypes.c_float * 3)(*self.images[image_idx].camera_center_host)   # no device read per frame
         with torch.cuda.device(dev):
-            rc = lib.gsx_sh_to_rgb(_ptr(pts), _ptr(sh), degree, n, center, _ptr(out), _stream_handle(dev))
+            rc = lib.gsx_sh_to_rgb_active(_ptr(pts), _ptr(sh), degree, self._active_sh_degree(), n, center, _ptr(out),
+                                          _stream_handle(dev))
         _ffi.check(rc)
         return out
 
@@ -376,6 +381,22 @@ class GaussianScene:
         g = self.gaussians
         degree = int(g.sh_degree)
         return _check_f32("sh", g.sh.reshape(n, (degree + 1) ** 2, 3), dev), degree
+
+    def _active_sh_degree(self) -> int:
+        """``gaussians.active_sh_degree``, checked against the stored degree (a container without the attribute: the stored
+        degree)."""
+        g = self.gaussians
+        stored = int(g.sh_degree)
+        active = int(getattr(g, "active_sh_degree", stored))
+        if not 0 <= active <= stored:
+            raise ValueError("gaussians.active_sh_degree = %d is outside 0..%d (sh_degree)" % (active, stored))
+        return active
+
+    def _sh_truncated(self) -> bool:
+        """An SH scene on its degree schedule: fewer bands active than stored.  Its frames are rendered from this camera's
+        evaluated colours (``_colors``), not from GsxParams.sh, whose projection kernel evaluates every stored band."""
+        g = self.gaussians
+        return getattr(g, "sh", None) is not None and self._active_sh_degree() < int(g.sh_degree)
 
     def _inputs(self, image_idx: Optional[int] = None, inline_sh: bool = False):
         """The five parameter tensors the library reads.  With ``inline_sh`` and an SH scene the last one is
@@ -528,6 +549,10 @@ class GaussianScene:
         Gaussian the frame listed on no tile; every such backward replaces it, ``DensityControl(statistic="screen")``
         consumes it.  It is the rasteriser's share, the published ``viewspace_points.grad[:, :2]``: an SH scene's
         view-direction term (gsx_sh_backward) reaches ``points.grad`` only.  Gradients and frame are the same bits either way.
+        ``gaussians.active_sh_degree`` below ``sh_degree`` (the SH degree schedule): the frame, with or without gradients,
+        is the one of the scene truncated to the active bands -- rendered from this camera's evaluated colours
+        (gsx_sh_to_rgb_active) instead of GsxParams.sh, one (N,3) array per frame; dL/dsh is zero in the inactive bands.
+        ``camera_buffer`` is then refused (ValueError).
         """
         if screen_statistics and not geometry_gradients:
             raise ValueError("screen_statistics=True needs geometry_gradients=True: the statistic comes out of the geometry "
@@ -574,7 +599,13 @@ class GaussianScene:
                     substrips, substrip_events):
         """Validates the arguments of ``render_image_hip`` and fills GsxParams: all but the per-view state (``_view_state``)."""
         _ffi.load()         # (a missing library is reported before anything about the arguments)
-        dev, n, tensors = self._inputs(image_idx, inline_sh=True)
+        truncated = self._sh_truncated()
+        if truncated and camera_buffer is not None:
+            raise ValueError("camera_buffer with gaussians.active_sh_degree = %d below sh_degree = %d: the frame is rendered "
+                             "from colours evaluated for camera %r, which a camera rewritten on the device would not "
+                             "follow; raise active_sh_degree to sh_degree first"
+                             % (self._active_sh_degree(), int(self.gaussians.sh_degree), image_idx))
+        dev, n, tensors = self._inputs(image_idx, inline_sh=not truncated)
         cam = self.images[image_idx].gsx_camera()
         width, height = cam.width, cam.height
         params, oi = self._frame_params(dev, n, layout, semantics)
@@ -783,8 +814,9 @@ class GaussianScene:
 
     def _sh_backward(self, image_idx: int, grad_colors: torch.Tensor,
                      with_points: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """gsx_sh_backward: (dL/dsh (N,K,3), dL/dpoints (N,3) through the view direction, or None without ``with_points``)
-        of this camera's view-dependent colours for dL/dcolour = ``grad_colors`` (N,3)."""
+        """gsx_sh_backward_active: (dL/dsh (N,K,3), exact zeros in the inactive bands; dL/dpoints (N,3) through the view
+        direction, or None without ``with_points``) of this camera's view-dependent colours for dL/dcolour =
+        ``grad_colors`` (N,3)."""
         lib = _ffi.load()
         g = self.gaussians
         with torch.no_grad():
@@ -798,8 +830,8 @@ class GaussianScene:
             gview = torch.empty((n, 3), dtype=torch.float32, device=dev) if with_points else None
             center = (ctypes.c_float * 3)(*self.images[image_idx].camera_center_host)
             with torch.cuda.device(dev):
-                rc = lib.gsx_sh_backward(_ptr(pts), _ptr(sh), degree, n, center, _ptr(gc), _ptr(gsh), _ptr(gview),
-                                         _stream_handle(dev))
+                rc = lib.gsx_sh_backward_active(_ptr(pts), _ptr(sh), degree, self._active_sh_degree(), n, center, _ptr(gc),
+                                                _ptr(gsh), _ptr(gview), _stream_handle(dev))
             _ffi.check(rc)
         return gsh, gview
 
@@ -873,6 +905,11 @@ class GaussianScene:
         no-sync frame has no host dependency at all."""
         if _wants_grad(self.gaussians):
             _refuse_with_grad("capture_frame")
+        if self._sh_truncated():
+            raise ValueError("capture_frame with gaussians.active_sh_degree = %d below sh_degree = %d: the graph would bake in "
+                             "a buffer of colours evaluated now, which goes stale with the next step; raise "
+                             "active_sh_degree to sh_degree first"
+                             % (self._active_sh_degree(), int(self.gaussians.sh_degree)))
         dev = self.gaussians.points.device
         _require_gpu(dev)
         cam = self.images[image_idx].gsx_camera()

@@ -11,13 +11,18 @@ and / or ``g.opacity.requires_grad_(True)``, and ``GaussianScene.render_image`` 
 ``render_image_hip`` then return a frame with a ``grad_fn`` whose backward runs in libgsx
 (gsx_render_backward); points, scales and quaternions get no gradient, like the reference's
 (``geometry_gradients=True`` delivers them).  An SH scene (``sh`` set) is differentiable when
-``g.sh.requires_grad_(True)``: dL/dsh comes from gsx_sh_backward.
+``g.sh.requires_grad_(True)``: dL/dsh comes from gsx_sh_backward.  ``active_sh_degree`` (0..``sh_degree``, default
+``sh_degree``) is the SH degree schedule of a fit: only the bands up to it are evaluated and differentiated, the arrays keep
+the stored layout (gsx_sh_to_rgb_active, gsx_sh_backward_active).
 """
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
+
+
+SH_C0 = 0.28209479177387814      # Y_0: colour = 0.5 + SH_C0 sh[0] at degree 0 (csrc/gsx_sh_device.h)
 
 
 class Gaussians:
@@ -39,6 +44,7 @@ class Gaussians:
         # build extension: spherical-harmonic colour (N,K,3); None = use `colors` like the reference
         self.sh: Optional[torch.Tensor] = None
         self.sh_degree = 0
+        self._active_sh_degree: Optional[int] = None      # None: the stored degree (``active_sh_degree``)
         # build extension (spatially_ordered): int32 (N,), the ORIGINAL index of the Gaussian in every row; None = the rows
         # are in the caller's own order
         self.original_index: Optional[torch.Tensor] = None
@@ -48,6 +54,46 @@ class Gaussians:
 
     def __len__(self) -> int:
         return int(self.points.shape[0])
+
+    @property
+    def active_sh_degree(self) -> int:
+        """The SH bands a frame evaluates and differentiates: 0..``sh_degree``, the stored degree unless set.  ``sh``, its
+        gradient and its Adam moments keep the stored layout (N, (sh_degree + 1)^2, 3); the coefficients of the inactive
+        bands are not read and receive an exact zero gradient."""
+        active = getattr(self, "_active_sh_degree", None)
+        return int(self.sh_degree) if active is None else min(int(active), int(self.sh_degree))
+
+    @active_sh_degree.setter
+    def active_sh_degree(self, degree: int) -> None:
+        if isinstance(degree, bool) or int(degree) != degree:
+            raise ValueError("active_sh_degree = %r is not an integer" % (degree,))
+        if not 0 <= int(degree) <= int(self.sh_degree):
+            raise ValueError("active_sh_degree = %r is outside 0..%d (sh_degree, the stored degree)"
+                             % (degree, int(self.sh_degree)))
+        self._active_sh_degree = int(degree)
+
+    def oneup_sh_degree(self) -> int:
+        """Raises ``active_sh_degree`` by one, up to the stored degree, and returns it (the published schedule calls this
+        every 1000 steps)."""
+        self.active_sh_degree = min(self.active_sh_degree + 1, int(self.sh_degree))
+        return self.active_sh_degree
+
+    def init_sh(self, degree: int) -> None:
+        """Turns an RGB container (a point cloud) into an SH one stored at ``degree``: ``sh[:, 0] = (colors - 0.5) / C0``,
+        so that degree 0 reproduces ``colors``, the higher bands zero, ``active_sh_degree`` 0 -- the published initialisation.
+        ``sh`` requires grad when ``colors`` did."""
+        if isinstance(degree, bool) or int(degree) != degree or not 0 <= int(degree) <= 3:
+            raise ValueError("init_sh: degree = %r is outside 0..3" % (degree,))
+        if self.sh is not None:
+            raise ValueError("init_sh: the container already holds SH coefficients (sh_degree %d)" % int(self.sh_degree))
+        degree = int(degree)
+        n = len(self)
+        colors = self.colors.detach().reshape(n, 3)
+        sh = torch.zeros((n, (degree + 1) ** 2, 3), dtype=torch.float32, device=colors.device)
+        sh[:, 0, :] = (colors - 0.5) / SH_C0
+        self.sh = sh.requires_grad_(bool(self.colors.requires_grad))
+        self.sh_degree = degree
+        self._active_sh_degree = 0
 
     def to(self, device) -> "Gaussians":
         dev = torch.device(device)
@@ -123,6 +169,7 @@ class Gaussians:
         p = self.points.reshape(n, 3)
         g = Gaussians.__new__(Gaussians)
         g.device, g.model_path, g.sh_degree = self.device, self.model_path, self.sh_degree
+        g._active_sh_degree = getattr(self, "_active_sh_degree", None)
         if n == 0:
             perm = torch.zeros(0, dtype=torch.int64, device=p.device)
         else:

@@ -1,6 +1,6 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--sh]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--sh [--active-degree A]]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
 gradients, median of HIP-event-bracketed frames), the whole backward call (median, host-synchronised as the call is) and
@@ -17,6 +17,9 @@ then gsx_sh_backward: the whole backward, the share of gsx_sh_backward in it, an
 over batches of back-to-back launches, bytes = n (24 + 24 K) (+ 12 n with the mean gradient), GB/s -- beside the forward
 kernel gsx_sh_to_rgb (n (24 + 12 K) bytes) timed the same way in the same run as the yardstick.  Both kernels alternate
 between two copies of the coefficients, so that no launch finds its 192 MB in the 256 MB last-level cache.
+--active-degree A (with --sh) sets Gaussians.active_sh_degree: the frame, the backward and the two kernels run on the first
+A bands of the degree-3 rows (gsx_sh_to_rgb_active / gsx_sh_backward_active; bytes = n (24 + 12 K_A + 12 K) and
+n (24 + 12 K_A)), and "in_turns" holds three rounds of the degree-3 kernels in turns with them, per launch.
 """
 from __future__ import annotations
 
@@ -107,7 +110,7 @@ def run(name, n, steps, warmup, geometry=False, screen=False):
     return out
 
 
-def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10):
+def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10, active=None):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -122,6 +125,10 @@ def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10):
         scene = GaussianScene(tmp, g)
     lib = _ffi.load()
     deg, k = g.sh_degree, (g.sh_degree + 1) ** 2
+    if active is not None:      # the SH degree schedule: frames, backward and the kernels below on the first `active` bands
+        g.active_sh_degree = active
+    act = g.active_sh_degree
+    ka = (act + 1) ** 2
     with torch.no_grad():
         st = {}
         frame = scene.render_image_hip(1, stats=st).clone()
@@ -150,11 +157,17 @@ def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10):
                     _ffi.check(launch(shs[i & 1]))
             return _median_ms(burst, steps, warmup) / batch
 
-        bwd = kernel_ms(lambda sh: lib.gsx_sh_backward(p(pts), p(sh), deg, n, center, p(gc), p(gsh), None, stream))
-        bwd_pts = kernel_ms(lambda sh: lib.gsx_sh_backward(p(pts), p(sh), deg, n, center, p(gc), p(gsh), p(gview), stream))
-        fwd = kernel_ms(lambda sh: lib.gsx_sh_to_rgb(p(pts), p(sh), deg, n, center, p(cols), stream))
+        stored = dict(
+            bwd=lambda sh: lib.gsx_sh_backward(p(pts), p(sh), deg, n, center, p(gc), p(gsh), None, stream),
+            bwd_pts=lambda sh: lib.gsx_sh_backward(p(pts), p(sh), deg, n, center, p(gc), p(gsh), p(gview), stream),
+            fwd=lambda sh: lib.gsx_sh_to_rgb(p(pts), p(sh), deg, n, center, p(cols), stream))
+        launches = stored if active is None else dict(
+            bwd=lambda sh: lib.gsx_sh_backward_active(p(pts), p(sh), deg, act, n, center, p(gc), p(gsh), None, stream),
+            bwd_pts=lambda sh: lib.gsx_sh_backward_active(p(pts), p(sh), deg, act, n, center, p(gc), p(gsh), p(gview), stream),
+            fwd=lambda sh: lib.gsx_sh_to_rgb_active(p(pts), p(sh), deg, act, n, center, p(cols), stream))
+        bwd, bwd_pts, fwd = (kernel_ms(launches[key]) for key in ("bwd", "bwd_pts", "fwd"))
         rate = lambda nbytes, ms: round(nbytes / ms / 1e6, 1)  # noqa: E731  (GB/s)
-        b_bwd, b_fwd = n * (24 + 24 * k), n * (24 + 12 * k)
+        b_bwd, b_fwd = n * (24 + 12 * ka + 12 * k), n * (24 + 12 * ka)
         whole_ms = whole(False)
         out = dict(workload="c3_trainedlike", n=n, sh_degree=deg, n_instances=int(st["n_instances"]),
                    forward_frame_ms=round(fwd_ms, 4), backward_ms=round(whole_ms, 4),
@@ -164,6 +177,15 @@ def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10):
                    sh_backward_with_points_ms=round(bwd_pts, 4), sh_backward_with_points_bytes=b_bwd + 12 * n,
                    sh_backward_with_points_gbps=rate(b_bwd + 12 * n, bwd_pts),
                    sh_to_rgb_ms=round(fwd, 4), sh_to_rgb_bytes=b_fwd, sh_to_rgb_gbps=rate(b_fwd, fwd))
+        if active is not None:
+            # the degree-`deg` kernels the strided instances stand in for, in turns with them: three rounds each, all kept
+            turns = {key: ([], []) for key in ("bwd", "bwd_pts", "fwd")}
+            for _ in range(3):
+                for key in turns:
+                    turns[key][0].append(round(kernel_ms(stored[key]), 4))
+                    turns[key][1].append(round(kernel_ms(launches[key]), 4))
+            out["active_degree"] = act
+            out["in_turns"] = {key: dict(stored_ms=v[0], active_ms=v[1]) for key, v in turns.items()}
         if geometry:
             geo_ms = whole(True)
             out["geometry"] = dict(backward_ms=round(geo_ms, 4), sh_backward_share=round(bwd_pts / geo_ms, 4))
@@ -177,11 +199,14 @@ def main():
     ap.add_argument("--geometry", action="store_true", help="also time gsx_render_backward_geometry")
     ap.add_argument("--screen", action="store_true", help="also time gsx_render_backward_screen, in turns with the geometry entry")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
+    ap.add_argument("--active-degree", type=int, default=None, help="with --sh: Gaussians.active_sh_degree (0..3), the "
+                    "gsx_sh_*_active entries, and the degree-3 kernels timed in turns with them")
     args = ap.parse_args()
     from intro_to_gaussian_splatting_amd import _ffi
 
     if args.sh:
-        print(json.dumps(dict(metric="sh_backward_ms", results=run_sh(args.steps, args.warmup, args.geometry))))
+        print(json.dumps(dict(metric="sh_backward_ms", results=run_sh(args.steps, args.warmup, args.geometry,
+                                                                       active=args.active_degree))))
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
     out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen) for name, n in WORKLOADS.items()}
