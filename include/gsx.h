@@ -446,6 +446,35 @@ GSX_API int gsx_render_backward_screen(const GsxCamera *camera, const float *mea
                                size_t workspace_bytes, void *stream);
 
 /*
+ * gsx_render_backward_screen plus the camera: the same arguments with two more device outputs behind screen_radius, the same
+ * refusals (grad_world2view or grad_full_proj NULL besides; grad_means2d and screen_radius may BOTH be NULL here), the same
+ * synchronisation, no hints touched, no float atomics: same inputs, same bits.  The older outputs hold the bits
+ * gsx_render_backward_screen writes.  workspace: gsx_backward_camera_workspace_bytes.
+ *   grad_world2view[16], grad_full_proj[16]: dL/d(entry) of GsxCamera.world2view and GsxCamera.full_proj, row-major in
+ *     the camera's own row-vector convention, the two matrices taken as INDEPENDENT inputs (a caller whose full_proj is
+ *     world2view @ P adds grad_full_proj @ P^T) and everything else of the camera (fx, fy, tan_fov*, camera_center) as
+ *     constant.  Per Gaussian on a tile list, with p the point, g_t the gradient of the view-space point t = [p,1] world2view,
+ *     dT the gradient of T = J W (W[i][j] = world2view[j][i], J the 2x3 EWA Jacobian) and gh the gradient of the homogeneous
+ *     point h = [p,1] full_proj (columns 0, 1, 3):
+ *       grad_world2view[k][c] += p_k g_t[c] + (J[0][c] dT[0][k] + J[1][c] dT[1][k])   (k, c < 3)
+ *       grad_world2view[3][c] += g_t[c]
+ *       grad_full_proj[k][c] += p_k gh_c,   grad_full_proj[3][c] += gh_c               (c in {0, 1, 3})
+ *     Column 3 of grad_world2view and column 2 of grad_full_proj are exact +0: nothing the frame computes reads them.  The
+ *     branch decisions (floored determinant, active clamp, culling, tile lists, stop) are piecewise constant.  A frame that
+ *     lists nothing writes 32 exact +0.  The sum over Gaussians runs in a fixed order: per 256 depth ranks the wave
+ *     butterflies and the four waves in order, then the blocks in eight interleaved stripes, each in rising order.
+ */
+GSX_API int gsx_render_backward_camera(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                               const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                               const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                               float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d /* may be NULL */,
+                               float *screen_radius /* may be NULL */, float *grad_world2view, float *grad_full_proj,
+                               const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_render_backward_camera needs (0 on invalid arguments). */
+GSX_API size_t gsx_backward_camera_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =
  * (R S)(R S)^T from linear scales (n,3) and quaternions (n,4) (w,x,y,z), the quaternion
  * normalised twice as the reference does.  The render entry points compute this inline; the

@@ -9,8 +9,9 @@ from .optim import GaussianAdam, expon_lr
 from .density import DensityControl
 from .knn import nearest3
 from .fit import Trainer, events_at
+from .pose import CameraRefiner
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
            "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3",
-           "Trainer", "events_at"]
+           "Trainer", "events_at", "CameraRefiner"]

@@ -385,6 +385,7 @@ thread_local float g_backward_ms[3] = {0.0f, 0.0f, 0.0f};
 struct GeometryGrads {
     float *means3d, *scales, *quats;
     float *means2d = nullptr, *radius = nullptr;
+    float *world2view = nullptr, *full_proj = nullptr;     // gsx_render_backward_camera: both, 16 floats each
 };
 
 // gsx_render_backward (geo == nullptr) and gsx_render_backward_geometry: one body.  The geometry call carves the third
@@ -414,7 +415,7 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     Carve c;
     int64_t cap;
     rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap,
-                         geo ? kCarveGeometry : kCarveBackward);
+                         geo ? (geo->world2view ? kCarveCamera : kCarveGeometry) : kCarveBackward);
     if (rc != GSX_OK) return rc;
     char *ws = (char *)workspace;
     StageTimer tm;
@@ -428,6 +429,10 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->quats, (size_t)n * 4, s));
         if (geo->means2d) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means2d, (size_t)n * 2, s));
         if (geo->radius) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->radius, (size_t)n, s));
+        if (geo->world2view) {      // a frame that lists nothing leaves 32 exact +0
+            GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->world2view, 16, s));
+            GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->full_proj, 16, s));
+        }
     }
     if (n == 0 || p.grid.count() == 0) {
         GSX_HIP(hipStreamSynchronize(s));
@@ -464,9 +469,12 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
     tm.mark();  // 2: raw records, prefix, compositing backward
     GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
-    if (geo)
+    if (geo) {
+        const gsx::CameraGrads cg{geo->world2view, geo->full_proj, (float *)(ws + c.cam_partials)};
         GSX_HIP(gsx::launch_backward_geometry(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
-                                              geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s));
+                                              geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s,
+                                              geo->world2view ? &cg : nullptr));
+    }
     tm.mark();  // 3: sums (and the geometry chain)
     GSX_HIP(hipStreamSynchronize(s));
 #ifdef GSX_TEST_HOOKS
@@ -666,6 +674,24 @@ int gsx_render_backward_screen(const GsxCamera *camera, const float *means3d, co
         return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
     if (!grad_means2d) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d is NULL");
     const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
+    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+}
+
+size_t gsx_backward_camera_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveCamera);
+}
+
+int gsx_render_backward_camera(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                               const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                               const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                               float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                               float *screen_radius, float *grad_world2view, float *grad_full_proj, const GsxParams *params,
+                               void *workspace, size_t workspace_bytes, void *stream) {
+    if (!grad_means3d || !grad_scales || !grad_quats)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
+    if (!grad_world2view || !grad_full_proj) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_world2view / grad_full_proj is NULL");
+    const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius, grad_world2view, grad_full_proj};
     return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
                            grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
 }

@@ -29,6 +29,9 @@
 // derivative (geometry_chain, below).  The colour-only kernels and their slots are the same code and layout either way.
 // gsx_render_backward_screen is the geometry call with two more per-Gaussian stores in the chain kernel: dL/d(NDC mean), which
 // the chain forms anyway on its way to dL/dpoint, and the radius project_raw_kernel left in the raw record's last word.
+// gsx_render_backward_camera is the screen call with the chain kernel's camera instance (backward_camera_chain_kernel): the
+// chain's g_t, dT and gh contracted with the point into 24 terms of dL/dworld2view and dL/dfull_proj per Gaussian, summed
+// per block with the butterflies above and LDS, and over the blocks by camera_reduce_kernel in a fixed order.
 //
 // alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
@@ -201,10 +204,15 @@ struct GeoCamera {
     float fx, fy, limx, limy, sx, sy;   // focal lengths, 1.3 tan(fov / 2), (width - 1) / 2, (height - 1) / 2
 };
 
+// kCamera (gsx_render_backward_camera): also this Gaussian's 24 terms of dL/dworld2view and dL/dfull_proj into gc, the
+// chain's own g_t, dT and gh contracted with the point instead of with the matrices (kCamTerms, below).  The other
+// instance is the text it was: gc is never touched.
+template <bool kCamera>
 __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float *__restrict__ p, const float *__restrict__ sc,
                                                const float *__restrict__ qin, const float4 QA, const float4 QB,
                                                float S1, float S2, float S3, float S4, float S5, float *__restrict__ gp,
-                                               float *__restrict__ gs, float *__restrict__ gq, float *__restrict__ gn) {
+                                               float *__restrict__ gs, float *__restrict__ gq, float *__restrict__ gn,
+                                               float *__restrict__ gc) {
     const float *V = cam.V, *F = cam.F;
     const float p0 = p[0], p1 = p[1], p2 = p[2];
     // ---- forward values
@@ -356,6 +364,23 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
     for (int k = 0; k < 3; ++k)
         gp[k] = ((gh0 * F[k * 4] + gh1 * F[k * 4 + 1]) + gh3 * F[k * 4 + 3]) +
                 ((g_t[0] * V[k * 4] + g_t[1] * V[k * 4 + 1]) + g_t[2] * V[k * 4 + 2]);
+    if constexpr (kCamera) {
+        // t_c = sum_k p_k V[k][c] + V[3][c]; T_ij = sum_k J_ik W_kj with W_kj = V[j][k]; h_c = sum_k p_k F[k][c] + F[3][c]
+        const float J0[3] = {j00, 0.0f, j02}, J1[3] = {0.0f, j11, j12};
+        const float gh[3] = {gh0, gh1, gh3}, pk[3] = {p0, p1, p2};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                gc[k * 3 + c] = pk[k] * g_t[c] + (J0[c] * dT[0][k] + J1[c] * dT[1][k]);
+                gc[12 + k * 3 + c] = pk[k] * gh[c];
+            }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            gc[9 + c] = g_t[c];
+            gc[21 + c] = gh[c];
+        }
+    }
 }
 
 // One wave per depth rank: the Gaussian's geometry slots [prefix[r], prefix[r + 1]) summed as backward_sum_kernel sums
@@ -400,7 +425,8 @@ __global__ void __launch_bounds__(256)
     const int64_t row = order[r];
     const Record rec = raw[row];
     float gp[3], gs[3], gq[4], gn[2];
-    geometry_chain(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq, gn);
+    geometry_chain<false>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq,
+                          gn, nullptr);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         grad_means3d[3 * row + k] = gp[k];
@@ -412,6 +438,96 @@ __global__ void __launch_bounds__(256)
         grad_means2d[2 * row] = gn[0];
         grad_means2d[2 * row + 1] = gn[1];
         if (screen_radius) screen_radius[row] = rec.c.w;
+    }
+}
+
+// ---- gsx_render_backward_camera: dL/dworld2view and dL/dfull_proj, the 24 entries that are not exact zeros.
+// kCamTerms values per Gaussian: [k * 3 + c] = dL/dV[k][c] (k < 4, c < 3; column 3 of V reaches nothing) and
+// [12 + k * 3 + j] = dL/dF[k][c], c = (0, 1, 3)[j] (column 2 of F, the depth, reaches nothing).  The sum over Gaussians
+// in a fixed order: within a wave the butterflies of wave_sum4, the block's four waves in wave order (LDS), one row of
+// `partials` per block; camera_reduce_kernel then adds the rows in kCamStripes interleaved stripes, each in rising row
+// order, and the stripes in stripe order.
+constexpr int kCamTerms = 24, kCamStripes = 8;
+
+// backward_geometry_chain_kernel with the camera terms: the same rows written with the same values, and no early
+// return -- every thread of the block takes part in the reduction, a rank past m or on no tile list with 24 zeros.
+__global__ void __launch_bounds__(256)
+    backward_camera_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                 const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m, GeoCamera cam,
+                                 const float *__restrict__ means3d, const float *__restrict__ scales,
+                                 const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                                 float *__restrict__ grad_scales, float *__restrict__ grad_quats,
+                                 float *__restrict__ grad_means2d, float *__restrict__ screen_radius,
+                                 float *__restrict__ partials) {
+    __shared__ float lds[4][kCamTerms];
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float gc[kCamTerms];
+#pragma unroll
+    for (int i = 0; i < kCamTerms; ++i) gc[i] = 0.0f;
+    uint32_t b = 0, e = 0;
+    if (r < m) {
+        b = prefix[r];
+        e = prefix[r + 1];
+    }
+    if (b != e) {
+        const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
+        const int64_t row = order[r];
+        const Record rec = raw[row];
+        float gp[3], gs[3], gq[4], gn[2];
+        geometry_chain<true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs,
+                             gq, gn, gc);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            grad_means3d[3 * row + k] = gp[k];
+            grad_scales[3 * row + k] = gs[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
+        if (grad_means2d) {
+            grad_means2d[2 * row] = gn[0];
+            grad_means2d[2 * row + 1] = gn[1];
+            if (screen_radius) screen_radius[row] = rec.c.w;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < kCamTerms / 4; ++g) {
+        const float v = wave_sum4(gc[4 * g], gc[4 * g + 1], gc[4 * g + 2], gc[4 * g + 3], lane);
+        if ((lane & 15) == 0) lds[wave][4 * g + (lane >> 4)] = v;      // component v of the group sits in lane 16 v
+    }
+    __syncthreads();
+    if (threadIdx.x < kCamTerms) {
+        const int i = threadIdx.x;
+        partials[(size_t)blockIdx.x * kCamTerms + i] = ((lds[0][i] + lds[1][i]) + lds[2][i]) + lds[3][i];
+    }
+}
+
+// One workgroup of kCamStripes x 32 threads: thread (stripe, i) adds rows stripe, stripe + kCamStripes, .. of term i,
+// thread i < 32 then adds the stripes and stores word i of both matrices (the eight structural zeros included).
+__global__ void __launch_bounds__(kCamStripes * 32)
+    camera_reduce_kernel(const float *__restrict__ partials, uint32_t rows, float *__restrict__ grad_world2view,
+                         float *__restrict__ grad_full_proj) {
+    __shared__ float lds[kCamStripes][kCamTerms];
+    const int i = threadIdx.x & 31, stripe = threadIdx.x >> 5;
+    if (i < kCamTerms) {
+        float acc = 0.0f;
+        for (uint32_t row = (uint32_t)stripe; row < rows; row += (uint32_t)kCamStripes) acc += partials[(size_t)row * kCamTerms + i];
+        lds[stripe][i] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 32) {
+        // word t of the 32 outputs: V[k][c] for t < 16, F[k][c] behind; which of the 24 terms, or none
+        const int t = threadIdx.x, k = (t & 15) >> 2, c = t & 3;
+        const bool isV = t < 16;
+        const int j = isV ? c : (c == 3 ? 2 : c);
+        const bool zero = isV ? c == 3 : c == 2;
+        float acc = 0.0f;
+        if (!zero) {
+            const int term = (isV ? 0 : 12) + k * 3 + j;
+#pragma unroll
+            for (int s = 0; s < kCamStripes; ++s) acc += lds[s][term];
+        }
+        (isV ? grad_world2view : grad_full_proj)[t & 15] = acc;
     }
 }
 
@@ -447,7 +563,8 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
 hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
                                     const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s) {
+                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
+                                    const CameraGrads *cg) {
     if (m == 0) return hipSuccess;
     GeoCamera cam;
     for (int i = 0; i < 16; ++i) {
@@ -461,9 +578,16 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
     cam.sx = ((float)camera.width - 1.0f) * 0.5f;
     cam.sy = ((float)camera.height - 1.0f) * 0.5f;
     backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
-    backward_geometry_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
-        geo_slots, prefix, order, raw, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
-        screen_radius);
+    const unsigned blocks = (unsigned)(((uint64_t)m + 255) / 256);
+    if (cg) {
+        backward_camera_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,
+                                                            grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius,
+                                                            cg->partials);
+        camera_reduce_kernel<<<1, kCamStripes * 32, 0, s>>>(cg->partials, blocks, cg->world2view, cg->full_proj);
+        return hipGetLastError();
+    }
+    backward_geometry_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,
+                                                          grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius);
     return hipGetLastError();
 }
 

@@ -478,9 +478,17 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
 // left in the rank's first slot), then one thread per rank runs the chain from dL/dQ and dL/dmean to the inputs
 // (gsx_backward.hip: geometry_chain) and scatters to rows (order[r]).  gsx_render_backward_screen: grad_means2d (n,2) gets
 // the chain's dL/d(NDC mean) and screen_radius (n, or null) the record's radius; null for gsx_render_backward_geometry
+// gsx_render_backward_camera (cg not null): the chain kernel's camera instance also leaves each block's 24 terms of
+// dL/dworld2view and dL/dfull_proj in a row of cg->partials (kCameraPartialBytes per 256 ranks, gsx_plan.h), and one
+// small kernel adds the rows in a fixed order into the two 4x4 outputs.
+struct CameraGrads {
+    float *world2view, *full_proj;   // device, 16 floats each
+    float *partials;                 // workspace
+};
 hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
                                     const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s);
+                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
+                                    const CameraGrads *cg = nullptr);
 
 }  // namespace gsx

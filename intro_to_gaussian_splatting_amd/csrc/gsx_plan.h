@@ -196,14 +196,16 @@ struct Carve {
     size_t tkeys0, tkeys1, tvals0, tvals1;  // cap x u32: tile ids / Gaussian indices (ping-pong)
     size_t ranges, longs, redo, sched_header, sched, counters, temp, temp_bytes, total;
     size_t raw, rank_of, prefix, bsum, slots;   // gsx_render_backward only (carve(.., backward)); 0 otherwise
-    size_t geo_slots;                           // gsx_render_backward_geometry only (kCarveGeometry); 0 otherwise
+    size_t geo_slots;                           // gsx_render_backward_geometry only (kCarveGeometry and up); 0 otherwise
+    size_t cam_partials;                        // gsx_render_backward_camera only (kCarveCamera); 0 otherwise
 };
 
 // Which entry point a workspace is carved for: the forward's regions alone, with gsx_render_backward's behind them, or
 // with gsx_render_backward_geometry's second slot array behind those.  (An int, so that the callers of the two-mode
 // carve that pass `true` keep meaning kCarveBackward.)
-enum { kCarveForward = 0, kCarveBackward = 1, kCarveGeometry = 2 };
+enum { kCarveForward = 0, kCarveBackward = 1, kCarveGeometry = 2, kCarveCamera = 3 };
 constexpr size_t kGeoSlotBytes = 32;   // two float4 per pair: (S1, S2, S3, S4), (S5, 0, 0, 0) -- gsx_backward.hip
+constexpr size_t kCameraPartialBytes = 24 * sizeof(float);   // per 256 depth ranks: one block's camera terms -- gsx_backward.hip
 
 // The 64-byte `counters` block: what the kernels of one frame hand to each other on the device.
 //   u32 [0] Gaussians behind the cull plane   [1] Gaussians kept by the depth sort (M)
@@ -213,7 +215,8 @@ enum { kCtrCulled = 0, kCtrKept = 1, kCtrPairs = 2, kCtrLong = 3 };
 
 // backward: gsx_render_backward's workspace -- the forward's regions for `cap` pairs, then per Gaussian its raw stage-1
 // record (launch_project_raw), its rank and the emission prefix, the scan's block sums, and one float4 slot per pair.
-// kCarveGeometry: the same layout byte for byte, then kGeoSlotBytes more per pair.
+// kCarveGeometry: the same layout byte for byte, then kGeoSlotBytes more per pair.  kCarveCamera: the geometry layout
+// byte for byte, then kCameraPartialBytes per 256 Gaussians.
 inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes, int backward = kCarveForward) {
     Carve c = {};
     size_t off = 0;
@@ -247,7 +250,8 @@ inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes,
         c.bsum = take((nn / 1024 + 2) * 4);
         c.slots = take(cc * 16);
     }
-    if (backward == kCarveGeometry) c.geo_slots = take(cc * kGeoSlotBytes);
+    if (backward >= kCarveGeometry) c.geo_slots = take(cc * kGeoSlotBytes);
+    if (backward == kCarveCamera) c.cam_partials = take((nn / 256 + 1) * kCameraPartialBytes);
     c.total = off;
     return c;
 }

@@ -11,6 +11,10 @@ it.  One step, numbered from 1:
 4. ``loss.backward()``;
 5. ``density.accumulate()``;
 6. ``opt.step()``, then ``opt.zero_grad()``;
+   With ``refine_poses`` the frame of 2 is rendered with ``camera_gradients=True`` besides, 4 leaves dL/dworld2view in
+   ``scene.images[idx].world2view.grad``, and ``refiner.step()`` (``CameraRefiner``: the pose chain and its Adam step on
+   the host, then ``set_world2view``) runs right here, after ``opt.zero_grad()`` and before the events: the Gaussians and
+   the camera both step along gradients of the SAME frame;
 7. the events ``events_at`` names for this step, in this order: ``density.densify_and_prune(generator)``,
    ``density.reset_opacity(opacity_reset_logit)``, ``gaussians.oneup_sh_degree()``.
 
@@ -26,6 +30,7 @@ import torch
 
 from .density import DensityControl
 from .optim import GROUP_NAMES, GaussianAdam
+from .pose import CameraRefiner
 
 EVENT_NAMES = ("densify", "opacity_reset", "sh_oneup")
 # the published rates (Kerbl et al. 2023); the position rate is per unit of scene extent there: scale it for the scene
@@ -70,13 +75,17 @@ class Trainer:
     ``lr``: name -> rate or callable of the step, as ``GaussianAdam`` takes it; the arrays it names that the container holds
     are set to require grad (an SH container trains ``sh``, never ``colors``).  ``statistic`` and ``density`` (keyword
     arguments) go to ``DensityControl``.  ``seed`` seeds both the view order (CPU) and the split positions (device).
-    The schedule arguments are ``events_at``'s.  ``opt`` and ``density`` are public: their knobs may be changed between steps."""
+    The schedule arguments are ``events_at``'s.  ``opt`` and ``density`` are public: their knobs may be changed between steps.
+    ``refine_poses``: None (every call and every bit as without it), or a dict of ``CameraRefiner`` keywords
+    (``lr_rotation`` and ``lr_translation`` are required there; ``indices`` defaults to the views of ``targets``): the
+    cameras are refined beside the Gaussians, ``refiner`` is public."""
 
     def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
                  tile_size: int = 16, statistic: str = "screen", density: Optional[dict] = None,
                  sh_degree_every: Optional[int] = 1000, densify_from: int = 500, densify_every: Optional[int] = 100,
                  densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000,
-                 opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0) -> None:
+                 opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0,
+                 refine_poses: Optional[dict] = None) -> None:
         g = scene.gaussians
         if not targets:
             raise ValueError("targets is empty: nothing to fit")
@@ -102,6 +111,10 @@ class Trainer:
         self.opacity_reset_logit = float(opacity_reset_logit)
         self.opt = GaussianAdam(g, lr=lr)
         self.density = DensityControl(g, optimizer=self.opt, scene=scene, statistic=statistic, **(density or {}))
+        self.refiner = None
+        if refine_poses is not None:
+            kw = dict(refine_poses)
+            self.refiner = CameraRefiner(scene, kw.pop("indices", sorted(self.targets)), **kw)
         self.step_count = 0
         self._views = sorted(self.targets)
         self._order: list = []
@@ -120,8 +133,12 @@ class Trainer:
         """One step.  Returns ((3,) device tensor: loss, l1, ssim; the view): nothing is read back to the host here."""
         scene, g = self.scene, self.gaussians
         idx = self._next_view()
-        frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
-                                       screen_statistics=self.statistic == "screen")
+        if self.refiner is None:
+            frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
+                                           screen_statistics=self.statistic == "screen")
+        else:
+            frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
+                                           screen_statistics=self.statistic == "screen", camera_gradients=True)
         terms: dict = {}
         loss = scene.photometric_loss(idx, frame, self.targets[idx], tile_size=self.tile_size,
                                       lambda_dssim=self.lambda_dssim, terms=terms)
@@ -129,6 +146,8 @@ class Trainer:
         self.density.accumulate()
         self.opt.step()
         self.opt.zero_grad()
+        if self.refiner is not None:
+            self.refiner.step()
         self.step_count += 1
         for event in self.events_at(self.step_count):
             if event == "densify":

@@ -246,6 +246,12 @@ class CapturedFrame:
         return self.out
 
 
+def _camera_wants_grad(image, camera: bool) -> bool:
+    """``camera_gradients=True`` and the view's ``world2view`` requires grad (grad mode on): the frame is differentiable for
+    the pose alone."""
+    return bool(camera) and torch.is_grad_enabled() and bool(getattr(image.world2view, "requires_grad", False))
+
+
 def _wants_grad(g, geometry: bool = False) -> bool:
     """Gradients are recorded for this render: grad mode is on and the colours or the opacity logits require grad --
     or, with ``geometry`` (``geometry_gradients=True``), the points, scales or quaternions -- or, on an SH scene, the
@@ -287,12 +293,16 @@ class _RenderImageFunction(torch.autograd.Function):
     ``scene.screen_statistics`` = (image_idx, dL/d(NDC mean) (N,2), screen radius (N,)) left for ``DensityControl``.  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
     colour), and gsx_sh_backward carries that on to dL/dsh and -- with geometry gradients -- adds the view direction's
     share to dL/dpoints; ``colors`` gets None (the frame does not read it).  The tensors are saved, so autograd's version
-    counters catch an in-place edit between forward and backward."""
+    counters catch an in-place edit between forward and backward.  ``world2view`` (None unless ``camera_gradients=True``
+    and the view's tensor requires grad) gets the total derivative of the pose: gsx_render_backward_camera's
+    dL/dworld2view + dL/dfull_proj @ projection_matrix^T, plus, on an SH scene, the camera centre's share."""
 
     @staticmethod
-    def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh):
+    def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh,
+                world2view=None):
         kw = dict(kw)
-        ctx.geometry = bool(kw.pop("geometry_gradients", False))
+        ctx.camera = world2view is not None
+        ctx.geometry = bool(kw.pop("geometry_gradients", False)) or ctx.camera
         ctx.screen = bool(kw.pop("screen_statistics", False))
         user_stats, st = kw.pop("stats", None), {}
         frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
@@ -310,19 +320,31 @@ class _RenderImageFunction(torch.autograd.Function):
         scene = ctx.scene
         want = ctx.needs_input_grad
         # the colour-only call gives the same colour and opacity bits; the screen entry runs whoever requires grad
-        geometry = ctx.geometry and (ctx.screen or any(want[5:8]))
+        camera = ctx.camera and want[11]
+        geometry = ctx.geometry and (ctx.screen or camera or any(want[5:8]))
         grads = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
-                                       ctx.n_instances, ctx.n_visible, geometry=geometry, screen=ctx.screen)
+                                       ctx.n_instances, ctx.n_visible, geometry=geometry, screen=ctx.screen, camera=camera)
         gc, go = grads[:2]
         gp, gs, gq = grads[2:5] if geometry else (None, None, None)
         if ctx.screen:
             scene.screen_statistics = (ctx.image_idx, grads[5], grads[6].view(-1))
+        gw2v = None
+        if camera:          # full_proj = world2view @ projection_matrix: the two partial derivatives into the total one
+            image = scene.images[ctx.image_idx]
+            gw2v = grads[-2] + grads[-1] @ image.projection_matrix.t()
         gsh = None
         if ctx.has_sh:      # gc is dL/d(view-dependent colour): on to the coefficients, and through the direction to the mean
             sh = ctx.saved_tensors[6]
-            gsh, gview = scene._sh_backward(ctx.image_idx, gc, with_points=geometry and want[5])
+            gsh, gview = scene._sh_backward(ctx.image_idx, gc, with_points=camera or (geometry and want[5]))
             gsh, gc = gsh.view(sh.shape), None
-            if gview is not None:
+            if gview is not None and camera:
+                # the direction is point - centre: dL/dcentre = -sum of the rows; centre = inverse(world2view)[3,:3], and
+                # d inverse(V) = -inverse(V) dV inverse(V), so dL/dV = -inverse(V)^T G inverse(V)^T with G[3,:3] = dL/dcentre
+                inv_t = image.view2world.t()
+                G = torch.zeros((4, 4), dtype=torch.float32, device=gview.device)
+                G[3, :3] = -gview.sum(0)
+                gw2v = gw2v - inv_t @ G @ inv_t
+            if gview is not None and gp is not None and want[5]:
                 gp = gp + gview
         return (None, None, None, None, None,
                 gp.view(points.shape) if gp is not None and want[5] else None,
@@ -330,7 +352,8 @@ class _RenderImageFunction(torch.autograd.Function):
                 gq.view(quaternions.shape) if gq is not None and want[7] else None,
                 go.view(opacity.shape) if want[8] else None,
                 gc.view(colors.shape) if gc is not None and want[9] else None,
-                gsh if want[10] else None)
+                gsh if want[10] else None,
+                gw2v)
 
 
 class GaussianScene:
@@ -353,6 +376,7 @@ class GaussianScene:
         self._pinned_pool = None
         self._pinned_next = 0
         self.screen_statistics = None   # (image_idx, dL/d(NDC mean) (N,2), radius (N,)) of the latest screen_statistics backward
+        self._pose_seen = {}          # image -> GaussianImage.pose_version its last frame was planned with (_check_pose)
 
     # ------------------------------------------------------------------ helpers
     def _colors(self, image_idx: int) -> torch.Tensor:
@@ -506,7 +530,7 @@ class GaussianScene:
                          tile_schedule: Optional[bool] = None, use_hints: bool = True,
                          substrips: Optional[Sequence[int]] = None, substrip_events: Optional[list] = None,
                          _private: Optional[dict] = None, geometry_gradients: bool = False,
-                         screen_statistics: bool = False) -> torch.Tensor:
+                         screen_statistics: bool = False, camera_gradients: bool = False) -> torch.Tensor:
         """Full forward render in libgsx (gsx_render_forward).
 
         semantics: "ref_cpu" (the reference's ``render_image``), "ref_cuda" (its CUDA kernel's rules
@@ -553,12 +577,24 @@ class GaussianScene:
         is the one of the scene truncated to the active bands -- rendered from this camera's evaluated colours
         (gsx_sh_to_rgb_active) instead of GsxParams.sh, one (N,3) array per frame; dL/dsh is zero in the inactive bands.
         ``camera_buffer`` is then refused (ValueError).
+        ``camera_gradients``: when ``scene.images[image_idx].world2view.requires_grad`` is set (and grad mode is on) the
+        frame is differentiable for the pose -- alone, or beside whichever Gaussian arrays require grad -- and
+        ``backward()`` leaves in ``world2view.grad`` the total derivative dL/dworld2view + dL/dfull_proj @
+        projection_matrix^T of gsx_render_backward_camera (full_proj_transform = world2view @ projection_matrix; the
+        intrinsics are constants), plus, on an SH scene, the share that reaches the pose through the camera centre
+        (the view direction's gradient of gsx_sh_backward_active, which this path always requests, through
+        inverse(world2view)[3,:3]).  It implies the geometry kernels whether or not a geometry array requires grad; the
+        Gaussian gradients and the frame are the same bits either way.  The frame is rendered from the ``GsxCamera`` baked
+        by the image: editing ``world2view`` in place does NOT move the camera, ``GaussianImage.set_world2view`` does
+        (``CameraRefiner`` steps the pose that way).  The refusals are those of the other gradient paths.
         """
         if screen_statistics and not geometry_gradients:
             raise ValueError("screen_statistics=True needs geometry_gradients=True: the statistic comes out of the geometry "
                              "backward (gsx_render_backward_screen)")
         g = self.gaussians
-        if _private is None and _wants_grad(g, bool(geometry_gradients)):
+        w2v = self.images[image_idx].world2view if _private is None and \
+            _camera_wants_grad(self.images[image_idx], camera_gradients) else None
+        if _private is None and (w2v is not None or _wants_grad(g, bool(geometry_gradients))):
             # gradients (gsx_render_backward, gsx_render_backward_geometry, gsx_sh_backward): the whole ref_cpu frame only
             for what, bad in _refusals(g, semantics, tile_window, out, substrips, no_sync, camera_buffer):
                 if bad:
@@ -567,7 +603,7 @@ class GaussianScene:
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
                       geometry_gradients=bool(geometry_gradients), screen_statistics=bool(screen_statistics))
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
-                                              g.opacity, g.colors, getattr(g, "sh", None))
+                                              g.opacity, g.colors, getattr(g, "sh", None), w2v)
         own = _OwnedFrame.of(_private)
         speculative = bool(no_sync and not timing)
         plan = self._plan_frame(image_idx, tile_size, layout, tile_window, out, out_origin, timing, semantics, background,
@@ -606,6 +642,7 @@ class GaussianScene:
                              "follow; raise active_sh_degree to sh_degree first"
                              % (self._active_sh_degree(), int(self.gaussians.sh_degree), image_idx))
         dev, n, tensors = self._inputs(image_idx, inline_sh=not truncated)
+        self._check_pose(image_idx)
         cam = self.images[image_idx].gsx_camera()
         width, height = cam.width, cam.height
         params, oi = self._frame_params(dev, n, layout, semantics)
@@ -773,11 +810,13 @@ class GaussianScene:
 
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
                          n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False,
-                         screen: bool = False) -> Tuple[torch.Tensor, ...]:
+                         screen: bool = False, camera: bool = False) -> Tuple[torch.Tensor, ...]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
         ``grad_frame``; with ``geometry`` gsx_render_backward_geometry: those two and (dL/dpoints (N,3), dL/dscales (N,3),
         dL/dquaternions (N,4)); with ``screen`` besides gsx_render_backward_screen: those five and (dL/d(NDC mean) (N,2),
-        screen radius (N,1)).  The projection, depth order and binning run again in the library (the same lists as the
+        screen radius (N,1)); with ``camera`` (with or without ``screen``) gsx_render_backward_camera: the same, and last
+        (dL/dworld2view (4,4), dL/dfull_proj (4,4)), the two matrices as independent inputs.
+        The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
         lib = _ffi.load()
@@ -796,19 +835,25 @@ class GaussianScene:
             outs = [gc, go]
             if geometry:
                 outs += [torch.empty((n, k), dtype=torch.float32, device=dev) for k in (3, 3, 4) + ((2, 1) if screen else ())]
-            elif screen:
-                raise ValueError("screen needs geometry: the statistic comes out of the geometry backward")
+            elif screen or camera:
+                raise ValueError("screen and camera need geometry: both come out of the geometry backward")
             cap = int(n_instances) + 4096
             size_fn = lib.gsx_backward_geometry_workspace_bytes if geometry else lib.gsx_backward_workspace_bytes
             entry = (lib.gsx_render_backward_screen if screen else lib.gsx_render_backward_geometry) if geometry \
                 else lib.gsx_render_backward
+            args = outs
+            if camera:
+                cam_outs = [torch.empty((4, 4), dtype=torch.float32, device=dev) for _ in range(2)]
+                args = outs + ([] if screen else [None, None]) + cam_outs       # grad_means2d, screen_radius: NULL
+                outs = outs + cam_outs
+                size_fn, entry = lib.gsx_backward_camera_workspace_bytes, lib.gsx_render_backward_camera
             with torch.cuda.device(dev):
                 nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
                 if nbytes == 0:
                     raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "the backward workspace function rejected the sizes")
                 ws = _WORKSPACE.get(dev, nbytes)
                 rc = entry(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(img), _ptr(gf),
-                           *[_ptr(t) for t in outs], ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
+                           *[_ptr(t) for t in args], ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
             _ffi.check(rc)
         return tuple(outs)
 
@@ -843,6 +888,22 @@ class GaussianScene:
             self._n_redo_seen[cap_key] = int(n_redo)
         if cap_key[2] is None and cap_key[3] == "ref_cpu":
             self._last_instances = n_instances
+
+    def _check_pose(self, image_idx) -> None:
+        """``GaussianImage.set_world2view`` moved this view since its last frame: what the scene keeps for the view from
+        earlier frames was measured at the old pose -- the pair capacity, the kept count, the n_redo count (which chooses
+        GSX_FLAG_PLAIN_FOOTPRINTS) and the GsxParams.hints buffers (depth-sort splitters, tile schedule) of every tile
+        size, window, rule set and stream.  All four are dropped for this view, so its next frame is a first frame.  The
+        scene-wide workspace sizing stays: it is a size, not a statement about a pose."""
+        version = getattr(self.images[image_idx], "pose_version", 0)
+        if self._pose_seen.get(image_idx, 0) == version:
+            return
+        self._pose_seen[image_idx] = version
+        for table in (self._cap_hints, self._kept_hints, self._n_redo_seen):
+            for key in [k for k in table if k[0] == image_idx]:
+                del table[key]
+        for key in [k for k in self._hints if k[0][0] == image_idx]:
+            del self._hints[key]
 
     def gaussians_changed(self) -> None:
         """Tell the scene that the ROWS of ``gaussians`` changed -- their number or which Gaussian a row holds
@@ -954,14 +1015,15 @@ class GaussianScene:
         return frame
 
     def render_image(self, image_idx: int, tile_size: int = 16, geometry_gradients: bool = False,
-                     screen_statistics: bool = False) -> torch.Tensor:
+                     screen_statistics: bool = False, camera_gradients: bool = False) -> torch.Tensor:
         """(W,H,3) float32 indexed [x,y]; same result as the reference's pure-Python
         ``render_image`` (gaussian_scene.py:200-238), computed on the GPU and -- like the reference,
         whose image is a CPU tensor (gaussian_scene.py:206) -- returned in host memory, so that
         ``plt.imshow(scene.render_image(i))`` keeps working.  ``render_image_hip`` is the same frame
-        left on the device.  ``geometry_gradients``, ``screen_statistics``: as in ``render_image_hip``."""
+        left on the device.  ``geometry_gradients``, ``screen_statistics``, ``camera_gradients``: as in
+        ``render_image_hip``."""
         frame = self.render_image_hip(image_idx, tile_size=tile_size, layout="wh3", geometry_gradients=geometry_gradients,
-                                      screen_statistics=screen_statistics)
+                                      screen_statistics=screen_statistics, camera_gradients=camera_gradients)
         # page-locked destination (torch's caching host allocator keeps the pages registered between
         # calls): the copy runs at PCIe rate instead of through a pageable staging loop
         host = torch.empty(frame.shape, dtype=frame.dtype, pin_memory=True)

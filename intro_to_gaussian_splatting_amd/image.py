@@ -81,21 +81,14 @@ class GaussianImage:
         P[2, 2] = 1.0 * zfar / (zfar - znear)
         P[2, 3] = -(zfar * znear) / (zfar - znear)
         projection = P.t().contiguous()
-        full_proj = world2view.unsqueeze(0).bmm(projection.unsqueeze(0)).squeeze(0)
 
         self.f_x, self.f_y, self.c_x, self.c_y = f_x.to(dev), f_y.to(dev), c_x.to(dev), c_y.to(dev)
-        self.R, self.T = R.unsqueeze(0).to(dev), T.to(dev)
         self.height, self.width = height.to(dev), width.to(dev)
         self.fovX, self.fovY = fovX.to(dev), fovY.to(dev)
         self.tan_fovX, self.tan_fovY = tan_fovX.to(dev), tan_fovY.to(dev)
         self.zfar, self.znear = zfar.to(dev), znear.to(dev)
         self.name = image.name
-        self.world2view = world2view.to(dev)
         self.projection_matrix = projection.to(dev)
-        self.full_proj_transform = full_proj.to(dev)
-        center = world2view.inverse()[3, :3]
-        self.camera_center = center.to(dev)
-        self.camera_center_host = tuple(float(v) for v in center)   # read per frame by the SH kernel's caller
         # carried for users of the reference's attribute surface; the render path does not read them
         # (splat/image.py:32-34, 39, 68-70; splat/utils.py:19-52)
         intrinsic = torch.zeros((3, 4), dtype=f32)
@@ -103,17 +96,54 @@ class GaussianImage:
         intrinsic[1, 1], intrinsic[1, 2] = f_y[0], c_y[0]
         intrinsic[2, 2] = 1.0
         self.intrinsic_matrix = intrinsic.to(dev)
-        self.extrinsic_matrix = extrinsic.to(dev)
-        self.projection = (intrinsic @ extrinsic).to(dev)
 
         cam = _ffi.GsxCamera()
-        cam.world2view[:] = world2view.reshape(-1).tolist()
-        cam.full_proj[:] = full_proj.reshape(-1).tolist()
         cam.tan_fovx, cam.tan_fovy = float(tan_fovX), float(tan_fovY)
         cam.fx, cam.fy = float(f_x), float(f_y)
         cam.width, cam.height = int(camera.width), int(camera.height)
-        cam.camera_center[:] = [float(v) for v in center]
         self._gsx_camera = cam
+        self._projection_host, self._intrinsic_host = projection, intrinsic     # what every pose is combined with
+        self.pose_version = 0       # counts set_world2view calls: a GaussianScene compares it with the one its frames saw
+        self._apply_pose(world2view, requires_grad=False)
+
+    def _apply_pose(self, world2view: torch.Tensor, requires_grad: bool) -> None:
+        """Everything that follows from the pose, from a host float32 (4,4) ``world2view`` (row-vector convention): the
+        constructor's own arithmetic, so the same pose gives the same bits."""
+        dev = self.device
+        projection = self._projection_host
+        extrinsic = world2view.t().contiguous()
+        full_proj = world2view.unsqueeze(0).bmm(projection.unsqueeze(0)).squeeze(0)
+        self.R, self.T = extrinsic[:3, :3].contiguous().unsqueeze(0).to(dev), extrinsic[:3, 3].contiguous().to(dev)
+        self.world2view = world2view.to(dev).clone().requires_grad_(requires_grad)     # a leaf of its own
+        self.full_proj_transform = full_proj.to(dev)
+        inverse = world2view.inverse()
+        center = inverse[3, :3]
+        self.view2world = inverse.to(dev)       # the pose's share of an SH scene's gradient goes through it (camera_gradients)
+        self.camera_center = center.to(dev)
+        self.camera_center_host = tuple(float(v) for v in center)   # read per frame by the SH kernel's caller
+        self.extrinsic_matrix = extrinsic.to(dev)
+        self.projection = (self._intrinsic_host @ extrinsic).to(dev)
+        cam = self._gsx_camera
+        cam.world2view[:] = world2view.reshape(-1).tolist()
+        cam.full_proj[:] = full_proj.reshape(-1).tolist()
+        cam.camera_center[:] = [float(v) for v in center]
+
+    def set_world2view(self, world2view: torch.Tensor) -> None:
+        """Moves the camera: ``world2view`` (4,4) float32, on any device, row-vector convention (its last column is
+        (0, 0, 0, 1) for a rigid pose; it is taken as given).  Re-derives what the constructor derives from the pose --
+        ``world2view``, ``full_proj_transform`` (the same float32 bmm), ``camera_center`` / ``camera_center_host``,
+        ``extrinsic_matrix``, ``R``, ``T``, ``projection`` and the ``GsxCamera`` the kernels read -- and leaves the
+        intrinsics alone.  The new ``world2view`` is a fresh leaf (no ``.grad``) that keeps the old one's
+        ``requires_grad``.  ``pose_version`` goes up by one: a ``GaussianScene`` then treats the view's next frame as the
+        first frame of a new pose.  Editing ``self.world2view`` in place does NOT move the camera: the kernels read the
+        ``GsxCamera`` baked here."""
+        if not torch.is_tensor(world2view) or tuple(world2view.shape) != (4, 4) or world2view.dtype != torch.float32:
+            raise ValueError("world2view must be a (4, 4) float32 tensor")
+        host = world2view.detach().to("cpu").contiguous().clone()
+        if not bool(torch.isfinite(host).all()):
+            raise ValueError("world2view holds a value that is not finite")
+        self._apply_pose(host, requires_grad=bool(self.world2view.requires_grad))
+        self.pose_version += 1
 
     def project_point_to_camera_perspective_projection(
             self, points: torch.Tensor, colors: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

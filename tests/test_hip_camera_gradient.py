@@ -1,0 +1,350 @@
+"""Camera gradients on the GPU: gsx_render_backward_camera (dL/dworld2view and dL/dfull_proj of the ref_cpu frame), held
+entry by entry against the float64 restatement (tests/camera_gradient_restatement.py) and against the reference's own
+autograd (tests/golden/camgrad_*.npz); ``camera_gradients=True`` through ``render_image_hip``; ``set_world2view`` on a
+scene; one ``Trainer`` step with ``refine_poses``.
+
+Bounds (test_camera_gradient_host.py): E_REF is the worst scaled error of the reference's own float32 autograd against the
+restatement, per matrix; the kernel is held to 12 E_REF against the restatement and 13 E_REF against the fixtures, the unit
+being the entry's sum of |terms|.  Everything else is bits.
+"""
+import numpy as np
+import pytest
+import torch
+
+import camera_gradient_restatement as cgr
+import geometry_backward_restatement as gbr
+import screen_gradient_restatement as sgr
+from test_camera_gradient_host import BOUND_FIXTURE, BOUND_RESTATEMENT, CAM_SCENES, fixture_inputs
+from test_hip_backward import DEV, _golden_scene, _oracle_pre, _scene
+from test_hip_geometry_backward import _camera
+
+pytestmark = pytest.mark.gpu
+
+# Worst error / scale measured on an MI355X over every test of this file that calls _check:
+#                 against the restatement                  against the reference's autograd
+#   world2view    5.83e-09  (rows1_48x48_n1)               6.27e-09  (rows1_48x48_n1)
+#   full_proj     6.41e-09  (edge: 1 of 500 visible)       9.11e-09  (tiny_48x48_n600)
+# (bounds: 12 E_REF = 3.49e-08, 6.64e-08 and 13 E_REF = 3.79e-08, 7.19e-08.)
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32)
+
+
+def _same(a, b):
+    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
+
+
+def _entry(scene, W, tile=16, screen=True, camera=True):
+    """(frame, outputs of the backward entry) for dL/dframe = W: gsx_render_backward_camera, or the screen / geometry
+    entry without ``camera``.  The camera entry's last two outputs are dL/dworld2view and dL/dfull_proj."""
+    st = {}
+    with torch.no_grad():
+        frame = scene.render_image_hip(1, tile_size=tile, stats=st)
+        outs = scene._render_backward(1, tile, "wh3", frame, W, int(st["n_instances"]), int(st["n_visible"]), geometry=True,
+                                      screen=screen, camera=camera)
+    return frame, outs, st
+
+
+def _restate(scene, sc, frame, W, tile):
+    """(gV, gF, scale of gV, scale of gF) float64 of the frame the kernel rendered."""
+    pre = _oracle_pre(scene, sc)
+    w, h = int(sc["width"]), int(sc["height"])
+    mom = gbr.moments(pre, frame.cpu().numpy(), W.cpu().numpy(), w, h, tile)
+    args = (pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene), None, None, w, h, tile)
+    return cgr.camera_backward(*args, moments=mom) + cgr.camera_backward(*args, absolute=True, moments=mom)
+
+
+def _check(tag, got_v, got_f, restated, fixture=None):
+    gV, gF, aV, aF = restated
+    for key, got, ref, scale in (("world2view", got_v, gV, aV), ("full_proj", got_f, gF, aF)):
+        got = got.cpu().numpy().astype(np.float64)
+        e = cgr.scaled_error(got, ref, scale)
+        line = "%s: %s: kernel vs restatement, max error / scale %.4g (bound %.3g)" % (tag, key, e, BOUND_RESTATEMENT[key])
+        if fixture is not None:
+            ef = cgr.scaled_error(got, fixture["grad_" + key], scale)
+            line += "; vs reference autograd %.4g (bound %.3g)" % (ef, BOUND_FIXTURE[key])
+        print(line)
+        assert np.isfinite(got).all(), (tag, key)
+        assert e <= BOUND_RESTATEMENT[key], (tag, key, e)
+        if fixture is not None:
+            assert ef <= BOUND_FIXTURE[key], (tag, key, ef)
+    # the structural zeros are exact +0
+    assert not _bits(got_v)[:, 3].any() and not _bits(got_f)[:, 2].any(), tag
+
+
+def _sc(base):
+    return {k: base[k] for k in ("points", "scales", "quaternions", "opacity", "width", "height")}
+
+
+@pytest.mark.parametrize("name", CAM_SCENES)
+def test_camera_entry_matches_reference_and_restatement(tmp_path, name):
+    from conftest import load_golden
+
+    gg, base = fixture_inputs(name)
+    scene = _golden_scene(tmp_path, base)
+    W = torch.from_numpy(base["W"]).to(DEV)
+    tile = int(base["tile"])
+    frame, outs, _ = _entry(scene, W, tile)
+    assert np.abs(frame.cpu().numpy() - base["image"]).max() <= 1e-4
+    gv, gf = outs[-2], outs[-1]
+    assert gv.shape == gf.shape == (4, 4) and gv.abs().max() > 0 and gf.abs().max() > 0
+    _check(name, gv, gf, _restate(scene, _sc(base), frame, W, tile), fixture=load_golden("camgrad_" + name))
+    # the older outputs are the screen entry's bits; without the two optional outputs the rest is the same bits again
+    _, screen, _ = _entry(scene, W, tile, camera=False)
+    assert len(screen) == 7 and len(outs) == 9
+    for a, b in zip(screen, outs):
+        assert _same(a, b)
+    _, bare, _ = _entry(scene, W, tile, screen=False)
+    assert len(bare) == 7
+    for a, b in zip(outs[:5] + outs[7:], bare):
+        assert _same(a, b)
+    # twice: the same 32 floats
+    _, again, _ = _entry(scene, W, tile)
+    assert _same(again[-2], gv) and _same(again[-1], gf)
+
+
+# ---- the reduction's edges, on 48 x 48 frames
+def _few(n, visible, seed):
+    from intro_to_gaussian_splatting_amd.synthetic import make_few_visible_scene
+
+    return make_few_visible_scene(n, 48, 48, seed=seed, visible=visible)
+
+
+def _c_visible(sc):
+    """How many Gaussians the C restatement's stage 1 keeps (no GPU)."""
+    from oracle import c_oracle, cpu_ref
+    from intro_to_gaussian_splatting_amd import GaussianImage
+    from intro_to_gaussian_splatting_amd.colmap import Camera, Image
+
+    im = GaussianImage(Camera(1, "PINHOLE", int(sc["width"]), int(sc["height"]),
+                              np.array([sc["fx"], sc["fy"], sc["cx"], sc["cy"]], np.float64)),
+                       Image(1, np.asarray(sc["qvec"]), np.asarray(sc["tvec"]), 1, "v"), device="cpu")
+    c = im.gsx_camera()
+    cam = cpu_ref.Camera(im.world2view.numpy(), im.full_proj_transform.numpy(), np.float32(c.tan_fovx), np.float32(c.tan_fovy),
+                         np.float32(c.fx), np.float32(c.fy), c.width, c.height)
+    colors = np.zeros((sc["points"].shape[0], 3), np.float32)
+    return c_oracle.preprocess(sc["points"], colors, sc["scales"], sc["quaternions"], sc["opacity"], cam)
+
+
+# (Gaussians, visible, seed): one and three visible (the two small row classes), one full chain block, one more
+EDGES = [(500, 1, 41), (500, 3, 43), (300, 256, 44), (300, 257, 44)]
+
+
+@pytest.mark.parametrize("n,visible,seed", EDGES)
+def test_reduction_edges(tmp_path, n, visible, seed):
+    sc = _few(n, visible, seed)
+    pre = _c_visible(sc)                    # on the CPU first: the generator gives that many depth ranks
+    assert np.asarray(pre.order).size == visible
+    scene = _scene(tmp_path, sc)
+    W = torch.from_numpy(np.random.default_rng(seed).standard_normal((48, 48, 3)).astype(np.float32)).to(DEV)
+    frame, outs, st = _entry(scene, W)
+    assert int(st["n_visible"]) == visible and frame.abs().max() > 0
+    _check("edge %d visible" % visible, outs[-2], outs[-1], _restate(scene, sc, frame, W, 16))
+    assert outs[-2].abs().max() > 0
+    _, again, _ = _entry(scene, W)
+    assert _same(again[-2], outs[-2]) and _same(again[-1], outs[-1])
+
+
+def test_no_visible_gaussian_gives_32_exact_zeros(tmp_path):
+    sc = _few(300, 0, 45)
+    assert np.asarray(_c_visible(sc).order).size == 0
+    scene = _scene(tmp_path, sc)
+    W = torch.ones((48, 48, 3), device=DEV)
+    frame, outs, st = _entry(scene, W)
+    assert int(st["n_visible"]) == 0 and not frame.any()
+    assert not _bits(outs[-2]).any() and not _bits(outs[-1]).any()
+    # one visible Gaussian that is on no tile list: the same
+    from conftest import load_golden
+
+    fwd = load_golden("onevisible_48x48_n7")
+    scene = _golden_scene(tmp_path, fwd)
+    frame, outs, st = _entry(scene, W, tile=int(fwd["tile"]))
+    assert int(st["n_visible"]) == 1 and not frame.any()
+    assert all(not _bits(o).any() for o in outs)
+
+
+def test_ranks_in_the_middle_of_a_block_on_no_tile_list(tmp_path):
+    from intro_to_gaussian_splatting_amd.synthetic import make_scene
+
+    sc = make_scene(300, 48, 48, seed=46)
+    pre = _c_visible(sc)
+    on = sgr.listed(pre, 48, 48, 16)
+    m = on.size
+    off = np.nonzero(~on)[0]
+    # unlisted ranks strictly inside the first chain block, with listed ranks on both sides of them
+    inside = [r for r in off if 0 < r < min(m, 256) - 1 and on[:r].any() and on[r + 1:min(m, 256)].any()]
+    assert m > 64 and len(inside) >= 3, (m, off)
+    scene = _scene(tmp_path, sc)
+    W = torch.from_numpy(np.random.default_rng(46).standard_normal((48, 48, 3)).astype(np.float32)).to(DEV)
+    frame, outs, st = _entry(scene, W)
+    assert int(st["n_visible"]) == m
+    _check("unlisted ranks", outs[-2], outs[-1], _restate(scene, sc, frame, W, 16))
+    rows = torch.from_numpy(np.asarray(pre.order, np.int64)[off]).to(DEV)
+    for o in outs[:7]:
+        assert not _bits(o)[rows].any()
+
+
+# ---- through render_image_hip
+def _loss_grad(scene, target, camera_gradients=True, **kw):
+    frame = scene.render_image_hip(1, camera_gradients=camera_gradients, **kw)
+    scene.photometric_loss(1, frame, target).backward()
+    return frame.detach()
+
+
+def test_world2view_grad_is_the_total_derivative_composed_by_hand(tmp_path):
+    from conftest import load_golden
+
+    base = load_golden("grad_small_64x48_n300")
+    scene = _golden_scene(tmp_path, base)
+    g, im = scene.gaussians, scene.images[1]
+    with torch.no_grad():
+        target = (scene.render_image_hip(1) * 0.5 + 0.1).clone()
+        assert scene.render_image_hip(1, camera_gradients=True).grad_fn is None
+    # nothing requires grad: no graph, whatever the flag says
+    assert scene.render_image_hip(1, camera_gradients=True).grad_fn is None
+    im.world2view.requires_grad_(True)
+    assert scene.render_image_hip(1).grad_fn is None                    # not without the flag
+    frame = _loss_grad(scene, target)                                   # the pose alone: no Gaussian array requires grad
+    got = im.world2view.grad.clone()
+    assert got.shape == (4, 4) and got.abs().max() > 0 and g.points.grad is None and g.colors.grad is None
+    # by hand: dL/dframe from the loss, the entry's two matrices, full_proj = world2view @ projection_matrix
+    f = frame.clone().requires_grad_(True)
+    scene.photometric_loss(1, f, target).backward()
+    _, outs, _ = _entry(scene, f.grad, screen=False)
+    assert _same(got, outs[-2] + outs[-1] @ im.projection_matrix.t())
+    # beside the Gaussian arrays: their gradients are the bits they were, the pose's too
+    im.world2view.grad = None
+    for name in ("points", "scales", "quaternions", "opacity", "colors"):
+        getattr(g, name).requires_grad_(True)
+    _loss_grad(scene, target, geometry_gradients=True, screen_statistics=True)
+    with_pose = {name: getattr(g, name).grad.clone() for name in ("points", "scales", "quaternions", "opacity", "colors")}
+    stat = scene.screen_statistics
+    assert _same(im.world2view.grad, got)
+    for name in with_pose:
+        getattr(g, name).grad = None
+    im.world2view.grad = None
+    _loss_grad(scene, target, camera_gradients=False, geometry_gradients=True, screen_statistics=True)
+    assert im.world2view.grad is None
+    for name in with_pose:
+        assert _same(getattr(g, name).grad, with_pose[name]), name
+    assert _same(stat[1], scene.screen_statistics[1]) and _same(stat[2], scene.screen_statistics[2])
+    # the refusals of the other gradient paths
+    with pytest.raises(ValueError):
+        scene.render_image_hip(1, camera_gradients=True, tile_window=(0, 1, 0, 1))
+    with pytest.raises(ValueError):
+        scene.render_image_hip(1, camera_gradients=True, semantics="std_3dgs")
+
+
+def test_sh_scene_adds_the_camera_centre_s_share(tmp_path):
+    from test_hip_sh_active import _scene as _sh_scene
+
+    scene = _sh_scene(tmp_path, 300, 2)
+    g, im = scene.gaussians, scene.images[1]
+    with torch.no_grad():
+        target = (scene.render_image_hip(1) * 0.5 + 0.1).clone()
+    im.world2view.requires_grad_(True)
+    with pytest.raises(ValueError):                                     # an SH scene whose coefficients do not require grad
+        scene.render_image_hip(1, camera_gradients=True)
+    g.sh.requires_grad_(True)
+    frame = _loss_grad(scene, target)
+    got = im.world2view.grad.clone()
+    f = frame.clone().requires_grad_(True)
+    scene.photometric_loss(1, f, target).backward()
+    _, outs, _ = _entry(scene, f.grad, screen=False)
+    raster = outs[-2] + outs[-1] @ im.projection_matrix.t()
+    _, gview = scene._sh_backward(1, outs[0], with_points=True)
+    assert gview.abs().max() > 0
+    G = torch.zeros((4, 4), device=DEV)
+    G[3, :3] = -gview.sum(0)
+    inv_t = im.view2world.t()
+    assert _same(got, raster - inv_t @ G @ inv_t) and not _same(got, raster)
+    # the share itself against float64: the restatement's formula on the kernel's dL/dcentre
+    share = (got - raster).cpu().numpy().astype(np.float64)
+    want = cgr.centre_share(im.world2view.detach().cpu().numpy(), G[3, :3].cpu().numpy())
+    assert np.abs(share - want).max() <= 1e-5 * np.abs(want).max()
+    # points.grad carries the view direction's share exactly when points require grad, as before
+    g.points.requires_grad_(True)
+    im.world2view.grad = None
+    _loss_grad(scene, target, geometry_gradients=True)
+    assert _same(im.world2view.grad, got) and _same(g.points.grad, outs[2] + gview)
+
+
+def test_set_world2view_renders_the_frame_of_a_scene_built_at_that_pose(tmp_path):
+    from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians
+    from intro_to_gaussian_splatting_amd.synthetic import make_scene, orbit_poses, write_colmap_text
+
+    sc = make_scene(400, 96, 80, seed=7)
+    pose = orbit_poses(3, step_deg=6.0, qvec=sc["qvec"], tvec=sc["tvec"])[2]
+    moved_sc = dict(sc, qvec=np.asarray(pose[0]), tvec=np.asarray(pose[1]))
+    a_dir, b_dir = tmp_path / "a", tmp_path / "b"
+    write_colmap_text(str(a_dir), sc)
+    write_colmap_text(str(b_dir), moved_sc)
+    mk = lambda: Gaussians.from_arrays(sc["points"], sc["colors_0_255"], sc["scales"], sc["quaternions"], sc["opacity"], device=DEV)  # noqa: E731
+    a, b = GaussianScene(str(a_dir), mk()), GaussianScene(str(b_dir), mk())
+    with torch.no_grad():
+        first = a.render_image_hip(1).clone()
+        a.render_image_hip(1)                                           # a second frame: the view's hints are in use
+        want = b.render_image_hip(1).clone()
+        assert not _same(first, want) and want.abs().max() > 0
+        assert a._cap_hints and a._hints
+        a.images[1].set_world2view(b.images[1].world2view)
+        assert bytes(a.images[1].gsx_camera()) == bytes(b.images[1].gsx_camera())
+        st = {}
+        moved = a.render_image_hip(1, stats=st)
+        assert _same(moved, want) and a._pose_seen[1] == 1
+        assert _same(a.render_image_hip(1), want)                       # and again, now with the new pose's hints
+        assert _same(a.preprocess(1).points_xy, b.preprocess(1).points_xy)
+        a.images[1].set_world2view(GaussianScene(str(a_dir), mk()).images[1].world2view)
+        assert _same(a.render_image_hip(1), first)
+
+
+# ---- the fit loop
+def test_one_trainer_step_with_refine_poses_is_the_calls_written_out(tmp_path):
+    from intro_to_gaussian_splatting_amd import CameraRefiner, DensityControl, GaussianAdam, Trainer
+    from test_hip_sh_active import DENSITY, LR, PERIODS, RESET_LOGIT, TRAINED, _fit_scene, _state
+
+    poses = dict(lr_rotation=2e-3, lr_translation=5e-3, betas=(0.9, 0.99), eps=1e-9)
+    seed = 5
+    scene, targets = _fit_scene(tmp_path, 1)
+    trainer = Trainer(scene, targets, lr=LR, lambda_dssim=0.2, tile_size=16, statistic="screen", density=DENSITY,
+                      opacity_reset_logit=RESET_LOGIT, seed=seed, refine_poses=poses, **PERIODS)
+    assert isinstance(trainer.refiner, CameraRefiner) and trainer.refiner.indices == [1, 2, 3]
+    before = {i: scene.images[i].world2view.detach().clone() for i in (1, 2, 3)}
+    losses, idx = trainer.step()
+
+    scene2, targets2 = _fit_scene(tmp_path, 1)
+    g = scene2.gaussians
+    for name in TRAINED:
+        getattr(g, name).requires_grad_(True)
+    opt = GaussianAdam(g, lr=LR)
+    dc = DensityControl(g, optimizer=opt, scene=scene2, statistic="screen", **DENSITY)
+    refiner = CameraRefiner(scene2, [1, 2, 3], **poses)
+    views = torch.Generator(device="cpu").manual_seed(seed)
+    idx2 = [(1, 2, 3)[i] for i in torch.randperm(3, generator=views).tolist()][0]
+    terms = {}
+    frame = scene2.render_image_hip(idx2, tile_size=16, geometry_gradients=True, screen_statistics=True, camera_gradients=True)
+    loss = scene2.photometric_loss(idx2, frame, targets2[idx2], tile_size=16, lambda_dssim=0.2, terms=terms)
+    loss.backward()
+    grad = scene2.images[idx2].world2view.grad.clone()
+    assert grad.abs().max() > 0
+    dc.accumulate()
+    opt.step()
+    opt.zero_grad()
+    assert refiner.step() == 1
+
+    assert idx == idx2 and _same(losses, torch.stack((loss.detach(), terms["l1"], terms["ssim"])))
+    got, want = _state(trainer.gaussians, trainer.opt), _state(g, opt)
+    for key in want:
+        assert _same(got[key], want[key]), key
+    for i in (1, 2, 3):
+        assert _same(scene.images[i].world2view.detach(), scene2.images[i].world2view.detach()), i
+        assert bytes(scene.images[i].gsx_camera()) == bytes(scene2.images[i].gsx_camera())
+        assert _same(scene.images[i].world2view.detach(), before[i]) == (i != idx)          # only the rendered view moved
+        assert scene.images[i].world2view.grad is None and scene.images[i].world2view.requires_grad
+    assert scene.images[idx].pose_version == 1
+    for k, v in refiner.state[idx].items():
+        assert torch.equal(v, trainer.refiner.state[idx][k]) if torch.is_tensor(v) else v == trainer.refiner.state[idx][k], k
+    # the next frame of the moved view is the frame of the new pose
+    with torch.no_grad():
+        assert _same(scene.render_image_hip(idx), scene2.render_image_hip(idx))

@@ -1,6 +1,7 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--sh [--active-degree A]]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera]
+                                                     [--workloads c3] [--sh [--active-degree A]]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
 gradients, median of HIP-event-bracketed frames), the whole backward call (median, host-synchronised as the call is) and
@@ -10,6 +11,10 @@ per-pair slots (16 per pair).  --geometry adds the same figures for gsx_render_b
 points, scales and quaternions too; 48 slot bytes per pair, the per-Gaussian chain counted with the sums).  --screen adds
 them for gsx_render_backward_screen (key "screen": the same work plus 12 bytes stored per Gaussian, dL/d(NDC mean) and the
 radius), its steps taking turns with the geometry entry's so that both see the same clocks ("screen_over_geometry").
+--camera takes gsx_render_backward_camera (24 more sums per Gaussian in the chain kernel, one small reduction launch, 32
+floats out) in turns with the geometry and the screen entry, three ways ("alternating_camera", "camera_over_screen");
+with --sh it takes the SH scene's whole camera-gradient backward (the camera entry, then gsx_sh_backward with the view
+direction's share) in turns with the same two calls through the screen entry.  --workloads picks among c2 and c3.
 
 --sh times the differentiable SH scene INSTEAD: the trained-like 1M scene with degree-3 coefficients (bench.py's
 c3_trainedlike).  Its backward is gsx_render_backward on this camera's evaluated colours (gsx_sh_to_rgb runs again) and
@@ -54,7 +59,19 @@ def _median_ms(fn, steps, warmup):
     return statistics.median(out)
 
 
-def run(name, n, steps, warmup, geometry=False, screen=False):
+def _in_turns(calls, steps, warmup):
+    """{name: (median ms, [min, max])} of the calls taken in turns, step by step: whatever the clocks do, they do to all."""
+    names = list(calls)
+    turns = {k: [] for k in names}
+    for i in range(len(names) * (warmup + steps)):
+        k = names[i % len(names)]
+        ms = _median_ms(calls[k], 1, 0)
+        if i >= len(names) * warmup:
+            turns[k].append(ms)
+    return {k: (round(statistics.median(v), 4), [round(min(v), 4), round(max(v), 4)]) for k, v in turns.items()}
+
+
+def run(name, n, steps, warmup, geometry=False, screen=False, camera=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -107,10 +124,18 @@ def run(name, n, steps, warmup, geometry=False, screen=False):
                                       geometry_min_max=[round(min(turns[0]), 4), round(max(turns[0]), 4)],
                                       screen_min_max=[round(min(turns[1]), 4), round(max(turns[1]), 4)])
             out["screen_over_geometry"] = round(scr_ms / geo_ms, 4)
+        if camera:
+            back = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
+                                                       geometry=True, **kw)
+            t = _in_turns(dict(geometry=back, screen=lambda: back(screen=True), camera=lambda: back(screen=True, camera=True)),
+                          steps, warmup)
+            out["alternating_camera"] = {k + "_ms": v[0] for k, v in t.items()}
+            out["alternating_camera"].update({k + "_min_max": v[1] for k, v in t.items()})
+            out["camera_over_screen"] = round(t["camera"][0] / t["screen"][0], 4)
     return out
 
 
-def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10, active=None):
+def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10, active=None, camera=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -189,6 +214,15 @@ def run_sh(steps, warmup, geometry=False, n=1_000_000, batch=10, active=None):
         if geometry:
             geo_ms = whole(True)
             out["geometry"] = dict(backward_ms=round(geo_ms, 4), sh_backward_share=round(bwd_pts / geo_ms, 4))
+        if camera:
+            def through(cam):
+                grads = scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"], geometry=True,
+                                               screen=True, camera=cam)
+                return scene._sh_backward(1, grads[0], with_points=True)
+            t = _in_turns(dict(screen=lambda: through(False), camera=lambda: through(True)), steps, warmup)
+            out["alternating_camera"] = {k + "_ms": v[0] for k, v in t.items()}
+            out["alternating_camera"].update({k + "_min_max": v[1] for k, v in t.items()})
+            out["camera_over_screen"] = round(t["camera"][0] / t["screen"][0], 4)
     return out
 
 
@@ -198,6 +232,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--geometry", action="store_true", help="also time gsx_render_backward_geometry")
     ap.add_argument("--screen", action="store_true", help="also time gsx_render_backward_screen, in turns with the geometry entry")
+    ap.add_argument("--camera", action="store_true", help="also time gsx_render_backward_camera, in turns with the geometry "
+                    "and the screen entry")
+    ap.add_argument("--workloads", default="c2,c3", help="comma-separated: which of c2, c3 to run (not with --sh)")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     ap.add_argument("--active-degree", type=int, default=None, help="with --sh: Gaussians.active_sh_degree (0..3), the "
                     "gsx_sh_*_active entries, and the degree-3 kernels timed in turns with them")
@@ -206,10 +243,11 @@ def main():
 
     if args.sh:
         print(json.dumps(dict(metric="sh_backward_ms", results=run_sh(args.steps, args.warmup, args.geometry,
-                                                                       active=args.active_degree))))
+                                                                       active=args.active_degree, camera=args.camera))))
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
-    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen) for name, n in WORKLOADS.items()}
+    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera)
+           for name, n in WORKLOADS.items() if name in args.workloads.split(",")}
     print(json.dumps(dict(metric="backward_ms", results=out)))
 
 

@@ -1,0 +1,137 @@
+"""Camera-gradient fixtures: the REFERENCE ITSELF under autograd, with its one graph cut mended.  Data only.
+
+Build container only, like tools/capture_geometry_grad_golden.py, whose recipe this follows: the same scenes from the
+same generator arguments, the same `_weight` rebound over the reference's compute_gaussian_weight (the same value as a
+tensor), nothing under oracle/ changed.  The reference's graph reaches the camera through two separate leaves, the
+image's world2view (the view-space point and W of the EWA projection, splat/gaussian_scene.py:61,84) and its
+full_proj_transform (the pixel mean, :87).  For every scene both are made leaves that require grad, L = sum(image * W)
+with the W of the geomgrad_ fixture, and
+
+    torch.autograd.grad(L, [world2view, full_proj_transform, points, scales, quaternions])
+
+of the reference's own render_image is recorded.  Before anything is written the tool ASSERTS that the rebinding and the
+two new leaves changed nothing else: the image must equal the committed fixture's image bit for bit (grad_<scene>.npz,
+or geomgrad_<scene>.npz where the scene has no grad_ fixture; W is read from that file), the three geometry gradients
+must equal the committed geomgrad_<scene>.npz bit for bit, and so must the three branch counts.
+
+    python tools/capture_camera_grad_golden.py            # all scenes
+    python tools/capture_camera_grad_golden.py tile2      # only those whose name contains "tile2"
+    python tools/capture_camera_grad_golden.py --check    # recount the branch table over the committed files
+
+Writes tests/golden/camgrad_<scene>.npz: grad_world2view (4,4), grad_full_proj (4,4), both float32 as autograd left them,
+and the three branch counts of the geomgrad_ fixture.  A full run refuses to finish if one of the three branches is hit
+by no scene of the set.
+"""
+from __future__ import annotations
+
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from capture_geometry_grad_golden import BRANCHES, OWN_STAGE1, STANDALONE, _weight, branch_counts  # noqa: E402
+from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
+
+SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "tile2_40x32_n80", "small_64x48_n300", "cull_96x80_n400", "wide_64x64_n400",
+          # the floored determinant (551 of its 600 footprints): none of the six above has one
+          "tiny_48x48_n600",
+          # three visible of 500: the small row class with culled rows around it
+          "rows3_48x48_n500"]
+# Not in the set: the other geomgrad_ scenes.  The graph through the geometry needs minutes and many GB each (needle, 110
+# Gaussians: over 21 GB); the eight above hit every branch.  Name one on the command line on a machine with the memory and
+# the time.
+EXTRA = ["small_80x64_n120_tile8", "tile12_dense_52x40_n900", "tile20_64x64_n300", "tile32_96x96_n400",
+         "needle_160x160_n110", "rows1_48x48_n500"]
+
+
+def capture(name: str, GaussianScene, Gaussians) -> None:
+    import torch
+
+    from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
+
+    own = name in OWN_STAGE1
+    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
+    tile = spec.pop("tile")
+    assert not spec.pop("defaults", False)
+    sc = _generate(spec)
+    gg = np.load(os.path.join(OUT_DIR, "geomgrad_" + name + ".npz"))
+    base = gg if (own or name in STANDALONE) else np.load(os.path.join(OUT_DIR, "grad_" + name + ".npz"))
+    with tempfile.TemporaryDirectory() as tmp:
+        write_colmap_text(os.path.join(tmp, "colmap"), sc)
+        g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
+        points = torch.from_numpy(sc["points"]).float().clone().requires_grad_(True)
+        scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
+        quats = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
+        g.points, g.scales, g.quaternions = points, scales, quats
+        g.colors = g.colors.detach().clone()
+        g.opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone()
+        scene = GaussianScene(os.path.join(tmp, "colmap"), g)
+        counts = branch_counts(scene, g)
+        im = scene.images[1]
+        V = im.world2view.detach().clone().requires_grad_(True)
+        F = im.full_proj_transform.detach().clone().requires_grad_(True)
+        im.world2view, im.full_proj_transform = V, F
+        t0 = time.time()
+        image = scene.render_image(1, tile_size=tile)
+        t_fwd = time.time() - t0
+        W = torch.from_numpy(np.asarray(base["W"]))
+        loss = (image * W).sum()
+        t0 = time.time()
+        gV, gF, gp, gs, gq = torch.autograd.grad(loss, [V, F, points, scales, quats])
+        t_bwd = time.time() - t0
+    image = image.detach().numpy()
+    assert np.array_equal(image.view(np.uint32), np.asarray(base["image"]).view(np.uint32)), \
+        name + ": the rebinding or the camera leaves changed the reference's image"
+    for key, got in (("grad_points", gp), ("grad_scales", gs), ("grad_quaternions", gq)):
+        assert np.array_equal(got.numpy(), gg[key]), "%s: %s differs from the committed geomgrad_ fixture" % (name, key)
+    for b in BRANCHES:
+        assert int(counts[b]) == int(gg[b]), (name, b)
+    gV, gF = gV.numpy(), gF.numpy()
+    assert gV.dtype == np.float32 and gV.shape == (4, 4) and gF.shape == (4, 4)
+    assert np.isfinite(gV).all() and np.isfinite(gF).all(), name
+    path = os.path.join(OUT_DIR, "camgrad_" + name + ".npz")
+    np.savez_compressed(path, grad_world2view=gV, grad_full_proj=gF, reference_forward_seconds=np.float64(t_fwd),
+                        reference_backward_seconds=np.float64(t_bwd), **counts)
+    print("camgrad_%s: N=%d floored=%d clamped=%d culled=%d max|gV|=%.3g max|gF|=%.3g gV col 3 %s gF col 2 %s "
+          "fwd=%.1fs bwd=%.1fs (%.1f KB)" % (
+              name, sc["points"].shape[0], counts["n_floored_det"], counts["n_clamped"], counts["n_culled"], np.abs(gV).max(),
+              np.abs(gF).max(), gV[:, 3].tolist(), gF[:, 2].tolist(), t_fwd, t_bwd, os.path.getsize(path) / 1024), flush=True)
+
+
+def check_branches() -> None:
+    """Every branch of the table must be hit by at least one committed file."""
+    total = dict.fromkeys(BRANCHES, 0)
+    for name in SCENES:
+        path = os.path.join(OUT_DIR, "camgrad_" + name + ".npz")
+        if os.path.exists(path):
+            z = np.load(path)
+            for b in BRANCHES:
+                total[b] += int(z[b])
+            print("%-28s floored=%4d clamped=%4d culled=%4d" % (name, *[int(z[b]) for b in BRANCHES]))
+    empty = [b for b in BRANCHES if total[b] == 0]
+    if empty:
+        raise SystemExit("refused: no scene of the set hits " + ", ".join(empty))
+
+
+def main() -> None:
+    only = sys.argv[1] if len(sys.argv) > 1 else ""
+    if only != "--check":
+        GaussianScene, Gaussians = _import_reference()
+        import splat.gaussian_scene as ref_scene
+
+        ref_scene.compute_gaussian_weight = _weight
+        for name in SCENES + [e for e in EXTRA if only and only in e]:
+            if only in name:
+                capture(name, GaussianScene, Gaussians)
+    if only in ("", "--check"):
+        check_branches()
+
+
+if __name__ == "__main__":
+    main()
