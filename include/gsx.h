@@ -475,6 +475,51 @@ GSX_API int gsx_render_backward_camera(const GsxCamera *camera, const float *mea
 GSX_API size_t gsx_backward_camera_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
 
 /*
+ * Expected depth and coverage of the GSX_SEM_REF_CPU frame: depth_out holds, per pixel, the two floats
+ *   D = sum_k T_k alpha_k z_k        A = sum_k T_k alpha_k
+ * over the pixel's tile list in list order, with the frame's two leading axes (GsxParams.layout) and 2 floats where the
+ * frame has 3.  alpha_k is the reference's alpha in the reference's operation order, T_1 = 1, the pixel stops before the
+ * first record with T_k (1 - alpha_k) < 1e-6 (a NaN stops it too) and EVERY listed record is walked: the gradient
+ * entries' walk, without gsx_render_forward's skip of records below 2^-26.  z_k is the view-space depth the depth order is
+ * built on -- the reference's points_view[:, 2], gsx_preprocess' `depths` -- in the row class the call runs with
+ * (GSX_FLAG_ONE_VISIBLE / GSX_FLAG_SMALL_BATCH).  D is not divided by A.  Every pixel is written: exact +0 where the frame
+ * has zeros (the last row and column of tiles, which REF_CPU does not render, and a frame that lists nothing).
+ * Projection, depth order and binning run again, as for gsx_render_backward: GsxParams.hints is neither read nor written.
+ * `colors` is read by that chain only (no depth depends on it).  The refusals and the synchronisation are
+ * gsx_render_backward's.  workspace: gsx_depth_workspace_bytes(n, width, height, tile, pairs) with at least the frame's
+ * pair count.
+ */
+GSX_API int gsx_render_depth(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                     const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *depth_out,
+                     const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_render_depth needs (0 on invalid arguments). */
+GSX_API size_t gsx_depth_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
+ * gsx_render_backward_screen for L(frame, depth image): the same arguments with the image gsx_render_depth wrote (`depth`)
+ * and dL/d(that image) (`grad_depth`, same layout) behind screen_radius; grad_means2d and screen_radius may BOTH be NULL.
+ * With gD = dL/dD and gA = dL/dA of a pixel, D_k and A_k its running sums including record k:
+ *   dL/dz_k      = sum over pixels T_k alpha_k gD, summed per Gaussian into Sz;  grad_means3d += Sz world2view[0:3][2]
+ *   dL/dalpha_k += T_k (z_k gD + gA) - ((D - D_k) gD + (A - A_k) gA) / (1 - alpha_k)
+ * added to the frame's dL/dalpha_k before anything is formed from it: grad_opacity_logit, grad_means3d, grad_scales,
+ * grad_quats, grad_means2d take depth's share through the same sums and the same chain (screen_radius is the forward's
+ * value as before; grad_colors gets nothing from depth).  The tile rectangle, culling and depth order are piecewise
+ * constant; the camera is a constant.  With grad_depth all +0 every output holds the bits gsx_render_backward_screen
+ * writes.  Same refusals (depth or grad_depth NULL besides), same synchronisation, no hints touched, no float atomics:
+ * same inputs, same bits.  workspace: gsx_backward_depth_workspace_bytes.
+ */
+GSX_API int gsx_render_backward_depth(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                              const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                              const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                              float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d /* may be NULL */,
+                              float *screen_radius /* may be NULL */, const float *depth, const float *grad_depth,
+                              const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_render_backward_depth needs (0 on invalid arguments). */
+GSX_API size_t gsx_backward_depth_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =
  * (R S)(R S)^T from linear scales (n,3) and quaternions (n,4) (w,x,y,z), the quaternion
  * normalised twice as the reference does.  The render entry points compute this inline; the

@@ -4,7 +4,7 @@ Gaussians, hand-written HIP kernels (libgsx.so, C ABI in include/gsx.h) do the w
 from .gaussians import Gaussians
 from .gaussian_scene import GaussianScene, NativeExtension, render_preprocessed
 from .image import GaussianImage
-from .loss import photometric_loss
+from .loss import depth_loss, photometric_loss
 from .optim import GaussianAdam, expon_lr
 from .density import DensityControl
 from .knn import nearest3
@@ -13,5 +13,5 @@ from .pose import CameraRefiner
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension", "photometric_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3",
+           "NativeExtension", "photometric_loss", "depth_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3",
            "Trainer", "events_at", "CameraRefiner"]

@@ -386,7 +386,40 @@ struct GeometryGrads {
     float *means3d, *scales, *quats;
     float *means2d = nullptr, *radius = nullptr;
     float *world2view = nullptr, *full_proj = nullptr;     // gsx_render_backward_camera: both, 16 floats each
+    const float *depth = nullptr, *grad_depth = nullptr;   // gsx_render_backward_depth: both, the (D, A) image and dL/d(D, A)
 };
+
+// What the gradient entries and gsx_render_depth cover: the reference's own frame, whole, RGB colours.
+int check_whole_ref_cpu(const Plan &p, const GsxCamera *camera, const GsxParams *params, const char *entry) {
+    if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "%s supports GSX_SEM_REF_CPU only", entry);
+    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
+    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s renders the whole frame: no tile window", entry);
+    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes the whole frame: no output window", entry);
+    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take substrips", entry);
+    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "%s synchronises: no GSX_FLAG_NO_SYNC", entry);
+    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "%s reads the camera argument: no camera_device", entry);
+    return GSX_OK;
+}
+
+// The forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort and the
+// count read-back (which synchronises).  On GSX_OK: order, rrect, sorted_vals and counts = (n_visible, D, M).
+int lists_again(const Plan &p, const Carve &c, char *ws, const GsxCamera &camera, const gsx::GaussiansIn &in, int64_t n,
+                int64_t cap, hipStream_t s, const uint32_t *&order, const uint32_t *&sorted_vals, int64_t (&counts)[3]) {
+    bool sampled;
+    int rc = project_and_sort(p, c, ws, camera, in, n, cap, nullptr, nullptr, s, order, sampled);
+    if (rc != GSX_OK) return rc;
+    uint32_t *counters = (uint32_t *)(ws + c.counters);
+    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
+    const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
+                              (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
+    const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
+    sorted_vals = nullptr;
+    rc = bin_pairs(p, c, ws, n, cap, rrect, order, counters + kCtrKept, sampled, bcnt, lt, nullptr, s, sorted_vals);
+    if (rc != GSX_OK) return rc;
+    return read_counts(c, ws, cap, true, nullptr, counts, s);
+}
 
 // gsx_render_backward (geo == nullptr) and gsx_render_backward_geometry: one body.  The geometry call carves the third
 // workspace mode, runs the tile kernel's geometry instance and, after the colour sums, the per-Gaussian chain.
@@ -399,23 +432,15 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     Plan p;
     int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
     if (rc != GSX_OK) return rc;
-    // what the backward pass covers: the reference's own frame, whole, RGB colours
-    if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward supports GSX_SEM_REF_CPU only");
-    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes RGB colours, not GsxParams.sh");
-    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward renders the whole frame: no tile window");
-    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward takes the whole frame: no output window");
-    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward does not take substrips");
-    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward synchronises: no GSX_FLAG_NO_SYNC");
-    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_backward reads the camera argument: no camera_device");
+    rc = check_whole_ref_cpu(p, camera, params, "gsx_render_backward");
+    if (rc != GSX_OK) return rc;
     rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
     if (rc != GSX_OK) return rc;
     if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
     Carve c;
     int64_t cap;
     rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap,
-                         geo ? (geo->world2view ? kCarveCamera : kCarveGeometry) : kCarveBackward);
+                         geo ? (geo->depth ? kCarveDepth : (geo->world2view ? kCarveCamera : kCarveGeometry)) : kCarveBackward);
     if (rc != GSX_OK) return rc;
     char *ws = (char *)workspace;
     StageTimer tm;
@@ -440,20 +465,10 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     }
     // ---- the forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
     const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const uint32_t *order;
-    bool sampled;
-    rc = project_and_sort(p, c, ws, *camera, in, n, cap, nullptr, nullptr, s, order, sampled);
-    if (rc != GSX_OK) return rc;
-    uint32_t *counters = (uint32_t *)(ws + c.counters);
+    const uint32_t *order, *sorted_vals;
     const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
-    const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
-                              (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
-    const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
-    const uint32_t *sorted_vals = nullptr;
-    rc = bin_pairs(p, c, ws, n, cap, rrect, order, counters + kCtrKept, sampled, bcnt, lt, nullptr, s, sorted_vals);
-    if (rc != GSX_OK) return rc;
     int64_t counts[3];
-    rc = read_counts(c, ws, cap, true, nullptr, counts, s);
+    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
     tm.mark();  // 1: the forward's stages
     if (rc != GSX_OK) return rc;
     const uint32_t m = (uint32_t)counts[2];
@@ -466,10 +481,19 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
     const gsx::BackwardTiles bt{raw, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots,
                                   geo_slots};
-    GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
+    if (geo && geo->depth) {
+        float *zrow = (float *)(ws + c.zrow);
+        GSX_HIP(gsx::launch_project_depth(*camera, means3d, n, p.small_batch, zrow, s));
+        GSX_HIP(gsx::launch_backward_tiles_depth(bt, gsx::DepthTiles{zrow, geo->depth, geo->grad_depth}, p.grid, p.out, s));
+    } else {
+        GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
+    }
     tm.mark();  // 2: raw records, prefix, compositing backward
     GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
-    if (geo) {
+    if (geo && geo->depth) {
+        GSX_HIP(gsx::launch_backward_geometry_depth(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
+                                                    geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s));
+    } else if (geo) {
         const gsx::CameraGrads cg{geo->world2view, geo->full_proj, (float *)(ws + c.cam_partials)};
         GSX_HIP(gsx::launch_backward_geometry(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
                                               geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s,
@@ -692,6 +716,69 @@ int gsx_render_backward_camera(const GsxCamera *camera, const float *means3d, co
         return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
     if (!grad_world2view || !grad_full_proj) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_world2view / grad_full_proj is NULL");
     const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius, grad_world2view, grad_full_proj};
+    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+}
+
+size_t gsx_depth_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveDepth);
+}
+
+size_t gsx_backward_depth_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveDepth);
+}
+
+int gsx_render_depth(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                     const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *depth_out,
+                     const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    if (!depth_out) return fail(GSX_ERR_INVALID_ARGUMENT, "depth_out is NULL");
+    Plan p;
+    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, depth_out, params, p);    // (the frame's descriptor: depth_index)
+    if (rc != GSX_OK) return rc;
+    rc = check_whole_ref_cpu(p, camera, params, "gsx_render_depth");
+    if (rc != GSX_OK) return rc;
+    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
+    if (rc != GSX_OK) return rc;
+    Carve c;
+    int64_t cap;
+    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, kCarveDepth);
+    if (rc != GSX_OK) return rc;
+    char *ws = (char *)workspace;
+    // every pixel: zeros where the frame has zeros (the unrendered last row and column of tiles, a frame that lists nothing)
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)depth_out, (size_t)camera->width * (size_t)camera->height * 2, s));
+    if (n == 0 || p.grid.count() == 0) {
+        GSX_HIP(hipStreamSynchronize(s));
+        return GSX_OK;
+    }
+    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
+    const uint32_t *order, *sorted_vals;
+    int64_t counts[3];
+    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
+    if (rc != GSX_OK) return rc;
+    if (counts[2] == 0 || counts[1] == 0) return GSX_OK;
+    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
+    float *zrow = (float *)(ws + c.zrow);
+    GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
+    GSX_HIP(gsx::launch_project_depth(*camera, means3d, n, p.small_batch, zrow, s));
+    GSX_HIP(gsx::launch_depth_tiles(raw, sorted_vals, (const uint2 *)(ws + c.ranges), zrow, p.grid, p.out, depth_out, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
+}
+
+int gsx_render_backward_depth(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                              const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                              const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                              float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                              float *screen_radius, const float *depth, const float *grad_depth, const GsxParams *params,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+    if (!grad_means3d || !grad_scales || !grad_quats)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
+    if (!depth || !grad_depth) return fail(GSX_ERR_INVALID_ARGUMENT, "depth / grad_depth is NULL");
+    GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
+    geo.depth = depth;
+    geo.grad_depth = grad_depth;
     return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
                            grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
 }

@@ -32,6 +32,12 @@
 // gsx_render_backward_camera is the screen call with the chain kernel's camera instance (backward_camera_chain_kernel): the
 // chain's g_t, dT and gh contracted with the point into 24 terms of dL/dworld2view and dL/dfull_proj per Gaussian, summed
 // per block with the butterflies above and LDS, and over the blocks by camera_reduce_kernel in a fixed order.
+// gsx_render_depth and gsx_render_backward_depth: expected depth D = sum T alpha z and coverage A = sum T alpha per pixel
+// (depth_tile_kernel, the backward's walk on the raw records plus one float per row, the view-space depth), and their
+// gradients fused into the one backward walk: the tile kernel's third instance (backward_tile_depth_kernel) adds depth's
+// term to dL/dalpha before u is formed and sums dL/dz per record beside the five moments; backward_depth_sum_kernel and
+// backward_depth_chain_kernel are the geometry kernels with that sixth sum, which reaches dL/dpoint through world2view's
+// third column.
 //
 // alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
@@ -140,9 +146,11 @@ __device__ __forceinline__ float wave_sum1(float v) {
     return v;
 }
 
-// backward_tile_kernel and backward_tile_geometry_kernel: one text, two instances (gsx_backward_tile.inc)
+// backward_tile_kernel, backward_tile_geometry_kernel and backward_tile_depth_kernel: one text, three instances
+// (gsx_backward_tile.inc)
 #define GSX_TILE_KERNEL backward_tile_kernel
 #define GSX_TILE_GEOMETRY false
+#define GSX_TILE_DEPTH 0
 #define GSX_TILE_ATTR
 #include "gsx_backward_tile.inc"
 #undef GSX_TILE_KERNEL
@@ -153,8 +161,95 @@ __device__ __forceinline__ float wave_sum1(float v) {
 #define GSX_TILE_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #include "gsx_backward_tile.inc"
 #undef GSX_TILE_KERNEL
-#undef GSX_TILE_GEOMETRY
+#undef GSX_TILE_DEPTH
 #undef GSX_TILE_ATTR
+// the depth instance: 24 more live floats than the geometry instance's 108 VGPRs, left to the compiler's own occupancy
+#define GSX_TILE_KERNEL backward_tile_depth_kernel
+#define GSX_TILE_DEPTH 1
+#define GSX_TILE_ATTR
+#include "gsx_backward_tile.inc"
+#undef GSX_TILE_KERNEL
+#undef GSX_TILE_GEOMETRY
+#undef GSX_TILE_DEPTH
+#undef GSX_TILE_ATTR
+
+// gsx_render_depth: (D, A) = (sum T alpha z, sum T alpha) of every pixel of every window tile, by the backward's walk --
+// one wave per tile, four pixels per lane, 64 records staged per batch, a tile of more than 256 pixels in chunks,
+// alpha_ref on every listed record (no 2^-26 skip), the pixel stopped before the record that fails kStopRefCpu.  D takes
+// one fmaf per record and A one add: backward_tile_depth_kernel accumulates both the same way, so its D_fin - D_k and
+// A_fin - A_k are exact zeros behind a pixel's last record.
+__global__ void __launch_bounds__(64)
+    depth_tile_kernel(const Record *__restrict__ raw, const uint32_t *__restrict__ vals, const uint2 *__restrict__ ranges,
+                      const float *__restrict__ zrow, TileGrid grid, OutDesc out, float *__restrict__ depth) {
+    __shared__ float4 sa[64], sb[64];
+    __shared__ float sz[64];
+    const uint32_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t nwy = (uint32_t)grid.nwy();
+    const int tx = grid.wx0 + (int)(t / nwy), ty = grid.wy0 + (int)(t % nwy);
+    const uint2 rg = ranges[t];
+    const uint32_t first = rg.x, last = rg.y & ~kLongFlag;
+    const int T = grid.tile;
+    const int64_t npx = (int64_t)T * T;
+    const float ox = (float)tx * (float)T, oy = (float)ty * (float)T;
+    for (int64_t chunk = 0; chunk < npx; chunk += 64 * kNpx) {
+        float fx[kNpx], fy[kNpx], Tr[kNpx], D[kNpx], A[kNpx];
+        int64_t at[kNpx];
+        bool live[kNpx], mine[kNpx];
+#pragma unroll
+        for (int j = 0; j < kNpx; ++j) {
+            const int64_t p = chunk + j * 64 + lane;
+            live[j] = mine[j] = p < npx;
+            const int x = live[j] ? (int)(p % T) : 0, y = live[j] ? (int)(p / T) : 0;
+            fx[j] = ox + (float)x;
+            fy[j] = oy + (float)y;
+            Tr[j] = 1.0f;
+            D[j] = A[j] = 0.0f;
+            at[j] = depth_index(out, tx * T + x, ty * T + y);
+        }
+        for (uint32_t b = first; b < last; b += 64) {
+            const uint32_t cnt = min(64u, last - b);
+            if ((uint32_t)lane < cnt) {
+                const uint32_t row = vals[b + lane];
+                const Record r = raw[row];
+                sa[lane] = r.a;
+                sb[lane] = r.b;
+                sz[lane] = zrow[row];
+            }
+            __syncthreads();
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < kNpx; ++j) any |= live[j];
+            if (__any(any)) {
+                for (uint32_t k = 0; k < cnt; ++k) {
+                    const float4 Ra = sa[k], Rb = sb[k];
+                    const float zk = sz[k];
+#pragma unroll
+                    for (int j = 0; j < kNpx; ++j) {
+                        if (!live[j]) continue;
+                        const float alpha = alpha_ref(Ra.x, Ra.y, Ra.z, Ra.w, Rb.x, Rb.y, Rb.z, fx[j], fy[j]);
+                        const float ta = Tr[j] * alpha;
+                        const float test = Tr[j] - ta;
+                        if (!(test >= kStopRefCpu)) {
+                            live[j] = false;
+                            continue;
+                        }
+                        D[j] = __builtin_fmaf(ta, zk, D[j]);
+                        A[j] += ta;
+                        Tr[j] = test;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < kNpx; ++j)
+            if (mine[j]) {
+                depth[at[j]] = D[j];
+                depth[at[j] + 1] = A[j];
+            }
+    }
+}
 
 // One wave per depth rank: its slots [prefix[r], prefix[r + 1]) summed lane-strided, then over the wave; lane 0 applies
 // the sigmoid chain and writes the Gaussian's row.
@@ -441,6 +536,62 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// ---- gsx_render_backward_depth: backward_geometry_sum_kernel with the sixth sum -- the five in the same operations and the
+// same order, Sz like S5 -- and backward_geometry_chain_kernel with Sz world2view[k][2] added to dL/dpoint_k, as a
+// separate addend and only where it is not zero: with dL/ddepth = 0 every row holds the screen entry's bits, a -0 included.
+__global__ void __launch_bounds__(256)
+    backward_depth_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m) {
+    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= m) return;
+    const uint32_t b = prefix[r], e = prefix[r + 1];
+    if (b == e) return;
+    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, a6 = 0.0f;
+    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
+        const float4 v = geo_slots[2 * (size_t)i], v5 = geo_slots[2 * (size_t)i + 1];
+        a1 += v.x; a2 += v.y; a3 += v.z; a4 += v.w; a5 += v5.x; a6 += v5.y;
+    }
+    const float v = wave_sum4(a1, a2, a3, a4, lane);
+    const float S5 = wave_sum1(a5), Sz = wave_sum1(a6);
+    const float S2 = __shfl(v, 16), S3 = __shfl(v, 32), S4 = __shfl(v, 48);
+    if (lane == 0) {
+        geo_slots[2 * (size_t)b] = make_float4(v, S2, S3, S4);
+        geo_slots[2 * (size_t)b + 1] = make_float4(S5, Sz, 0.0f, 0.0f);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+    backward_depth_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m, GeoCamera cam,
+                                const float *__restrict__ means3d, const float *__restrict__ scales,
+                                const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                                float *__restrict__ grad_scales, float *__restrict__ grad_quats,
+                                float *__restrict__ grad_means2d, float *__restrict__ screen_radius) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t b = prefix[r];
+    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
+    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
+    const int64_t row = order[r];
+    const Record rec = raw[row];
+    float gp[3], gs[3], gq[4], gn[2];
+    geometry_chain<false>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq,
+                          gn, nullptr);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float gz = S5.y * cam.V[k * 4 + 2];       // dL/dz dz/dp_k
+        grad_means3d[3 * row + k] = gz != 0.0f ? gp[k] + gz : gp[k];
+        grad_scales[3 * row + k] = gs[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
+    if (grad_means2d) {
+        grad_means2d[2 * row] = gn[0];
+        grad_means2d[2 * row + 1] = gn[1];
+        if (screen_radius) screen_radius[row] = rec.c.w;
+    }
+}
+
 // ---- gsx_render_backward_camera: dL/dworld2view and dL/dfull_proj, the 24 entries that are not exact zeros.
 // kCamTerms values per Gaussian: [k * 3 + c] = dL/dV[k][c] (k < 4, c < 3; column 3 of V reaches nothing) and
 // [12 + k * 3 + j] = dL/dF[k][c], c = (0, 1, 3)[j] (column 2 of F, the depth, reaches nothing).  The sum over Gaussians
@@ -552,6 +703,20 @@ hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, 
     return hipGetLastError();
 }
 
+hipError_t launch_backward_tiles_depth(const BackwardTiles &bt, const DepthTiles &dt, const TileGrid &grid, const OutDesc &out,
+                                       hipStream_t s) {
+    if (grid.count() <= 0) return hipSuccess;
+    backward_tile_depth_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out, dt);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_tiles(const Record *raw, const uint32_t *vals, const uint2 *ranges, const float *zrow,
+                              const TileGrid &grid, const OutDesc &out, float *depth, hipStream_t s) {
+    if (grid.count() <= 0) return hipSuccess;
+    depth_tile_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(raw, vals, ranges, zrow, grid, out, depth);
+    return hipGetLastError();
+}
+
 hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *raw,
                                 uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s) {
     if (m == 0) return hipSuccess;
@@ -560,12 +725,7 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
     return hipGetLastError();
 }
 
-hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                    const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
-                                    const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
-                                    const CameraGrads *cg) {
-    if (m == 0) return hipSuccess;
+static GeoCamera geo_camera(const GsxCamera &camera) {
     GeoCamera cam;
     for (int i = 0; i < 16; ++i) {
         cam.V[i] = camera.world2view[i];
@@ -577,6 +737,16 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
     cam.limy = 1.3f * camera.tan_fovy;
     cam.sx = ((float)camera.width - 1.0f) * 0.5f;
     cam.sy = ((float)camera.height - 1.0f) * 0.5f;
+    return cam;
+}
+
+hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                    const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
+                                    const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
+                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
+                                    const CameraGrads *cg) {
+    if (m == 0) return hipSuccess;
+    const GeoCamera cam = geo_camera(camera);
     backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
     const unsigned blocks = (unsigned)(((uint64_t)m + 255) / 256);
     if (cg) {
@@ -588,6 +758,19 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
     }
     backward_geometry_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,
                                                           grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_geometry_depth(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                          const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
+                                          const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
+                                          float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    const GeoCamera cam = geo_camera(camera);
+    backward_depth_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
+    backward_depth_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
+        geo_slots, prefix, order, raw, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
+        screen_radius);
     return hipGetLastError();
 }
 

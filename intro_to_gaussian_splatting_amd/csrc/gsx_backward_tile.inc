@@ -1,8 +1,10 @@
-// The compositing backward's tile kernel, included twice by gsx_backward.hip (inside its anonymous namespace):
+// The compositing backward's tile kernel, included three times by gsx_backward.hip (inside its anonymous namespace):
 //   GSX_TILE_KERNEL = backward_tile_kernel,          GSX_TILE_GEOMETRY = false: gsx_render_backward's, the colour-only instance
 //   GSX_TILE_KERNEL = backward_tile_geometry_kernel, GSX_TILE_GEOMETRY = true:  gsx_render_backward_geometry's
-// Two plain kernels from one text rather than a template or a shared device function: the colour-only kernel keeps its
-// name and compiles to the instructions it had before the geometry instance existed.
+//   GSX_TILE_KERNEL = backward_tile_depth_kernel,    GSX_TILE_GEOMETRY = true, GSX_TILE_DEPTH = 1: gsx_render_backward_depth's
+// Plain kernels from one text rather than a template or a shared device function: the colour-only kernel keeps its
+// name and compiles to the instructions it had before the geometry instance existed, and both keep theirs beside the
+// depth instance, whose text sits in #if GSX_TILE_DEPTH blocks.
 //
 // One wave per window tile.  Its pixels are taken 256 at a time (a 16x16 tile: once), four per lane; the list is staged
 // 64 records per batch.  For a tile of more than 256 pixels the later chunks add their sums to the slots the first one
@@ -12,12 +14,29 @@
 // pixels, into the pair's two float4 of bt.geo_slots: (S1, S2, S3, S4), (S5, 0, 0, 0).  Same walk, same stop rule; the
 // four colour sums take the same operations in the same order as in the colour-only instance, whose code GEO = false
 // leaves as it was.
+// DEPTH (gsx_render_backward_depth): the geometry instance with two more channels per pixel, expected depth D = sum T alpha z
+// and coverage A = sum T alpha, accumulated as depth_tile_kernel accumulates them (one fmaf, one add).  With gD = dL/dD and
+// gA = dL/dA of the pixel, dL/dalpha gains T (z gD + gA) - ((D_fin - D_k) gD + (A_fin - A_k) gA) / (1 - alpha), added to the
+// frame's two terms as separate addends BEFORE u is formed -- so the opacity sum and the five moments carry depth's share
+// with no further code, and with gD = gA = +0 every sum is the geometry instance's, bit for bit (x + (+0) = x, and every
+// accumulator starts at +0, so no -0 survives in either instance) -- and a sixth sum per record, Sz = sum T alpha gD =
+// dL/dz, into the second float4 of the pair's geometry slot: (S5, Sz, 0, 0).
+#if GSX_TILE_DEPTH
+__global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTiles bt, TileGrid grid, OutDesc out, DepthTiles dt) {
+#else
 __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTiles bt, TileGrid grid, OutDesc out) {
+#endif
     constexpr bool GEO = GSX_TILE_GEOMETRY;
     __shared__ float4 sa[64], sb[64], sc[64];
     __shared__ uint32_t sslot[64];
     __shared__ float ssum[64 * 4];
-    __shared__ float sgeo[GEO ? 64 * 5 : 1];
+#if GSX_TILE_DEPTH
+    constexpr int kGeoSums = 6;
+    __shared__ float sz[64];
+#else
+    constexpr int kGeoSums = 5;
+#endif
+    __shared__ float sgeo[GEO ? 64 * kGeoSums : 1];
     const uint32_t t = blockIdx.x;
     const int lane = threadIdx.x;
     const uint32_t nwy = (uint32_t)grid.nwy();
@@ -31,6 +50,9 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
         float fx[kNpx], fy[kNpx], Tr[kNpx], C0[kNpx], C1[kNpx], C2[kNpx], F0[kNpx], F1[kNpx], F2[kNpx], G0[kNpx], G1[kNpx],
             G2[kNpx];
         bool live[kNpx];
+#if GSX_TILE_DEPTH
+        float Dr[kNpx], Ar[kNpx], DF[kNpx], AF[kNpx], gD[kNpx], gA[kNpx];
+#endif
 #pragma unroll
         for (int j = 0; j < kNpx; ++j) {
             const int64_t p = chunk + j * 64 + lane;
@@ -46,6 +68,14 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                 F0[j] = bt.image[at]; F1[j] = bt.image[at + 1]; F2[j] = bt.image[at + 2];
                 G0[j] = bt.grad_image[at]; G1[j] = bt.grad_image[at + 1]; G2[j] = bt.grad_image[at + 2];
             }
+#if GSX_TILE_DEPTH
+            Dr[j] = Ar[j] = DF[j] = AF[j] = gD[j] = gA[j] = 0.0f;
+            if (live[j]) {
+                const int64_t at2 = depth_index(out, tx * T + x, ty * T + y);
+                DF[j] = dt.depth[at2]; AF[j] = dt.depth[at2 + 1];
+                gD[j] = dt.grad_depth[at2]; gA[j] = dt.grad_depth[at2 + 1];
+            }
+#endif
         }
         for (uint32_t b = first; b < last; b += 64) {
             const uint32_t cnt = min(64u, last - b);
@@ -58,6 +88,9 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                 sa[lane] = r.a;
                 sb[lane] = r.b;
                 sc[lane] = r.c;
+#if GSX_TILE_DEPTH
+                sz[lane] = dt.zrow[row];
+#endif
                 sslot[lane] = bt.prefix[rank] + (uint32_t)(tx - R.x0) * h + (uint32_t)(ty - R.y0);
             }
             __syncthreads();
@@ -67,8 +100,14 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                 for (int j = 0; j < kNpx; ++j) any |= live[j];
                 float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, du = 0.0f;
                 float m1 = 0.0f, m2 = 0.0f, m3 = 0.0f, m4 = 0.0f, m5 = 0.0f;
+#if GSX_TILE_DEPTH
+                float mz = 0.0f;
+#endif
                 if (__any(any)) {
                     const float4 A = sa[k], B = sb[k], Cc = sc[k];
+#if GSX_TILE_DEPTH
+                    const float zk = sz[k];
+#endif
 #pragma unroll
                     for (int j = 0; j < kNpx; ++j) {
                         if (!live[j]) continue;
@@ -84,7 +123,16 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                         C2[j] = __builtin_fmaf(ta, Cc.z, C2[j]);
                         const float cg = (Cc.x * G0[j] + Cc.y * G1[j]) + Cc.z * G2[j];
                         const float rest = ((F0[j] - C0[j]) * G0[j] + (F1[j] - C1[j]) * G1[j]) + (F2[j] - C2[j]) * G2[j];
+#if GSX_TILE_DEPTH
+                        Dr[j] = __builtin_fmaf(ta, zk, Dr[j]);
+                        Ar[j] += ta;
+                        const float zg = zk * gD[j] + gA[j];
+                        const float restd = (DF[j] - Dr[j]) * gD[j] + (AF[j] - Ar[j]) * gA[j];
+                        const float da = Tr[j] * (cg + zg) - (rest + restd) / (1.0f - alpha);
+                        mz = __builtin_fmaf(ta, gD[j], mz);
+#else
                         const float da = Tr[j] * cg - rest / (1.0f - alpha);
+#endif
                         d0 = __builtin_fmaf(ta, G0[j], d0);
                         d1 = __builtin_fmaf(ta, G1[j], d1);
                         d2 = __builtin_fmaf(ta, G2[j], d2);
@@ -107,8 +155,12 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                 if ((lane & 15) == 0) ssum[k * 4 + (lane >> 4)] = v;
                 if constexpr (GEO) {
                     const float w = wave_sum4(m1, m2, m3, m4, lane), w5 = wave_sum1(m5);
-                    if ((lane & 15) == 0) sgeo[k * 5 + (lane >> 4)] = w;
-                    if (lane == 0) sgeo[k * 5 + 4] = w5;
+                    if ((lane & 15) == 0) sgeo[k * kGeoSums + (lane >> 4)] = w;
+                    if (lane == 0) sgeo[k * kGeoSums + 4] = w5;
+#if GSX_TILE_DEPTH
+                    const float wz = wave_sum1(mz);
+                    if (lane == 0) sgeo[k * kGeoSums + 5] = wz;
+#endif
                 }
             }
             __syncthreads();
@@ -121,13 +173,21 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                 }
                 *dst = v;
                 if constexpr (GEO) {
-                    float4 g0 = make_float4(sgeo[lane * 5], sgeo[lane * 5 + 1], sgeo[lane * 5 + 2], sgeo[lane * 5 + 3]);
-                    float4 g1 = make_float4(sgeo[lane * 5 + 4], 0.0f, 0.0f, 0.0f);
+                    const float *sg = sgeo + lane * kGeoSums;
+                    float4 g0 = make_float4(sg[0], sg[1], sg[2], sg[3]);
+#if GSX_TILE_DEPTH
+                    float4 g1 = make_float4(sg[4], sg[5], 0.0f, 0.0f);
+#else
+                    float4 g1 = make_float4(sg[4], 0.0f, 0.0f, 0.0f);
+#endif
                     float4 *gdst = bt.geo_slots + 2 * (size_t)sslot[lane];
                     if (chunk > 0) {
                         const float4 o0 = gdst[0], o1 = gdst[1];
                         g0 = make_float4(o0.x + g0.x, o0.y + g0.y, o0.z + g0.z, o0.w + g0.w);
                         g1.x += o1.x;
+#if GSX_TILE_DEPTH
+                        g1.y += o1.y;
+#endif
                     }
                     gdst[0] = g0;
                     gdst[1] = g1;

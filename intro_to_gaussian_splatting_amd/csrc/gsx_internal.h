@@ -194,6 +194,9 @@ hipError_t launch_pack_preprocessed(const PreprocessedIn &in, int64_t n, const T
                                     Record *rec, TileRect *rect, float4 *bbox, hipStream_t s);
 // The backward pass: per row, (x, y, Q00, Q01), (Q10, Q11, op, sigmoid(logit)), (r, g, b, radius) -- project_raw_kernel.
 hipError_t launch_project_raw(const GsxCamera &cam, const GaussiansIn &in, int64_t n, int visible_rows, Record *raw, hipStream_t s);
+// The view-space depth of every row, row4_view(p, world2view, 2, vis): the value project_raw_kernel builds its record on
+// and the depth order its key (the reference's points_view[:, 2], PreprocessedScene.depths), same operations, same bits.
+hipError_t launch_project_depth(const GsxCamera &cam, const float *means3d, int64_t n, int visible_rows, float *zrow, hipStream_t s);
 hipError_t launch_covariance3d(const float *scales, const float *quats, int64_t n, float *out, hipStream_t s);
 hipError_t launch_covariance2d(const GsxCamera &cam, const float *points, const float *cov3d, int64_t n, float *out,
                                hipStream_t s);
@@ -471,6 +474,25 @@ struct BackwardTiles {
     float4 *geo_slots = nullptr;
 };
 hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
+// gsx_render_depth / gsx_render_backward_depth: the depth image holds (D, A) per pixel, D = sum T alpha z the expected
+// depth and A = sum T alpha the coverage, with the frame's two leading axes and 2 floats where the frame has 3 -- the
+// float index of frame pixel (px, py) in it, from the frame's descriptor (whose strides are multiples of 3):
+__host__ __device__ inline int64_t depth_index(const OutDesc &o, int px, int py) {
+    return ((int64_t)(px - o.x0) * (o.stride_x / 3) + (int64_t)(py - o.y0) * (o.stride_y / 3)) * 2;
+}
+struct DepthTiles {
+    const float *zrow;            // launch_project_depth, by row: the view-space depth the depth order is built on
+    const float *depth;           // gsx_render_depth's image (backward only)
+    const float *grad_depth;      // dL/d(depth image), same layout (backward only)
+};
+// The tile kernel's depth instance: bt as for launch_backward_tiles with geo_slots set; the pair's second geometry float4
+// becomes (S5, Sz, 0, 0), Sz = sum T alpha dL/dD = dL/dz of the record over the tile.
+hipError_t launch_backward_tiles_depth(const BackwardTiles &bt, const DepthTiles &dt, const TileGrid &grid, const OutDesc &out,
+                                       hipStream_t s);
+// gsx_render_depth: one wave per window tile walks its list as the backward does (alpha_ref, kStopRefCpu, every listed
+// record) and writes (D, A) of every pixel of its tile.  raw, vals, ranges as in BackwardTiles.
+hipError_t launch_depth_tiles(const Record *raw, const uint32_t *vals, const uint2 *ranges, const float *zrow,
+                              const TileGrid &grid, const OutDesc &out, float *depth, hipStream_t s);
 // slots of each rank summed in emission order, the sigmoid chain applied, scattered to rows (order[r])
 hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *raw,
                                 uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
@@ -490,5 +512,11 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
                                     float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
                                     const CameraGrads *cg = nullptr);
+// gsx_render_backward_depth: the same with the sixth sum Sz beside S5 (backward_depth_sum_kernel, in the same order), and
+// the chain adds Sz world2view[0:3][2] to dL/dpoint: z = p . world2view[:3][2] + world2view[3][2] (no camera terms).
+hipError_t launch_backward_geometry_depth(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                          const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
+                                          const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
+                                          float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s);
 
 }  // namespace gsx

@@ -198,13 +198,14 @@ struct Carve {
     size_t raw, rank_of, prefix, bsum, slots;   // gsx_render_backward only (carve(.., backward)); 0 otherwise
     size_t geo_slots;                           // gsx_render_backward_geometry only (kCarveGeometry and up); 0 otherwise
     size_t cam_partials;                        // gsx_render_backward_camera only (kCarveCamera); 0 otherwise
+    size_t zrow;                                // gsx_render_depth / gsx_render_backward_depth only (kCarveDepth); 0 otherwise
 };
 
 // Which entry point a workspace is carved for: the forward's regions alone, with gsx_render_backward's behind them, or
 // with gsx_render_backward_geometry's second slot array behind those.  (An int, so that the callers of the two-mode
-// carve that pass `true` keep meaning kCarveBackward.)
-enum { kCarveForward = 0, kCarveBackward = 1, kCarveGeometry = 2, kCarveCamera = 3 };
-constexpr size_t kGeoSlotBytes = 32;   // two float4 per pair: (S1, S2, S3, S4), (S5, 0, 0, 0) -- gsx_backward.hip
+// carve that pass `true` keep meaning kCarveBackward.)  kCarveDepth: gsx_render_depth's and gsx_render_backward_depth's.
+enum { kCarveForward = 0, kCarveBackward = 1, kCarveGeometry = 2, kCarveCamera = 3, kCarveDepth = 4 };
+constexpr size_t kGeoSlotBytes = 32;   // two float4 per pair: (S1, S2, S3, S4), (S5, Sz | 0, 0, 0) -- gsx_backward.hip
 constexpr size_t kCameraPartialBytes = 24 * sizeof(float);   // per 256 depth ranks: one block's camera terms -- gsx_backward.hip
 
 // The 64-byte `counters` block: what the kernels of one frame hand to each other on the device.
@@ -216,7 +217,8 @@ enum { kCtrCulled = 0, kCtrKept = 1, kCtrPairs = 2, kCtrLong = 3 };
 // backward: gsx_render_backward's workspace -- the forward's regions for `cap` pairs, then per Gaussian its raw stage-1
 // record (launch_project_raw), its rank and the emission prefix, the scan's block sums, and one float4 slot per pair.
 // kCarveGeometry: the same layout byte for byte, then kGeoSlotBytes more per pair.  kCarveCamera: the geometry layout
-// byte for byte, then kCameraPartialBytes per 256 Gaussians.
+// byte for byte, then kCameraPartialBytes per 256 Gaussians.  kCarveDepth: the geometry layout byte for byte, then one
+// float per Gaussian, its view-space depth (launch_project_depth).
 inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes, int backward = kCarveForward) {
     Carve c = {};
     size_t off = 0;
@@ -252,6 +254,7 @@ inline Carve carve(int64_t n, int64_t cap, int64_t max_tiles, size_t temp_bytes,
     }
     if (backward >= kCarveGeometry) c.geo_slots = take(cc * kGeoSlotBytes);
     if (backward == kCarveCamera) c.cam_partials = take((nn / 256 + 1) * kCameraPartialBytes);
+    if (backward == kCarveDepth) c.zrow = take(nn * sizeof(float));
     c.total = off;
     return c;
 }

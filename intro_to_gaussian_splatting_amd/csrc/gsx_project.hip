@@ -1015,6 +1015,15 @@ __global__ void __launch_bounds__(kBlock)
     r.c = make_float4(c[0], c[1], c[2], o.radius);
     raw[g] = r;
 }
+
+// gsx_render_depth / gsx_render_backward_depth: tz alone, as project_raw_kernel forms it.
+__global__ void __launch_bounds__(kBlock)
+    project_depth_kernel(GsxCamera cam, const float *__restrict__ means3d, int64_t n, int vis, float *__restrict__ zrow) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= n) return;
+    const float *p = means3d + 3 * g;
+    zrow[g] = row4_view(p[0], p[1], p[2], cam.world2view, 2, vis);
+}
 }  // namespace
 
 // sh_degree < 0: in.colors is (n,3) RGB; 0..3: in.colors is (n, (degree+1)^2, 3) spherical harmonics.
@@ -1050,6 +1059,12 @@ hipError_t launch_pack_preprocessed(const PreprocessedIn &in, int64_t n, const T
 hipError_t launch_project_raw(const GsxCamera &cam, const GaussiansIn &in, int64_t n, int visible_rows, Record *raw, hipStream_t s) {
     if (n == 0) return hipSuccess;
     project_raw_kernel<<<blocks_for(n), kBlock, 0, s>>>(cam, in, n, visible_rows ? visible_rows : rows_class(n), raw);
+    return hipGetLastError();
+}
+
+hipError_t launch_project_depth(const GsxCamera &cam, const float *means3d, int64_t n, int visible_rows, float *zrow, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    project_depth_kernel<<<blocks_for(n), kBlock, 0, s>>>(cam, means3d, n, visible_rows ? visible_rows : rows_class(n), zrow);
     return hipGetLastError();
 }
 

@@ -18,6 +18,11 @@ it.  One step, numbered from 1:
 7. the events ``events_at`` names for this step, in this order: ``density.densify_and_prune(generator)``,
    ``density.reset_opacity(opacity_reset_logit)``, ``gaussians.oneup_sh_degree()``.
 
+With ``depth_targets`` (image index -> (W,H) depth map) step 2 is ``frame, depth = scene.render_image_depth_hip(idx,
+tile_size, screen_statistics=statistic == "screen")`` and step 3 adds ``lambda_depth * depth_loss(depth,
+depth_targets[idx], scene.rendered_region(idx, tile_size))`` for the views that have a target; nothing else in the order
+changes.  Without it every call is the one above.
+
 The coefficients keep ONE learning rate: a second rate for the higher bands, as published, needs an Adam group over a strided
 part of ``sh`` and is not built.
 """
@@ -29,6 +34,7 @@ from typing import Callable, Dict, Iterable, Optional, Tuple
 import torch
 
 from .density import DensityControl
+from .loss import depth_loss
 from .optim import GROUP_NAMES, GaussianAdam
 from .pose import CameraRefiner
 
@@ -68,6 +74,32 @@ def events_at(step: int, sh_degree_every: Optional[int] = 1000, densify_from: in
     return tuple(due)
 
 
+def _check_depth_targets(scene, targets, depth_targets, lambda_depth, refine_poses):
+    """(dict or None, float): ``Trainer``'s ``depth_targets`` and ``lambda_depth``, refused by name."""
+    lam = float(lambda_depth)
+    if not (lam >= 0.0 and math.isfinite(lam)):
+        raise ValueError("lambda_depth = %r is not a finite non-negative number" % (lambda_depth,))
+    if depth_targets is None:
+        if lam != 0.0:
+            raise ValueError("lambda_depth = %r without depth_targets: there is no depth to weigh" % (lambda_depth,))
+        return None, 0.0
+    if refine_poses is not None:
+        raise ValueError("depth_targets cannot be combined with refine_poses: render_image_depth_hip has no pose gradient")
+    out = dict(depth_targets)
+    for idx, t in out.items():
+        if idx not in targets:
+            raise ValueError("depth_targets names image %r, which targets does not have" % (idx,))
+        cam = scene.images[idx].gsx_camera()
+        want = (int(cam.width), int(cam.height))
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != want:
+            raise ValueError("depth_targets[%r] must be a float32 tensor of shape %s (W, H), got %s" % (
+                idx, want, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.device != scene.gaussians.points.device:
+            raise ValueError("depth_targets[%r] is on %s, the scene's Gaussians on %s" % (idx, t.device,
+                                                                                         scene.gaussians.points.device))
+    return out, lam
+
+
 class Trainer:
     """Fits ``scene.gaussians`` to ``targets`` (image index -> (W,H,3) float32 tensor on the scene's GPU, the layout of
     ``render_image_hip``) with the composition of this module's docstring.
@@ -78,14 +110,19 @@ class Trainer:
     The schedule arguments are ``events_at``'s.  ``opt`` and ``density`` are public: their knobs may be changed between steps.
     ``refine_poses``: None (every call and every bit as without it), or a dict of ``CameraRefiner`` keywords
     (``lr_rotation`` and ``lr_translation`` are required there; ``indices`` defaults to the views of ``targets``): the
-    cameras are refined beside the Gaussians, ``refiner`` is public."""
+    cameras are refined beside the Gaussians, ``refiner`` is public.
+    ``depth_targets``: None (every call and every bit as without it), or a dict image index -> (W,H) float32 depth map on
+    the scene's GPU, view-space depth, 0 where unknown: the step renders ``render_image_depth_hip`` and adds
+    ``lambda_depth * depth_loss`` over the rendered region for the views the dict names.  Not with ``refine_poses``: the
+    pose has no gradient through depth."""
 
     def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
                  tile_size: int = 16, statistic: str = "screen", density: Optional[dict] = None,
                  sh_degree_every: Optional[int] = 1000, densify_from: int = 500, densify_every: Optional[int] = 100,
                  densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000,
                  opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0,
-                 refine_poses: Optional[dict] = None) -> None:
+                 refine_poses: Optional[dict] = None, depth_targets: Optional[Dict[int, torch.Tensor]] = None,
+                 lambda_depth: float = 0.0) -> None:
         g = scene.gaussians
         if not targets:
             raise ValueError("targets is empty: nothing to fit")
@@ -100,6 +137,7 @@ class Trainer:
         lr.pop("colors" if has_sh else "sh", None)              # the frame reads one of the two
         if not 0.0 <= float(lambda_dssim) <= 1.0:
             raise ValueError("lambda_dssim = %r is outside [0, 1]" % (lambda_dssim,))
+        self.depth_targets, self.lambda_depth = _check_depth_targets(scene, targets, depth_targets, lambda_depth, refine_poses)
         self._schedule = dict(sh_degree_every=sh_degree_every, densify_from=int(densify_from), densify_every=densify_every,
                               densify_until=int(densify_until), opacity_reset_every=opacity_reset_every)
         events_at(1, **self._schedule)                          # refuses a bad period here, not at step 1000
@@ -133,7 +171,11 @@ class Trainer:
         """One step.  Returns ((3,) device tensor: loss, l1, ssim; the view): nothing is read back to the host here."""
         scene, g = self.scene, self.gaussians
         idx = self._next_view()
-        if self.refiner is None:
+        depth = None
+        if self.depth_targets is not None:
+            frame, depth = scene.render_image_depth_hip(idx, tile_size=self.tile_size,
+                                                        screen_statistics=self.statistic == "screen")
+        elif self.refiner is None:
             frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
                                            screen_statistics=self.statistic == "screen")
         else:
@@ -142,6 +184,9 @@ class Trainer:
         terms: dict = {}
         loss = scene.photometric_loss(idx, frame, self.targets[idx], tile_size=self.tile_size,
                                       lambda_dssim=self.lambda_dssim, terms=terms)
+        if depth is not None and idx in self.depth_targets:
+            loss = loss + self.lambda_depth * depth_loss(depth, self.depth_targets[idx],
+                                                         scene.rendered_region(idx, self.tile_size))
         loss.backward()
         self.density.accumulate()
         self.opt.step()

@@ -356,6 +356,55 @@ class _RenderImageFunction(torch.autograd.Function):
                 gw2v)
 
 
+class _RenderImageDepthFunction(torch.autograd.Function):
+    """(frame, depth image) of the ref_cpu frame as a function of (points, scales, quaternions, opacity, colors, sh): the
+    frame of ``_RenderImageFunction`` and gsx_render_depth's (D, A).  Backward: gsx_render_backward_depth, once, for
+    dL/dframe and dL/ddepth together (either may be missing: zeros); the SH share as in ``_RenderImageFunction``."""
+
+    @staticmethod
+    def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh):
+        ctx.screen = bool(kw.get("screen_statistics", False))
+        user_stats, st = kw.get("stats", None), {}
+        frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st)
+        if user_stats is not None:
+            user_stats.update(st)
+        ctx.scene, ctx.image_idx, ctx.tile_size, ctx.layout = scene, image_idx, tile_size, layout
+        ctx.n_instances, ctx.n_visible = int(st["n_instances"]), int(st["n_visible"])
+        depth = scene._render_depth(image_idx, tile_size, layout, ctx.n_instances, ctx.n_visible)
+        ctx.has_sh = sh is not None
+        ctx.save_for_backward(points, scales, quaternions, opacity, colors, frame, depth, *((sh,) if ctx.has_sh else ()))
+        return frame, depth
+
+    @staticmethod
+    def backward(ctx, grad_frame, grad_depth):
+        points, scales, quaternions, opacity, colors, frame, depth = ctx.saved_tensors[:7]
+        scene = ctx.scene
+        want = ctx.needs_input_grad
+        if grad_frame is None:
+            grad_frame = torch.zeros_like(frame)
+        if grad_depth is None:
+            grad_depth = torch.zeros_like(depth)
+        grads = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame, ctx.n_instances,
+                                       ctx.n_visible, geometry=True, screen=ctx.screen, depth=depth, grad_depth=grad_depth)
+        gc, go, gp, gs, gq = grads[:5]
+        if ctx.screen:
+            scene.screen_statistics = (ctx.image_idx, grads[5], grads[6].view(-1))
+        gsh = None
+        if ctx.has_sh:
+            sh = ctx.saved_tensors[7]
+            gsh, gview = scene._sh_backward(ctx.image_idx, gc, with_points=want[5])
+            gsh, gc = gsh.view(sh.shape), None
+            if gview is not None:
+                gp = gp + gview
+        return (None, None, None, None, None,
+                gp.view(points.shape) if want[5] else None,
+                gs.view(scales.shape) if want[6] else None,
+                gq.view(quaternions.shape) if want[7] else None,
+                go.view(opacity.shape) if want[8] else None,
+                gc.view(colors.shape) if gc is not None and want[9] else None,
+                gsh if want[10] else None)
+
+
 class GaussianScene:
     def __init__(self, colmap_path: str, gaussians: Gaussians) -> None:
         cameras = read_camera_file(colmap_path)
@@ -810,12 +859,16 @@ class GaussianScene:
 
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
                          n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False,
-                         screen: bool = False, camera: bool = False) -> Tuple[torch.Tensor, ...]:
+                         screen: bool = False, camera: bool = False, depth: Optional[torch.Tensor] = None,
+                         grad_depth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
         ``grad_frame``; with ``geometry`` gsx_render_backward_geometry: those two and (dL/dpoints (N,3), dL/dscales (N,3),
         dL/dquaternions (N,4)); with ``screen`` besides gsx_render_backward_screen: those five and (dL/d(NDC mean) (N,2),
         screen radius (N,1)); with ``camera`` (with or without ``screen``) gsx_render_backward_camera: the same, and last
-        (dL/dworld2view (4,4), dL/dfull_proj (4,4)), the two matrices as independent inputs.
+        (dL/dworld2view (4,4), dL/dfull_proj (4,4)), the two matrices as independent inputs.  With ``depth`` (needs
+        ``geometry``, excludes ``camera``) gsx_render_backward_depth: the screen entry's outputs -- the five, or with
+        ``screen`` the seven -- for L(frame, depth image), ``depth`` the image ``_render_depth`` returned and ``grad_depth``
+        dL/d(that image).
         The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
@@ -837,6 +890,14 @@ class GaussianScene:
                 outs += [torch.empty((n, k), dtype=torch.float32, device=dev) for k in (3, 3, 4) + ((2, 1) if screen else ())]
             elif screen or camera:
                 raise ValueError("screen and camera need geometry: both come out of the geometry backward")
+            if depth is not None:
+                if not geometry or camera:
+                    raise ValueError("depth needs geometry and excludes camera: gsx_render_backward_depth has no pose gradient")
+                dimg = _check_f32("depth", depth.detach(), dev)
+                gd = _check_f32("grad_depth", grad_depth.detach(), dev)
+                if tuple(gd.shape) != tuple(dimg.shape) or tuple(dimg.shape) != tuple(img.shape[:2]) + (2,):
+                    raise ValueError("depth has shape %s and grad_depth %s, the frame %s" % (tuple(dimg.shape), tuple(gd.shape),
+                                                                                          tuple(img.shape)))
             cap = int(n_instances) + 4096
             size_fn = lib.gsx_backward_geometry_workspace_bytes if geometry else lib.gsx_backward_workspace_bytes
             entry = (lib.gsx_render_backward_screen if screen else lib.gsx_render_backward_geometry) if geometry \
@@ -847,6 +908,9 @@ class GaussianScene:
                 args = outs + ([] if screen else [None, None]) + cam_outs       # grad_means2d, screen_radius: NULL
                 outs = outs + cam_outs
                 size_fn, entry = lib.gsx_backward_camera_workspace_bytes, lib.gsx_render_backward_camera
+            if depth is not None:
+                args = outs + ([] if screen else [None, None]) + [dimg, gd]     # grad_means2d, screen_radius: NULL
+                size_fn, entry = lib.gsx_backward_depth_workspace_bytes, lib.gsx_render_backward_depth
             with torch.cuda.device(dev):
                 nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
                 if nbytes == 0:
@@ -856,6 +920,64 @@ class GaussianScene:
                            *[_ptr(t) for t in args], ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
             _ffi.check(rc)
         return tuple(outs)
+
+    def _render_depth(self, image_idx: int, tile_size: int, layout: str, n_instances: int, n_visible: int) -> torch.Tensor:
+        """gsx_render_depth: the (D, A) image of the whole ref_cpu frame, (W,H,2) for ``layout`` "wh3" and (H,W,2) for "hw3";
+        ``n_instances`` and ``n_visible`` are the frame's counts (its workspace and row class)."""
+        lib = _ffi.load()
+        with torch.no_grad():
+            dev, n, tensors = self._inputs(image_idx)
+            tensors = [t.detach() for t in tensors]
+            cam = self.images[image_idx].gsx_camera()
+            params, _ = self._frame_params(dev, n, layout, "ref_cpu")
+            params.flags |= _ffi.rows_flag(n, n_visible)
+            shape = (cam.width, cam.height, 2) if layout == "wh3" else (cam.height, cam.width, 2)
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+            cap = int(n_instances) + 4096
+            with torch.cuda.device(dev):
+                nbytes = lib.gsx_depth_workspace_bytes(n, cam.width, cam.height, tile_size, cap)
+                if nbytes == 0:
+                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_depth_workspace_bytes rejected the sizes")
+                ws = _WORKSPACE.get(dev, nbytes)
+                rc = lib.gsx_render_depth(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(out),
+                                          ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
+            _ffi.check(rc)
+        return out
+
+    def render_image_depth_hip(self, image_idx: int, tile_size: int = 16, layout: str = "wh3",
+                               screen_statistics: bool = False, stats: Optional[dict] = None):
+        """``(frame, depth)`` of the whole ref_cpu frame.  ``frame`` is ``render_image_hip``'s, bit for bit; ``depth`` has
+        the frame's two leading axes and a last axis of 2: expected depth ``D = sum T alpha z`` and coverage
+        ``A = sum T alpha`` (gsx_render_depth; ``z`` the view-space depth, ``D`` not divided by ``A`` -- write ``D / A``
+        in torch where it is wanted).  Under ``no_grad``, or when none of ``points``, ``scales``, ``quaternions``,
+        ``opacity``, ``colors`` / ``sh`` requires grad, neither has a ``grad_fn``.  Otherwise both come out of one autograd
+        function whose ``backward`` runs gsx_render_backward_depth once, for whichever of dL/dframe and dL/ddepth arrived
+        (a missing one counts as zeros), and delivers gradients to those of the five arrays that require grad: the
+        geometry gradients need no opt-in here.  ``screen_statistics=True`` leaves ``scene.screen_statistics`` as
+        ``render_image_hip(..., screen_statistics=True)`` does, depth's share included.  An SH scene's dL/dcolour goes
+        through gsx_sh_backward as for the frame (depth adds nothing to it).  The refusals of the frame's gradient path
+        apply with or without gradients; a view whose ``world2view`` requires grad is refused: the pose has no gradient
+        through depth yet."""
+        if layout not in ("wh3", "hw3"):
+            raise ValueError("layout must be 'wh3' or 'hw3', got %r" % (layout,))
+        g = self.gaussians
+        for what, bad in _refusals(g):
+            if bad:
+                _refuse_with_grad(what)
+        if torch.is_grad_enabled() and getattr(self.images[image_idx].world2view, "requires_grad", False):
+            raise ValueError("render_image_depth_hip has no pose gradient: world2view of image %r requires grad, and the "
+                             "gradient through depth (Sz [p, 1] into a column of dL/dworld2view) is not implemented; "
+                             "detach the pose or render the frame with render_image_hip(camera_gradients=True)" % (image_idx,))
+        if _wants_grad(g, True):
+            kw = dict(stats=stats, screen_statistics=bool(screen_statistics))
+            return _RenderImageDepthFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
+                                                   g.opacity, g.colors, getattr(g, "sh", None))
+        with torch.no_grad():
+            st = {}
+            frame = self.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st)
+            if stats is not None:
+                stats.update(st)
+            return frame, self._render_depth(image_idx, tile_size, layout, int(st["n_instances"]), int(st["n_visible"]))
 
     def _sh_backward(self, image_idx: int, grad_colors: torch.Tensor,
                      with_points: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:

@@ -100,3 +100,32 @@ def photometric_loss(frame: torch.Tensor, target: torch.Tensor, lambda_dssim: fl
     if terms is not None:
         terms["l1"], terms["ssim"] = out[1], out[2]
     return loss
+
+
+def depth_loss(depth: torch.Tensor, target: torch.Tensor, region: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """The mean of ``|D - A t|`` over the region's pixels with ``t > 0``, as a 0-d tensor: ``depth`` is the (A, B, 2) image
+    of ``GaussianScene.render_image_depth_hip`` -- expected depth ``D`` and coverage ``A`` -- and ``target`` an (A, B) map of
+    metric depths ``t`` in view space, 0 (or less, or NaN) where there is no measurement.  The form is linear in both maps
+    and divides by nothing: where a pixel is half covered it compares ``D`` with half the target.  ``region=(a, b)`` crops
+    the two leading axes (None: the whole image; a frame's last tile row and column are never rendered:
+    ``GaussianScene.rendered_region``).  With no valid pixel the result is a zero that is still connected to ``depth``.
+    Elementwise torch over one frame: there is no kernel behind it, and nothing waits for the device."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or depth.shape[2] != 2:
+        raise ValueError("depth must be an (A, B, 2) tensor (D, A), got %s" % (
+            tuple(depth.shape) if isinstance(depth, torch.Tensor) else type(depth).__name__,))
+    if not isinstance(target, torch.Tensor) or tuple(target.shape) != tuple(depth.shape[:2]):
+        raise ValueError("target must be an %s tensor of depths, got %s" % (
+            tuple(depth.shape[:2]), tuple(target.shape) if isinstance(target, torch.Tensor) else type(target).__name__))
+    if target.device != depth.device:
+        raise ValueError("target is on %s, depth on %s" % (target.device, depth.device))
+    if target.requires_grad:
+        raise ValueError("target requires grad: depth_loss differentiates the depth image alone (pass target.detach())")
+    if region is not None:
+        a, b = int(region[0]), int(region[1])
+        if not (1 <= a <= depth.shape[0] and 1 <= b <= depth.shape[1]):
+            raise ValueError("region %s does not fit the leading axes %s" % (region, tuple(depth.shape[:2])))
+        depth, target = depth[:a, :b], target[:a, :b]
+    valid = target > 0
+    t = torch.where(valid, target, torch.zeros_like(target)).to(depth.dtype)
+    residual = (depth[..., 0] - depth[..., 1] * t).abs() * valid.to(depth.dtype)
+    return residual.sum() / valid.sum().clamp(min=1).to(depth.dtype)

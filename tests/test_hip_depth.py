@@ -1,0 +1,593 @@
+"""Depth and coverage on the GPU (gsx_render_depth, gsx_render_backward_depth through ``render_image_depth_hip``): the two
+maps against the float64 restatement (tests/depth_restatement.py) and against the composed frame over the colours
+(z, 1, 0); the five gradients of L(frame, D, A) Gaussian by Gaussian against the restatement, the reference's own autograd
+(tests/golden/depthgrad_*.npz) and the composed path of two existing backwards; the bit identities.
+
+Bounds (test_depth_host.py): E_REF is the worst per-Gaussian scaled error of the reference's own float32 autograd against
+the restatement over all depthgrad_ fixtures, per output.  The kernel is held to 12 E_REF against the restatement and to
+13 E_REF against the fixtures.  The maps are held to the project's frame tolerance, 1e-4 on A and 1e-4 times the scene's
+largest listed z on D.  What the kernels measured on an MI355X is recorded below.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+
+import backward_restatement
+import depth_restatement as dr
+import geometry_backward_restatement as gbr
+import test_geometry_backward_host as geo_host
+from test_backward_host import TOL as COLOUR_TOL
+from test_depth_host import BOUND_FIXTURE, BOUND_RESTATEMENT, DEPTH_SCENES, depth_fixture
+from test_hip_backward import DEV, _golden_scene, _oracle_pre, _scene
+from test_hip_density import Guarded
+from test_hip_geometry_backward import _W, _camera
+from test_hip_geometry_backward_edges import _poison
+
+pytestmark = pytest.mark.gpu
+
+# Worst figures measured on an MI355X over the tests of this file that print them:
+#   maps against the restatement   |dD| / z_listed 3.37e-07, |dA| 7.65e-07 (tile12_dense_52x40_n900)
+#   maps against the composed frame              7.16e-07,        1.79e-06 (tiny_48x48_n600)           bound 1e-4
+#   error / scale    against the restatement  (bound 12 E_REF)     against the reference's autograd  (bound 13 E_REF)
+#   points           7.122e-08  (1.84e-07)                         6.928e-08  (2.00e-07)
+#   scales           1.631e-07  (4.33e-07)                         1.528e-07  (4.69e-07)
+#   quaternions      3.307e-09  (5.07e-08)                         4.939e-09  (5.49e-08)
+#   colors           1.927e-06  (2.33e-06)                         1.918e-06  (2.52e-06)
+#   opacity          5.815e-07  (5.83e-07)                         5.514e-07  (6.32e-07)
+# every one of them on tiny_48x48_n600; the next scene is a factor 5 (opacity, cull_96x80_n400: 1.09e-07) to 9 (colours)
+# below.  The opacity figure sits 0.3 % inside its bound, and it is alpha_ref's, not the depth code's: alpha_ref rounds
+# power * log2(e) to float32 before the exponential (gsx_internal.h), a relative error of |power| log2(e) 2^-24 in alpha,
+# and tiny's 0.1 px footprints are graded many sigmas out.  The float64 restatement run on the CPU with that one rounding
+# put into its alpha, and nothing else changed, is 5.95e-07 of the scale away from itself on the opacity (colours
+# 1.92e-06, points 7.0e-08, scales 1.6e-07).  Same inputs give the same bits, so the figure does not move from run to run.
+# fused against composed (test_fused_gradients_agree_with_the_composed_path): at most 0.0095 of the sum of both bounds.
+NAMES = dr.OUTPUTS
+
+
+def _np(t):
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def _depth_grads(scene, W, Wd, tile=16, only=None, **kw):
+    """(frame, depth, {name: gradient}) of L = <W, frame> + <Wd, depth> for the five tensors (only: those named).  W or
+    Wd None: that image is not used by the loss."""
+    g = scene.gaussians
+    for name in NAMES:
+        t = getattr(g, name)
+        t.requires_grad_(only is None or name in only)
+        t.grad = None
+    frame, depth = scene.render_image_depth_hip(1, tile_size=tile, **kw)
+    assert frame.grad_fn is not None and depth.grad_fn is not None
+    loss = 0
+    if W is not None:
+        loss = loss + (frame * W).sum()
+    if Wd is not None:
+        loss = loss + (depth * Wd).sum()
+    loss.backward()
+    out = {name: (None if getattr(g, name).grad is None else getattr(g, name).grad.detach().clone()) for name in NAMES}
+    for name in NAMES:
+        getattr(g, name).requires_grad_(False)
+        getattr(g, name).grad = None
+    return frame.detach(), depth.detach(), out
+
+
+def _check(scene, sc, frame, depth, W, Wd, tile, grads, tag, fixture=None):
+    """The five gradients against the restatement (12 E_REF per output) and, with `fixture`, against the reference's
+    autograd (13 E_REF), per Gaussian.  Returns the restatement's result (five gradients, five scales)."""
+    pre = _oracle_pre(scene, sc)
+    w, h = int(sc["width"]), int(sc["height"])
+    n = sc["points"].shape[0]
+    out = dr.depth_backward(pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene), _np(frame), _np(W), _np(depth),
+                            _np(Wd), w, h, tile, with_scale=True)
+    got = [_np(grads[name]).astype(np.float64).reshape(n, -1) for name in NAMES]
+    errs = dr.per_output_errors(got, out[:5], out[5:])
+    errs_f = None if fixture is None else dr.per_output_errors(got, [fixture["grad_" + k].reshape(n, -1) for k in NAMES], out[5:])
+    for name in NAMES:
+        line = "%s: %s: kernel vs restatement, max error / scale %.4g (bound %.3g)" % (tag, name, errs[name], BOUND_RESTATEMENT[name])
+        if errs_f is not None:
+            line += "; vs reference autograd %.4g (bound %.3g)" % (errs_f[name], BOUND_FIXTURE[name])
+        print(line)
+    for k, name in enumerate(NAMES):
+        assert np.isfinite(got[k]).all(), (tag, name)
+        assert errs[name] <= BOUND_RESTATEMENT[name], (tag, name, errs[name])
+        if errs_f is not None:
+            assert errs_f[name] <= BOUND_FIXTURE[name], (tag, name, errs_f[name])
+    return out
+
+
+def _row_depths(scene, n):
+    """(z per row (n,) float32 on the device, 0 for a culled row: the `depths` gsx_preprocess reports; rows on the order)."""
+    with torch.no_grad():
+        pre = scene.preprocess(1)
+        z = torch.zeros(n, dtype=torch.float32, device=DEV)
+        z[scene.last_order.long()] = pre.depths
+    return z
+
+
+def _composed_maps(scene, tile, layout="wh3"):
+    """The composed (D, A): ``render_image_hip`` under no_grad with colours (z, 1, 0)."""
+    g = scene.gaussians
+    n = g.points.shape[0]
+    z = _row_depths(scene, n)
+    keep = g.colors
+    g.colors = torch.stack([z, torch.ones_like(z), torch.zeros_like(z)], 1).contiguous()
+    try:
+        with torch.no_grad():
+            out = scene.render_image_hip(1, tile_size=tile, layout=layout).clone()
+    finally:
+        g.colors = keep
+    assert not out[..., 2].any()
+    return out[..., :2]
+
+
+def _check_maps(scene, sc, depth, tile, tag):
+    """D and A against the restatement and against the composed frame: 1e-4 on A, 1e-4 z_listed on D."""
+    pre = _oracle_pre(scene, sc)
+    w, h = int(sc["width"]), int(sc["height"])
+    _, D, A, info = dr.forward(pre, w, h, tile)
+    zl = max(info["z_listed"], 1e-30)
+    got = _np(depth).astype(np.float64)
+    comp = _np(_composed_maps(scene, tile)).astype(np.float64)
+    eD, eA = np.abs(got[..., 0] - D).max() / zl, np.abs(got[..., 1] - A).max()
+    cD, cA = np.abs(got[..., 0] - comp[..., 0]).max() / zl, np.abs(got[..., 1] - comp[..., 1]).max()
+    print("%s: maps vs restatement: |dD| / z_listed %.3g, |dA| %.3g; vs composed frame %.3g, %.3g (z_listed %.4g, %d pixels "
+          "stopped, longest list %d)" % (tag, eD, eA, cD, cA, zl, info["stopped"], info["longest"]))
+    assert eD <= 1e-4 and eA <= 1e-4 and cD <= 1e-4 and cA <= 1e-4, (tag, eD, eA, cD, cA)
+    return info
+
+
+def _sc(base):
+    return {k: base[k] for k in ("points", "scales", "quaternions", "opacity", "width", "height")}
+
+
+@pytest.mark.parametrize("name", DEPTH_SCENES)
+def test_maps_and_gradients_match_reference_and_restatement(tmp_path, name):
+    """Tiles 2, 16 and 20 (a tile of 400 pixels: two chunks), the one- and three-visible row classes, culled rows."""
+    dg, base, fwd = depth_fixture(name)
+    scene = _golden_scene(tmp_path, base)
+    tile = int(base["tile"])
+    W = torch.from_numpy(base["W"]).to(DEV)
+    Wd = torch.from_numpy(np.stack([dg["W_D"], dg["W_A"]], -1)).to(DEV)
+    with torch.no_grad():
+        plain = scene.render_image_hip(1, tile_size=tile)
+        f0, d0 = scene.render_image_depth_hip(1, tile_size=tile)
+    assert f0.grad_fn is None and d0.grad_fn is None and torch.equal(f0, plain)
+    frame, depth, grads = _depth_grads(scene, W, Wd, tile=tile)
+    assert torch.equal(frame.view(torch.int32), plain.view(torch.int32)) and torch.equal(depth.view(torch.int32), d0.view(torch.int32))
+    assert depth.shape == frame.shape[:2] + (2,)
+    sc = _sc(base)
+    _check_maps(scene, sc, depth, tile, name)
+    zmax = float(dg["z_max"])
+    assert np.abs(_np(depth)[..., 0] - dg["D"]).max() <= 1e-4 * zmax and np.abs(_np(depth)[..., 1] - dg["A"]).max() <= 1e-4
+    out = _check(scene, sc, frame, depth, W, Wd, tile, grads, name, fixture=dg)
+    dead = (np.abs(base["grad_colors"]).sum(1) == 0) & (np.abs(out[0]).sum(1) == 0)       # culled, or on no composited pixel
+    for key in NAMES:
+        assert not _np(grads[key])[dead].any(), key
+    if name.startswith("cull"):
+        assert dead.sum() >= 112
+
+
+@pytest.mark.parametrize("name", ["small_80x64_n120_tile8", "tile12_dense_52x40_n900", "dense_48x48_n1500"])
+def test_tile_8_and_lists_longer_than_a_batch_match_restatement(tmp_path, name):
+    """Tile 8 (a quarter-filled chunk), tile 12 with lists of more than 64 records (several batches), and the dense scene,
+    whose pixels reach the stop rule."""
+    base = load_golden("grad_" + name)
+    scene = _golden_scene(tmp_path, base)
+    tile, w, h = int(base["tile"]), int(base["width"]), int(base["height"])
+    W, Wd = _W((w, h, 3), 31), _W((w, h, 2), 32)
+    frame, depth, grads = _depth_grads(scene, W, Wd, tile=tile)
+    sc = _sc(base)
+    info = _check_maps(scene, sc, depth, tile, name)
+    if "dense" in name:
+        assert info["longest"] > 64, info
+    if name == "dense_48x48_n1500":
+        assert info["stopped"] > 0, info
+    _check(scene, sc, frame, depth, W, Wd, tile, grads, name)
+
+
+def test_unrendered_margin_and_a_scene_without_visible_gaussians_are_exact_zeros(tmp_path):
+    """The last tile row and column, and the m == 0 return: the image comes from torch.empty, the zeros must be written."""
+    from intro_to_gaussian_splatting_amd.synthetic import make_few_visible_scene, make_scene
+
+    sc = make_scene(500, 72, 56, seed=21)
+    scene = _scene(tmp_path, sc)
+    for layout in ("wh3", "hw3"):
+        poison = [torch.full((72, 56, k), float("nan"), device=DEV) for k in (2, 3, 2, 3)]       # freed blocks of the images' sizes
+        poison[0].sum()
+        del poison
+        with torch.no_grad():
+            frame, depth = scene.render_image_depth_hip(1, layout=layout)
+        if layout == "hw3":
+            frame, depth = frame.permute(1, 0, 2), depth.permute(1, 0, 2)
+        a, b = scene.rendered_region(1, 16)
+        assert (a, b) == (64, 48) and torch.isfinite(depth).all()
+        assert depth[:a, :b, 1].max() > 0.5 and not depth[a:].any() and not depth[:, b:].any()
+        assert torch.equal(frame[a:], torch.zeros_like(frame[a:]))
+    sc0 = make_few_visible_scene(64, 48, 48, seed=5, visible=0)
+    (tmp_path / "none").mkdir()
+    scene0 = _scene(tmp_path / "none", sc0)
+    torch.full((48, 48, 2), float("nan"), device=DEV).sum()
+    spacers = _poison(64)
+    frame, depth, grads = _depth_grads(scene0, _W((48, 48, 3), 5), _W((48, 48, 2), 6))
+    del spacers
+    assert not frame.any() and not depth.any() and depth.shape == (48, 48, 2)
+    for key, width in (("points", 3), ("scales", 3), ("quaternions", 4), ("colors", 3), ("opacity", 1)):
+        assert grads[key].shape == (64, width) and not grads[key].any(), key
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("name", ["tiny_48x48_n600", "tile20_64x64_n300", "rows3_48x48_n3"])
+def test_zero_depth_gradient_gives_the_screen_entry_s_bits(tmp_path, name):
+    """dL/ddepth = 0: all seven outputs of gsx_render_backward_depth are gsx_render_backward_screen's, bit for bit."""
+    dg, base, fwd = depth_fixture(name)
+    scene = _golden_scene(tmp_path, base)
+    tile = int(base["tile"])
+    W = torch.from_numpy(base["W"]).to(DEV)
+    st = {}
+    with torch.no_grad():
+        frame, depth = scene.render_image_depth_hip(1, tile_size=tile, stats=st)
+    args = (1, tile, "wh3", frame, W, st["n_instances"], st["n_visible"])
+    screen = scene._render_backward(*args, geometry=True, screen=True)
+    fused = scene._render_backward(*args, geometry=True, screen=True, depth=depth, grad_depth=torch.zeros_like(depth))
+    assert len(screen) == len(fused) == 7
+    for k, (a, b) in enumerate(zip(screen, fused)):
+        assert a.abs().max() > 0 and torch.equal(_bits(a), _bits(b)), k
+    # and the five without the screen outputs (NULL, NULL) are the same five
+    five = scene._render_backward(*args, geometry=True, depth=depth, grad_depth=torch.zeros_like(depth))
+    assert len(five) == 5 and all(torch.equal(_bits(a), _bits(b)) for a, b in zip(five, screen))
+
+
+def test_fused_gradients_agree_with_the_composed_path(tmp_path):
+    """Random dL/dframe and dL/ddepth: the fused gradients against two existing backwards -- the frame's, and the frame over
+    colours (z, 1, 0) with dL/dframe = (gD, gA, 0) -- plus dL/dcolors[:, 0] world2view[:3, 2] on the points by hand.  Each
+    path is within its own bound of the truth: 12 E_REF of this file times the fused scale; 12 E_REF of the geometry tests
+    (colour paths: their TOL) times each composed backward's own scale."""
+    base = load_golden("grad_small_64x48_n300")
+    scene = _golden_scene(tmp_path, base)
+    g = scene.gaussians
+    n, w, h, tile = 300, 64, 48, 16
+    W, Wd = _W((w, h, 3), 41), _W((w, h, 2), 42)
+    frame, depth, fused = _depth_grads(scene, W, Wd)
+    sc = _sc(base)
+    out = _check(scene, sc, frame, depth, W, Wd, tile, fused, "composition: fused")
+    # ---- the composed path
+    names = ("points", "scales", "quaternions", "colors", "opacity")
+
+    def backward_of(W3):
+        for name in names:
+            getattr(g, name).requires_grad_(True)
+            getattr(g, name).grad = None
+        f = scene.render_image_hip(1, tile_size=tile, geometry_gradients=True)
+        (f * W3).sum().backward()
+        got = {name: getattr(g, name).grad.detach().clone() for name in names}
+        for name in names:
+            getattr(g, name).requires_grad_(False)
+            getattr(g, name).grad = None
+        return f.detach(), got
+
+    f1, g1 = backward_of(W)
+    z = _row_depths(scene, n)
+    keep = g.colors
+    g.colors = torch.stack([z, torch.ones_like(z), torch.zeros_like(z)], 1).contiguous()
+    W2 = torch.cat([Wd, torch.zeros((w, h, 1), device=DEV)], -1)
+    f2, g2 = backward_of(W2)
+    pre2 = _oracle_pre(scene, sc)         # (its colours are (z, 1, 0))
+    g.colors = keep
+    col = scene.images[1].world2view[:3, 2].to(DEV)
+    composed = {"points": g1["points"] + g2["points"] + g2["colors"][:, :1] * col[None, :],
+                "scales": g1["scales"] + g2["scales"], "quaternions": g1["quaternions"] + g2["quaternions"],
+                "colors": g1["colors"], "opacity": g1["opacity"] + g2["opacity"]}
+    # ---- each composed backward's own scale
+    pre1, cam = _oracle_pre(scene, sc), _camera(scene)
+    s1 = gbr.geometry_backward(pre1, sc["points"], sc["scales"], sc["quaternions"], cam, _np(f1), _np(W), w, h, tile, with_scale=True)[3:]
+    s2 = gbr.geometry_backward(pre2, sc["points"], sc["scales"], sc["quaternions"], cam, _np(f2), _np(W2), w, h, tile, with_scale=True)[3:]
+    c1 = backward_restatement.backward(pre1, _np(f1), _np(W), w, h, tile, n, with_scale=True)[2:]
+    c2 = backward_restatement.backward(pre2, _np(f2), _np(W2), w, h, tile, n, with_scale=True)[2:]
+    vcol = float(np.abs(_np(col)).sum())
+    allowed = {"points": 12 * geo_host.E_REF["points"] * (s1[0] + s2[0]) + COLOUR_TOL * c2[0] * vcol,
+               "scales": 12 * geo_host.E_REF["scales"] * (s1[1] + s2[1]),
+               "quaternions": 12 * geo_host.E_REF["quaternions"] * (s1[2] + s2[2]),
+               "colors": COLOUR_TOL * c1[0], "opacity": COLOUR_TOL * (c1[1] + c2[1])}
+    for k, name in enumerate(NAMES):
+        bound = BOUND_RESTATEMENT[name] * out[5 + k] + allowed[name] + backward_restatement.SUBNORMAL
+        diff = np.abs(_np(fused[name]).astype(np.float64) - _np(composed[name]).astype(np.float64)).reshape(n, -1)
+        worst = float((diff / np.maximum(bound, 1e-300)[:, None]).max())
+        print("composition: %s: fused vs composed, worst |difference| / (sum of both bounds) %.3g" % (name, worst))
+        assert (diff <= bound[:, None]).all(), (name, worst)
+    assert torch.equal(fused["colors"], g1["colors"])          # depth adds nothing to dL/dcolour: the same bits
+
+
+def test_depth_gradient_alone_expanded_and_through_a_select(tmp_path):
+    """dL/ddepth arrives alone (the frame unused by the loss); dL/ddepth is an expanded tensor; the loss reads one channel
+    through a select: the same bits as the dense, explicit forms."""
+    dg, base, fwd = depth_fixture("small_64x48_n300")
+    scene = _golden_scene(tmp_path, base)
+    Wd = _W((64, 48, 2), 51)
+    _, depth, alone = _depth_grads(scene, None, Wd)
+    _, _, zeros = _depth_grads(scene, torch.zeros((64, 48, 3), device=DEV), Wd)
+    assert not alone["colors"].any() and alone["points"].abs().max() > 0
+    for k in NAMES:
+        assert torch.equal(_bits(alone[k]), _bits(zeros[k])), k
+    # an expanded dL/ddepth: sum(depth) has the gradient ones.expand(...)
+    g = scene.gaussians
+    for name in NAMES:
+        getattr(g, name).requires_grad_(True)
+        getattr(g, name).grad = None
+    frame, d = scene.render_image_depth_hip(1)
+    d.sum().backward()
+    expanded = {k: getattr(g, k).grad.detach().clone() for k in NAMES}
+    for name in NAMES:
+        getattr(g, name).grad = None
+    frame, d = scene.render_image_depth_hip(1)
+    d[..., 0].sum().backward()                    # a select: dL/dA = 0
+    select = {k: getattr(g, k).grad.detach().clone() for k in NAMES}
+    for name in NAMES:
+        getattr(g, name).requires_grad_(False)
+        getattr(g, name).grad = None
+    ones = torch.ones((64, 48, 2), device=DEV)
+    _, _, dense = _depth_grads(scene, None, ones)
+    only_d = ones.clone()
+    only_d[..., 1] = 0
+    _, _, dense_d = _depth_grads(scene, None, only_d)
+    for k in NAMES:
+        assert torch.equal(_bits(expanded[k]), _bits(dense[k])) and torch.equal(_bits(select[k]), _bits(dense_d[k])), k
+    assert not torch.equal(dense["points"], dense_d["points"])
+    # only the tensors that require grad receive one
+    _, _, some = _depth_grads(scene, None, Wd, only=("scales", "opacity"))
+    assert some["points"] is None and some["quaternions"] is None and some["colors"] is None
+    assert torch.equal(some["scales"], alone["scales"]) and torch.equal(some["opacity"], alone["opacity"])
+
+
+def test_deterministic_follows_spatial_order_and_layout(tmp_path):
+    from intro_to_gaussian_splatting_amd import GaussianScene
+
+    gg = load_golden("grad_trainedlike_128x128_n3000")
+    scene = _golden_scene(tmp_path, gg)
+    W, Wd = torch.from_numpy(gg["W"]).to(DEV), _W((128, 128, 2), 61)
+    f, d, a = _depth_grads(scene, W, Wd)
+    _, d2, b = _depth_grads(scene, W, Wd)
+    assert torch.equal(_bits(d), _bits(d2))
+    for k in NAMES:
+        assert a[k].abs().max() > 0 and torch.equal(_bits(a[k]), _bits(b[k])), k
+    with torch.no_grad():
+        ordered = scene.gaussians.spatially_ordered()
+    scene2 = GaussianScene(str(tmp_path), ordered)
+    f3, d3, c = _depth_grads(scene2, W, Wd)
+    oi = ordered.original_index.long()
+    assert torch.equal(_bits(d3), _bits(d)) and torch.equal(_bits(f3), _bits(f))
+    for k in NAMES:
+        assert torch.equal(_bits(c[k]), _bits(a[k][oi])), k
+    fh, dh, e = _depth_grads(scene, W.permute(1, 0, 2).contiguous(), Wd.permute(1, 0, 2).contiguous(), layout="hw3")
+    assert dh.shape == (128, 128, 2) and torch.equal(_bits(dh.permute(1, 0, 2)), _bits(d))
+    for k in NAMES:
+        assert torch.equal(_bits(e[k]), _bits(a[k])), k
+
+
+def test_screen_statistics_carry_depth_s_share(tmp_path):
+    """screen_statistics=True leaves scene.screen_statistics as the screen entry does: with dL/ddepth = 0 the frame path's
+    bits, with a depth gradient another dL/d(NDC mean) and the same radius."""
+    dg, base, fwd = depth_fixture("small_64x48_n300")
+    scene = _golden_scene(tmp_path, base)
+    g = scene.gaussians
+    W = torch.from_numpy(base["W"]).to(DEV)
+    g.points.requires_grad_(True)
+    frame = scene.render_image_hip(1, geometry_gradients=True, screen_statistics=True)
+    (frame * W).sum().backward()
+    idx, gn0, r0 = scene.screen_statistics
+    p0 = g.points.grad.clone()
+    g.points.grad = None
+    g.points.requires_grad_(False)
+    scene.screen_statistics = None
+    _, _, plain = _depth_grads(scene, W, None, screen_statistics=True)
+    idx1, gn1, r1 = scene.screen_statistics
+    assert idx == idx1 == 1 and torch.equal(_bits(gn0), _bits(gn1)) and torch.equal(_bits(r0), _bits(r1))
+    assert torch.equal(_bits(plain["points"]), _bits(p0))
+    _depth_grads(scene, W, _W((64, 48, 2), 71), screen_statistics=True)
+    _, gn2, r2 = scene.screen_statistics
+    assert torch.equal(_bits(r2), _bits(r0)) and not torch.equal(gn2, gn0) and gn2.shape == (300, 2)
+    scene.screen_statistics = None
+    _depth_grads(scene, W, None)
+    assert scene.screen_statistics is None
+
+
+def test_sh_scene_goes_through_the_sh_backward_unchanged(tmp_path):
+    """An SH scene: with dL/ddepth = 0 its dL/dsh (and the other gradients) are the screen path's bits; with a depth
+    gradient dL/dsh is still those bits (depth adds nothing to dL/dcolour)."""
+    from intro_to_gaussian_splatting_amd.synthetic import make_scene
+
+    sc = make_scene(400, 64, 48, seed=9)
+    scene = _scene(tmp_path, sc)
+    g = scene.gaussians
+    gen = torch.Generator(device=DEV).manual_seed(9)
+    g.sh = (torch.randn((400, 4, 3), generator=gen, device=DEV) * 0.3).contiguous()
+    g.sh_degree = 1
+    W, Wd = _W((64, 48, 3), 81), _W((64, 48, 2), 82)
+    names = ("points", "scales", "quaternions", "opacity", "sh")
+
+    def run(fn):
+        for name in names:
+            getattr(g, name).requires_grad_(True)
+            getattr(g, name).grad = None
+        fn().backward()
+        got = {name: getattr(g, name).grad.detach().clone() for name in names}
+        for name in names:
+            getattr(g, name).requires_grad_(False)
+            getattr(g, name).grad = None
+        return got
+
+    screen = run(lambda: (scene.render_image_hip(1, geometry_gradients=True) * W).sum())
+    zero = run(lambda: (scene.render_image_depth_hip(1)[0] * W).sum())
+    both = run(lambda: sum((img * w).sum() for img, w in zip(scene.render_image_depth_hip(1), (W, Wd))))
+    for k in names:
+        assert screen[k].abs().max() > 0 and torch.equal(_bits(zero[k]), _bits(screen[k])), k
+    assert torch.equal(_bits(both["sh"]), _bits(screen["sh"])) and not torch.equal(both["points"], screen["points"])
+    g.sh.requires_grad_(False)
+    with pytest.raises(ValueError, match="SH scene"):           # the gradient path's refusal, with or without gradients
+        with torch.no_grad():
+            scene.render_image_depth_hip(1)
+
+
+def test_world2view_that_requires_grad_is_refused(tmp_path):
+    dg, base, fwd = depth_fixture("tile2_40x32_n80")
+    scene = _golden_scene(tmp_path, base)
+    scene.gaussians.points.requires_grad_(True)
+    scene.images[1].world2view.requires_grad_(True)
+    with pytest.raises(ValueError, match="no pose gradient"):
+        scene.render_image_depth_hip(1, tile_size=2)
+    scene.images[1].world2view.requires_grad_(False)
+    frame, depth = scene.render_image_depth_hip(1, tile_size=2)
+    assert depth.grad_fn is not None
+    scene.gaussians.points.requires_grad_(False)
+
+
+@pytest.mark.parametrize("n,w,h,tile", [(300, 64, 48, 16), (80, 40, 32, 2), (1, 48, 48, 16)])
+def test_entries_stay_between_guarded_margins(tmp_path, n, w, h, tile):
+    """Both entries at exactly their workspace size, every array between two 64-element sentinel margins."""
+    from intro_to_gaussian_splatting_amd import _ffi
+    from intro_to_gaussian_splatting_amd.synthetic import make_scene
+
+    lib = _ffi.load()
+    sc = make_scene(n, w, h, seed=40 if n == 1 else 3)
+    scene = _scene(tmp_path, sc)
+    st = {}
+    with torch.no_grad():
+        frame, depth = scene.render_image_depth_hip(1, tile_size=tile, stats=st)
+    dev, nn, tensors = scene._inputs(1)
+    cam = scene.images[1].gsx_camera()
+    params, _ = scene._frame_params(dev, n, "wh3", "ref_cpu")
+    params.flags |= _ffi.rows_flag(n, int(st["n_visible"]))
+    cap = int(st["n_instances"]) + 1
+    stream = ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+    need = int(lib.gsx_depth_workspace_bytes(n, w, h, tile, cap))
+    assert need > 0 and need == int(lib.gsx_backward_depth_workspace_bytes(n, w, h, tile, cap)) and need % 256 == 0
+    ws, out = Guarded(need // 4), Guarded(w * h * 2)
+    assert ws.view.data_ptr() % 256 == 0
+    rc = lib.gsx_render_depth(ctypes.byref(cam), *[t.data_ptr() for t in tensors], n, tile, out.view.data_ptr(), ctypes.byref(params),
+                              ws.view.data_ptr(), need, stream)
+    torch.cuda.synchronize()
+    assert rc == 0, lib.gsx_last_error()
+    assert ws.intact() and out.intact(), "a write outside an array"
+    assert torch.equal(_bits(out.view.view(w, h, 2)), _bits(depth))
+    outs = [Guarded(n * k) for k in (3, 1, 3, 3, 4, 2, 1)]
+    gimg, gdep = Guarded(w * h * 3), Guarded(w * h * 2)
+    gimg.view.copy_(_W((w * h * 3,), 1))
+    gdep.view.copy_(_W((w * h * 2,), 2))
+    ws = Guarded(need // 4)
+    rc = lib.gsx_render_backward_depth(ctypes.byref(cam), *[t.data_ptr() for t in tensors], n, tile, frame.data_ptr(),
+                                       gimg.view.data_ptr(), *[o.view.data_ptr() for o in outs], depth.data_ptr(),
+                                       gdep.view.data_ptr(), ctypes.byref(params), ws.view.data_ptr(), need, stream)
+    torch.cuda.synchronize()
+    assert rc == 0, lib.gsx_last_error()
+    assert ws.intact() and gimg.intact() and gdep.intact() and all(o.intact() for o in outs), "a write outside an array"
+    assert all(torch.isfinite(o.view).all() for o in outs) and outs[2].view.abs().max() > 0
+
+
+# ---- the fit loop
+LR = {"points": 2e-4, "scales": 2e-3, "quaternions": 1e-3, "opacity": 2e-2, "colors": 5e-3}
+TRAINED = tuple(LR)
+DENSITY = dict(grad_threshold=2e-5, dense_scale=0.05, prune_logit=-4.5)
+LAMBDA_DEPTH = 0.25
+
+
+def _fit_scene(path, seed):
+    """(tiny_48x48_n600 perturbed; the frame and the depth map D / A, 0 where uncovered, rendered before the perturbation)."""
+    base = load_golden("grad_tiny_48x48_n600")
+    path.mkdir(exist_ok=True)
+    scene = _golden_scene(path, base)
+    g = scene.gaussians
+    rs = np.random.RandomState(seed)
+    with torch.no_grad():
+        frame, depth = scene.render_image_depth_hip(1)
+        target = frame.clone()
+        covered = depth[..., 1] > 0.05
+        target_depth = torch.where(covered, depth[..., 0] / depth[..., 1].clamp(min=1e-6), torch.zeros_like(depth[..., 0])).contiguous()
+        g.points.add_(torch.from_numpy(rs.normal(0, 0.05, size=tuple(g.points.shape)).astype(np.float32)).to(DEV))
+        g.opacity.add_(torch.from_numpy(rs.normal(0, 0.5, size=tuple(g.opacity.shape)).astype(np.float32)).to(DEV))
+    return scene, {1: target}, {1: target_depth}
+
+
+def _state(g, opt):
+    out = {name: getattr(g, name).detach().clone() for name in TRAINED}
+    out.update({"m_" + name: opt.exp_avg[name].clone() for name in TRAINED})
+    out.update({"v_" + name: opt.exp_avg_sq[name].clone() for name in TRAINED})
+    return out
+
+
+def test_trainer_with_depth_targets_is_the_composition_written_out(tmp_path):
+    from intro_to_gaussian_splatting_amd import DensityControl, GaussianAdam, Trainer, depth_loss
+
+    steps, seed = 6, 5
+    periods = dict(sh_degree_every=None, densify_every=4, opacity_reset_every=None, densify_from=0, densify_until=100)
+    scene, targets, depths = _fit_scene(tmp_path / "a", 1)
+    trainer = Trainer(scene, targets, lr=LR, lambda_dssim=0.2, tile_size=16, statistic="screen", density=DENSITY, seed=seed,
+                      depth_targets=depths, lambda_depth=LAMBDA_DEPTH, **periods)
+    seen = []
+    trainer.fit(steps, callback=lambda t, losses, idx: seen.append((losses, idx, len(t.gaussians))))
+
+    scene2, targets2, depths2 = _fit_scene(tmp_path / "b", 1)
+    g = scene2.gaussians
+    for name in TRAINED:
+        getattr(g, name).requires_grad_(True)
+    opt = GaussianAdam(g, lr=LR)
+    dc = DensityControl(g, optimizer=opt, scene=scene2, statistic="screen", **DENSITY)
+    split = torch.Generator(device=DEV).manual_seed(seed)
+    by_hand = []
+    for s in range(1, steps + 1):
+        terms = {}
+        frame, depth = scene2.render_image_depth_hip(1, tile_size=16, screen_statistics=True)
+        loss = scene2.photometric_loss(1, frame, targets2[1], tile_size=16, lambda_dssim=0.2, terms=terms)
+        loss = loss + LAMBDA_DEPTH * depth_loss(depth, depths2[1], scene2.rendered_region(1, 16))
+        loss.backward()
+        dc.accumulate()
+        opt.step()
+        opt.zero_grad()
+        if s % 4 == 0:
+            dc.densify_and_prune(generator=split)
+        by_hand.append((torch.stack((loss.detach(), terms["l1"], terms["ssim"])), 1, len(g)))
+    print("rows per step", [n for _, _, n in seen])
+    assert [v[1:] for v in seen] == [v[1:] for v in by_hand]
+    assert all(torch.equal(_bits(a[0]), _bits(b[0])) for a, b in zip(seen, by_hand))
+    got, want = _state(trainer.gaussians, trainer.opt), _state(g, opt)
+    for key in want:
+        assert torch.equal(_bits(got[key]), _bits(want[key])), key
+    assert trainer.opt.step_count == opt.step_count == steps
+
+    # depth_targets=None: the frame-only step, bit for bit as before (the depth term is not a zero added)
+    scene3, targets3, _ = _fit_scene(tmp_path / "c", 1)
+    plain = Trainer(scene3, targets3, lr=LR, lambda_dssim=0.2, tile_size=16, statistic="screen", density=DENSITY, seed=seed, **periods)
+    first = plain.step()[0]
+    scene4, targets4, _ = _fit_scene(tmp_path / "d", 1)
+    g4 = scene4.gaussians
+    for name in TRAINED:
+        getattr(g4, name).requires_grad_(True)
+    terms = {}
+    f4 = scene4.render_image_hip(1, tile_size=16, geometry_gradients=True, screen_statistics=True)
+    l4 = scene4.photometric_loss(1, f4, targets4[1], tile_size=16, lambda_dssim=0.2, terms=terms)
+    assert torch.equal(_bits(first), _bits(torch.stack((l4.detach(), terms["l1"], terms["ssim"]))))
+    assert not torch.equal(first, seen[0][0])
+
+
+def test_thirty_steps_lower_the_depth_loss(tmp_path):
+    from intro_to_gaussian_splatting_amd import Trainer, depth_loss
+
+    scene, targets, depths = _fit_scene(tmp_path / "fit", 2)
+    region = scene.rendered_region(1, 16)
+
+    def measure():
+        with torch.no_grad():
+            return float(depth_loss(scene.render_image_depth_hip(1)[1], depths[1], region))
+
+    before = measure()
+    trainer = Trainer(scene, targets, lr={"points": 2e-3, "opacity": 2e-2, "scales": 2e-3}, sh_degree_every=None, densify_every=None,
+                      opacity_reset_every=None, seed=0, depth_targets=depths, lambda_depth=1.0)
+    trainer.fit(30)
+    after = measure()
+    print("thirty steps with depth targets: depth_loss %.6g -> %.6g" % (before, after))
+    assert before > 0 and after < before

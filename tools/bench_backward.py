@@ -1,6 +1,6 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth]
                                                      [--workloads c3] [--sh [--active-degree A]]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
@@ -15,6 +15,12 @@ radius), its steps taking turns with the geometry entry's so that both see the s
 floats out) in turns with the geometry and the screen entry, three ways ("alternating_camera", "camera_over_screen");
 with --sh it takes the SH scene's whole camera-gradient backward (the camera entry, then gsx_sh_backward with the view
 direction's share) in turns with the same two calls through the screen entry.  --workloads picks among c2 and c3.
+--depth (key "depth") takes, in turns in one session: gsx_render_backward_depth for a random dL/dframe and dL/ddepth
+("fused"), the screen entry for the same dL/dframe ("screen"), gsx_render_depth alone ("depth_forward"), the frame
+("frame") and the two calls the composed path adds, the frame over colours (z, 1, 0) ("frame_z") and its geometry
+backward ("backward_z").  "fused_render_side_ms" = frame + depth_forward + fused against "composed_render_side_ms" =
+frame + frame_z + screen + backward_z, the medians added; "stages" holds the GSX_FLAG_TIMING stages of the screen and the
+fused backward (stage chain again; raw records, prefix and the tile kernel; sums and chain), medians of `steps` calls.
 
 --sh times the differentiable SH scene INSTEAD: the trained-like 1M scene with degree-3 coefficients (bench.py's
 c3_trainedlike).  Its backward is gsx_render_backward on this camera's evaluated colours (gsx_sh_to_rgb runs again) and
@@ -71,7 +77,7 @@ def _in_turns(calls, steps, warmup):
     return {k: (round(statistics.median(v), 4), [round(min(v), 4), round(max(v), 4)]) for k, v in turns.items()}
 
 
-def run(name, n, steps, warmup, geometry=False, screen=False, camera=False):
+def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -132,6 +138,54 @@ def run(name, n, steps, warmup, geometry=False, screen=False, camera=False):
             out["alternating_camera"] = {k + "_ms": v[0] for k, v in t.items()}
             out["alternating_camera"].update({k + "_min_max": v[1] for k, v in t.items()})
             out["camera_over_screen"] = round(t["camera"][0] / t["screen"][0], 4)
+        if depth:
+            back = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
+                                                       geometry=True, **kw)
+            dimg = scene._render_depth(1, 16, "wh3", st["n_instances"], st["n_visible"])
+            gen = torch.Generator(device=frame.device).manual_seed(1)
+            Wd = torch.randn(dimg.shape, device=frame.device, generator=gen)
+            # the composed path: the frame over colours (z, 1, 0) and its geometry backward for dL/dframe = (gD, gA, 0)
+            pre = scene.preprocess(1)
+            z = torch.zeros(n, dtype=torch.float32, device=frame.device)
+            z[scene.last_order.long()] = pre.depths
+            del pre
+            colors, zcolors = g.colors, torch.stack([z, torch.ones_like(z), torch.zeros_like(z)], 1).contiguous()
+            W2 = torch.cat([Wd, torch.zeros_like(Wd[..., :1])], -1).contiguous()
+
+            def over_z(fn):
+                def call():
+                    g.colors = zcolors
+                    try:
+                        return fn()
+                    finally:
+                        g.colors = colors
+                return call
+
+            frame_z = over_z(lambda: scene.render_image_hip(1))().clone()
+            back_z = over_z(lambda **kw: scene._render_backward(1, 16, "wh3", frame_z, W2, st["n_instances"], st["n_visible"],
+                                                                geometry=True))
+            fused = lambda **kw: back(screen=True, depth=dimg, grad_depth=Wd, **kw)  # noqa: E731
+            t = _in_turns(dict(screen=lambda: back(screen=True), fused=fused,
+                               depth_forward=lambda: scene._render_depth(1, 16, "wh3", st["n_instances"], st["n_visible"]),
+                               frame=lambda: scene.render_image_hip(1), frame_z=over_z(lambda: scene.render_image_hip(1)),
+                               backward_z=back_z), steps, warmup)
+            d = {k + "_ms": v[0] for k, v in t.items()}
+            d.update({k + "_min_max": v[1] for k, v in t.items()})
+            d["fused_over_screen"] = round(t["fused"][0] / t["screen"][0], 4)
+            d["fused_render_side_ms"] = round(t["frame"][0] + t["depth_forward"][0] + t["fused"][0], 4)
+            d["composed_render_side_ms"] = round(t["frame"][0] + t["frame_z"][0] + t["screen"][0] + t["backward_z"][0], 4)
+            d["fused_over_composed"] = round(d["fused_render_side_ms"] / d["composed_render_side_ms"], 4)
+            stages = {}
+            for key, call in (("screen", lambda **kw: back(screen=True, **kw)), ("fused", fused)):
+                rows = []
+                for _ in range(steps):
+                    call(flags=_ffi.GSX_FLAG_TIMING)
+                    ms = (ctypes.c_float * 3)()
+                    _ffi.check(lib.gsx_debug_backward_stage_ms(ms))
+                    rows.append(list(ms))
+                stages[key] = [round(statistics.median(r[i] for r in rows), 4) for i in range(3)]
+            d["stages"] = stages
+            out["depth"] = d
     return out
 
 
@@ -234,6 +288,8 @@ def main():
     ap.add_argument("--screen", action="store_true", help="also time gsx_render_backward_screen, in turns with the geometry entry")
     ap.add_argument("--camera", action="store_true", help="also time gsx_render_backward_camera, in turns with the geometry "
                     "and the screen entry")
+    ap.add_argument("--depth", action="store_true", help="also time gsx_render_backward_depth and gsx_render_depth in turns "
+                    "with the screen entry and with the composed path's two frames and two backwards")
     ap.add_argument("--workloads", default="c2,c3", help="comma-separated: which of c2, c3 to run (not with --sh)")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     ap.add_argument("--active-degree", type=int, default=None, help="with --sh: Gaussians.active_sh_degree (0..3), the "
@@ -246,7 +302,7 @@ def main():
                                                                        active=args.active_degree, camera=args.camera))))
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
-    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera)
+    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera, args.depth)
            for name, n in WORKLOADS.items() if name in args.workloads.split(",")}
     print(json.dumps(dict(metric="backward_ms", results=out)))
 

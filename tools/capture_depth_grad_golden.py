@@ -1,0 +1,136 @@
+"""Depth-and-coverage fixtures: the REFERENCE ITSELF under autograd, with its one graph cut mended.  Data only.
+
+Build container only, like tools/capture_geometry_grad_golden.py, whose recipe this follows: the same scenes from the
+same generator arguments, the same `_weight` rebound over the reference's compute_gaussian_weight (the same value as a
+tensor), nothing under oracle/ changed.  The reference composites linearly in the colours, so its own render_image
+yields expected depth D = sum T alpha z and coverage A = sum T alpha as the first two channels of a frame whose colours
+are (z, 1, 0), with z the reference's points_view[:, 2] (PreprocessedScene.depths) KEPT IN THE GRAPH: the scene's
+`preprocess` is wrapped at run time so that the tuple it returns carries that colour array in place of its own.
+
+For every scene the reference renders twice: once with the scene's colours (frame, weights W of the geomgrad_ fixture) and
+once with colours (z, 1, 0) (D, A, seeded weights W_D and W_A).  The loss is
+
+    L = sum(frame * W) + sum(D * W_D) + sum(A * W_A)
+
+whose gradient with respect to [points, scales, quaternions, colors, opacity] is taken per render and added in float32.
+Before anything is written the tool ASSERTS that the first render's image and five gradients equal the committed
+geomgrad_<scene>.npz / grad_<scene>.npz bit for bit.
+
+    python tools/capture_depth_grad_golden.py            # all scenes
+    python tools/capture_depth_grad_golden.py tile2      # only those whose name contains "tile2"
+
+Writes tests/golden/depthgrad_<scene>.npz: D, A (W,H), W_D, W_A (W,H), the five gradients of L (grad_points, grad_scales,
+grad_quaternions, grad_colors, grad_opacity) and the second render's share alone (depth_grad_points, depth_grad_scales,
+depth_grad_quaternions, depth_grad_opacity; its grad_colors is zero: no depth depends on a colour), z_max the largest
+visible depth.  Scene, W, the frame and the frame's gradients are in the geomgrad_ / grad_ fixtures of the same name.
+"""
+from __future__ import annotations
+
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from capture_geometry_grad_golden import OWN_STAGE1, STANDALONE, _weight  # noqa: E402
+from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
+
+SCENES = ["tile2_40x32_n80", "tiny_48x48_n600", "small_64x48_n300", "cull_96x80_n400", "rows1_48x48_n1", "rows3_48x48_n3",
+          # a tile of more than 256 pixels: the tile kernels take it in two chunks
+          "tile20_64x64_n300"]
+# Not in the set: the other geomgrad_ scenes.  Each needs two graphs through the geometry, minutes and many GB apiece
+# (needle, 110 Gaussians: over 21 GB for one); name one on the command line on a machine with the memory and the time.
+EXTRA = ["small_80x64_n120_tile8", "tile12_dense_52x40_n900", "tile32_96x96_n400", "wide_64x64_n400", "needle_160x160_n110",
+         "rows1_48x48_n500", "rows3_48x48_n500"]
+
+
+def capture(name: str, GaussianScene, Gaussians) -> None:
+    import torch
+
+    from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
+
+    own = name in OWN_STAGE1
+    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
+    tile = spec.pop("tile")
+    assert not spec.pop("defaults", False)
+    sc = _generate(spec)
+    with tempfile.TemporaryDirectory() as tmp:
+        write_colmap_text(os.path.join(tmp, "colmap"), sc)
+        g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
+        points = torch.from_numpy(sc["points"]).float().clone().requires_grad_(True)
+        scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
+        quats = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
+        colors = g.colors.detach().clone().requires_grad_(True)
+        opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone().requires_grad_(True)
+        g.points, g.scales, g.quaternions, g.colors, g.opacity = points, scales, quats, colors, opacity
+        scene = GaussianScene(os.path.join(tmp, "colmap"), g)
+        leaves = [points, scales, quats, colors, opacity]
+        # ---- the frame: what the committed fixtures hold
+        t0 = time.time()
+        image = scene.render_image(1, tile_size=tile)
+        W = torch.from_numpy(np.random.default_rng(1000 + len(name)).standard_normal(tuple(image.shape)).astype(np.float32))
+        g1 = torch.autograd.grad((image * W).sum(), leaves, allow_unused=True)
+        g1 = [np.zeros(tuple(t.shape), np.float32) if v is None else v.numpy() for v, t in zip(g1, leaves)]
+        geo = np.load(os.path.join(OUT_DIR, "geomgrad_" + name + ".npz"))
+        com = geo if (name in STANDALONE or own) else np.load(os.path.join(OUT_DIR, "grad_" + name + ".npz"))
+        for key, got in (("image", image.detach().numpy()), ("W", W.numpy()), ("grad_colors", g1[3]), ("grad_opacity", g1[4])):
+            assert np.array_equal(got.view(np.uint32), com[key].view(np.uint32)), "%s: %s differs from the committed fixture" % (name, key)
+        for key, got in (("grad_points", g1[0]), ("grad_scales", g1[1]), ("grad_quaternions", g1[2])):
+            assert np.array_equal(got.view(np.uint32), geo[key].view(np.uint32)), "%s: %s differs from geomgrad_" % (name, key)
+        del image
+        # ---- depth and coverage: the same render_image over colours (z, 1, 0), z in the graph
+        original = scene.preprocess
+        seen = {}
+
+        def preprocess(image_idx):
+            pre = original(image_idx)
+            z = pre.depths
+            seen["z_max"] = float(z.max()) if z.numel() else 0.0
+            return pre._replace(colors=torch.stack([z, torch.ones_like(z), torch.zeros_like(z)], dim=1))
+
+        scene.preprocess = preprocess
+        try:
+            second = scene.render_image(1, tile_size=tile)
+        finally:
+            del scene.preprocess
+        D, A = second[..., 0], second[..., 1]
+        assert not second[..., 2].any(), name
+        rng = np.random.default_rng(2000 + len(name))
+        W_D = torch.from_numpy(rng.standard_normal(tuple(D.shape)).astype(np.float32))
+        W_A = torch.from_numpy(rng.standard_normal(tuple(A.shape)).astype(np.float32))
+        g2 = torch.autograd.grad((D * W_D).sum() + (A * W_A).sum(), leaves, allow_unused=True)
+        g2 = [np.zeros(tuple(t.shape), np.float32) if v is None else v.numpy() for v, t in zip(g2, leaves)]
+        seconds = time.time() - t0
+    assert not g2[3].any(), name + ": a depth gradient reached the colours"
+    total = [a + b for a, b in zip(g1, g2)]
+    for arr in total:
+        assert np.isfinite(arr).all(), name
+    out = dict(D=D.detach().numpy(), A=A.detach().numpy(), W_D=W_D.numpy(), W_A=W_A.numpy(), z_max=np.float32(seen["z_max"]),
+               grad_points=total[0], grad_scales=total[1], grad_quaternions=total[2], grad_colors=total[3], grad_opacity=total[4],
+               depth_grad_points=g2[0], depth_grad_scales=g2[1], depth_grad_quaternions=g2[2], depth_grad_opacity=g2[4])
+    path = os.path.join(OUT_DIR, "depthgrad_" + name + ".npz")
+    np.savez_compressed(path, **out)
+    print("depthgrad_%s: N=%d max D=%.3g max A=%.3g z_max=%.3g max|depth gp|=%.3g max|depth gs|=%.3g max|depth gq|=%.3g "
+          "max|depth go|=%.3g %.0fs (%.0f KB)" % (name, sc["points"].shape[0], out["D"].max(), out["A"].max(), seen["z_max"],
+                                                   np.abs(g2[0]).max(), np.abs(g2[1]).max(), np.abs(g2[2]).max(),
+                                                   np.abs(g2[4]).max(), seconds, os.path.getsize(path) / 1024), flush=True)
+
+
+def main() -> None:
+    only = sys.argv[1] if len(sys.argv) > 1 else ""
+    GaussianScene, Gaussians = _import_reference()
+    import splat.gaussian_scene as ref_scene
+
+    ref_scene.compute_gaussian_weight = _weight
+    for name in SCENES + [e for e in EXTRA if only and only in e]:
+        if only in name:
+            capture(name, GaussianScene, Gaussians)
+
+
+if __name__ == "__main__":
+    main()
