@@ -624,6 +624,50 @@ GSX_API int gsx_photometric_loss(const float *image, int64_t image_row_stride, c
 GSX_API size_t gsx_photometric_loss_workspace_bytes(int32_t rows, int32_t cols, int32_t with_grad);
 
 /*
+ * Build extension: the loss above for photographs -- a per-pixel weight m (a mask: sky, passers-by, a matte, the
+ * undistortion border) and a per-view exposure E, a 3 x 4 affine colour transform applied to the frame before it meets the
+ * target (auto-exposure and white balance differ from shot to shot; the published implementation learns the same term beside
+ * the Gaussians).  Symbols as above; sums run over the region's pixels:
+ *   x'_i = ((E_i0 x_0 + E_i1 x_1) + E_i2 x_2) + E_i3      each product and sum rounded to float32, in this order;
+ *                                                         x' = x when exposure is NULL
+ *   outside the region x' is 0, not E_i3: the windows see the two images as if cropped, as above
+ *   W    = sum m                                          (rows * cols when weight is NULL)
+ *   l1   = sum_pix m sum_ch |x' - y| / (3 W)
+ *   ssim = sum_pix m sum_ch (A1 A2 / (B1 B2)) / (3 W)     the SSIM map is formed from x' and y unweighted; m weighs the map
+ *   loss = (1 - lambda) l1 + lambda (1 - ssim)
+ *   g'   = (1 - lambda) m sign(x' - y) / (3 W) + G*(w m Dmu) + 2 x' G*(w m Dp) + y G*(w m Dq),   w = -lambda / (3 W)
+ *   dL/dx      = E[:, :3]^T g'           per region pixel (g' itself when exposure is NULL)
+ *   dL/dE[i,j] = sum_pix g'_i x_j (j < 3),  dL/dE[i,3] = sum_pix g'_i
+ *   W == 0: loss_out = (0, 0, 0, 0), every gradient an exact +0
+ * A pixel with m = 0 still reaches the loss through the windows of its neighbours within 5 pixels: m weighs the SSIM map,
+ * it does not hide the pixel from the windows (multiplying the images by m would fit black into the hole).  A caller who
+ * wants a hard cut dilates the mask by 5 pixels.
+ * weight: DEVICE (rows x cols) float32, a row every weight_row_stride floats (>= cols), or NULL; finite and >= 0 is the
+ * caller's contract, nothing checks it.  exposure: DEVICE 12 floats, row-major 3 x 4, or NULL -- device memory, so that a
+ * step of the exposure never synchronises.  loss_out (DEVICE, 4 floats) receives loss, l1, ssim, W.  grad_image as above.
+ * grad_exposure (DEVICE 12 floats, or NULL) receives dL/dE; it needs exposure and grad_image.
+ * With weight == NULL and exposure == NULL the call runs the kernels of gsx_photometric_loss: loss_out[0..2] and grad_image
+ * hold the same bits, loss_out[3] = rows * cols.  Otherwise 1 / W is not known while the maps are formed: they are stored
+ * unscaled, the one workgroup that sums the per-tile partials in double leaves 1 / (3 W) in the workspace, and the gradient
+ * kernel multiplies; W is never read back.  No atomics, every sum in a fixed order: same inputs, same bits (dL/dE included),
+ * and loss_out holds the same bits with and without the gradients.
+ * Refused with GSX_ERR_INVALID_ARGUMENT before any HIP call: everything gsx_photometric_loss refuses; weight_row_stride <
+ * cols when weight is given; grad_exposure without exposure or without grad_image.  workspace:
+ * gsx_photometric_loss_weighted_workspace_bytes(rows, cols, grad_image != NULL).  Does not synchronise, does not allocate.
+ */
+GSX_API int gsx_photometric_loss_weighted(const float *image, int64_t image_row_stride, const float *target,
+                                          int64_t target_row_stride, const float *weight /* may be NULL */,
+                                          int64_t weight_row_stride, const float *exposure /* may be NULL */, int32_t rows,
+                                          int32_t cols, float lambda_dssim, float *loss_out /* 4 floats */,
+                                          float *grad_image /* may be NULL */, int64_t grad_row_stride,
+                                          float *grad_exposure /* may be NULL */, void *workspace, size_t workspace_bytes,
+                                          void *stream);
+
+/* Bytes of device workspace gsx_photometric_loss_weighted needs: what gsx_photometric_loss needs, three partial sums per
+ * tile, the scale slot and, with_grad != 0, twelve partial sums of dL/dE per tile (0 on invalid arguments). */
+GSX_API size_t gsx_photometric_loss_weighted_workspace_bytes(int32_t rows, int32_t cols, int32_t with_grad);
+
+/*
  * Build extension (the reference has no training loop): one Adam step (Kingma & Ba 2015) over up to GSX_ADAM_MAX_GROUPS
  * parameter arrays of the same n rows -- the arrays of a Gaussian container -- in ONE kernel launch, in place.  What it
  * steps along are the gradients the calls above wrote.  Those are exact zeros for every Gaussian that is culled or on no

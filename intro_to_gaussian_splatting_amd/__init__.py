@@ -10,8 +10,9 @@ from .density import DensityControl
 from .knn import nearest3
 from .fit import Trainer, events_at
 from .pose import CameraRefiner
+from .exposure import ExposureRefiner
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
            "NativeExtension", "photometric_loss", "depth_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3",
-           "Trainer", "events_at", "CameraRefiner"]
+           "Trainer", "events_at", "CameraRefiner", "ExposureRefiner"]

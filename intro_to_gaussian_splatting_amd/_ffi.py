@@ -159,6 +159,9 @@ SIGNATURES = {
     "gsx_photometric_loss": (ctypes.c_int, [_FP, c_int64, _FP, c_int64, c_int32, c_int32, c_float, _FP, _FP, c_int64,
                                             c_void_p, c_size_t, c_void_p]),
     "gsx_photometric_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "gsx_photometric_loss_weighted": (ctypes.c_int, [_FP, c_int64, _FP, c_int64, _FP, c_int64, _FP, c_int32, c_int32, c_float,
+                                                     _FP, _FP, c_int64, _FP, c_void_p, c_size_t, c_void_p]),
+    "gsx_photometric_loss_weighted_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "gsx_adam_step": (ctypes.c_int, [POINTER(GsxAdamGroup), c_int32, c_int64, c_int64, c_float, c_float, c_float,
                                      ctypes.c_uint32, c_void_p]),
     "gsx_density_accumulate": (ctypes.c_int, [_FP, c_int32, c_int64, _FP, c_void_p, c_void_p]),

@@ -881,6 +881,52 @@ int gsx_photometric_loss(const float *image, int64_t image_row_stride, const flo
     return GSX_OK;
 }
 
+size_t gsx_photometric_loss_weighted_workspace_bytes(int32_t rows, int32_t cols, int32_t with_grad) {
+    LossWeightedCarve c;
+    return loss_weighted_carve(rows, cols, with_grad != 0, c) ? c.total : 0;
+}
+
+int gsx_photometric_loss_weighted(const float *image, int64_t image_row_stride, const float *target, int64_t target_row_stride,
+                                  const float *weight, int64_t weight_row_stride, const float *exposure, int32_t rows,
+                                  int32_t cols, float lambda_dssim, float *loss_out, float *grad_image, int64_t grad_row_stride,
+                                  float *grad_exposure, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
+    if (!target) return fail(GSX_ERR_INVALID_ARGUMENT, "target is NULL");
+    if (!loss_out) return fail(GSX_ERR_INVALID_ARGUMENT, "loss_out is NULL");
+    if (rows <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "rows = %d is not positive", rows);
+    if (cols <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "cols = %d is not positive", cols);
+    const int64_t need = 3 * (int64_t)cols;
+    if (image_row_stride < need)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "image_row_stride %lld is below 3 cols = %lld", (long long)image_row_stride, (long long)need);
+    if (target_row_stride < need)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "target_row_stride %lld is below 3 cols = %lld", (long long)target_row_stride, (long long)need);
+    if (grad_image && grad_row_stride < need)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_row_stride %lld is below 3 cols = %lld", (long long)grad_row_stride, (long long)need);
+    if (weight && weight_row_stride < (int64_t)cols)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "weight_row_stride %lld is below cols = %d", (long long)weight_row_stride, cols);
+    if (grad_exposure && !exposure) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_exposure without exposure");
+    if (grad_exposure && !grad_image) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_exposure without grad_image");
+    if (!(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f))      // (a NaN fails both comparisons)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lambda_dssim %g is outside [0, 1]", (double)lambda_dssim);
+    LossWeightedCarve c;
+    if (!loss_weighted_carve(rows, cols, grad_image != nullptr, c))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "rows x cols = %d x %d is more than 2^31 - 1 tiles of %d x %d", rows, cols, kLossTile, kLossTile);
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    if (workspace_bytes < c.total)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_photometric_loss_weighted_workspace_bytes(%d, %d, %d) = %zu",
+                    workspace_bytes, rows, cols, grad_image ? 1 : 0, c.total);
+    const gsx::LossImages im{image, target, grad_image, image_row_stride, target_row_stride, grad_row_stride, rows, cols};
+    if (!weight && !exposure) {     // the kernels and the bits of gsx_photometric_loss; the carve starts with its carve
+        GSX_HIP(gsx::launch_photometric_loss(im, lambda_dssim, loss_out, (char *)workspace, c.base, (hipStream_t)stream));
+        GSX_HIP(gsx::launch_loss_weight_sum(rows, cols, loss_out, (hipStream_t)stream));
+        return GSX_OK;
+    }
+    const gsx::LossWeights wt{weight, weight_row_stride, exposure, grad_exposure};
+    GSX_HIP(gsx::launch_photometric_loss_weighted(im, wt, lambda_dssim, loss_out, (char *)workspace, c, (hipStream_t)stream));
+    return GSX_OK;
+}
+
 int gsx_adam_step(const GsxAdamGroup *groups, int32_t n_groups, int64_t n, int64_t step, float beta1, float beta2, float eps,
                   uint32_t flags, void *stream) {
     if (!groups) return fail(GSX_ERR_INVALID_ARGUMENT, "groups is NULL");

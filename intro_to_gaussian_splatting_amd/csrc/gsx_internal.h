@@ -322,6 +322,21 @@ struct LossImages {
 hipError_t launch_photometric_loss(const LossImages &im, float lambda, float *loss_out, char *ws, const plan::LossCarve &c,
                                    hipStream_t s);
 
+// ---- gsx_loss_weighted.hip
+// gsx_photometric_loss_weighted behind its argument checks, with a weight or an exposure (with neither the entry calls
+// launch_photometric_loss and launch_loss_weight_sum): loss_out = (loss, l1, ssim, W); dloss/dimage when im.grad, dloss/dE
+// when grad_exposure.  `ws` is carved by `c` (plan::loss_weighted_carve with with_grad = im.grad != NULL).
+struct LossWeights {
+    const float *weight;               // DEVICE (rows x cols), a row every weight_stride floats, or NULL: all ones
+    int64_t weight_stride;
+    const float *exposure;             // DEVICE 12 floats, row-major 3 x 4, or NULL: the identity
+    float *grad_exposure;              // DEVICE 12 floats, or NULL
+};
+hipError_t launch_photometric_loss_weighted(const LossImages &im, const LossWeights &wt, float lambda, float *loss_out, char *ws,
+                                            const plan::LossWeightedCarve &c, hipStream_t s);
+// loss_out[3] = rows * cols, what W is without a weight.
+hipError_t launch_loss_weight_sum(int32_t rows, int32_t cols, float *loss_out, hipStream_t s);
+
 // ---- gsx_adam.hip
 // gsx_adam_step behind its argument checks.  One workgroup per kAdamRows rows; the whole struct is the kernel's argument.
 constexpr int kAdamRows = 256;

@@ -292,6 +292,34 @@ inline bool loss_carve(int32_t rows, int32_t cols, bool with_grad, LossCarve &c)
     return true;
 }
 
+// ---- gsx_photometric_loss_weighted (gsx_loss_weighted.hip): the carve above first, at the same offsets (with neither a
+// weight nor an exposure the call runs the kernels above on it), then
+//   sums       kLossWeightedSums floats per tile: sum m, sum m ssim-map, sum m |x' - y|
+//   scale      kLossScaleFloats floats the reduce kernel leaves for the gradient kernel: (1 - lambda) / (3 W),
+//              -lambda / (3 W), W, unused -- the first two +0 when W == 0 (W never reaches the host)
+//   exposure   with_grad only: the twelve per-tile partial sums of dL/dE (whether or not the call has an exposure: the size
+//              is asked for before the call is made)
+constexpr int kLossWeightedSums = 3, kLossScaleFloats = 4, kLossExposureTerms = 12;
+struct LossWeightedCarve {
+    LossCarve base;
+    size_t sums, scale, exposure, total;   // byte offsets
+};
+inline bool loss_weighted_carve(int32_t rows, int32_t cols, bool with_grad, LossWeightedCarve &c) {
+    c = LossWeightedCarve{};
+    if (!loss_carve(rows, cols, with_grad, c.base)) return false;
+    size_t off = c.base.total;             // a multiple of 256; < 2^47, and what follows is < 2^31 * 64 bytes
+    auto take = [&](size_t bytes) {
+        size_t at = off;
+        off = align_up(off + bytes);
+        return at;
+    };
+    c.sums = take((size_t)c.base.tiles * kLossWeightedSums * sizeof(float));
+    c.scale = take(kLossScaleFloats * sizeof(float));
+    if (with_grad) c.exposure = take((size_t)c.base.tiles * kLossExposureTerms * sizeof(float));
+    c.total = off;
+    return true;
+}
+
 inline int64_t max_tiles_of(int32_t width, int32_t height, int32_t tile) {
     return (int64_t)((width + tile - 1) / tile) * ((height + tile - 1) / tile);
 }

@@ -23,6 +23,13 @@ tile_size, screen_statistics=statistic == "screen")`` and step 3 adds ``lambda_d
 depth_targets[idx], scene.rendered_region(idx, tile_size))`` for the views that have a target; nothing else in the order
 changes.  Without it every call is the one above.
 
+With ``masks`` (image index -> (W,H) weight) and/or ``exposure`` (an ``ExposureRefiner``) step 3 is
+``scene.photometric_loss(..., weight=masks.get(idx), exposure=exposure_refiner.exposure(idx))`` -- the weighted loss of
+gsx_photometric_loss_weighted, one call, with dL/dexposure left in the view's leaf by step 4 -- and
+``exposure_refiner.step()`` runs in step 6 after ``opt.zero_grad()``, where the pose refiner's does; with both refiners the
+pose refiner runs first.  A view that has neither a mask nor an exposure makes the call of step 3 as written there.  The depth
+term is not masked.  Without the two arguments every call is the one above.
+
 The coefficients keep ONE learning rate: a second rate for the higher bands, as published, needs an Adam group over a strided
 part of ``sh`` and is not built.
 """
@@ -34,6 +41,7 @@ from typing import Callable, Dict, Iterable, Optional, Tuple
 import torch
 
 from .density import DensityControl
+from .exposure import ExposureRefiner
 from .loss import depth_loss
 from .optim import GROUP_NAMES, GaussianAdam
 from .pose import CameraRefiner
@@ -100,6 +108,25 @@ def _check_depth_targets(scene, targets, depth_targets, lambda_depth, refine_pos
     return out, lam
 
 
+def _check_masks(scene, targets, masks):
+    """dict or None: ``Trainer``'s ``masks``, refused by name."""
+    if masks is None:
+        return None
+    out = dict(masks)
+    for idx, t in out.items():
+        if idx not in targets:
+            raise ValueError("masks names image %r, which targets does not have" % (idx,))
+        cam = scene.images[idx].gsx_camera()
+        want = (int(cam.width), int(cam.height))
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != want:
+            raise ValueError("masks[%r] must be a float32 tensor of shape %s (W, H), got %s" % (
+                idx, want, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.device != scene.gaussians.points.device:
+            raise ValueError("masks[%r] is on %s, the scene's Gaussians on %s" % (idx, t.device,
+                                                                                 scene.gaussians.points.device))
+    return out
+
+
 class Trainer:
     """Fits ``scene.gaussians`` to ``targets`` (image index -> (W,H,3) float32 tensor on the scene's GPU, the layout of
     ``render_image_hip``) with the composition of this module's docstring.
@@ -114,7 +141,12 @@ class Trainer:
     ``depth_targets``: None (every call and every bit as without it), or a dict image index -> (W,H) float32 depth map on
     the scene's GPU, view-space depth, 0 where unknown: the step renders ``render_image_depth_hip`` and adds
     ``lambda_depth * depth_loss`` over the rendered region for the views the dict names.  Not with ``refine_poses``: the
-    pose has no gradient through depth."""
+    pose has no gradient through depth.
+    ``masks``: None, or a dict image index -> (W,H) float32 weight on the scene's GPU, finite and >= 0 (``photometric_loss``'s
+    ``weight``); views it does not name are unweighted.  ``exposure``: None, or a dict of ``ExposureRefiner`` keywords
+    (``lr`` is required there; ``indices`` defaults to the views of ``targets``): a (3, 4) colour transform per view is
+    learned beside the Gaussians, ``exposure_refiner`` is public.  With both None every call and every bit is as without
+    them.  The masks weigh the photometric term alone: the depth term is NOT masked."""
 
     def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
                  tile_size: int = 16, statistic: str = "screen", density: Optional[dict] = None,
@@ -122,7 +154,8 @@ class Trainer:
                  densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000,
                  opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0,
                  refine_poses: Optional[dict] = None, depth_targets: Optional[Dict[int, torch.Tensor]] = None,
-                 lambda_depth: float = 0.0) -> None:
+                 lambda_depth: float = 0.0, masks: Optional[Dict[int, torch.Tensor]] = None,
+                 exposure: Optional[dict] = None) -> None:
         g = scene.gaussians
         if not targets:
             raise ValueError("targets is empty: nothing to fit")
@@ -138,6 +171,9 @@ class Trainer:
         if not 0.0 <= float(lambda_dssim) <= 1.0:
             raise ValueError("lambda_dssim = %r is outside [0, 1]" % (lambda_dssim,))
         self.depth_targets, self.lambda_depth = _check_depth_targets(scene, targets, depth_targets, lambda_depth, refine_poses)
+        self.masks = _check_masks(scene, targets, masks)
+        if exposure is not None and "lr" not in dict(exposure):
+            raise ValueError("exposure needs an lr: ExposureRefiner has no default rate")
         self._schedule = dict(sh_degree_every=sh_degree_every, densify_from=int(densify_from), densify_every=densify_every,
                               densify_until=int(densify_until), opacity_reset_every=opacity_reset_every)
         events_at(1, **self._schedule)                          # refuses a bad period here, not at step 1000
@@ -153,6 +189,10 @@ class Trainer:
         if refine_poses is not None:
             kw = dict(refine_poses)
             self.refiner = CameraRefiner(scene, kw.pop("indices", sorted(self.targets)), **kw)
+        self.exposure_refiner = None
+        if exposure is not None:
+            kw = dict(exposure)
+            self.exposure_refiner = ExposureRefiner(scene, kw.pop("indices", sorted(self.targets)), **kw)
         self.step_count = 0
         self._views = sorted(self.targets)
         self._order: list = []
@@ -161,6 +201,15 @@ class Trainer:
 
     def events_at(self, step: int) -> Tuple[str, ...]:
         return events_at(step, **self._schedule)
+
+    def _weighting(self, idx: int) -> dict:
+        """The ``weight`` and ``exposure`` keywords of view ``idx``'s loss call; empty when it has neither."""
+        kw = {}
+        if self.masks is not None and idx in self.masks:
+            kw["weight"] = self.masks[idx]
+        if self.exposure_refiner is not None and idx in self.exposure_refiner.exposures:
+            kw["exposure"] = self.exposure_refiner.exposure(idx)
+        return kw
 
     def _next_view(self) -> int:
         if not self._order:     # a new epoch: every view once, in a fresh order
@@ -183,7 +232,7 @@ class Trainer:
                                            screen_statistics=self.statistic == "screen", camera_gradients=True)
         terms: dict = {}
         loss = scene.photometric_loss(idx, frame, self.targets[idx], tile_size=self.tile_size,
-                                      lambda_dssim=self.lambda_dssim, terms=terms)
+                                      lambda_dssim=self.lambda_dssim, terms=terms, **self._weighting(idx))
         if depth is not None and idx in self.depth_targets:
             loss = loss + self.lambda_depth * depth_loss(depth, self.depth_targets[idx],
                                                          scene.rendered_region(idx, self.tile_size))
@@ -193,6 +242,8 @@ class Trainer:
         self.opt.zero_grad()
         if self.refiner is not None:
             self.refiner.step()
+        if self.exposure_refiner is not None:
+            self.exposure_refiner.step()
         self.step_count += 1
         for event in self.events_at(self.step_count):
             if event == "densify":
@@ -212,17 +263,32 @@ class Trainer:
 
     def evaluate(self, indices: Optional[Iterable[int]] = None) -> Dict[int, Dict[str, float]]:
         """image index -> ``l1``, ``ssim`` (the loss's own terms) and ``psnr`` (dB, peak 1) of the current frame against its
-        target over ``rendered_region``, under ``no_grad``; one host read per view."""
+        target over ``rendered_region``, under ``no_grad``; one host read per view.  A view with a mask or an exposure is
+        measured as it is trained: the loss terms are the weighted ones, and the PSNR is that of the exposure-corrected
+        frame with the mask's weights, ``mse = sum m (x' - y)^2 / (3 sum m)`` (infinite when every weight is zero)."""
         out = {}
         with torch.no_grad():
             for idx in (self._views if indices is None else indices):
                 target = self.targets[idx]
                 frame = self.scene.render_image_hip(idx, tile_size=self.tile_size)
                 terms: dict = {}
+                kw = self._weighting(idx)
                 self.scene.photometric_loss(idx, frame, target, tile_size=self.tile_size, lambda_dssim=self.lambda_dssim,
-                                            terms=terms)
+                                            terms=terms, **kw)
                 a, b = self.scene.rendered_region(idx, self.tile_size)
-                mse = ((frame[:a, :b] - target[:a, :b]) ** 2).mean()
+                if not kw:
+                    mse = ((frame[:a, :b] - target[:a, :b]) ** 2).mean()
+                else:
+                    shown = frame[:a, :b]
+                    if "exposure" in kw:
+                        E = kw["exposure"].detach()
+                        shown = shown @ E[:, :3].t() + E[:, 3]
+                    sq = ((shown - target[:a, :b]) ** 2).sum(dim=2)
+                    if "weight" in kw:
+                        m = kw["weight"][:a, :b]
+                        mse = (m * sq).sum() / (3.0 * m.sum())      # 0 / 0 = NaN with every weight zero: reported as inf
+                    else:
+                        mse = sq.mean() / 3.0
                 l1, ssim, mse = (float(v) for v in torch.stack((terms["l1"], terms["ssim"], mse)).tolist())
-                out[idx] = dict(l1=l1, ssim=ssim, psnr=math.inf if mse == 0.0 else -10.0 * math.log10(mse))
+                out[idx] = dict(l1=l1, ssim=ssim, psnr=math.inf if (mse == 0.0 or mse != mse) else -10.0 * math.log10(mse))
         return out

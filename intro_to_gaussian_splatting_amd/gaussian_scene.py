@@ -1167,14 +1167,19 @@ class GaussianScene:
         return (w, h) if layout == "wh3" else (h, w)
 
     def photometric_loss(self, image_idx: int, frame: torch.Tensor, target: torch.Tensor, tile_size: int = 16,
-                         lambda_dssim: float = 0.2, layout: str = "wh3", terms: Optional[dict] = None) -> torch.Tensor:
+                         lambda_dssim: float = 0.2, layout: str = "wh3", terms: Optional[dict] = None,
+                         weight: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``loss.photometric_loss`` of a ``ref_cpu`` frame of this camera against ``target`` over ``rendered_region``: the
-        rim no tile covers takes no part and receives an exact zero gradient."""
+        rim no tile covers takes no part and receives an exact zero gradient.  ``weight`` (a per-pixel weight of the frame's
+        two leading axes) and ``exposure`` (a (3, 4) colour transform of the frame) are passed through as they are."""
         region = self.rendered_region(image_idx, tile_size, layout)
         if region[0] <= 0 or region[1] <= 0:
             raise ValueError("a %s frame of camera %r has no rendered tile at tile_size %d (extent <= tile)" % (
                 layout, image_idx, tile_size))
-        return photometric_loss(frame, target, lambda_dssim=lambda_dssim, region=region, terms=terms)
+        if weight is None and exposure is None:
+            return photometric_loss(frame, target, lambda_dssim=lambda_dssim, region=region, terms=terms)
+        return photometric_loss(frame, target, lambda_dssim=lambda_dssim, region=region, terms=terms, weight=weight,
+                                exposure=exposure)
 
     def render_images(self, image_indices, tile_size: int = 16):
         """``render_image`` for a sequence of cameras -- the reference's own loop renders one image index after another
