@@ -825,6 +825,89 @@ GSX_API int gsx_density_apply(const GsxDensityGroup *groups /* host */, int32_t 
                               void *stream);
 
 /*
+ * Build extension: fixed-budget densification, the second standard strategy of the field (3DGS-MCMC, Kheradmand et al. 2024):
+ * two per-step calls -- the gradients of the two regularisers, and an opacity-gated noise step on the positions -- and a
+ * round of two calls that relocates dead Gaussians onto live ones drawn in proportion to opacity and grows the container
+ * towards its budget the same way.  It needs no densification statistic.  Device pointers only, the caller owns all memory,
+ * nothing is allocated.  Throughout: opacity is the LOGIT, scales are linear, every array is contiguous float32, n <= 2^30.
+ * Every float32 operation below is rounded on its own (no fused multiply-add; divide and sqrt correctly rounded); expf is the
+ * device's.  sigma(o) = 1 / (1 + exp(-o)).
+ *
+ * gsx_mcmc_regularize: the gradients of  lambda_opacity mean_i sigma(o_i) + lambda_scale mean_ic |s_ic|, added in place,
+ * one launch (the VALUE of the two terms is not computed).  With co = (float)((double)lambda_opacity / n) and
+ * cs = (float)((double)lambda_scale / (3 n)), per row i, in float32:
+ *   sg = 1 / (1 + expf(-o_i));   grad_opacity[i] = grad_opacity[i] + co * (sg * (1 - sg));
+ *   grad_scales[i][c] = s_ic > 0 ? grad_scales[i][c] + cs : (s_ic < 0 ? grad_scales[i][c] - cs : grad_scales[i][c])
+ * (a scale of +-0 or NaN leaves its element's bits).  A lambda of exactly 0 leaves its gradient array untouched, and its
+ * two pointers are not looked at.  Does not synchronise.  n == 0 is GSX_OK.  Refused (GSX_ERR_INVALID_ARGUMENT,
+ * gsx_last_error names the argument, before any HIP call): n < 0 or n > 2^30; a lambda that is negative or not finite; when
+ * n > 0 and the lambda is not 0: opacity or grad_opacity, scales or grad_scales NULL.
+ *
+ * gsx_mcmc_perturb: points[i] += delta_i in place, one launch; 17 floats read and 3 written per row.  noise is (n,3), standard
+ * normal draws of the caller.  Per row, in float32, in this order:
+ *   sg = 1 / (1 + expf(-o));   gate = 1 / (1 + expf(-(gate_k * ((1 - sg) - gate_x0))));
+ *   nrm = sqrtf(((qw qw + qx qx) + qy qy) + qz qz);   (w, x, y, z) = q / nrm  (four divides; NO fallback for nrm == 0);
+ *   R as in gsx_density_apply;
+ *   u_c = (R[0][c] e0 + R[1][c] e1) + R[2][c] e2;         (R^T e)
+ *   v_c = (s_c s_c) u_c;
+ *   d_k = (rate gate) ((R[k][0] v0 + R[k][1] v1) + R[k][2] v2);     (rate * gate is one product, formed first)
+ *   if d_0, d_1 and d_2 are all finite: points[i][k] = points[i][k] + d_k; otherwise the row keeps its bits (a zero
+ *   quaternion, a NaN in the noise: training does not die of one bad row).
+ * That is delta = rate gate Sigma e with Sigma = R diag(s^2) R^T.  The published gate is gate_k = 100, gate_x0 = 0.995, the
+ * published rate 5e5 x the position learning rate.  Does not synchronise.  n == 0 is GSX_OK.  Refused: n < 0 or n > 2^30;
+ * rate, gate_k or gate_x0 not finite, rate or gate_k negative; when n > 0, any of the five pointers NULL.
+ *
+ * gsx_mcmc_plan: who is dead, who is drawn, how often -- exact integer arithmetic, a pure function of its inputs.
+ *   row i is DEAD when opacity[i] <= dead_logit (float32; a NaN fails it);
+ *   weights[i] = dead or opacity[i] not finite ? 0 : max(1, rint(2^22 sigma(o_i)))      (sigma in double);
+ *   P = the exclusive prefix sum of the weights in uint64, total = their sum (<= 2^52);
+ *   output row j (0 <= j < n_out, n_out >= n) is DRAWN when j >= n (a new row) or row j is dead:
+ *     t = min(total - 1, (uint64) floor(uniforms[j] * (double) total))        (one IEEE double multiplication)
+ *     source[j] = the unique s with P[s] <= t < P[s] + weights[s];   count[s] += 1   (an integer atomic)
+ *   every other row: source[j] = j.  count[s] is 0 for a row nobody drew.
+ *   total == 0: every source[j] = min(j, n - 1), every count 0.
+ * uniforms is DEVICE (n_out) float64 in [0, 1) (a value outside, or a NaN, is clamped into the range of t); row j reads its
+ * own slot only.  weights (n) uint32, source (n_out) int32, count (n) uint32 are written whole.  counts_host (HOST, 3 x
+ * int64) receives n_dead, n_live (rows of non-zero weight), n_new = n_out - n; the call synchronises `stream` once, after
+ * its last launch.  workspace: gsx_mcmc_workspace_bytes(n) bytes, 256-byte aligned.  n == 0 is GSX_OK with three zeros
+ * (n_out must be 0 then).  Refused: n < 0 or n > 2^30; n_out < n or n_out > 2^30; dead_logit NaN; opacity, uniforms, weights,
+ * source, count (n > 0), counts_host or workspace NULL; a workspace that is not 256-byte aligned; fewer bytes than asked for:
+ * GSX_ERR_WORKSPACE_TOO_SMALL.
+ *
+ * gsx_mcmc_apply: every group g is rewritten from src (n, width) into dst (n_out, width), all groups in one launch.  For
+ * output row j: s = source[j], c = count[s], N = min(c + 1, GSX_MCMC_N_MAX).
+ *   N == 1 (then s == j): every group copies the row's bits.
+ *   N > 1 (the source row itself and each of its copies alike): GSX_MCMC_COPY: the bits of row s.  GSX_MCMC_ZERO_MOVED (Adam's
+ *   moments): +0.  GSX_MCMC_OPACITY (width 1) and GSX_MCMC_SCALES (width 3): the published relocation, in double:
+ *     a = min(sigma(o_s), 1 - 2^-24);   x = -expm1(log1p(-a) / N);                          (= 1 - (1 - a)^(1/N))
+ *     D = sum_{i=1..N} sum_{k=0..i-1} ((C(i-1,k) (-1)^k) x^(k+1)) / sqrt(k+1), ONE accumulator, i outer, k inner, each term
+ *         added as written; C(i-1,0) = 1, C(i-1,k+1) = (C(i-1,k) (i-1-k)) / (k+1) (exact), x^(k+1) by running multiplication;
+ *     opacity: the logit log(p / (1 - p)) of p = min(max(x, (double) min_opacity), 1 - 2^-24), rounded to float32;
+ *     scales:  (float)((a / D) * (double) s_sc).
+ *   The clamp of a keeps the alternating sum away from catastrophic cancellation: its terms are bounded by x (1 + x)^(N-1).
+ * A source[j] outside 0 .. n-1 is read as min(j, n - 1) with N = 1: a broken plan stays inside the arrays.  Does not
+ * synchronise.  n == 0 or n_out == 0 is GSX_OK with nothing launched.  Refused, before any HIP call: groups, source or count
+ * NULL; n_groups outside 1 .. GSX_DENSITY_MAX_GROUPS; n < 0 or n > 2^30; n_out < n or n_out > 2^30; min_opacity outside
+ * (0, 1); in a group: width outside 1 .. 2^20, an unknown role, src or dst NULL, dst == src; more than one OPACITY or SCALES
+ * group; OPACITY of a width other than 1, SCALES other than 3; a SCALES group without an OPACITY group.
+ */
+#define GSX_MCMC_N_MAX 51    /* the published n_max: the largest N the relocation is evaluated for */
+enum { GSX_MCMC_COPY = 0, GSX_MCMC_ZERO_MOVED = 1, GSX_MCMC_OPACITY = 2, GSX_MCMC_SCALES = 3 };
+GSX_API int gsx_mcmc_regularize(const float *opacity /* (n) */, const float *scales /* (n,3) */, int64_t n, float lambda_opacity,
+                                float lambda_scale, float *grad_opacity /* (n) */, float *grad_scales /* (n,3) */, void *stream);
+GSX_API int gsx_mcmc_perturb(float *points /* (n,3) */, const float *scales /* (n,3) */, const float *quaternions /* (n,4) */,
+                             const float *opacity /* (n) */, const float *noise /* (n,3) */, int64_t n, float rate, float gate_k,
+                             float gate_x0, void *stream);
+GSX_API size_t gsx_mcmc_workspace_bytes(int64_t n);   /* 0 on invalid arguments (n < 0 or n > 2^30) */
+GSX_API int gsx_mcmc_plan(const float *opacity /* (n) */, int64_t n, float dead_logit, int64_t n_out,
+                          const double *uniforms /* (n_out) */, uint32_t *weights /* (n) */, int32_t *source /* (n_out) */,
+                          uint32_t *count /* (n) */, void *workspace, size_t workspace_bytes, int64_t *counts_host /* 3 */,
+                          void *stream);
+GSX_API int gsx_mcmc_apply(const GsxDensityGroup *groups /* host; role: GSX_MCMC_COPY .. GSX_MCMC_SCALES */, int32_t n_groups,
+                           int64_t n, int64_t n_out, const int32_t *source /* (n_out) */, const uint32_t *count /* (n) */,
+                           float min_opacity, void *stream);
+
+/*
  * Build extension: scale initialisation.  The reference's Gaussians.initialize_scale (splat/gaussians.py:35-52: the mean of
  * the three smallest neighbour distances; switched off there, its n x n x 3 difference tensor does not fit) as one call that
  * is exact: for every one of n points the distances to its three nearest OTHER points.  Device pointers only, the caller owns

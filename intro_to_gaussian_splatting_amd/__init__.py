@@ -7,6 +7,7 @@ from .image import GaussianImage
 from .loss import depth_loss, photometric_loss
 from .optim import GaussianAdam, expon_lr
 from .density import DensityControl
+from .mcmc import MCMCControl
 from .knn import nearest3
 from .fit import Trainer, events_at
 from .pose import CameraRefiner
@@ -14,5 +15,6 @@ from .exposure import ExposureRefiner
 from .schema import PreprocessedScene
 
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
-           "NativeExtension", "photometric_loss", "depth_loss", "GaussianAdam", "expon_lr", "DensityControl", "nearest3",
+           "NativeExtension", "photometric_loss", "depth_loss", "GaussianAdam", "expon_lr", "DensityControl", "MCMCControl",
+           "nearest3",
            "Trainer", "events_at", "CameraRefiner", "ExposureRefiner"]

@@ -49,6 +49,11 @@ GSX_DENSITY_ZERO_NEW = 1
 GSX_DENSITY_POINTS = 2
 GSX_DENSITY_SCALES = 3
 GSX_DENSITY_QUATS = 4
+GSX_MCMC_N_MAX = 51
+GSX_MCMC_COPY = 0
+GSX_MCMC_ZERO_MOVED = 1
+GSX_MCMC_OPACITY = 2
+GSX_MCMC_SCALES = 3
 GSX_KNN_RULE_REFERENCE = 0
 GSX_KNN_RULE_PUBLISHED = 1
 
@@ -173,6 +178,13 @@ SIGNATURES = {
                                                c_size_t, POINTER(c_int64), c_void_p]),
     "gsx_density_apply": (ctypes.c_int, [POINTER(GsxDensityGroup), c_int32, c_int64, c_int64, _FP, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    "gsx_mcmc_regularize": (ctypes.c_int, [_FP, _FP, c_int64, c_float, c_float, _FP, _FP, c_void_p]),
+    "gsx_mcmc_perturb": (ctypes.c_int, [_FP] * 5 + [c_int64, c_float, c_float, c_float, c_void_p]),
+    "gsx_mcmc_workspace_bytes": (c_size_t, [c_int64]),
+    "gsx_mcmc_plan": (ctypes.c_int, [_FP, c_int64, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     POINTER(c_int64), c_void_p]),
+    "gsx_mcmc_apply": (ctypes.c_int, [POINTER(GsxDensityGroup), c_int32, c_int64, c_int64, c_void_p, c_void_p, c_float,
+                                      c_void_p]),
     "gsx_knn3_workspace_bytes": (c_size_t, [c_int64]),
     "gsx_knn3": (ctypes.c_int, [_FP, c_int64, c_void_p, c_int32, _FP, _FP, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
 }

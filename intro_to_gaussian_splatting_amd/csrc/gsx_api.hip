@@ -1123,6 +1123,149 @@ int gsx_density_apply(const GsxDensityGroup *groups, int32_t n_groups, int64_t n
     return GSX_OK;
 }
 
+int gsx_mcmc_regularize(const float *opacity, const float *scales, int64_t n, float lambda_opacity, float lambda_scale,
+                        float *grad_opacity, float *grad_scales, void *stream) {
+    if (n < 0 || n > kMcmcMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (!(lambda_opacity >= 0.0f && lambda_opacity <= FLT_MAX))     // (a NaN fails both comparisons)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lambda_opacity %g is negative or not finite", (double)lambda_opacity);
+    if (!(lambda_scale >= 0.0f && lambda_scale <= FLT_MAX))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lambda_scale %g is negative or not finite", (double)lambda_scale);
+    if (n > 0 && lambda_opacity != 0.0f) {
+        if (!opacity) return fail(GSX_ERR_INVALID_ARGUMENT, "opacity is NULL");
+        if (!grad_opacity) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_opacity is NULL");
+    }
+    if (n > 0 && lambda_scale != 0.0f) {
+        if (!scales) return fail(GSX_ERR_INVALID_ARGUMENT, "scales is NULL");
+        if (!grad_scales) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_scales is NULL");
+    }
+    if (n == 0) return GSX_OK;
+    gsx::McmcRegularizeArgs a;
+    memset(&a, 0, sizeof a);
+    uintptr_t bits = 0;
+    if (lambda_opacity != 0.0f) {
+        a.opacity = opacity;
+        a.grad_opacity = grad_opacity;
+        bits |= reinterpret_cast<uintptr_t>(opacity) | reinterpret_cast<uintptr_t>(grad_opacity);
+    }
+    if (lambda_scale != 0.0f) {
+        a.scales = scales;
+        a.grad_scales = grad_scales;
+        bits |= reinterpret_cast<uintptr_t>(scales) | reinterpret_cast<uintptr_t>(grad_scales);
+    }
+    a.n = n;
+    // the host scalars: once per call, in double, rounded to float (include/gsx.h)
+    a.coef_opacity = (float)((double)lambda_opacity / (double)n);
+    a.coef_scale = (float)((double)lambda_scale / (3.0 * (double)n));
+    a.vec = (bits & 15u) == 0;
+    GSX_HIP(gsx::launch_mcmc_regularize(a, (hipStream_t)stream));
+    return GSX_OK;
+}
+
+int gsx_mcmc_perturb(float *points, const float *scales, const float *quaternions, const float *opacity, const float *noise,
+                     int64_t n, float rate, float gate_k, float gate_x0, void *stream) {
+    if (n < 0 || n > kMcmcMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (!(rate >= 0.0f && rate <= FLT_MAX)) return fail(GSX_ERR_INVALID_ARGUMENT, "rate %g is negative or not finite", (double)rate);
+    if (!(gate_k >= 0.0f && gate_k <= FLT_MAX)) return fail(GSX_ERR_INVALID_ARGUMENT, "gate_k %g is negative or not finite", (double)gate_k);
+    if (!(gate_x0 >= -FLT_MAX && gate_x0 <= FLT_MAX)) return fail(GSX_ERR_INVALID_ARGUMENT, "gate_x0 %g is not finite", (double)gate_x0);
+    if (n == 0) return GSX_OK;
+    if (!points) return fail(GSX_ERR_INVALID_ARGUMENT, "points is NULL");
+    if (!scales) return fail(GSX_ERR_INVALID_ARGUMENT, "scales is NULL");
+    if (!quaternions) return fail(GSX_ERR_INVALID_ARGUMENT, "quaternions is NULL");
+    if (!opacity) return fail(GSX_ERR_INVALID_ARGUMENT, "opacity is NULL");
+    if (!noise) return fail(GSX_ERR_INVALID_ARGUMENT, "noise is NULL");
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(scales) |
+                           reinterpret_cast<uintptr_t>(quaternions) | reinterpret_cast<uintptr_t>(opacity) |
+                           reinterpret_cast<uintptr_t>(noise);
+    const gsx::McmcPerturbArgs a{points, scales, quaternions, opacity, noise, n, rate, gate_k, gate_x0, (bits & 15u) == 0};
+    GSX_HIP(gsx::launch_mcmc_perturb(a, (hipStream_t)stream));
+    return GSX_OK;
+}
+
+size_t gsx_mcmc_workspace_bytes(int64_t n) {
+    McmcCarve c;
+    return mcmc_carve(n, c) ? c.total : 0;
+}
+
+int gsx_mcmc_plan(const float *opacity, int64_t n, float dead_logit, int64_t n_out, const double *uniforms, uint32_t *weights,
+                  int32_t *source, uint32_t *count, void *workspace, size_t workspace_bytes, int64_t *counts_host, void *stream) {
+    McmcCarve c;
+    if (!mcmc_carve(n, c)) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (n_out < n || n_out > kMcmcMaxRows || (n == 0 && n_out != 0))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n_out = %lld is outside n = %lld .. 2^30", (long long)n_out, (long long)n);
+    if (dead_logit != dead_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "dead_logit is NaN");
+    if (!counts_host) return fail(GSX_ERR_INVALID_ARGUMENT, "counts_host is NULL");
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    if (workspace_bytes < c.total)
+        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_mcmc_workspace_bytes(%lld) = %zu", workspace_bytes,
+                    (long long)n, c.total);
+    if (n > 0) {
+        if (!opacity) return fail(GSX_ERR_INVALID_ARGUMENT, "opacity is NULL");
+        if (!uniforms) return fail(GSX_ERR_INVALID_ARGUMENT, "uniforms is NULL");
+        if (!weights) return fail(GSX_ERR_INVALID_ARGUMENT, "weights is NULL");
+        if (!source) return fail(GSX_ERR_INVALID_ARGUMENT, "source is NULL");
+        if (!count) return fail(GSX_ERR_INVALID_ARGUMENT, "count is NULL");
+    }
+    for (int i = 0; i < 3; ++i) counts_host[i] = 0;
+    if (n == 0) return GSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const gsx::McmcPlanArgs a{opacity, uniforms, weights, count, source, n, n_out, dead_logit};
+    GSX_HIP(gsx::launch_mcmc_plan(a, (char *)workspace, c, s));
+    GSX_HIP(hipMemcpyAsync(counts_host, workspace, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    counts_host[2] = n_out - n;
+    return GSX_OK;
+}
+
+int gsx_mcmc_apply(const GsxDensityGroup *groups, int32_t n_groups, int64_t n, int64_t n_out, const int32_t *source,
+                   const uint32_t *count, float min_opacity, void *stream) {
+    if (!groups) return fail(GSX_ERR_INVALID_ARGUMENT, "groups is NULL");
+    if (n_groups < 1 || n_groups > GSX_DENSITY_MAX_GROUPS)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n_groups = %d is outside 1 .. %d", n_groups, GSX_DENSITY_MAX_GROUPS);
+    if (n < 0 || n > kMcmcMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
+    if (n_out < n || n_out > kMcmcMaxRows || (n == 0 && n_out != 0))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n_out = %lld is outside n = %lld .. 2^30", (long long)n_out, (long long)n);
+    if (!(min_opacity > 0.0f && min_opacity < 1.0f))        // (a NaN fails both comparisons)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "min_opacity %g is outside (0, 1)", (double)min_opacity);
+    gsx::McmcApplyArgs a;
+    memset(&a, 0, sizeof a);
+    int at[4] = {-1, -1, -1, -1};           // by role: the group that has it
+    for (int i = 0; i < n_groups; ++i) {
+        const GsxDensityGroup &g = groups[i];
+        if (g.width < 1 || g.width > gsx::kMcmcMaxWidth)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].width = %d is outside 1 .. %d", i, g.width, gsx::kMcmcMaxWidth);
+        if (g.role < GSX_MCMC_COPY || g.role > GSX_MCMC_SCALES)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].role = %d is unknown", i, g.role);
+        if (g.role >= GSX_MCMC_OPACITY) {
+            static const char *const names[] = {"", "", "OPACITY", "SCALES"};
+            if (at[g.role] >= 0)
+                return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].role: a second %s group (groups[%d] is one)", i, names[g.role], at[g.role]);
+            const int want = g.role == GSX_MCMC_SCALES ? 3 : 1;
+            if (g.width != want)
+                return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].width = %d: a %s group has width %d", i, g.width, names[g.role], want);
+            at[g.role] = i;
+        }
+        if (n > 0 && !g.src) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].src is NULL", i);
+        if (n_out > 0 && !g.dst) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].dst is NULL", i);
+        if (g.dst && g.dst == g.src) return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].dst equals src: the rewrite is out of place", i);
+        a.group[i] = gsx::DensityGroupArgs{g.src, g.dst, g.width, g.role};
+    }
+    if (at[GSX_MCMC_SCALES] >= 0 && at[GSX_MCMC_OPACITY] < 0)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "groups[%d].role: a SCALES group needs an OPACITY group in the same call", at[GSX_MCMC_SCALES]);
+    if (n == 0 || n_out == 0) return GSX_OK;
+    if (!source) return fail(GSX_ERR_INVALID_ARGUMENT, "source is NULL");
+    if (!count) return fail(GSX_ERR_INVALID_ARGUMENT, "count is NULL");
+    a.source = source;
+    a.count = count;
+    a.opacity = at[GSX_MCMC_OPACITY] >= 0 ? groups[at[GSX_MCMC_OPACITY]].src : nullptr;
+    a.n = n;
+    a.n_out = n_out;
+    a.n_groups = n_groups;
+    a.min_opacity = min_opacity;
+    GSX_HIP(gsx::launch_mcmc_apply(a, (hipStream_t)stream));
+    return GSX_OK;
+}
+
 size_t gsx_knn3_workspace_bytes(int64_t n) {
     KnnCarve c;
     return knn_carve(n, c) ? c.total : 0;

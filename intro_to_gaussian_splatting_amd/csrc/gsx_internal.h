@@ -418,6 +418,46 @@ hipError_t launch_density_plan_screen(const float *grad_sum, const uint32_t *see
                                       const float *radius_max, float prune_radius, int64_t n, const GsxDensityRules &rules,
                                       char *ws, const DensityCarve &c, hipStream_t s);
 
+// ---- gsx_mcmc.hip
+// gsx_mcmc_regularize / _perturb / _plan / _apply behind their argument checks.  The plan's workspace: plan::McmcCarve.
+constexpr int kMcmcRows = 256;                  // output rows of one workgroup of the apply kernel (kDensityRows, kAdamRows)
+constexpr int kMcmcMaxWidth = 1 << 20;          // a block's run of a group, 256 * width floats, is indexed with 32 bits
+struct McmcRegularizeArgs {
+    const float *opacity, *scales;
+    float *grad_opacity, *grad_scales;          // null: that side is off (its lambda is 0)
+    int64_t n;
+    float coef_opacity, coef_scale;             // lambda_opacity / n, lambda_scale / (3 n): in double, rounded to float
+    int32_t vec;                                // every base in use is 16-byte aligned
+};
+struct McmcPerturbArgs {
+    float *points;
+    const float *scales, *quats, *opacity, *noise;
+    int64_t n;
+    float rate, gate_k, gate_x0;
+    int32_t vec;
+};
+struct McmcPlanArgs {
+    const float *opacity;
+    const double *uniforms;
+    uint32_t *weights, *count;
+    int32_t *source;
+    int64_t n, n_out;
+    float dead_logit;
+};
+struct McmcApplyArgs {
+    DensityGroupArgs group[24];                 // role: GSX_MCMC_COPY ..
+    const int32_t *source;
+    const uint32_t *count;
+    const float *opacity;                       // the OPACITY group's src, or null without one
+    int64_t n, n_out;
+    int32_t n_groups;
+    float min_opacity;
+};
+hipError_t launch_mcmc_regularize(const McmcRegularizeArgs &args, hipStream_t s);
+hipError_t launch_mcmc_perturb(const McmcPerturbArgs &args, hipStream_t s);
+hipError_t launch_mcmc_plan(const McmcPlanArgs &args, char *ws, const plan::McmcCarve &c, hipStream_t s);
+hipError_t launch_mcmc_apply(const McmcApplyArgs &args, hipStream_t s);
+
 // ---- gsx_knn.hip
 // gsx_knn3 behind its argument checks.  The workspace of n rows (KnnCarve):
 //   header  kKnnHeader bytes: uint64 (query, candidate) pairs evaluated (zeroed and read only when the caller asks)

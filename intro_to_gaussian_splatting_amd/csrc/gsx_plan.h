@@ -320,6 +320,32 @@ inline bool loss_weighted_carve(int32_t rows, int32_t cols, bool with_grad, Loss
     return true;
 }
 
+// ---- gsx_mcmc_plan (gsx_mcmc.hip): the n rows are cut into scan blocks of kMcmcScanRows rows, one workgroup each.
+//   header   kMcmcHeader bytes: int64 n_dead, n_live; uint64 total (the sum of the weights)
+//   prefix   uint32 per row, padded to whole scan blocks: the exclusive sum of the weights of the rows before it IN ITS
+//            BLOCK (at most 1023 * 2^22 < 2^32)
+//   bsum     uint64 per scan block (+1): the weights of the blocks before it; bsum[blocks] = total
+//   btally   two uint32 per scan block: its dead rows, then its rows of non-zero weight
+constexpr int kMcmcScanRows = 1024;
+constexpr int64_t kMcmcMaxRows = (int64_t)1 << 30;
+constexpr size_t kMcmcHeader = 256;
+struct McmcCarve {
+    size_t prefix, bsum, btally, total;    // byte offsets
+    uint32_t scan_blocks;
+};
+// false: n < 0 or n > 2^30.  At most 2^20 blocks: nothing below comes near 64 bits.
+inline bool mcmc_carve(int64_t n, McmcCarve &c) {
+    c = McmcCarve{};
+    if (n < 0 || n > kMcmcMaxRows) return false;
+    const size_t nsb = (size_t)((n + kMcmcScanRows - 1) / kMcmcScanRows);
+    c.scan_blocks = (uint32_t)nsb;
+    c.prefix = kMcmcHeader;
+    c.bsum = c.prefix + align_up(nsb * kMcmcScanRows * sizeof(uint32_t));
+    c.btally = c.bsum + align_up((nsb + 1) * sizeof(uint64_t));
+    c.total = c.btally + align_up(2 * nsb * sizeof(uint32_t));
+    return true;
+}
+
 inline int64_t max_tiles_of(int32_t width, int32_t height, int32_t tile) {
     return (int64_t)((width + tile - 1) / tile) * ((height + tile - 1) / tile);
 }

@@ -30,6 +30,13 @@ gsx_photometric_loss_weighted, one call, with dL/dexposure left in the view's le
 pose refiner runs first.  A view that has neither a mask nor an exposure makes the call of step 3 as written there.  The depth
 term is not masked.  Without the two arguments every call is the one above.
 
+With ``strategy="mcmc"`` (fixed-budget densification, ``MCMCControl``) the order is the same and four calls differ: the frame
+of step 2 is rendered with ``geometry_gradients=True`` and NO ``screen_statistics``; step 5 is ``density.regularize()``
+instead of ``accumulate()``; ``density.perturb(generator)`` runs in step 6 after ``opt.zero_grad()`` and before the refiners;
+the "densify" event of step 7 runs ``density.relocate(generator)``, and "opacity_reset" is never due.  The loss that is
+returned stays the photometric one: the regularisers enter through their gradients only.  With ``strategy="adaptive"``, the
+default, every call is the one above.
+
 The coefficients keep ONE learning rate: a second rate for the higher bands, as published, needs an Adam group over a strided
 part of ``sh`` and is not built.
 """
@@ -41,6 +48,7 @@ from typing import Callable, Dict, Iterable, Optional, Tuple
 import torch
 
 from .density import DensityControl
+from .mcmc import MCMCControl
 from .exposure import ExposureRefiner
 from .loss import depth_loss
 from .optim import GROUP_NAMES, GaussianAdam
@@ -50,6 +58,14 @@ EVENT_NAMES = ("densify", "opacity_reset", "sh_oneup")
 # the published rates (Kerbl et al. 2023); the position rate is per unit of scene extent there: scale it for the scene
 DEFAULT_LR = {"points": 1.6e-4, "scales": 5e-3, "quaternions": 1e-3, "opacity": 5e-2, "colors": 2.5e-3, "sh": 2.5e-3}
 DEFAULT_OPACITY_RESET_LOGIT = math.log(0.01 / 0.99)         # the published reset: opacity at most 0.01
+STRATEGIES = ("adaptive", "mcmc")
+
+
+class _Default(int):
+    """The value of an argument nobody passed: an int like any other, told apart by identity."""
+
+
+_OPACITY_RESET_EVERY = _Default(3000)
 
 
 def _period(name: str, value) -> int:
@@ -146,17 +162,40 @@ class Trainer:
     ``weight``); views it does not name are unweighted.  ``exposure``: None, or a dict of ``ExposureRefiner`` keywords
     (``lr`` is required there; ``indices`` defaults to the views of ``targets``): a (3, 4) colour transform per view is
     learned beside the Gaussians, ``exposure_refiner`` is public.  With both None every call and every bit is as without
-    them.  The masks weigh the photometric term alone: the depth term is NOT masked."""
+    them.  The masks weigh the photometric term alone: the depth term is NOT masked.
+    ``strategy``: ``"adaptive"`` (default: ``DensityControl``, every call and every bit as without the argument) or
+    ``"mcmc"``: fixed-budget densification, ``density`` is then an ``MCMCControl`` built with the keywords of ``mcmc`` (a
+    dict; ``cap_max`` is required there).  The "densify" event runs ``relocate()`` and there is no opacity reset: an explicit
+    ``opacity_reset_every``, ``density=`` or ``statistic=`` is refused together with ``"mcmc"``, as is ``mcmc=`` without it."""
 
     def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
-                 tile_size: int = 16, statistic: str = "screen", density: Optional[dict] = None,
+                 tile_size: int = 16, statistic: Optional[str] = None, density: Optional[dict] = None,
                  sh_degree_every: Optional[int] = 1000, densify_from: int = 500, densify_every: Optional[int] = 100,
-                 densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000,
+                 densify_until: int = 15000, opacity_reset_every: Optional[int] = _OPACITY_RESET_EVERY,
                  opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0,
                  refine_poses: Optional[dict] = None, depth_targets: Optional[Dict[int, torch.Tensor]] = None,
                  lambda_depth: float = 0.0, masks: Optional[Dict[int, torch.Tensor]] = None,
-                 exposure: Optional[dict] = None) -> None:
+                 exposure: Optional[dict] = None, strategy: str = "adaptive", mcmc: Optional[dict] = None) -> None:
         g = scene.gaussians
+        if strategy not in STRATEGIES:
+            raise ValueError("strategy = %r is neither 'adaptive' nor 'mcmc'" % (strategy,))
+        if strategy == "mcmc":
+            if density is not None:
+                raise ValueError("density= goes to DensityControl, the adaptive strategy: with strategy='mcmc' pass mcmc=")
+            if statistic is not None:
+                raise ValueError("statistic= is the adaptive strategy's: strategy='mcmc' needs no densification statistic")
+            if opacity_reset_every is not _OPACITY_RESET_EVERY:
+                raise ValueError("opacity_reset_every cannot be combined with strategy='mcmc': it has no opacity reset")
+            if mcmc is None or "cap_max" not in dict(mcmc):
+                raise ValueError("strategy='mcmc' needs mcmc=dict(cap_max=...): the budget has no default")
+            opacity_reset_every = None
+        else:
+            if mcmc is not None:
+                raise ValueError("mcmc= goes to MCMCControl: pass strategy='mcmc' with it")
+            if statistic is None:
+                statistic = "screen"
+            if opacity_reset_every is _OPACITY_RESET_EVERY:
+                opacity_reset_every = int(opacity_reset_every)
         if not targets:
             raise ValueError("targets is empty: nothing to fit")
         for idx in targets:
@@ -184,7 +223,11 @@ class Trainer:
         self.lambda_dssim, self.tile_size, self.statistic = float(lambda_dssim), int(tile_size), statistic
         self.opacity_reset_logit = float(opacity_reset_logit)
         self.opt = GaussianAdam(g, lr=lr)
-        self.density = DensityControl(g, optimizer=self.opt, scene=scene, statistic=statistic, **(density or {}))
+        self.strategy = strategy
+        if strategy == "mcmc":
+            self.density = MCMCControl(g, optimizer=self.opt, scene=scene, **dict(mcmc))
+        else:
+            self.density = DensityControl(g, optimizer=self.opt, scene=scene, statistic=statistic, **(density or {}))
         self.refiner = None
         if refine_poses is not None:
             kw = dict(refine_poses)
@@ -237,16 +280,23 @@ class Trainer:
             loss = loss + self.lambda_depth * depth_loss(depth, self.depth_targets[idx],
                                                          scene.rendered_region(idx, self.tile_size))
         loss.backward()
-        self.density.accumulate()
+        if self.strategy == "mcmc":
+            self.density.regularize()
+        else:
+            self.density.accumulate()
         self.opt.step()
         self.opt.zero_grad()
+        if self.strategy == "mcmc":
+            self.density.perturb(generator=self._split_generator)
         if self.refiner is not None:
             self.refiner.step()
         if self.exposure_refiner is not None:
             self.exposure_refiner.step()
         self.step_count += 1
         for event in self.events_at(self.step_count):
-            if event == "densify":
+            if event == "densify" and self.strategy == "mcmc":
+                self.density.relocate(generator=self._split_generator)
+            elif event == "densify":
                 self.density.densify_and_prune(generator=self._split_generator)
             elif event == "opacity_reset":
                 self.density.reset_opacity(self.opacity_reset_logit)

@@ -1,0 +1,416 @@
+"""Fixed-budget densification on the GPU: gsx_mcmc_plan / gsx_mcmc_apply / gsx_mcmc_regularize / gsx_mcmc_perturb against
+tests/mcmc_restatement.py, ``MCMCControl`` and ``Trainer(strategy="mcmc")`` against the same composition written out here.
+
+The plan is compared element for element with the integer restatement evaluated on the kernel's OWN weights (which are held
+to +-1 of the float64 restatement: the device's double exp); the apply bit for bit, except the relocated opacity logits and
+scales: within 1 float32 ulp of the float64 restatement rounded to float32 (a 1e-9 relative difference before rounding can
+move the rounded value by one).  The two per-step kernels are held to 12 x the recorded float32 reference errors of
+tests/test_mcmc_host.py, in the units fixed there; the largest measured multiple is printed."""
+import ctypes
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import mcmc_restatement as mr
+from test_mcmc_host import E_REF_PERTURB, E_REF_REGULARIZE, MIN_OPACITY, plan_case
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+PLAN_SIZES = (1, 2, 1023, 1024, 1025, 3000)
+MULTIPLE = 12.0
+
+
+def _lib():
+    from intro_to_gaussian_splatting_amd import _ffi
+
+    return _ffi, _ffi.load()
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32)
+
+
+def _same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def _based(src, lead):
+    """A contiguous device copy of ``src`` whose base is 16-byte aligned (``lead`` 0) or only 4-byte aligned (1 .. 3)."""
+    src = _dev(src)
+    whole = torch.empty(8 + src.numel(), dtype=src.dtype, device=DEV)
+    off = (-(whole.data_ptr() // 4)) % 4 + lead
+    view = whole[off:off + src.numel()].view(src.shape)
+    view.copy_(src)
+    assert (view.data_ptr() % 16 == 0) == (lead == 0)
+    return whole, view
+
+
+def _n_outs(n):
+    return sorted({n, n + 1, int(math.floor(1.05 * n))})
+
+
+def _plan(o, dead_logit, n_out, u):
+    """(weights uint32, source int32, count uint32, counts) of gsx_mcmc_plan."""
+    _ffi, lib = _lib()
+    n = len(o)
+    need = lib.gsx_mcmc_workspace_bytes(n)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    od, ud = _dev(o), _dev(u)
+    w = torch.full((n,), -7, dtype=torch.int32, device=DEV)
+    count = torch.full((n,), -7, dtype=torch.int32, device=DEV)
+    source = torch.full((n_out,), -7, dtype=torch.int32, device=DEV)
+    host = (ctypes.c_int64 * 3)(-1, -1, -1)
+    rc = lib.gsx_mcmc_plan(od.data_ptr(), n, float(dead_logit), n_out, ud.data_ptr(), w.data_ptr(), source.data_ptr(),
+                           count.data_ptr(), ws.data_ptr(), need, host, _stream())
+    _ffi.check(rc)
+    return w.cpu().numpy().view(np.uint32), source.cpu().numpy(), count.cpu().numpy().view(np.uint32), tuple(int(v) for v in host)
+
+
+def _check_plan(o, dead_logit, n_out, u):
+    w, source, count, counts = _plan(o, dead_logit, n_out, u)
+    want_w = mr.weights_of(o, dead_logit)
+    assert np.abs(w.astype(np.int64) - want_w.astype(np.int64)).max() <= 1                      # every row
+    assert np.array_equal(w == 0, want_w == 0)
+    want_source, want_count, want_counts, _ = mr.plan(w, o, dead_logit, n_out, u)
+    assert np.array_equal(source, want_source) and np.array_equal(count, want_count) and counts == want_counts
+    return w, source, count, counts
+
+
+# ---------------------------------------------------------------------------------------------------- plan
+@pytest.mark.parametrize("n", PLAN_SIZES)
+def test_plan_equals_the_integer_restatement(n):
+    for n_out in _n_outs(n):
+        o, dead_logit, u = plan_case(n, n_out)
+        w, source, count, counts = _check_plan(o, dead_logit, n_out, u)
+        again = _plan(o, dead_logit, n_out, u)                       # the same inputs twice: the same bits
+        assert np.array_equal(again[0], w) and np.array_equal(again[1], source) and np.array_equal(again[2], count)
+        assert again[3] == counts
+        if n >= 16:
+            assert w[o == np.float32(20.0)].min() == 2 ** 22 and counts[0] > 0          # sigma saturates: the largest weight
+
+
+def test_plan_one_live_row_among_two_thousand_dead_and_nobody_alive():
+    n = 2001
+    o = np.full(n, -9.0, np.float32)
+    o[1234] = 0.5
+    u = np.random.RandomState(5).random_sample(n)
+    w, source, count, counts = _check_plan(o, np.float32(-5.3), n, u)
+    assert counts == (2000, 1, 0) and count[1234] == 2000 and (source == 1234).all()
+    o[1234] = -9.0
+    w, source, count, counts = _check_plan(o, np.float32(-5.3), n + 100, np.random.RandomState(6).random_sample(n + 100))
+    assert counts == (n, 0, 100) and not count.any() and not w.any()
+    assert np.array_equal(source, np.minimum(np.arange(n + 100), n - 1))
+
+
+def test_relocate_raises_when_nobody_is_alive_and_rewrites_nothing():
+    from intro_to_gaussian_splatting_amd import Gaussians, MCMCControl
+
+    n = 50
+    rs = np.random.RandomState(1)
+    g = Gaussians.from_arrays(rs.normal(size=(n, 3)).astype(np.float32), rs.randint(0, 255, size=(n, 3)).astype(np.float32),
+                              np.full((n, 3), 0.05, np.float32), np.tile(np.float32([1, 0, 0, 0]), (n, 1)),
+                              np.full((n, 1), -9.0, np.float32), device=DEV)
+    mc = MCMCControl(g, cap_max=60)
+    before = g.points.clone()
+    with pytest.raises(ValueError, match="no Gaussian is alive"):
+        mc.relocate()
+    assert len(g) == n and torch.equal(g.points, before)
+
+
+# ---------------------------------------------------------------------------------------------------- apply
+SPEC = [("copy1", 1, mr.COPY), ("copy4", 4, mr.COPY), ("copy48", 48, mr.COPY), ("m3", 3, mr.ZERO_MOVED), ("m48", 48, mr.ZERO_MOVED),
+        ("opacity", 1, mr.OPACITY), ("scales", 3, mr.SCALES)]
+
+
+def _apply_case(o, rs):
+    n = len(o)
+    src = {}
+    for name, width, role in SPEC:
+        if role == mr.OPACITY:
+            a = o.reshape(n, 1).copy()          # (NaN and infinite rows have weight 0: never a source, copied as bits)
+        elif role == mr.SCALES:
+            a = np.exp(rs.uniform(np.log(0.003), np.log(0.3), size=(n, 3)))
+        else:
+            a = rs.normal(size=(n, width))
+        src[name] = np.ascontiguousarray(a, np.float32)
+    return src
+
+
+def _apply(src, n_out, source, count, lead=0):
+    _ffi, lib = _lib()
+    n = len(count)
+    groups = (_ffi.GsxDensityGroup * len(SPEC))()
+    keep, dst = [], {}
+    for i, (name, width, role) in enumerate(SPEC):
+        whole, view = _based(src[name], lead)
+        wd, out = _based(np.full((n_out, width), 12345.0, np.float32), lead)
+        keep += [whole, wd]
+        dst[name] = out
+        groups[i].src, groups[i].dst, groups[i].width, groups[i].role = view.data_ptr(), out.data_ptr(), width, role
+    sd, cd = _dev(source), _dev(count.view(np.int32))
+    rc = lib.gsx_mcmc_apply(groups, len(SPEC), n, n_out, sd.data_ptr(), cd.data_ptr(), MIN_OPACITY, _stream())
+    _ffi.check(rc)
+    torch.cuda.synchronize()
+    return {name: t.cpu().numpy() for name, t in dst.items()}
+
+
+def _check_apply(o, dead_logit, n_out, u, lead=0, seed=0):
+    n = len(o)
+    _, source, count, _ = _plan(o, dead_logit, n_out, u)
+    src = _apply_case(o, np.random.RandomState(77 + seed + n))
+    got = _apply(src, n_out, source, count, lead)
+    want, moved = mr.apply([(src[name], role) for name, _, role in SPEC], source, count, MIN_OPACITY)
+    N = np.minimum(count.astype(np.int64)[source] + 1, mr.N_MAX)
+    assert np.array_equal(moved, N > 1) and (source[~moved] == np.arange(n_out)[~moved]).all()
+    worst = 0.0
+    for (name, width, role), ref in zip(SPEC, want):
+        out = got[name]
+        assert out.shape == ref.shape
+        assert _same(out[~moved], src[name][source[~moved]]), name                  # N = 1: the row's bits, moments included
+        if role == mr.COPY:
+            assert _same(out[moved], src[name][source[moved]]), name
+        elif role == mr.ZERO_MOVED:
+            assert not out[moved].view(np.int32).any(), name                        # +0
+        else:
+            a, b = out[moved].astype(np.float64), ref[moved].astype(np.float64)
+            assert np.isfinite(a).all(), name
+            ulp = np.spacing(np.abs(ref[moved])).astype(np.float64)
+            if a.size:
+                worst = max(worst, float((np.abs(a - b) / ulp).max()))
+            assert (np.abs(a - b) <= ulp).all(), (name, float((np.abs(a - b) / ulp).max()))
+        # all N copies of one source are bit-identical to each other
+        if moved.any():
+            order = np.argsort(source[moved], kind="stable")
+            rows, srcs = out[moved][order].view(np.int32), source[moved][order]
+            same_src = srcs[1:] == srcs[:-1]
+            assert (rows[1:][same_src] == rows[:-1][same_src]).all(), name
+    return worst, int(moved.sum()), int(N.max())
+
+
+@pytest.mark.parametrize("n", PLAN_SIZES)
+def test_apply_equals_the_restatement(n):
+    for n_out in _n_outs(n):
+        o, dead_logit, u = plan_case(n, n_out)
+        worst, n_moved, n_top = _check_apply(o, dead_logit, n_out, u)
+        print("n = %d, n_out = %d: %d moved rows, largest N %d, relocated values within %.2f ulp" % (n, n_out, n_moved, n_top, worst))
+
+
+@pytest.mark.parametrize("lead", [1, 3])
+def test_apply_on_bases_that_are_only_float_aligned(lead):
+    o, dead_logit, u = plan_case(1025, 1076)
+    _check_apply(o, dead_logit, 1076, u, lead=lead)
+
+
+def test_apply_clamps_n_at_fifty_one():
+    n = 2001
+    o = np.full(n, -9.0, np.float32)
+    o[700] = 3.0
+    u = np.random.RandomState(5).random_sample(n + 100)
+    worst, n_moved, n_top = _check_apply(o, np.float32(-5.3), n + 100, u)
+    assert n_moved == n + 100 and n_top == mr.N_MAX
+
+
+# ---------------------------------------------------------------------------------------------------- regularize, perturb
+def _regularize(c, lo, ls, lead=0):
+    _ffi, lib = _lib()
+    n = len(c["opacity"])
+    keep = {k: _based(c[k], lead) for k in ("opacity", "scales", "grad_opacity", "grad_scales")}
+    t = {k: v[1] for k, v in keep.items()}
+    rc = lib.gsx_mcmc_regularize(t["opacity"].data_ptr(), t["scales"].data_ptr(), n, lo, ls, t["grad_opacity"].data_ptr(),
+                                 t["grad_scales"].data_ptr(), _stream())
+    _ffi.check(rc)
+    torch.cuda.synchronize()
+    assert _same(t["opacity"].cpu().numpy(), c["opacity"]) and _same(t["scales"].cpu().numpy(), c["scales"])
+    return t["grad_opacity"].cpu().numpy(), t["grad_scales"].cpu().numpy()
+
+
+def _perturb(c, rate, k, x0, lead=0):
+    _ffi, lib = _lib()
+    n = len(c["opacity"])
+    keep = {name: _based(c[name], lead) for name in ("points", "scales", "quats", "opacity", "noise")}
+    t = {name: v[1] for name, v in keep.items()}
+    rc = lib.gsx_mcmc_perturb(t["points"].data_ptr(), t["scales"].data_ptr(), t["quats"].data_ptr(), t["opacity"].data_ptr(),
+                              t["noise"].data_ptr(), n, rate, k, x0, _stream())
+    _ffi.check(rc)
+    torch.cuda.synchronize()
+    for name in ("scales", "quats", "opacity", "noise"):
+        assert _same(t[name].cpu().numpy(), c[name]), name
+    return t["points"].cpu().numpy()
+
+
+@pytest.mark.parametrize("lead", [0, 2])
+@pytest.mark.parametrize("n", mr.STEP_SIZES)
+def test_regularize_within_twelve_reference_errors(n, lead):
+    R = mr.STEP_RULES
+    c = mr.step_inputs(n)
+    lo, ls = R["lambda_opacity"], R["lambda_scale"]
+    go, gs = _regularize(c, lo, ls, lead)
+    e = mr.regularize_error(go, gs, c, lo, ls)
+    print("regularize n = %d lead %d: error %.4g of the coefficient = %.2f x E_REF_REGULARIZE" % (n, lead, e, e / E_REF_REGULARIZE))
+    assert e <= MULTIPLE * E_REF_REGULARIZE
+    if n >= 5:
+        assert gs[0, 0] == c["grad_scales"][0, 0] and gs[0, 1] < c["grad_scales"][0, 1]     # sign(0) = 0, sign(-0.02) = -1
+    # a lambda of 0 on one side: that array's bits are unchanged, the other side is what it was with both
+    go0, gs0 = _regularize(c, 0.0, ls, lead)
+    assert _same(go0, c["grad_opacity"]) and _same(gs0, gs)
+    go1, gs1 = _regularize(c, lo, 0.0, lead)
+    assert _same(gs1, c["grad_scales"]) and _same(go1, go)
+
+
+@pytest.mark.parametrize("lead", [0, 2])
+@pytest.mark.parametrize("n", mr.STEP_SIZES)
+def test_perturb_within_twelve_reference_errors(n, lead):
+    R = mr.STEP_RULES
+    c = mr.step_inputs(n)
+    args = (c["points"], c["scales"], c["quats"], c["opacity"], c["noise"], R["rate"], R["gate_k"], R["gate_x0"])
+    got = _perturb(c, R["rate"], R["gate_k"], R["gate_x0"], lead)
+    want, d64, kept = mr.perturb_f64(*args)
+    unit = mr.perturb_norm(c["scales"], c["noise"], R["rate"])
+    if n >= 5:
+        assert list(np.nonzero(kept)[0]) == [1, 2]                  # the zero quaternion, the NaN noise
+    assert _same(got[kept], c["points"][kept])                      # a row whose step is not finite keeps its bits
+    live = ~kept
+    ulp = np.spacing(np.abs(want[live]).astype(np.float32)).astype(np.float64)
+    err = np.abs(got[live].astype(np.float64) - want[live])
+    multiple = float((np.maximum(err - ulp, 0.0).max(axis=1) / (E_REF_PERTURB * unit[live])).max())
+    print("perturb n = %d lead %d: largest error beyond one ulp of the point = %.2f x E_REF_PERTURB" % (n, lead, multiple))
+    assert (err <= MULTIPLE * E_REF_PERTURB * unit[live][:, None] + ulp).all()
+    if n >= 5:
+        moved = np.abs(got.astype(np.float64) - c["points"].astype(np.float64)).max(axis=1)
+        assert moved[3] <= np.spacing(np.abs(c["points"][3])).max()         # opaque: gate ~ 0
+        assert 0.0 < moved[4] <= 0.63 * unit[4] * 1.001                     # nearly dead: gate at its ceiling of 0.6225
+    assert _same(_perturb(c, R["rate"], R["gate_k"], R["gate_x0"], lead), got)
+
+
+# ---------------------------------------------------------------------------------------------------- end to end
+TRAINED = ("points", "scales", "quaternions", "opacity", "colors")
+LR = {"colors": 0.02, "opacity": 0.02, "quaternions": 1e-3, "points": 1e-3, "scales": 5e-3}
+N0, CAP, STEPS = 2000, 2600, 40
+MCMC = dict(cap_max=CAP, noise_lr=1e4)
+PERIODS = dict(sh_degree_every=None, densify_every=5, densify_from=0, densify_until=100)
+
+
+def _scene(path, n=N0, size=64, seed=2):
+    """(scene, target): the synthetic scene of tests/test_hip_density.py at 2000 Gaussians, a 64 x 64 frame of 16 tiles; the
+    target is the frame of the scene before its colours, opacities, positions and scales were disturbed."""
+    from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians
+    from intro_to_gaussian_splatting_amd.synthetic import make_scene, write_colmap_text
+
+    sc = make_scene(n, size, size, seed=seed, sigma_scale=2.0)
+    os.makedirs(str(path), exist_ok=True)
+    write_colmap_text(str(path), sc)
+    g = Gaussians.from_arrays(sc["points"], sc["colors_0_255"], sc["scales"], sc["quaternions"], sc["opacity"], device=DEV)
+    scene = GaussianScene(str(path), g)
+    rs = np.random.RandomState(seed)
+    noise = lambda t, sigma: torch.from_numpy(rs.normal(0, sigma, size=tuple(t.shape)).astype(np.float32)).to(DEV)  # noqa: E731
+    with torch.no_grad():
+        target = scene.render_image_hip(1).clone()
+        g.colors.add_(noise(g.colors, 0.15)).clamp_(0.0, 1.0)
+        g.opacity.add_(noise(g.opacity, 1.5))
+        g.points.add_(noise(g.points, 0.02))
+        g.scales.mul_(torch.exp(noise(g.scales, 0.1)))
+    return scene, {1: target}
+
+
+def _state(g, opt):
+    out = {name: getattr(g, name).detach().clone() for name in TRAINED}
+    out.update({"m_" + name: opt.exp_avg[name].clone() for name in TRAINED})
+    out.update({"v_" + name: opt.exp_avg_sq[name].clone() for name in TRAINED})
+    return out
+
+
+def _fit(path, seed):
+    from intro_to_gaussian_splatting_amd import MCMCControl, Trainer
+
+    scene, targets = _scene(path)
+    trainer = Trainer(scene, targets, lr=LR, lambda_dssim=0.2, tile_size=16, seed=seed, strategy="mcmc", mcmc=MCMC, **PERIODS)
+    assert isinstance(trainer.density, MCMCControl)
+    seen = []
+    trainer.fit(STEPS, callback=lambda t, losses, idx: seen.append((losses, idx, len(t.gaussians))))
+    return trainer, seen
+
+
+def test_trainer_mcmc_is_the_composition_written_out_and_keeps_its_budget(tmp_path):
+    from intro_to_gaussian_splatting_amd import GaussianAdam, MCMCControl
+
+    seed = 5
+    trainer, seen = _fit(tmp_path / "a", seed)
+    rows = [n for _, _, n in seen]
+    losses = torch.stack([v[0] for v in seen]).cpu().numpy()
+    print("rows per step", rows, "loss first %.6g last %.6g" % (losses[0, 0], losses[-1, 0]))
+    assert max(rows) <= CAP and rows[-1] == CAP and rows[0] == N0 and rows == sorted(rows)
+    assert rows[4] == 2100 and rows[9] == 2205                              # floor(1.05 n), round by round
+    assert np.isfinite(losses).all()
+    assert trainer.scene.screen_statistics is None                          # no statistic was exported
+
+    # the same by hand: fit.py's docstring for strategy="mcmc"
+    scene2, targets2 = _scene(tmp_path / "b")
+    g = scene2.gaussians
+    for name in TRAINED:
+        getattr(g, name).requires_grad_(True)
+    opt = GaussianAdam(g, lr=LR)
+    mc = MCMCControl(g, optimizer=opt, scene=scene2, **MCMC)
+    gen = torch.Generator(device=DEV).manual_seed(seed)
+    by_hand = []
+    for s in range(1, STEPS + 1):
+        terms = {}
+        frame = scene2.render_image_hip(1, tile_size=16, geometry_gradients=True)
+        loss = scene2.photometric_loss(1, frame, targets2[1], tile_size=16, lambda_dssim=0.2, terms=terms)
+        loss.backward()
+        mc.regularize()
+        opt.step()
+        opt.zero_grad()
+        mc.perturb(generator=gen)
+        if s % 5 == 0:
+            counts = mc.relocate(generator=gen)
+            assert counts["n_out"] == len(g) and counts["n_new"] >= 0 and counts["n_live"] > 0
+        by_hand.append((torch.stack((loss.detach(), terms["l1"], terms["ssim"])), 1, len(g)))
+    assert [v[1:] for v in seen] == [v[1:] for v in by_hand]
+    assert all(torch.equal(_bits(a[0]), _bits(b[0])) for a, b in zip(seen, by_hand))
+    got, want = _state(trainer.gaussians, trainer.opt), _state(g, opt)
+    for key in want:
+        assert torch.equal(_bits(got[key]), _bits(want[key])), key
+    for name in TRAINED:
+        assert getattr(g, name).is_leaf and getattr(g, name).requires_grad and getattr(g, name).grad is None
+
+
+def test_two_mcmc_fits_from_one_seed_give_identical_containers(tmp_path):
+    a, _ = _fit(tmp_path / "a", 9)
+    b, _ = _fit(tmp_path / "b", 9)
+    sa, sb = _state(a.gaussians, a.opt), _state(b.gaussians, b.opt)
+    for key in sa:
+        assert torch.equal(_bits(sa[key]), _bits(sb[key])), key
+    c, _ = _fit(tmp_path / "c", 10)
+    assert not torch.equal(_bits(c.gaussians.points), _bits(a.gaussians.points))
+
+
+def test_the_default_strategy_gives_the_bits_it_gives_with_the_argument_absent(tmp_path):
+    from intro_to_gaussian_splatting_amd import DensityControl, Trainer
+
+    density = dict(grad_threshold=2e-5, dense_scale=0.05, prune_logit=-4.5)
+    periods = dict(sh_degree_every=None, densify_every=5, densify_from=0, densify_until=100, opacity_reset_every=7)
+    out = []
+    for i, kw in enumerate((dict(), dict(strategy="adaptive"))):
+        scene, targets = _scene(tmp_path / str(i))
+        t = Trainer(scene, targets, lr=LR, lambda_dssim=0.2, tile_size=16, seed=3, density=density, opacity_reset_logit=-2.0,
+                    **periods, **kw)                    # (a reset above prune_logit: the next round does not prune every row)
+        assert isinstance(t.density, DensityControl) and t.statistic == "screen" and t.strategy == "adaptive"
+        losses = []
+        t.fit(12, callback=lambda tr, triple, idx: losses.append(triple))
+        out.append((_state(t.gaussians, t.opt), torch.stack(losses)))
+    assert torch.equal(_bits(out[0][1]), _bits(out[1][1]))
+    for key in out[0][0]:
+        assert torch.equal(_bits(out[0][0][key]), _bits(out[1][0][key])), key
