@@ -446,6 +446,32 @@ GSX_API int gsx_render_backward_screen(const GsxCamera *camera, const float *mea
                                size_t workspace_bytes, void *stream);
 
 /*
+ * gsx_render_backward_screen plus the ABSOLUTE screen statistic (AbsGS's answer to "gradient collision", gsplat's absgrad): the
+ * same arguments with one more output behind screen_radius, the same refusals (and grad_means2d, screen_radius or
+ * grad_means2d_abs NULL: all three are required here), the same synchronisation, the same workspace
+ * (gsx_backward_geometry_workspace_bytes), no float atomics: same inputs, same bits.  The seven older outputs hold the bits
+ * gsx_render_backward_screen writes.
+ *   grad_means2d_abs (n,2): grad_means2d is a signed sum over the pixels a Gaussian touches, and over fine detail the terms
+ *     cancel.  This is the sum of their absolute values, per component.  For every composited (Gaussian, pixel), with u and
+ *     d = mean - pixel as above, u0 = u * d0, u1 = u * d1 (the products S1 and S2 add up) and the conic as stored:
+ *       tx = fmaf(2.0f * q00, u0, (q01 + q10) * u1)              ty = fmaf(q01 + q10, u0, (2.0f * q11) * u1)
+ *       Tx = sum |tx|,  Ty = sum |ty|      over the pixels of every tile that composites the Gaussian, under the stop rule
+ *       grad_means2d_abs = ((0.5f * Tx) * |sx|, (0.5f * Ty) * |sy|)
+ *     so that the same sums WITHOUT the absolute value are grad_means2d up to rounding, and grad_means2d_abs >= |grad_means2d|
+ *     componentwise up to rounding.  The sums run in a fixed order: per tile over the lane's pixels, then a fixed butterfly
+ *     over the wave, the chunks of a tile of more than 256 pixels in rising order; per Gaussian over its tiles lane-strided
+ *     in emission order, then the same butterfly.  Written for every row: exact +0 for a Gaussian that is culled or on no
+ *     tile list.  gsx_density_accumulate_screen takes it in place of grad_means2d; the published threshold of 2e-4
+ *     belongs to the signed statistic, not to this one.
+ */
+GSX_API int gsx_render_backward_screen_abs(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                                   const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                                   const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                                   float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                                   float *screen_radius, float *grad_means2d_abs, const GsxParams *params, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
+/*
  * gsx_render_backward_screen plus the camera: the same arguments with two more device outputs behind screen_radius, the same
  * refusals (grad_world2view or grad_full_proj NULL besides; grad_means2d and screen_radius may BOTH be NULL here), the same
  * synchronisation, no hints touched, no float atomics: same inputs, same bits.  The older outputs hold the bits

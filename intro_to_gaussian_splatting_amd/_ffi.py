@@ -144,6 +144,8 @@ SIGNATURES = {
     "gsx_backward_geometry_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),
     "gsx_render_backward_screen": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 9 +
                                    [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
+    "gsx_render_backward_screen_abs": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 10 +
+                                       [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
     "gsx_render_backward_camera": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 11 +
                                    [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
     "gsx_backward_camera_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),

@@ -387,6 +387,7 @@ struct GeometryGrads {
     float *means2d = nullptr, *radius = nullptr;
     float *world2view = nullptr, *full_proj = nullptr;     // gsx_render_backward_camera: both, 16 floats each
     const float *depth = nullptr, *grad_depth = nullptr;   // gsx_render_backward_depth: both, the (D, A) image and dL/d(D, A)
+    float *means2d_abs = nullptr;                           // gsx_render_backward_screen_abs: (n,2); excludes the two lines above
 };
 
 // What the gradient entries and gsx_render_depth cover: the reference's own frame, whole, RGB colours.
@@ -454,6 +455,7 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->quats, (size_t)n * 4, s));
         if (geo->means2d) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means2d, (size_t)n * 2, s));
         if (geo->radius) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->radius, (size_t)n, s));
+        if (geo->means2d_abs) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means2d_abs, (size_t)n * 2, s));
         if (geo->world2view) {      // a frame that lists nothing leaves 32 exact +0
             GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->world2view, 16, s));
             GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->full_proj, 16, s));
@@ -485,6 +487,8 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         float *zrow = (float *)(ws + c.zrow);
         GSX_HIP(gsx::launch_project_depth(*camera, means3d, n, p.small_batch, zrow, s));
         GSX_HIP(gsx::launch_backward_tiles_depth(bt, gsx::DepthTiles{zrow, geo->depth, geo->grad_depth}, p.grid, p.out, s));
+    } else if (geo && geo->means2d_abs) {
+        GSX_HIP(gsx::launch_backward_tiles_abs(bt, p.grid, p.out, s));
     } else {
         GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
     }
@@ -497,7 +501,7 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         const gsx::CameraGrads cg{geo->world2view, geo->full_proj, (float *)(ws + c.cam_partials)};
         GSX_HIP(gsx::launch_backward_geometry(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
                                               geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s,
-                                              geo->world2view ? &cg : nullptr));
+                                              geo->world2view ? &cg : nullptr, geo->means2d_abs));
     }
     tm.mark();  // 3: sums (and the geometry chain)
     GSX_HIP(hipStreamSynchronize(s));
@@ -698,6 +702,23 @@ int gsx_render_backward_screen(const GsxCamera *camera, const float *means3d, co
         return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
     if (!grad_means2d) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d is NULL");
     const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
+    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+}
+
+int gsx_render_backward_screen_abs(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                                   const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                                   const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                                   float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                                   float *screen_radius, float *grad_means2d_abs, const GsxParams *params, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
+    if (!grad_means3d || !grad_scales || !grad_quats)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
+    if (!grad_means2d) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d is NULL");
+    if (!screen_radius) return fail(GSX_ERR_INVALID_ARGUMENT, "screen_radius is NULL");
+    if (!grad_means2d_abs) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d_abs is NULL");
+    GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
+    geo.means2d_abs = grad_means2d_abs;
     return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
                            grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
 }

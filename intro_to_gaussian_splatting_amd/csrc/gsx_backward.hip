@@ -38,6 +38,9 @@
 // term to dL/dalpha before u is formed and sums dL/dz per record beside the five moments; backward_depth_sum_kernel and
 // backward_depth_chain_kernel are the geometry kernels with that sixth sum, which reaches dL/dpoint through world2view's
 // third column.
+// gsx_render_backward_screen_abs: the screen call with the tile kernel's fourth instance (backward_tile_abs_kernel), which
+// also sums the ABSOLUTE value of every pixel's term of dL/dmean per record, and backward_geometry_abs_sum_kernel, the
+// geometry sum with those two sums beside the five moments and one more store per Gaussian; the chain kernel is the same.
 //
 // alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
@@ -146,11 +149,23 @@ __device__ __forceinline__ float wave_sum1(float v) {
     return v;
 }
 
-// backward_tile_kernel, backward_tile_geometry_kernel and backward_tile_depth_kernel: one text, three instances
-// (gsx_backward_tile.inc)
+// Sums of a and of b over the 64 lanes in a fixed order, a's left in lanes 0..31 and b's in lanes 32..63: the halves are
+// exchanged as in wave_sum4 (one shuffle), then the remaining value is reduced over the 32 lanes.  6 shuffles for two sums.
+__device__ __forceinline__ float wave_sum2(float a, float b, int lane) {
+    const bool up = (lane & 32) != 0;
+    float v = up ? b : a;
+    v += __shfl_xor(up ? a : b, 32);
+#pragma unroll
+    for (int s = 16; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
+// backward_tile_kernel, backward_tile_geometry_kernel, backward_tile_depth_kernel and backward_tile_abs_kernel: one text,
+// four instances (gsx_backward_tile.inc)
 #define GSX_TILE_KERNEL backward_tile_kernel
 #define GSX_TILE_GEOMETRY false
 #define GSX_TILE_DEPTH 0
+#define GSX_TILE_ABS 0
 #define GSX_TILE_ATTR
 #include "gsx_backward_tile.inc"
 #undef GSX_TILE_KERNEL
@@ -169,8 +184,19 @@ __device__ __forceinline__ float wave_sum1(float v) {
 #define GSX_TILE_ATTR
 #include "gsx_backward_tile.inc"
 #undef GSX_TILE_KERNEL
+#undef GSX_TILE_DEPTH
+#undef GSX_TILE_ABS
+#undef GSX_TILE_ATTR
+// the abs instance: the geometry instance with two more accumulators and three hoisted conic sums, held to its occupancy
+#define GSX_TILE_KERNEL backward_tile_abs_kernel
+#define GSX_TILE_DEPTH 0
+#define GSX_TILE_ABS 1
+#define GSX_TILE_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
+#include "gsx_backward_tile.inc"
+#undef GSX_TILE_KERNEL
 #undef GSX_TILE_GEOMETRY
 #undef GSX_TILE_DEPTH
+#undef GSX_TILE_ABS
 #undef GSX_TILE_ATTR
 
 // gsx_render_depth: (D, A) = (sum T alpha z, sum T alpha) of every pixel of every window tile, by the backward's walk --
@@ -536,6 +562,41 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// ---- gsx_render_backward_screen_abs: backward_geometry_sum_kernel with the two absolute sums backward_tile_abs_kernel left
+// in the .z and .w of its pairs' second geometry float4 -- the five moments in the same operations and the same order, so
+// the chain after it gives the screen entry's bits; Tx and Ty lane-strided over [prefix[r], prefix[r + 1]) in rising order
+// like them, then wave_sum2's fixed exchange and butterfly: no atomics -- and a store per Gaussian,
+//     grad_means2d_abs[row] = ((0.5f * Tx) * hx, (0.5f * Ty) * hy),   hx = |sx|, hy = |sy|
+// the chain's half extents.  One pass over the slots and one launch for both; a rank on no tile list keeps the +0 the
+// launch stored.
+__global__ void __launch_bounds__(256)
+    backward_geometry_abs_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                     const uint32_t *__restrict__ order, uint32_t m, float hx, float hy,
+                                     float *__restrict__ grad_means2d_abs) {
+    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= m) return;
+    const uint32_t b = prefix[r], e = prefix[r + 1];
+    if (b == e) return;
+    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, ax = 0.0f, ay = 0.0f;
+    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
+        const float4 v = geo_slots[2 * (size_t)i], v5 = geo_slots[2 * (size_t)i + 1];
+        a1 += v.x; a2 += v.y; a3 += v.z; a4 += v.w; a5 += v5.x; ax += v5.z; ay += v5.w;
+    }
+    const float v = wave_sum4(a1, a2, a3, a4, lane);
+    const float S5 = wave_sum1(a5);
+    const float S2 = __shfl(v, 16), S3 = __shfl(v, 32), S4 = __shfl(v, 48);
+    const float Txy = wave_sum2(ax, ay, lane);
+    const float Ty = __shfl(Txy, 32);
+    if (lane == 0) {
+        geo_slots[2 * (size_t)b] = make_float4(v, S2, S3, S4);
+        geo_slots[2 * (size_t)b + 1] = make_float4(S5, 0.0f, 0.0f, 0.0f);
+        const int64_t row = order[r];
+        grad_means2d_abs[2 * row] = (0.5f * Txy) * hx;
+        grad_means2d_abs[2 * row + 1] = (0.5f * Ty) * hy;
+    }
+}
+
 // ---- gsx_render_backward_depth: backward_geometry_sum_kernel with the sixth sum -- the five in the same operations and the
 // same order, Sz like S5 -- and backward_geometry_chain_kernel with Sz world2view[k][2] added to dL/dpoint_k, as a
 // separate addend and only where it is not zero: with dL/ddepth = 0 every row holds the screen entry's bits, a -0 included.
@@ -703,6 +764,12 @@ hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, 
     return hipGetLastError();
 }
 
+hipError_t launch_backward_tiles_abs(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s) {
+    if (grid.count() <= 0) return hipSuccess;
+    backward_tile_abs_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_backward_tiles_depth(const BackwardTiles &bt, const DepthTiles &dt, const TileGrid &grid, const OutDesc &out,
                                        hipStream_t s) {
     if (grid.count() <= 0) return hipSuccess;
@@ -744,10 +811,14 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
                                     const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
                                     float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
-                                    const CameraGrads *cg) {
+                                    const CameraGrads *cg, float *grad_means2d_abs) {
     if (m == 0) return hipSuccess;
     const GeoCamera cam = geo_camera(camera);
-    backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
+    if (grad_means2d_abs)
+        backward_geometry_abs_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(
+            geo_slots, prefix, order, m, fabsf(cam.sx), fabsf(cam.sy), grad_means2d_abs);
+    else
+        backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
     const unsigned blocks = (unsigned)(((uint64_t)m + 255) / 256);
     if (cg) {
         backward_camera_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,

@@ -1,10 +1,12 @@
-// The compositing backward's tile kernel, included three times by gsx_backward.hip (inside its anonymous namespace):
+// The compositing backward's tile kernel, included four times by gsx_backward.hip (inside its anonymous namespace):
 //   GSX_TILE_KERNEL = backward_tile_kernel,          GSX_TILE_GEOMETRY = false: gsx_render_backward's, the colour-only instance
 //   GSX_TILE_KERNEL = backward_tile_geometry_kernel, GSX_TILE_GEOMETRY = true:  gsx_render_backward_geometry's
 //   GSX_TILE_KERNEL = backward_tile_depth_kernel,    GSX_TILE_GEOMETRY = true, GSX_TILE_DEPTH = 1: gsx_render_backward_depth's
+//   GSX_TILE_KERNEL = backward_tile_abs_kernel,      GSX_TILE_GEOMETRY = true, GSX_TILE_ABS = 1: gsx_render_backward_screen_abs'
 // Plain kernels from one text rather than a template or a shared device function: the colour-only kernel keeps its
 // name and compiles to the instructions it had before the geometry instance existed, and both keep theirs beside the
-// depth instance, whose text sits in #if GSX_TILE_DEPTH blocks.
+// depth instance, whose text sits in #if GSX_TILE_DEPTH blocks, and beside the abs instance, whose text sits in
+// #if GSX_TILE_ABS blocks.
 //
 // One wave per window tile.  Its pixels are taken 256 at a time (a 16x16 tile: once), four per lane; the list is staged
 // 64 records per batch.  For a tile of more than 256 pixels the later chunks add their sums to the slots the first one
@@ -21,6 +23,11 @@
 // with no further code, and with gD = gA = +0 every sum is the geometry instance's, bit for bit (x + (+0) = x, and every
 // accumulator starts at +0, so no -0 survives in either instance) -- and a sixth sum per record, Sz = sum T alpha gD =
 // dL/dz, into the second float4 of the pair's geometry slot: (S5, Sz, 0, 0).
+// ABS (gsx_render_backward_screen_abs): the geometry instance with two more sums per record, of the ABSOLUTE value of each
+// pixel's term of dL/dmean = -1/2 (Q + Q^T) sum u d: Tx = sum |fmaf(2 q00, u d0, (q01 + q10) (u d1))| and
+// Ty = sum |fmaf(q01 + q10, u d0, (2 q11) (u d1))|, u d0 and u d1 the very products S1 and S2 add up, into the free words of
+// the second float4: (S5, 0, Tx, Ty).  The factor 1/2 is left to backward_geometry_abs_sum_kernel.  Every other sum takes the
+// geometry instance's operations in its order.
 #if GSX_TILE_DEPTH
 __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTiles bt, TileGrid grid, OutDesc out, DepthTiles dt) {
 #else
@@ -33,6 +40,8 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
 #if GSX_TILE_DEPTH
     constexpr int kGeoSums = 6;
     __shared__ float sz[64];
+#elif GSX_TILE_ABS
+    constexpr int kGeoSums = 7;
 #else
     constexpr int kGeoSums = 5;
 #endif
@@ -103,10 +112,16 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
 #if GSX_TILE_DEPTH
                 float mz = 0.0f;
 #endif
+#if GSX_TILE_ABS
+                float mx = 0.0f, my = 0.0f;
+#endif
                 if (__any(any)) {
                     const float4 A = sa[k], B = sb[k], Cc = sc[k];
 #if GSX_TILE_DEPTH
                     const float zk = sz[k];
+#endif
+#if GSX_TILE_ABS
+                    const float qxx = 2.0f * A.z, qxy = A.w + B.x, qyy = 2.0f * B.y;      // Q + Q^T
 #endif
 #pragma unroll
                     for (int j = 0; j < kNpx; ++j) {
@@ -147,6 +162,10 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                             m3 = __builtin_fmaf(u0, e0, m3);
                             m4 = __builtin_fmaf(u0, e1, m4);
                             m5 = __builtin_fmaf(u1, e1, m5);
+#if GSX_TILE_ABS
+                            mx += fabsf(__builtin_fmaf(qxx, u0, qxy * u1));
+                            my += fabsf(__builtin_fmaf(qxy, u0, qyy * u1));
+#endif
                         }
                         Tr[j] = test;
                     }
@@ -160,6 +179,10 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
 #if GSX_TILE_DEPTH
                     const float wz = wave_sum1(mz);
                     if (lane == 0) sgeo[k * kGeoSums + 5] = wz;
+#endif
+#if GSX_TILE_ABS
+                    const float wxy = wave_sum2(mx, my, lane);
+                    if ((lane & 31) == 0) sgeo[k * kGeoSums + 5 + (lane >> 5)] = wxy;      // Tx in lane 0, Ty in lane 32
 #endif
                 }
             }
@@ -177,6 +200,8 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                     float4 g0 = make_float4(sg[0], sg[1], sg[2], sg[3]);
 #if GSX_TILE_DEPTH
                     float4 g1 = make_float4(sg[4], sg[5], 0.0f, 0.0f);
+#elif GSX_TILE_ABS
+                    float4 g1 = make_float4(sg[4], 0.0f, sg[5], sg[6]);
 #else
                     float4 g1 = make_float4(sg[4], 0.0f, 0.0f, 0.0f);
 #endif
@@ -187,6 +212,10 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                         g1.x += o1.x;
 #if GSX_TILE_DEPTH
                         g1.y += o1.y;
+#endif
+#if GSX_TILE_ABS
+                        g1.z += o1.z;
+                        g1.w += o1.w;
 #endif
                     }
                     gdst[0] = g0;

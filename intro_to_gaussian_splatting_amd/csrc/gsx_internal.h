@@ -529,6 +529,10 @@ struct BackwardTiles {
     float4 *geo_slots = nullptr;
 };
 hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
+// gsx_render_backward_screen_abs: the tile kernel's abs instance, bt as above with geo_slots set; the pair's second geometry
+// float4 becomes (S5, 0, Tx, Ty), the sums over the tile's pixels of the absolute value of each pixel's term of
+// (Q + Q^T) u d (gsx_backward_tile.inc).  launch_backward_geometry with grad_means2d_abs then sums them beside the moments.
+hipError_t launch_backward_tiles_abs(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
 // gsx_render_depth / gsx_render_backward_depth: the depth image holds (D, A) per pixel, D = sum T alpha z the expected
 // depth and A = sum T alpha the coverage, with the frame's two leading axes and 2 floats where the frame has 3 -- the
 // float index of frame pixel (px, py) in it, from the frame's descriptor (whose strides are multiples of 3):
@@ -558,6 +562,9 @@ hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, con
 // gsx_render_backward_camera (cg not null): the chain kernel's camera instance also leaves each block's 24 terms of
 // dL/dworld2view and dL/dfull_proj in a row of cg->partials (kCameraPartialBytes per 256 ranks, gsx_plan.h), and one
 // small kernel adds the rows in a fixed order into the two 4x4 outputs.
+// gsx_render_backward_screen_abs (grad_means2d_abs not null, cg null; after launch_backward_tiles_abs): the sum kernel's abs
+// instance adds Tx and Ty beside the five moments, in emission order and a fixed butterfly, and stores
+// (0.5 Tx |sx|, 0.5 Ty |sy|) to the Gaussian's row of grad_means2d_abs (n,2), which the caller has zeroed.
 struct CameraGrads {
     float *world2view, *full_proj;   // device, 16 floats each
     float *partials;                 // workspace
@@ -566,7 +573,7 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
                                     const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                     const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
                                     float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
-                                    const CameraGrads *cg = nullptr);
+                                    const CameraGrads *cg = nullptr, float *grad_means2d_abs = nullptr);
 // gsx_render_backward_depth: the same with the sixth sum Sz beside S5 (backward_depth_sum_kernel, in the same order), and
 // the chain adds Sz world2view[0:3][2] to dL/dpoint: z = p . world2view[:3][2] + world2view[3][2] (no camera terms).
 hipError_t launch_backward_geometry_depth(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,

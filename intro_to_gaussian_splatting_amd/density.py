@@ -42,17 +42,27 @@ class DensityControl:
     loss per NDC unit, the published convention, and the published 2e-4 means what it means there -- and counts a Gaussian as
     seen whenever the frame listed it on a tile, zero gradient or not (gsx_density_accumulate_screen).  It also keeps the
     largest screen radius seen, ``radius_max``, and a round PRUNES, besides the rules above, where that is above
-    ``prune_radius`` pixels (``math.inf``: never; gsx_density_plan_screen)."""
+    ``prune_radius`` pixels (``math.inf``: never; gsx_density_plan_screen).
+    ``"screen_abs"`` (needs ``scene``): AbsGS's statistic, gsplat's ``absgrad``.  dL/d(NDC mean) is a signed sum over the pixels
+    a Gaussian touches; a large Gaussian over fine detail gets terms of both signs, they cancel, and the blur never splits.
+    Render with ``geometry_gradients=True, screen_statistics="abs"``; ``accumulate()`` then adds the norm of the ABSOLUTE
+    statistic (gsx_render_backward_screen_abs: per component the sum of the absolute values of the pixels' terms) through the
+    same gsx_density_accumulate_screen, so seen-if-listed, ``radius_max`` and ``prune_radius`` work exactly as for
+    ``"screen"``.  The unit is still loss per NDC unit, but the value is never below the signed one and on this project's
+    fixtures is typically several times it: the published 2e-4 belongs to the SIGNED statistic, and this project has
+    measured no value for the absolute one -- ``grad_threshold`` has no default that means anything here; set it for the
+    scene."""
 
-    STATISTICS = ("points", "screen")
+    STATISTICS = ("points", "screen", "screen_abs")
+    _SCREEN = ("screen", "screen_abs")          # the statistics that read scene.screen_statistics and keep radius_max
 
     def __init__(self, gaussians, optimizer=None, scene=None, grad_threshold: float = 2e-4, dense_scale: float = 0.01,
                  prune_logit: float = -5.3, prune_scale: float = math.inf, split_shrink: float = 1.6,
                  max_gaussians: Optional[int] = None, statistic: str = "points", prune_radius: float = math.inf) -> None:
         if statistic not in self.STATISTICS:
-            raise ValueError("statistic = %r is neither 'points' nor 'screen'" % (statistic,))
-        if statistic == "screen" and scene is None:
-            raise ValueError("statistic='screen' needs scene: accumulate() reads scene.screen_statistics")
+            raise ValueError("statistic = %r is neither 'points' nor 'screen' nor 'screen_abs'" % (statistic,))
+        if statistic in self._SCREEN and scene is None:
+            raise ValueError("statistic=%r needs scene: accumulate() reads scene.screen_statistics" % (statistic,))
         if math.isnan(float(prune_radius)):
             raise ValueError("prune_radius is NaN")
         if getattr(gaussians, "original_index", None) is not None:
@@ -77,7 +87,7 @@ class DensityControl:
         n = len(gaussians)
         self.grad_sum = torch.zeros(n, dtype=torch.float32, device=dev)
         self.seen = torch.zeros(n, dtype=torch.int32, device=dev)        # (the library's uint32)
-        self.radius_max = torch.zeros(n, dtype=torch.float32, device=dev) if statistic == "screen" else None
+        self.radius_max = torch.zeros(n, dtype=torch.float32, device=dev) if statistic in self._SCREEN else None
         self._workspace: Optional[torch.Tensor] = None
         self._groups = (_ffi.GsxDensityGroup * _ffi.GSX_DENSITY_MAX_GROUPS)()
 
@@ -114,7 +124,7 @@ class DensityControl:
         counts = (ctypes.c_int64 * 4)()
         rules = self._rules(grad_threshold)
         with torch.cuda.device(dev):
-            if self.statistic == "screen":
+            if self.statistic in self._SCREEN:
                 rc = _ffi.load().gsx_density_plan_screen(self.grad_sum.data_ptr(), self.seen.data_ptr(), g.scales.data_ptr(),
                                                          g.opacity.data_ptr(), self.radius_max.data_ptr(), self.prune_radius, n,
                                                          ctypes.byref(rules), self._workspace.data_ptr(),
@@ -129,9 +139,9 @@ class DensityControl:
     # ------------------------------------------------------------------ the surface
     def accumulate(self) -> None:
         """After ``backward()``: adds |points.grad| of every Gaussian with a non-zero gradient row to the statistic and counts
-        it as seen (gsx_density_accumulate).  Allocates nothing after the first call.  ``statistic="screen"``: consumes
-        ``scene.screen_statistics`` instead (``_accumulate_screen``)."""
-        if self.statistic == "screen":
+        it as seen (gsx_density_accumulate).  Allocates nothing after the first call.  ``statistic="screen"`` and
+        ``"screen_abs"``: consume ``scene.screen_statistics`` instead (``_accumulate_screen``)."""
+        if self.statistic in self._SCREEN:
             return self._accumulate_screen()
         g = self.gaussians
         grad = g.points.grad
@@ -154,12 +164,21 @@ class DensityControl:
     def _accumulate_screen(self) -> None:
         """After a ``backward()`` of a frame rendered with ``screen_statistics=True``: adds the norm of dL/d(NDC mean) of
         every Gaussian the frame listed to the statistic, counts it as seen and keeps its largest radius
-        (gsx_density_accumulate_screen), then sets ``scene.screen_statistics`` to None: one backward is counted once."""
+        (gsx_density_accumulate_screen), then sets ``scene.screen_statistics`` to None: one backward is counted once.
+        ``statistic="screen_abs"``: the same call on the absolute statistic, the fourth entry ``screen_statistics="abs"``
+        leaves; ``"screen"`` reads the first three entries of either tuple."""
         stat = self.scene.screen_statistics
         if stat is None:
-            raise ValueError("scene.screen_statistics is None: render with geometry_gradients=True, screen_statistics=True and "
-                             "call backward() before every accumulate()")
-        _, grad, radius = stat
+            raise ValueError("scene.screen_statistics is None: render with geometry_gradients=True, screen_statistics=%s and "
+                             "call backward() before every accumulate()"
+                             % ("'abs'" if self.statistic == "screen_abs" else "True"))
+        if self.statistic == "screen_abs":
+            if len(stat) < 4:
+                raise ValueError("scene.screen_statistics holds no absolute statistic: statistic='screen_abs' needs frames "
+                                 "rendered with screen_statistics='abs', not True")
+            _, _, radius, grad = stat[:4]
+        else:
+            _, grad, radius = stat[:3]
         n = len(self.gaussians)
         if grad.shape[0] != n or radius.shape[0] != n or self.grad_sum.shape[0] != n:
             raise ValueError("the container has %d rows, scene.screen_statistics %d and the statistic %d: rows changed "

@@ -23,6 +23,10 @@ tile_size, screen_statistics=statistic == "screen")`` and step 3 adds ``lambda_d
 depth_targets[idx], scene.rendered_region(idx, tile_size))`` for the views that have a target; nothing else in the order
 changes.  Without it every call is the one above.
 
+With ``statistic="screen_abs"`` (the absolute screen statistic, ``DensityControl``) step 2 passes
+``screen_statistics="abs"``; nothing else changes.  It is refused together with ``refine_poses`` or ``depth_targets``: the
+pose and depth backward entries have no absolute statistic.
+
 With ``masks`` (image index -> (W,H) weight) and/or ``exposure`` (an ``ExposureRefiner``) step 3 is
 ``scene.photometric_loss(..., weight=masks.get(idx), exposure=exposure_refiner.exposure(idx))`` -- the weighted loss of
 gsx_photometric_loss_weighted, one call, with dL/dexposure left in the view's leaf by step 4 -- and
@@ -194,6 +198,9 @@ class Trainer:
                 raise ValueError("mcmc= goes to MCMCControl: pass strategy='mcmc' with it")
             if statistic is None:
                 statistic = "screen"
+            if statistic == "screen_abs" and (refine_poses is not None or depth_targets is not None):
+                raise ValueError("statistic='screen_abs' cannot be combined with refine_poses or depth_targets: neither "
+                                 "gsx_render_backward_camera nor gsx_render_backward_depth has the absolute statistic")
             if opacity_reset_every is _OPACITY_RESET_EVERY:
                 opacity_reset_every = int(opacity_reset_every)
         if not targets:
@@ -267,6 +274,8 @@ class Trainer:
         if self.depth_targets is not None:
             frame, depth = scene.render_image_depth_hip(idx, tile_size=self.tile_size,
                                                         screen_statistics=self.statistic == "screen")
+        elif self.statistic == "screen_abs":
+            frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True, screen_statistics="abs")
         elif self.refiner is None:
             frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
                                            screen_statistics=self.statistic == "screen")

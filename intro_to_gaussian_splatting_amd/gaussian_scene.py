@@ -246,6 +246,16 @@ class CapturedFrame:
         return self.out
 
 
+def _screen_mode(screen_statistics):
+    """``screen_statistics`` as the render calls take it: False, True (gsx_render_backward_screen) or ``"abs"``
+    (gsx_render_backward_screen_abs).  Any other string is refused; any other value counts as a bool, as it always has."""
+    if isinstance(screen_statistics, str):
+        if screen_statistics != "abs":
+            raise ValueError("screen_statistics = %r is neither a bool nor 'abs'" % (screen_statistics,))
+        return "abs"
+    return bool(screen_statistics)
+
+
 def _camera_wants_grad(image, camera: bool) -> bool:
     """``camera_gradients=True`` and the view's ``world2view`` requires grad (grad mode on): the frame is differentiable for
     the pose alone."""
@@ -290,7 +300,8 @@ class _RenderImageFunction(torch.autograd.Function):
     reference.  With ``geometry_gradients=True``: gsx_render_backward_geometry -- also dL/dpoints, dL/dscales (linear
     scales) and dL/dquaternions, each for the tensors that require grad; the colour and opacity gradients are the same
     bits.  With ``screen_statistics=True`` besides: gsx_render_backward_screen, the same five gradients, and
-    ``scene.screen_statistics`` = (image_idx, dL/d(NDC mean) (N,2), screen radius (N,)) left for ``DensityControl``.  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
+    ``scene.screen_statistics`` = (image_idx, dL/d(NDC mean) (N,2), screen radius (N,)) left for ``DensityControl``; with
+    ``screen_statistics="abs"`` gsx_render_backward_screen_abs, the same and a fourth entry, the absolute statistic (N,2).  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
     colour), and gsx_sh_backward carries that on to dL/dsh and -- with geometry gradients -- adds the view direction's
     share to dL/dpoints; ``colors`` gets None (the frame does not read it).  The tensors are saved, so autograd's version
     counters catch an in-place edit between forward and backward.  ``world2view`` (None unless ``camera_gradients=True``
@@ -303,7 +314,8 @@ class _RenderImageFunction(torch.autograd.Function):
         kw = dict(kw)
         ctx.camera = world2view is not None
         ctx.geometry = bool(kw.pop("geometry_gradients", False)) or ctx.camera
-        ctx.screen = bool(kw.pop("screen_statistics", False))
+        mode = kw.pop("screen_statistics", False)
+        ctx.screen, ctx.screen_abs = bool(mode), mode == "abs"
         user_stats, st = kw.pop("stats", None), {}
         frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
         if user_stats is not None:
@@ -323,10 +335,13 @@ class _RenderImageFunction(torch.autograd.Function):
         camera = ctx.camera and want[11]
         geometry = ctx.geometry and (ctx.screen or camera or any(want[5:8]))
         grads = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
-                                       ctx.n_instances, ctx.n_visible, geometry=geometry, screen=ctx.screen, camera=camera)
+                                       ctx.n_instances, ctx.n_visible, geometry=geometry, screen=ctx.screen, camera=camera,
+                                       screen_abs=ctx.screen_abs)
         gc, go = grads[:2]
         gp, gs, gq = grads[2:5] if geometry else (None, None, None)
-        if ctx.screen:
+        if ctx.screen_abs:
+            scene.screen_statistics = (ctx.image_idx, grads[5], grads[6].view(-1), grads[7])
+        elif ctx.screen:
             scene.screen_statistics = (ctx.image_idx, grads[5], grads[6].view(-1))
         gw2v = None
         if camera:          # full_proj = world2view @ projection_matrix: the two partial derivatives into the total one
@@ -424,7 +439,8 @@ class GaussianScene:
         self._part_events = {}        # (stream, K) -> K HIP events the library records behind the parts of a frame
         self._pinned_pool = None
         self._pinned_next = 0
-        self.screen_statistics = None   # (image_idx, dL/d(NDC mean) (N,2), radius (N,)) of the latest screen_statistics backward
+        # (image_idx, dL/d(NDC mean) (N,2), radius (N,)) of the latest screen_statistics backward; "abs": + the absolute one (N,2)
+        self.screen_statistics = None
         self._pose_seen = {}          # image -> GaussianImage.pose_version its last frame was planned with (_check_pose)
 
     # ------------------------------------------------------------------ helpers
@@ -622,6 +638,11 @@ class GaussianScene:
         Gaussian the frame listed on no tile; every such backward replaces it, ``DensityControl(statistic="screen")``
         consumes it.  It is the rasteriser's share, the published ``viewspace_points.grad[:, :2]``: an SH scene's
         view-direction term (gsx_sh_backward) reaches ``points.grad`` only.  Gradients and frame are the same bits either way.
+        ``screen_statistics="abs"``: the backward runs gsx_render_backward_screen_abs instead and leaves a 4-tuple, the three
+        entries above -- the same bits -- and the ABSOLUTE statistic (N,2): per component the sum over the Gaussian's pixels of
+        the absolute value of each pixel's term of dL/d(NDC mean), which a large Gaussian over fine detail does not cancel
+        (AbsGS's "gradient collision"); ``DensityControl(statistic="screen_abs")`` consumes it.  Not with
+        ``camera_gradients=True`` (ValueError): the pose entry has no absolute statistic.
         ``gaussians.active_sh_degree`` below ``sh_degree`` (the SH degree schedule): the frame, with or without gradients,
         is the one of the scene truncated to the active bands -- rendered from this camera's evaluated colours
         (gsx_sh_to_rgb_active) instead of GsxParams.sh, one (N,3) array per frame; dL/dsh is zero in the inactive bands.
@@ -637,9 +658,14 @@ class GaussianScene:
         by the image: editing ``world2view`` in place does NOT move the camera, ``GaussianImage.set_world2view`` does
         (``CameraRefiner`` steps the pose that way).  The refusals are those of the other gradient paths.
         """
+        screen_statistics = _screen_mode(screen_statistics)
         if screen_statistics and not geometry_gradients:
-            raise ValueError("screen_statistics=True needs geometry_gradients=True: the statistic comes out of the geometry "
-                             "backward (gsx_render_backward_screen)")
+            raise ValueError("screen_statistics=%r needs geometry_gradients=True: the statistic comes out of the geometry "
+                             "backward (gsx_render_backward_screen)" % (screen_statistics,))
+        if screen_statistics == "abs" and camera_gradients:
+            raise ValueError("screen_statistics='abs' cannot be combined with camera_gradients=True: "
+                             "gsx_render_backward_camera has no absolute statistic; pass screen_statistics=True with the pose, "
+                             "or refine the pose in frames of its own")
         g = self.gaussians
         w2v = self.images[image_idx].world2view if _private is None and \
             _camera_wants_grad(self.images[image_idx], camera_gradients) else None
@@ -650,7 +676,7 @@ class GaussianScene:
                     _refuse_with_grad(what)
             kw = dict(stats=stats, timing=timing, generic_kernels=generic_kernels, tile_counts=tile_counts,
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
-                      geometry_gradients=bool(geometry_gradients), screen_statistics=bool(screen_statistics))
+                      geometry_gradients=bool(geometry_gradients), screen_statistics=screen_statistics)
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
                                               g.opacity, g.colors, getattr(g, "sh", None), w2v)
         own = _OwnedFrame.of(_private)
@@ -860,7 +886,7 @@ class GaussianScene:
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
                          n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False,
                          screen: bool = False, camera: bool = False, depth: Optional[torch.Tensor] = None,
-                         grad_depth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
+                         grad_depth: Optional[torch.Tensor] = None, screen_abs: bool = False) -> Tuple[torch.Tensor, ...]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
         ``grad_frame``; with ``geometry`` gsx_render_backward_geometry: those two and (dL/dpoints (N,3), dL/dscales (N,3),
         dL/dquaternions (N,4)); with ``screen`` besides gsx_render_backward_screen: those five and (dL/d(NDC mean) (N,2),
@@ -868,7 +894,8 @@ class GaussianScene:
         (dL/dworld2view (4,4), dL/dfull_proj (4,4)), the two matrices as independent inputs.  With ``depth`` (needs
         ``geometry``, excludes ``camera``) gsx_render_backward_depth: the screen entry's outputs -- the five, or with
         ``screen`` the seven -- for L(frame, depth image), ``depth`` the image ``_render_depth`` returned and ``grad_depth``
-        dL/d(that image).
+        dL/d(that image).  With ``screen_abs`` (needs ``geometry`` and ``screen``, excludes ``camera`` and ``depth``)
+        gsx_render_backward_screen_abs: the seven and (the absolute screen statistic (N,2)).
         The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
@@ -886,8 +913,12 @@ class GaussianScene:
             gc = torch.empty((n, 3), dtype=torch.float32, device=dev)
             go = torch.empty((n, 1), dtype=torch.float32, device=dev)
             outs = [gc, go]
+            if screen_abs and (not geometry or not screen or camera or depth is not None):
+                raise ValueError("screen_abs needs geometry and screen and excludes camera and depth: only "
+                                 "gsx_render_backward_screen_abs has the absolute statistic")
             if geometry:
-                outs += [torch.empty((n, k), dtype=torch.float32, device=dev) for k in (3, 3, 4) + ((2, 1) if screen else ())]
+                outs += [torch.empty((n, k), dtype=torch.float32, device=dev)
+                         for k in (3, 3, 4) + ((2, 1) if screen else ()) + ((2,) if screen_abs else ())]
             elif screen or camera:
                 raise ValueError("screen and camera need geometry: both come out of the geometry backward")
             if depth is not None:
@@ -902,6 +933,8 @@ class GaussianScene:
             size_fn = lib.gsx_backward_geometry_workspace_bytes if geometry else lib.gsx_backward_workspace_bytes
             entry = (lib.gsx_render_backward_screen if screen else lib.gsx_render_backward_geometry) if geometry \
                 else lib.gsx_render_backward
+            if screen_abs:
+                entry = lib.gsx_render_backward_screen_abs
             args = outs
             if camera:
                 cam_outs = [torch.empty((4, 4), dtype=torch.float32, device=dev) for _ in range(2)]
@@ -960,6 +993,9 @@ class GaussianScene:
         through depth yet."""
         if layout not in ("wh3", "hw3"):
             raise ValueError("layout must be 'wh3' or 'hw3', got %r" % (layout,))
+        if _screen_mode(screen_statistics) == "abs":
+            raise ValueError("screen_statistics='abs' is not available in render_image_depth_hip: gsx_render_backward_depth "
+                             "has no absolute statistic; pass screen_statistics=True, or render the frame with render_image_hip")
         g = self.gaussians
         for what, bad in _refusals(g):
             if bad:

@@ -1,6 +1,6 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth] [--screen-abs]
                                                      [--workloads c3] [--sh [--active-degree A]]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
@@ -15,6 +15,10 @@ radius), its steps taking turns with the geometry entry's so that both see the s
 floats out) in turns with the geometry and the screen entry, three ways ("alternating_camera", "camera_over_screen");
 with --sh it takes the SH scene's whole camera-gradient backward (the camera entry, then gsx_sh_backward with the view
 direction's share) in turns with the same two calls through the screen entry.  --workloads picks among c2 and c3.
+--screen-abs (key "screen_abs") takes gsx_render_backward_screen_abs (the tile kernel's abs instance: two more sums per record
+and pixel, 8 more bytes stored per pair, two more sums in the per-Gaussian sum kernel, 8 more bytes stored per Gaussian) in turns with
+the screen entry in one session: both medians with their minimum and maximum ("screen_abs_over_screen"), and the
+GSX_FLAG_TIMING stages of both, medians of `steps` calls.
 --depth (key "depth") takes, in turns in one session: gsx_render_backward_depth for a random dL/dframe and dL/ddepth
 ("fused"), the screen entry for the same dL/dframe ("screen"), gsx_render_depth alone ("depth_forward"), the frame
 ("frame") and the two calls the composed path adds, the frame over colours (z, 1, 0) ("frame_z") and its geometry
@@ -77,7 +81,7 @@ def _in_turns(calls, steps, warmup):
     return {k: (round(statistics.median(v), 4), [round(min(v), 4), round(max(v), 4)]) for k, v in turns.items()}
 
 
-def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False):
+def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False, screen_abs=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -138,6 +142,24 @@ def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, dept
             out["alternating_camera"] = {k + "_ms": v[0] for k, v in t.items()}
             out["alternating_camera"].update({k + "_min_max": v[1] for k, v in t.items()})
             out["camera_over_screen"] = round(t["camera"][0] / t["screen"][0], 4)
+        if screen_abs:
+            back = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
+                                                       geometry=True, screen=True, **kw)
+            calls = dict(screen=back, screen_abs=lambda **kw: back(screen_abs=True, **kw))
+            t = _in_turns(calls, steps, warmup)
+            d = {k + "_ms": v[0] for k, v in t.items()}
+            d.update({k + "_min_max": v[1] for k, v in t.items()})
+            d["screen_abs_over_screen"] = round(t["screen_abs"][0] / t["screen"][0], 4)
+            d["stages"] = {}
+            for key, call in calls.items():
+                stages = []
+                for _ in range(steps):
+                    call(flags=_ffi.GSX_FLAG_TIMING)
+                    ms = (ctypes.c_float * 3)()
+                    _ffi.check(lib.gsx_debug_backward_stage_ms(ms))
+                    stages.append(list(ms))
+                d["stages"][key] = [round(statistics.median(s[i] for s in stages), 4) for i in range(3)]
+            out["screen_abs"] = d
         if depth:
             back = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
                                                        geometry=True, **kw)
@@ -290,6 +312,8 @@ def main():
                     "and the screen entry")
     ap.add_argument("--depth", action="store_true", help="also time gsx_render_backward_depth and gsx_render_depth in turns "
                     "with the screen entry and with the composed path's two frames and two backwards")
+    ap.add_argument("--screen-abs", action="store_true", help="also time gsx_render_backward_screen_abs, in turns with the "
+                    "screen entry")
     ap.add_argument("--workloads", default="c2,c3", help="comma-separated: which of c2, c3 to run (not with --sh)")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     ap.add_argument("--active-degree", type=int, default=None, help="with --sh: Gaussians.active_sh_degree (0..3), the "
@@ -302,7 +326,7 @@ def main():
                                                                        active=args.active_degree, camera=args.camera))))
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
-    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera, args.depth)
+    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera, args.depth, args.screen_abs)
            for name, n in WORKLOADS.items() if name in args.workloads.split(",")}
     print(json.dumps(dict(metric="backward_ms", results=out)))
 
