@@ -293,6 +293,68 @@ def _refuse_with_grad(what: str) -> None:
                      "requires_grad" % what)
 
 
+_ROW_ARRAYS = ("points", "scales", "quaternions", "opacity")
+# what a differentiable frame's forward saw of the state its backward reads again (_pending_snapshot / _check_pending)
+_PendingState = namedtuple("_PendingState", "scene image_idx image pose_version gaussians bands arrays original_index "
+                                            "row_of_index")
+
+
+def _raw_active_sh_degree(g) -> int:
+    return int(getattr(g, "active_sh_degree", int(g.sh_degree)))
+
+
+def _pending_snapshot(scene, image_idx, points, scales, quaternions, opacity, colors, sh) -> _PendingState:
+    """What the backward of a differentiable frame of view ``image_idx`` will read again from the live scene and cannot
+    otherwise verify, as the forward saw it: the view's ``GaussianImage`` and its ``pose_version``; on an SH scene
+    (``sh`` given) ``sh_degree`` and the checked active degree; the storage address and shape of the five arrays the
+    forward was given (``colors``, or ``sh`` on an SH scene); the ``original_index`` / ``row_of_index`` tensors; the
+    container itself.  Host values only: nothing is read from the device.  The arrays are kept alive by the caller
+    (``save_for_backward``), so an address cannot be handed out again while the frame is pending."""
+    g = scene.gaussians
+    image = scene.images[image_idx]
+    bands = None if sh is None else (int(g.sh_degree), scene._active_sh_degree())
+    given = dict(zip(_ROW_ARRAYS, (points, scales, quaternions, opacity)))
+    given["colors" if sh is None else "sh"] = colors if sh is None else sh
+    arrays = tuple((name, int(t.data_ptr()), tuple(t.shape)) for name, t in given.items())
+    return _PendingState(scene, image_idx, image, int(getattr(image, "pose_version", 0)), g, bands, arrays,
+                         getattr(g, "original_index", None), getattr(g, "row_of_index", None))
+
+
+def _check_pending(state: _PendingState) -> None:
+    """The comparison to ``_pending_snapshot``, before a backward launches anything: RuntimeError naming the view and what
+    changed -- ``pose`` (the view's image was replaced, or ``set_world2view`` was called, with whatever matrix),
+    ``active_sh_degree`` / ``sh_degree``, or the array that was REPLACED (another storage or another shape).  An edit in
+    place is not looked for here: autograd's version counters report it.  No device read, no synchronisation."""
+    scene, idx = state.scene, state.image_idx
+
+    def refuse(what: str) -> None:
+        raise RuntimeError("the backward of the frame of view %r was refused: %s changed between its forward and its "
+                           "backward, and the backward reads the live scene again (projection, depth order and binning "
+                           "are recomputed): render the frame again and call backward on the new one" % (idx, what))
+
+    image = scene.images.get(idx) if hasattr(scene.images, "get") else scene.images[idx]
+    if image is not state.image or int(getattr(image, "pose_version", 0)) != state.pose_version:
+        refuse("the pose (GaussianImage.set_world2view)")
+    g = scene.gaussians
+    if g is not state.gaussians:
+        refuse("scene.gaussians (the container was replaced)")
+    if state.bands is not None:
+        if getattr(g, "sh", None) is None or int(g.sh_degree) != state.bands[0]:
+            refuse("gaussians.sh_degree")
+        if _raw_active_sh_degree(g) != state.bands[1]:
+            refuse("gaussians.active_sh_degree (%d at the forward, %d now)" % (state.bands[1], _raw_active_sh_degree(g)))
+    elif getattr(g, "sh", None) is not None:
+        refuse("gaussians.sh (an RGB scene at the forward)")
+    for name, address, shape in state.arrays:
+        t = getattr(g, name, None)
+        if not torch.is_tensor(t) or int(t.data_ptr()) != address or tuple(t.shape) != shape:
+            refuse("gaussians.%s (the array was replaced: %s at the forward, %s now)"
+                   % (name, shape, tuple(t.shape) if torch.is_tensor(t) else None))
+    for name, seen in (("original_index", state.original_index), ("row_of_index", state.row_of_index)):
+        if getattr(g, name, None) is not seen:
+            refuse("gaussians.%s (the row order)" % name)
+
+
 class _RenderImageFunction(torch.autograd.Function):
     """The ref_cpu frame as a function of (points, scales, quaternions, opacity, colors, sh); ``sh`` is None for an RGB
     scene.  Forward: the frame ``render_image_hip`` returns without gradients, bit for bit.  Backward:
@@ -303,8 +365,14 @@ class _RenderImageFunction(torch.autograd.Function):
     ``scene.screen_statistics`` = (image_idx, dL/d(NDC mean) (N,2), screen radius (N,)) left for ``DensityControl``; with
     ``screen_statistics="abs"`` gsx_render_backward_screen_abs, the same and a fourth entry, the absolute statistic (N,2).  An SH scene: the library is handed this camera's evaluated colours, so its dL/dcolors is dL/d(view-dependent
     colour), and gsx_sh_backward carries that on to dL/dsh and -- with geometry gradients -- adds the view direction's
-    share to dL/dpoints; ``colors`` gets None (the frame does not read it).  The tensors are saved, so autograd's version
-    counters catch an in-place edit between forward and backward.  ``world2view`` (None unless ``camera_gradients=True``
+    share to dL/dpoints; ``colors`` gets None (the frame does not read it).  The backward does not use what the forward computed:
+    it reads the live scene again (the arrays, the row order, the view's camera, the active SH degree) and trusts only
+    the forward's counts.  Two checks hold the two together.  The tensors are saved, so autograd's version counters catch
+    an edit IN PLACE between forward and backward (autograd's error).  ``_check_pending`` catches what autograd cannot
+    see -- ``set_world2view`` on the view, ``active_sh_degree`` / ``sh_degree`` changed, an array, the row order or the
+    container REPLACED (``densify_and_prune``, ``relocate``, an assignment) -- and refuses the backward by name
+    (RuntimeError) before anything is launched.  Frames of other views, tile sizes or scenes rendered in between change
+    nothing.  ``world2view`` (None unless ``camera_gradients=True``
     and the view's tensor requires grad) gets the total derivative of the pose: gsx_render_backward_camera's
     dL/dworld2view + dL/dfull_proj @ projection_matrix^T, plus, on an SH scene, the camera centre's share."""
 
@@ -323,12 +391,14 @@ class _RenderImageFunction(torch.autograd.Function):
         ctx.scene, ctx.image_idx, ctx.tile_size, ctx.layout = scene, image_idx, tile_size, layout
         ctx.n_instances, ctx.n_visible = int(st["n_instances"]), int(st["n_visible"])
         ctx.has_sh = sh is not None
+        ctx.pending = _pending_snapshot(scene, image_idx, points, scales, quaternions, opacity, colors, sh)
         ctx.save_for_backward(points, scales, quaternions, opacity, colors, frame, *((sh,) if ctx.has_sh else ()))
         return frame
 
     @staticmethod
     def backward(ctx, grad_frame):
         points, scales, quaternions, opacity, colors, frame = ctx.saved_tensors[:6]
+        _check_pending(ctx.pending)         # before any library call: the backward reads the live scene again
         scene = ctx.scene
         want = ctx.needs_input_grad
         # the colour-only call gives the same colour and opacity bits; the screen entry runs whoever requires grad
@@ -374,7 +444,9 @@ class _RenderImageFunction(torch.autograd.Function):
 class _RenderImageDepthFunction(torch.autograd.Function):
     """(frame, depth image) of the ref_cpu frame as a function of (points, scales, quaternions, opacity, colors, sh): the
     frame of ``_RenderImageFunction`` and gsx_render_depth's (D, A).  Backward: gsx_render_backward_depth, once, for
-    dL/dframe and dL/ddepth together (either may be missing: zeros); the SH share as in ``_RenderImageFunction``."""
+    dL/dframe and dL/ddepth together (either may be missing: zeros); the SH share as in ``_RenderImageFunction``, and the
+    same two checks between forward and backward: autograd's version counters for an edit in place, ``_check_pending`` for a
+    pose, an SH degree or an array that was replaced."""
 
     @staticmethod
     def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh):
@@ -387,12 +459,14 @@ class _RenderImageDepthFunction(torch.autograd.Function):
         ctx.n_instances, ctx.n_visible = int(st["n_instances"]), int(st["n_visible"])
         depth = scene._render_depth(image_idx, tile_size, layout, ctx.n_instances, ctx.n_visible)
         ctx.has_sh = sh is not None
+        ctx.pending = _pending_snapshot(scene, image_idx, points, scales, quaternions, opacity, colors, sh)
         ctx.save_for_backward(points, scales, quaternions, opacity, colors, frame, depth, *((sh,) if ctx.has_sh else ()))
         return frame, depth
 
     @staticmethod
     def backward(ctx, grad_frame, grad_depth):
         points, scales, quaternions, opacity, colors, frame, depth = ctx.saved_tensors[:7]
+        _check_pending(ctx.pending)
         scene = ctx.scene
         want = ctx.needs_input_grad
         if grad_frame is None:
@@ -629,14 +703,20 @@ class GaussianScene:
         under the reference's autograd).  ``geometry_gradients=True`` also records gradients when only ``points``,
         ``scales`` or ``quaternions`` require grad, and delivers dL/dpoints, dL/dscales and dL/dquaternions
         (gsx_render_backward_geometry) to those of the three that do.  The frame is the same bits either way.
+        Several differentiable frames -- of other views, through ``render_image_depth_hip`` too -- may be pending before the
+        first ``backward()``; each backward recomputes its view from the live scene, so ``set_world2view`` on the view, another
+        ``active_sh_degree``, or a parameter array REPLACED (``DensityControl.densify_and_prune``, ``MCMCControl.relocate``, an
+        assignment) between a frame's forward and its backward is refused by name (RuntimeError: render the frame again); an
+        edit in place is autograd's own error.
         An SH scene is differentiable when ``gaussians.sh`` requires grad: dL/dsh (gsx_sh_backward) and dL/dopacity, and
         with ``geometry_gradients=True`` the geometry too, dL/dpoints including the share that reaches the mean through the
         view direction; an SH scene whose ``sh`` does not require grad is refused when gradients are asked for.
         ``screen_statistics`` (needs ``geometry_gradients=True``): when the frame is differentiable its ``backward()`` runs
         gsx_render_backward_screen -- whichever tensors require grad -- and leaves ``scene.screen_statistics`` =
         (image_idx, dL/d(NDC mean) (N,2), screen radius in pixels (N,)), one row per row of the container, zeros for a
-        Gaussian the frame listed on no tile; every such backward replaces it, ``DensityControl(statistic="screen")``
-        consumes it.  It is the rasteriser's share, the published ``viewspace_points.grad[:, :2]``: an SH scene's
+        Gaussian the frame listed on no tile; every such backward replaces it -- with several such frames pending the slot
+        holds the view whose backward ran LAST, which is autograd's choice, not the order of the forwards --,
+        ``DensityControl(statistic="screen")`` consumes it.  It is the rasteriser's share, the published ``viewspace_points.grad[:, :2]``: an SH scene's
         view-direction term (gsx_sh_backward) reaches ``points.grad`` only.  Gradients and frame are the same bits either way.
         ``screen_statistics="abs"``: the backward runs gsx_render_backward_screen_abs instead and leaves a 4-tuple, the three
         entries above -- the same bits -- and the ABSOLUTE statistic (N,2): per component the sum over the Gaussian's pixels of

@@ -43,10 +43,10 @@ def _grads(scene, W, tile=16, **kw):
     return frame.detach(), g.colors.grad.detach().clone(), g.opacity.grad.detach().clone()
 
 
-def _oracle_pre(scene, sc):
+def _oracle_pre(scene, sc, idx=1):
     from oracle import c_oracle, cpu_ref
 
-    im = scene.images[1]
+    im = scene.images[idx]
     c = im.gsx_camera()
     cam = cpu_ref.Camera(im.world2view.cpu().numpy(), im.full_proj_transform.cpu().numpy(), np.float32(c.tan_fovx),
                          np.float32(c.tan_fovy), np.float32(c.fx), np.float32(c.fy), c.width, c.height)

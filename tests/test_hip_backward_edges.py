@@ -21,9 +21,9 @@ pytestmark = pytest.mark.gpu
 KEPT_MAX_256 = 1536 * 1024      # gsx_sort.hip kKeptMax256: above it (without a kept hint) the depth sort takes LSD
 
 
-def _check(scene, sc, frame, W, tile, gc, go, tag, tiles=None):
+def _check(scene, sc, frame, W, tile, gc, go, tag, tiles=None, idx=1):
     """gc, go against the restatement: per Gaussian (TOL) and max-normalised (REL).  frame, W: (width, height, 3)."""
-    pre = _oracle_pre(scene, sc)
+    pre = _oracle_pre(scene, sc, idx)
     n = sc["points"].shape[0]
     w, h = int(sc["width"]), int(sc["height"])
     as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)  # noqa: E731

@@ -35,23 +35,23 @@ def _same(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
-def _entry(scene, W, tile=16, screen=True, camera=True):
+def _entry(scene, W, tile=16, screen=True, camera=True, idx=1):
     """(frame, outputs of the backward entry) for dL/dframe = W: gsx_render_backward_camera, or the screen / geometry
     entry without ``camera``.  The camera entry's last two outputs are dL/dworld2view and dL/dfull_proj."""
     st = {}
     with torch.no_grad():
-        frame = scene.render_image_hip(1, tile_size=tile, stats=st)
-        outs = scene._render_backward(1, tile, "wh3", frame, W, int(st["n_instances"]), int(st["n_visible"]), geometry=True,
+        frame = scene.render_image_hip(idx, tile_size=tile, stats=st)
+        outs = scene._render_backward(idx, tile, "wh3", frame, W, int(st["n_instances"]), int(st["n_visible"]), geometry=True,
                                       screen=screen, camera=camera)
     return frame, outs, st
 
 
-def _restate(scene, sc, frame, W, tile):
+def _restate(scene, sc, frame, W, tile, idx=1):
     """(gV, gF, scale of gV, scale of gF) float64 of the frame the kernel rendered."""
-    pre = _oracle_pre(scene, sc)
+    pre = _oracle_pre(scene, sc, idx)
     w, h = int(sc["width"]), int(sc["height"])
     mom = gbr.moments(pre, frame.cpu().numpy(), W.cpu().numpy(), w, h, tile)
-    args = (pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene), None, None, w, h, tile)
+    args = (pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene, idx), None, None, w, h, tile)
     return cgr.camera_backward(*args, moments=mom) + cgr.camera_backward(*args, absolute=True, moments=mom)
 
 

@@ -52,7 +52,7 @@ def _np(t):
     return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
 
-def _depth_grads(scene, W, Wd, tile=16, only=None, **kw):
+def _depth_grads(scene, W, Wd, tile=16, only=None, idx=1, **kw):
     """(frame, depth, {name: gradient}) of L = <W, frame> + <Wd, depth> for the five tensors (only: those named).  W or
     Wd None: that image is not used by the loss."""
     g = scene.gaussians
@@ -60,7 +60,7 @@ def _depth_grads(scene, W, Wd, tile=16, only=None, **kw):
         t = getattr(g, name)
         t.requires_grad_(only is None or name in only)
         t.grad = None
-    frame, depth = scene.render_image_depth_hip(1, tile_size=tile, **kw)
+    frame, depth = scene.render_image_depth_hip(idx, tile_size=tile, **kw)
     assert frame.grad_fn is not None and depth.grad_fn is not None
     loss = 0
     if W is not None:
@@ -75,13 +75,13 @@ def _depth_grads(scene, W, Wd, tile=16, only=None, **kw):
     return frame.detach(), depth.detach(), out
 
 
-def _check(scene, sc, frame, depth, W, Wd, tile, grads, tag, fixture=None):
+def _check(scene, sc, frame, depth, W, Wd, tile, grads, tag, fixture=None, idx=1):
     """The five gradients against the restatement (12 E_REF per output) and, with `fixture`, against the reference's
     autograd (13 E_REF), per Gaussian.  Returns the restatement's result (five gradients, five scales)."""
-    pre = _oracle_pre(scene, sc)
+    pre = _oracle_pre(scene, sc, idx)
     w, h = int(sc["width"]), int(sc["height"])
     n = sc["points"].shape[0]
-    out = dr.depth_backward(pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene), _np(frame), _np(W), _np(depth),
+    out = dr.depth_backward(pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene, idx), _np(frame), _np(W), _np(depth),
                             _np(Wd), w, h, tile, with_scale=True)
     got = [_np(grads[name]).astype(np.float64).reshape(n, -1) for name in NAMES]
     errs = dr.per_output_errors(got, out[:5], out[5:])

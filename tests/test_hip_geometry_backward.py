@@ -32,15 +32,15 @@ def _W(shape, seed):
     return torch.from_numpy(np.random.default_rng(seed).standard_normal(shape).astype(np.float32)).to(DEV)
 
 
-def _all_grads(scene, W, tile=16, geometry=True, only=None, **kw):
-    """(frame, {name: gradient}) of L = <W, frame> for the five tensors (only: those named)."""
+def _all_grads(scene, W, tile=16, geometry=True, only=None, idx=1, **kw):
+    """(frame, {name: gradient}) of L = <W, frame> of view `idx` for the five tensors (only: those named)."""
     g = scene.gaussians
     names = GEOMETRY + ("colors", "opacity")
     for name in names:
         t = getattr(g, name)
         t.requires_grad_(only is None or name in only)
         t.grad = None
-    frame = scene.render_image_hip(1, tile_size=tile, geometry_gradients=geometry, **kw)
+    frame = scene.render_image_hip(idx, tile_size=tile, geometry_gradients=geometry, **kw)
     (frame * W).sum().backward()
     out = {name: (None if getattr(g, name).grad is None else getattr(g, name).grad.detach().clone()) for name in names}
     for name in names:
@@ -49,22 +49,22 @@ def _all_grads(scene, W, tile=16, geometry=True, only=None, **kw):
     return frame.detach(), out
 
 
-def _camera(scene):
+def _camera(scene, idx=1):
     from oracle import cpu_ref
 
-    im = scene.images[1]
+    im = scene.images[idx]
     c = im.gsx_camera()
     return cpu_ref.Camera(im.world2view.cpu().numpy(), im.full_proj_transform.cpu().numpy(), np.float32(c.tan_fovx),
                           np.float32(c.tan_fovy), np.float32(c.fx), np.float32(c.fy), c.width, c.height)
 
 
-def _check(scene, sc, frame, W, tile, grads, tag, tiles=None, fixture=None):
+def _check(scene, sc, frame, W, tile, grads, tag, tiles=None, fixture=None, idx=1):
     """The three geometry gradients against the restatement (12 E_REF per output) and, with `fixture`, against the
     reference's autograd (13 E_REF), per Gaussian.  Returns the restatement's gradients."""
-    pre = _oracle_pre(scene, sc)
+    pre = _oracle_pre(scene, sc, idx)
     w, h = int(sc["width"]), int(sc["height"])
     as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)  # noqa: E731
-    out = gbr.geometry_backward(pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene), as_np(frame), as_np(W),
+    out = gbr.geometry_backward(pre, sc["points"], sc["scales"], sc["quaternions"], _camera(scene, idx), as_np(frame), as_np(W),
                                 w, h, tile, tiles=tiles, with_scale=True)
     for k, name in enumerate(GEOMETRY):
         got = as_np(grads[name]).astype(np.float64)

@@ -142,14 +142,14 @@ def _sh_scene(tmp_path, degree, seed=11):
 NAMES = ("points", "scales", "quaternions", "opacity", "colors", "sh")
 
 
-def _grads(scene, W, want, geometry):
+def _grads(scene, W, want, geometry, idx=1):
     g = scene.gaussians
     for name in NAMES:
         t = getattr(g, name)
         if t is not None:
             t.requires_grad_(name in want)
             t.grad = None
-    frame = scene.render_image_hip(1, geometry_gradients=geometry)
+    frame = scene.render_image_hip(idx, geometry_gradients=geometry)
     (frame * W).sum().backward()
     out = {name: (None if getattr(g, name) is None or getattr(g, name).grad is None else getattr(g, name).grad.detach().clone())
            for name in NAMES}
