@@ -121,6 +121,11 @@ class GsxDensityRules(ctypes.Structure):
                 ("split_shrink", c_float), ("flags", ctypes.c_uint32)]
 
 
+class GsxTransform(ctypes.Structure):
+    _fields_ = [("R", c_float * 9), ("s", c_float), ("t", c_float * 3), ("q_R", c_float * 4),
+                ("M1", c_float * 9), ("M2", c_float * 25), ("M3", c_float * 49)]
+
+
 # name -> (restype, argtypes); every symbol include/gsx.h declares.
 _FP = c_void_p  # device float*
 SIGNATURES = {
@@ -189,6 +194,7 @@ SIGNATURES = {
                                       c_void_p]),
     "gsx_knn3_workspace_bytes": (c_size_t, [c_int64]),
     "gsx_knn3": (ctypes.c_int, [_FP, c_int64, c_void_p, c_int32, _FP, _FP, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
+    "gsx_transform_gaussians": (ctypes.c_int, [_FP, _FP, _FP, _FP, c_int32, c_int64, POINTER(GsxTransform), c_void_p]),
 }
 
 # csrc/gsx_debug.h

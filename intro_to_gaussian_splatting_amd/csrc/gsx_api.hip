@@ -995,6 +995,40 @@ int gsx_adam_step(const GsxAdamGroup *groups, int32_t n_groups, int64_t n, int64
     return GSX_OK;
 }
 
+int gsx_transform_gaussians(float *points, float *scales, float *quaternions, float *sh, int32_t sh_degree, int64_t n,
+                            const GsxTransform *transform, void *stream) {
+    if (n < 0) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is negative", (long long)n);
+    if (n > (int64_t)0x7fffffff * kTransformRows)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is more than 2^31 - 1 blocks of %d rows", (long long)n, kTransformRows);
+    if (sh_degree < 0 || sh_degree > 3) return fail(GSX_ERR_INVALID_ARGUMENT, "sh_degree = %d is outside 0..3", sh_degree);
+    if (!transform) return fail(GSX_ERR_INVALID_ARGUMENT, "transform is NULL");
+    static_assert(sizeof(GsxTransform) == 100 * sizeof(float), "GsxTransform is 100 floats without padding");
+    const struct { const char *name; const float *v; int count; } fields[] = {
+        {"R", transform->R, 9},   {"s", &transform->s, 1},   {"t", transform->t, 3},   {"q_R", transform->q_R, 4},
+        {"M1", transform->M1, 9}, {"M2", transform->M2, 25}, {"M3", transform->M3, 49}};
+    for (const auto &f : fields)
+        for (int i = 0; i < f.count; ++i)
+            if (!(f.v[i] >= -FLT_MAX && f.v[i] <= FLT_MAX))         // (a NaN fails both)
+                return fail(GSX_ERR_INVALID_ARGUMENT, "transform->%s[%d] = %g is not finite", f.name, i, (double)f.v[i]);
+    if (!(transform->s > 0.0f)) return fail(GSX_ERR_INVALID_ARGUMENT, "transform->s = %g is not positive", (double)transform->s);
+    if (n == 0) return GSX_OK;
+    if (!points) return fail(GSX_ERR_INVALID_ARGUMENT, "points is NULL");
+    if (!scales) return fail(GSX_ERR_INVALID_ARGUMENT, "scales is NULL");
+    if (!quaternions) return fail(GSX_ERR_INVALID_ARGUMENT, "quaternions is NULL");
+    if (sh_degree > 0 && !sh) return fail(GSX_ERR_INVALID_ARGUMENT, "sh is NULL with sh_degree = %d", sh_degree);
+    TransformArgs a;
+    memset(&a, 0, sizeof a);
+    a.points = points;
+    a.scales = scales;
+    a.quats = quaternions;
+    a.sh = sh_degree > 0 ? sh : nullptr;
+    a.n = n;
+    a.vec = (reinterpret_cast<uintptr_t>(sh) & 15u) == 0;
+    a.T = *transform;
+    GSX_HIP(gsx::launch_transform(a, sh_degree, (hipStream_t)stream));
+    return GSX_OK;
+}
+
 int gsx_density_accumulate(const float *grad, int32_t width, int64_t n, float *grad_sum, uint32_t *seen, void *stream) {
     if (n < 0 || n > kDensityMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
     if (width < 1 || width > kDensityMaxWidth)

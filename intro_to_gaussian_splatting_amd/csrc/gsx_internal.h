@@ -358,6 +358,18 @@ struct AdamArgs {
 };
 hipError_t launch_adam(const AdamArgs &args, bool skip_zero_rows, hipStream_t s);
 
+// ---- gsx_transform.hip
+// gsx_transform_gaussians behind its argument checks.  One workgroup per kTransformRows rows; the whole struct is the kernel's
+// argument (the matrices are read with scalar loads).
+constexpr int kTransformRows = 256;             // kAdamRows, sh::kBlock, block_bounds
+struct TransformArgs {
+    float *points, *scales, *quats, *sh;        // sh: nullptr when degree == 0
+    int64_t n;
+    int32_t vec;                                // sh is 16-byte aligned
+    GsxTransform T;
+};
+hipError_t launch_transform(const TransformArgs &args, int degree, hipStream_t s);
+
 // ---- gsx_density.hip
 // gsx_density_accumulate / _plan / _apply behind their argument checks.  The workspace of n rows (DensityCarve):
 //   header  kDensityHeader bytes: int64 n, n_out, n_pruned, n_cloned, n_split; float split_shrink at kDensityShrinkAt

@@ -59,7 +59,8 @@ from .optim import GROUP_NAMES, GaussianAdam
 from .pose import CameraRefiner
 
 EVENT_NAMES = ("densify", "opacity_reset", "sh_oneup")
-# the published rates (Kerbl et al. 2023); the position rate is per unit of scene extent there: scale it for the scene
+# the published rates (Kerbl et al. 2023); the position rate is per unit of scene extent there: scale it for the scene, or
+# move the scene into those units once, before the fit: GaussianScene.normalize()
 DEFAULT_LR = {"points": 1.6e-4, "scales": 5e-3, "quaternions": 1e-3, "opacity": 5e-2, "colors": 2.5e-3, "sh": 2.5e-3}
 DEFAULT_OPACITY_RESET_LOGIT = math.log(0.01 / 0.99)         # the published reset: opacity at most 0.01
 STRATEGIES = ("adaptive", "mcmc")

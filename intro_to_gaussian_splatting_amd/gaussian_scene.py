@@ -1157,6 +1157,66 @@ class GaussianScene:
         self._last_instances = 0
         self.screen_statistics = None       # its rows were the old rows
 
+    # ------------------------------------------------------------------ the world's frame
+    def _move_views(self, sim) -> None:
+        """Every view follows the world transform ``sim`` (x' = s R x + t) so that it sees what it saw.  With the view's
+        rigid pose x_view = Rc x + T (``world2view`` is its transpose, row-vector convention): x = R^T (x' - t) / s, and the
+        new RIGID pose is the one with x'_view = s x_view: Rc' = Rc R^T (orthonormal: s is not folded into it),
+        T' = s T - Rc' t; the last column of ``world2view`` stays (0, 0, 0, 1).  Float64 on the host, rounded once."""
+        import numpy as np
+
+        for image in self.images.values():
+            V = image.world2view.detach().to("cpu", torch.float64).numpy()
+            Rc, T = V[:3, :3].T, V[3, :3]
+            Rn = Rc @ sim.R.T
+            W = np.zeros((4, 4))
+            W[:3, :3] = Rn.T
+            W[3, :3] = sim.s * T - Rn @ sim.t
+            W[3, 3] = 1.0
+            image.set_world2view(torch.from_numpy(W.astype(np.float32)))
+
+    def transform(self, R, s: float = 1.0, t=None):
+        """Re-expresses the whole scene in the world ``x' = s R x + t``: the Gaussians (``Gaussians.transform``: one
+        gsx_transform_gaussians launch) AND every view (``set_world2view``), so that every frame is unchanged -- up to
+        rounding, and up to the discrete decisions rounding can flip (a tile rectangle's edge, a cull, a depth tie).
+        View space is SCALED by ``s``: view-space depths, ``render_image_depth_hip``'s D, and the distances the near
+        (z_view >= 0.2) and far tests compare all grow by ``s``; coverage does not change.  ``depth_targets`` of a fit are
+        the caller's to scale.  Everything kept per view from earlier frames is dropped (``gaussians_changed``); a frame
+        captured earlier (``capture_frame``) has the old camera baked in: capture it again, or ``set_camera`` one that was
+        captured with ``movable_camera=True``.  Adam
+        moments, ``DensityControl`` / ``MCMCControl`` statistics and thresholds are not touched: transform before a fit or
+        after one.  Returns the validated ``transform.Similarity`` (unpacks as ``(R, s, t)``)."""
+        from .transform import similarity
+
+        sim = similarity(R, s, t)
+        self.gaussians.transform(*sim)
+        self._move_views(sim)
+        self.gaussians_changed()
+        return sim
+
+    def cameras_extent(self):
+        """``(center, radius)``: the normalisation of the published 3D Gaussian Splatting trainer -- the mean of the camera
+        centres (float64 numpy, (3,)) and 1.1 x the largest distance of a camera centre from it (a float)."""
+        import numpy as np
+
+        centers = np.array([image.camera_center_host for image in self.images.values()], dtype=np.float64).reshape(-1, 3)
+        center = centers.mean(axis=0)
+        radius = 1.1 * float(np.sqrt(((centers - center[None, :]) ** 2).sum(axis=1)).max())
+        return center, radius
+
+    def normalize(self):
+        """Moves the scene into the frame the published trainer's rates and thresholds are quoted in: the camera centres'
+        mean at the origin and ``cameras_extent()[1] == 1`` (``s = 1 / radius``, ``t = -center / radius``, ``R = I``).
+        ``DEFAULT_LR``'s position rate, ``DensityControl(dense_scale=, prune_scale=)`` and ``MCMCControl(noise_lr=)`` then
+        apply as quoted.  Returns the triple: ``scene.transform(*transform.inverse(triple))`` puts the scene back, before
+        ``save_trained`` for instance.  Refused when all cameras share one centre (radius 0)."""
+        import numpy as np
+
+        center, radius = self.cameras_extent()
+        if not radius > 0.0:
+            raise ValueError("cameras_extent() has radius %r: the scene has no extent to normalise by" % (radius,))
+        return self.transform(np.eye(3), 1.0 / radius, -center / radius)
+
     def _pinned_slot(self) -> torch.Tensor:
         """One 64-byte slot of a pinned ring (pinning memory per frame would dominate the frame)."""
         if self._pinned_pool is None:

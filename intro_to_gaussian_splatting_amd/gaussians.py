@@ -210,6 +210,60 @@ class Gaussians:
             else:
                 self.scales.copy_(scale.expand(n, 3))
 
+    def transform(self, R, s: float = 1.0, t=None) -> None:
+        """Moves the container into the world ``x' = s R x + t`` (``R`` a proper rotation, ``s > 0``; validated by
+        ``transform.similarity``), IN PLACE, in one library call (gsx_transform_gaussians, include/gsx.h):
+        ``points' = s R p + t``, ``scales' = s scales``, ``quaternions' = q_R (x) q`` (not renormalised) and, for an SH
+        container, every STORED band of ``sh`` rotated by the matrices of ``transform.sh_rotation_matrices`` -- whatever
+        ``active_sh_degree`` is -- so that the colour seen along ``R d`` is the colour that was seen along ``d``.
+        ``opacity`` and ``colors`` do not change.  The library writes through raw pointers; the tensors' versions are
+        bumped, so a spatially ordered container's ``current_block_bounds()`` recomputes.  ``.grad``s are left as they are,
+        and an optimiser's moments are NOT rotated (``exp_avg_sq`` is not covariant): transform before a fit or after one.
+        Cameras do not move: ``GaussianScene.transform`` moves them along."""
+        import ctypes
+
+        from . import _ffi
+        from .transform import sh_rotation_matrices, similarity
+
+        sim = similarity(R, s, t)
+        n = len(self)
+        degree = int(self.sh_degree) if self.sh is not None else 0
+        arrays = [("points", self.points, 3), ("scales", self.scales, 3), ("quaternions", self.quaternions, 4)]
+        if self.sh is not None:
+            if not 0 <= degree <= 3:
+                raise ValueError("sh_degree = %r is outside 0..3" % (self.sh_degree,))
+            arrays.append(("sh", self.sh, 3 * (degree + 1) ** 2))
+        dev = self.points.device
+        for name, a, width in arrays:
+            if a.device.type != "cuda":
+                raise ValueError("%s is on %s: transform runs only as a HIP kernel on an AMD GPU (torch device 'cuda'); "
+                                 "there is no CPU fallback" % (name, a.device))
+            if a.device != dev:
+                raise ValueError("%s is on %s, points on %s" % (name, a.device, dev))
+            if a.dtype != torch.float32 or not a.is_contiguous() or a.shape[0] != n or a.numel() != n * width:
+                raise ValueError("%s must be a contiguous float32 tensor of %d rows of %d" % (name, n, width))
+            if torch.is_grad_enabled() and not a.is_leaf:
+                raise ValueError("%s is not a leaf and gradients are enabled: an in-place transform would invalidate the "
+                                 "graph that made it; detach it or call transform under torch.no_grad()" % name)
+        T = _ffi.GsxTransform()
+        T.R[:] = [float(v) for v in sim.R.reshape(-1)]
+        T.s = sim.s
+        T.t[:] = [float(v) for v in sim.t]
+        T.q_R[:] = [float(v) for v in sim.q]
+        for field, M in zip(("M1", "M2", "M3"), sh_rotation_matrices(sim.R)):
+            getattr(T, field)[:] = [float(v) for v in M.reshape(-1)]
+        if n == 0:              # (an empty tensor has no address to hand over)
+            return
+        with torch.cuda.device(dev):
+            rc = _ffi.load().gsx_transform_gaussians(
+                self.points.data_ptr(), self.scales.data_ptr(), self.quaternions.data_ptr(),
+                self.sh.data_ptr() if self.sh is not None else None, degree, n, ctypes.byref(T),
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _ffi.check(rc)
+        # the library wrote through raw pointers: tell torch (current_block_bounds reads _version)
+        for _, a, _ in arrays:
+            torch.autograd.graph.increment_version(a)
+
     def get_3d_covariance_matrix(self) -> torch.Tensor:
         """(N,3,3) Sigma = (R S)(R S)^T, computed on the GPU (gsx_covariance_3d); same result as the
         reference's method (splat/gaussians.py:54-69).  The render path does not call this (the
