@@ -28,7 +28,8 @@ def _rotation(qvec) -> np.ndarray:
 def make_scene(n: int, width: int, height: int, seed: int = 0, behind_fraction: float = 0.0,
                qvec=TREEHILL_QVEC, tvec=TREEHILL_TVEC, spread: float = 1.0,
                sigma_scale: float = 1.0, cluster_fraction: float = 0.0, cluster_area: float = 0.05,
-               cluster_center=(0.35, -0.2), sigma_ln: float = 0.5) -> Dict[str, np.ndarray]:
+               cluster_center=(0.35, -0.2), sigma_ln: float = 0.5, fx: float = None,
+               fy: float = None) -> Dict[str, np.ndarray]:
     """Returns float32 arrays ``points (n,3)``, ``colors_0_255 (n,3)``, ``scales (n,3)`` (linear),
     ``quaternions (n,4)`` (w,x,y,z, unnormalised), ``opacity (n,1)`` (logit) plus the camera
     ``qvec, tvec, fx, fy, cx, cy, width, height``.
@@ -37,7 +38,9 @@ def make_scene(n: int, width: int, height: int, seed: int = 0, behind_fraction: 
     additionally moves that share of the points behind the z >= 0.2 cull plane (drawn last, so
     the default stream is unchanged).  ``spread`` > 1 places points up to that multiple of the
     frustum's half-width off axis (beyond 1.3 the EWA clamp of splat/utils.py:336-337 is active),
-    ``sigma_scale`` scales the footprints; both leave the random stream untouched.
+    ``sigma_scale`` scales the footprints; both leave the random stream untouched.  ``fx``, ``fy`` (pixels; each
+    defaults to ``0.75 * width``) give the camera unequal focal lengths: the points are placed in its own frustum
+    (``tanx``, ``tany``), the footprints are sized by ``fx``; neither draws anything.
 
     Heavy-tailed variant (not a BASELINE config; trained scenes are never uniform): ``cluster_fraction`` of
     the Gaussians (chosen by one more uniform draw, after everything else) are moved into a window of
@@ -46,7 +49,8 @@ def make_scene(n: int, width: int, height: int, seed: int = 0, behind_fraction: 
     ``cluster_fraction=0.5, cluster_area=0.05, sigma_ln=1.0`` gives tile lists whose longest is ~20x the mean.
     """
     rs = np.random.RandomState(seed)
-    fx = fy = 0.75 * width
+    fx = 0.75 * width if fx is None else float(fx)
+    fy = 0.75 * width if fy is None else float(fy)
     tanx, tany = width / (2 * fx), height / (2 * fy)
     z = rs.uniform(2.0, 10.0, n)
     u = rs.uniform(-1.0, 1.0, n)
@@ -82,7 +86,7 @@ def make_scene(n: int, width: int, height: int, seed: int = 0, behind_fraction: 
 
 
 def make_trained_like_scene(n: int, width: int, height: int, seed: int = 0, qvec=TREEHILL_QVEC, tvec=TREEHILL_TVEC,
-                            sh_degree: int = 3) -> Dict[str, np.ndarray]:
+                            sh_degree: int = 3, fx: float = None, fy: float = None) -> Dict[str, np.ndarray]:
     """A scene with the statistics of a TRAINED 3DGS checkpoint rather than of a uniform cloud (BASELINE config 3 as
     written is a trained Treehill ``.ply``, which is not available offline; not a BASELINE config itself):
       * view-clustered: 65 % of the Gaussians sit in 24 clusters (surfaces) of different size and depth, the rest is
@@ -92,9 +96,11 @@ def make_trained_like_scene(n: int, width: int, height: int, seed: int = 0, qvec
       * bimodal opacity: half nearly transparent (logit ~ N(-3, 1)), half nearly opaque (logit ~ N(4, 1.5));
       * degree-``sh_degree`` spherical harmonics (published 3DGS convention): DC from a base colour, higher bands
         ~ N(0, 0.15 / (1 + band)) -- view-dependent colour, clamped at 0 by the evaluation like a trained one.
-    Same fields as ``make_scene`` plus ``sh (n, (sh_degree+1)^2, 3)``; a stream of its own (seed + 7919)."""
+    Same fields as ``make_scene`` plus ``sh (n, (sh_degree+1)^2, 3)``; a stream of its own (seed + 7919).  ``fx``, ``fy``
+    as in ``make_scene``."""
     rs = np.random.RandomState(seed + 7919)
-    fx = fy = 0.75 * width
+    fx = 0.75 * width if fx is None else float(fx)
+    fy = 0.75 * width if fy is None else float(fy)
     tanx, tany = width / (2 * fx), height / (2 * fy)
     n_cl = 24
     cl_u, cl_v = rs.uniform(-0.85, 0.85, n_cl), rs.uniform(-0.85, 0.85, n_cl)
@@ -177,11 +183,13 @@ def make_tie_scene(n: int, width: int, height: int, seed: int = 0, levels: int =
     return sc
 
 
-def make_few_visible_scene(n: int, width: int, height: int, seed: int = 0, visible: int = 2) -> Dict[str, np.ndarray]:
+def make_few_visible_scene(n: int, width: int, height: int, seed: int = 0, visible: int = 2,
+                           **camera) -> Dict[str, np.ndarray]:
     """``make_scene`` with all but the first ``visible`` Gaussians moved behind the camera (view depth -1 .. -3): the
     reference then multiplies at most three Jacobians at once in ``J @ W`` (splat/utils.py:354), which its BLAS sums in
-    another order than larger batches (oracle/probe_torch_order.py; GSX_FLAG_SMALL_BATCH in include/gsx.h)."""
-    sc = make_scene(n=n, width=width, height=height, seed=seed)
+    another order than larger batches (oracle/probe_torch_order.py; GSX_FLAG_SMALL_BATCH in include/gsx.h).  ``camera``:
+    ``make_scene``'s ``qvec``, ``tvec``, ``fx``, ``fy``."""
+    sc = make_scene(n=n, width=width, height=height, seed=seed, **camera)
     R, t = _rotation(sc["qvec"]), np.asarray(sc["tvec"], dtype=np.float64)
     rs = np.random.RandomState(seed + 15485863)
     m = n - visible

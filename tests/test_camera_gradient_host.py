@@ -109,19 +109,23 @@ def _with(cam, V=None, F=None):
 
 
 def test_restatement_matches_central_differences_of_a_float64_forward():
-    """Each of the 12 + 12 free entries of world2view and full_proj perturbed by +-h on a scene of three Gaussians: the
-    central difference of test_geometry_backward_host._loss64 (float64 stage 1, frozen lists and depth order) against
-    the restatement's gradient of that forward.  An entry whose perturbation flips a stop decision is dropped."""
+    """On a scene of three Gaussians."""
+    assert fixture_inputs("rows3_48x48_n3")[1]["points"].shape[0] <= 6
+    central_differences("rows3_48x48_n3")
+
+
+def central_differences(name):
+    """Each of the 12 + 12 free entries of world2view and full_proj perturbed by +-h: the central difference of
+    test_geometry_backward_host._loss64 (float64 stage 1, frozen lists and depth order) against the restatement's gradient
+    of that forward.  An entry whose perturbation flips a stop decision is dropped, at most 2 of the 24."""
     from oracle import cpu_ref
 
-    name = "rows3_48x48_n3"
     gg, base = fixture_inputs(name)
     fwd = forward_fixture(name)
     pre, cam32 = golden_preprocessed(fwd), oracle_camera(fwd)
     cam = _with(cam32, np.asarray(cam32.world2view, np.float64), np.asarray(cam32.full_proj, np.float64))
     w, h, tile = int(base["width"]), int(base["height"]), int(base["tile"])
     W = base["W"]
-    assert base["points"].shape[0] <= 6
     lists = {}
     for x0 in cpu_ref.tile_origins(w, tile):
         for y0 in cpu_ref.tile_origins(h, tile):
@@ -160,7 +164,8 @@ def test_restatement_matches_central_differences_of_a_float64_forward():
             fd = (Ls[0] - Ls[1]) / (2 * FD_H)
             worst = max(worst, abs(fd - grads[key][k, c]) / scale)
             assert abs(fd - grads[key][k, c]) <= FD_TOL * scale, (key, k, c, fd, grads[key][k, c])
-    print("finite differences: %d entries, %d dropped for a stop flip, worst |fd - grad| / max|grad| = %.3g" % (tried, dropped, worst))
+    print("%s: finite differences: %d entries, %d dropped for a stop flip, worst |fd - grad| / max|grad| = %.3g" % (
+        name, tried, dropped, worst))
     assert tried == 24 and dropped <= 2
     # the structural zeros: the forward does not read those columns at all
     for key, col in (("V", 3), ("F", 2)):

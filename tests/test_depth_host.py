@@ -135,6 +135,10 @@ def _theta_forward(pre, theta, cam, w, h, tile, tiles=None):
 
 
 def test_restatement_matches_central_differences_of_its_float64_forward():
+    central_differences("tile2_40x32_n80")
+
+
+def central_differences(name):
     """Every coordinate of FD_GAUSSIANS Gaussians -- 3 of the point, 3 scales, 4 of the quaternion, the opacity logit --
     perturbed by +-h: the central difference of L = <W, frame> + <W_D, D> + <W_A, A> against the restatement's gradient,
     to FD_TOL of the row's largest entry.  Lists, order and stop decisions are held at the unperturbed float32 values, so
@@ -142,7 +146,6 @@ def test_restatement_matches_central_differences_of_its_float64_forward():
     others cancel exactly), which keeps the rounding of L itself out of it."""
     from oracle import cpu_ref
 
-    name = "tile2_40x32_n80"
     dg, base, fwd = depth_fixture(name)
     pre, cam = golden_preprocessed(fwd), oracle_camera(fwd)
     w, h, tile = int(base["width"]), int(base["height"]), int(base["tile"])
@@ -182,7 +185,7 @@ def test_restatement_matches_central_differences_of_its_float64_forward():
                 tried += 1
                 worst = max(worst, abs(fd - g) / scale)
                 assert abs(fd - g) <= FD_TOL * scale, (key, int(row), j, fd, g)
-    print("finite differences: %d coordinates, none dropped, worst |fd - grad| / max|grad row| = %.3g" % (tried, worst))
+    print("%s: finite differences: %d coordinates, none dropped, worst |fd - grad| / max|grad row| = %.3g" % (name, tried, worst))
     assert tried == FD_GAUSSIANS * 11
 
 

@@ -37,6 +37,10 @@ GEOM_SCENES = ["tile2_40x32_n80", "small_64x48_n300", "small_80x64_n120_tile8", 
 STANDALONE = ("wide_64x64_n400", "cull_96x80_n400")     # no grad_ fixture: the geomgrad_ file carries its own inputs
 # no forward fixture either: the geomgrad_ file also carries the reference's own stage 1 (camera constants, pre_ arrays)
 OWN_STAGE1 = ("rows1_48x48_n1", "rows3_48x48_n3", "rows1_48x48_n500", "rows3_48x48_n500")
+# the scenes at the cameras of tests/camera_cases.py are stored the same way; tests/test_camera_cases_host.py holds them to
+# their own E_REF_CAM, so they are not in GEOM_SCENES
+CAMERA_SCENES = ("cam_aniso_64x48_n120", "cam_aniso_tall_48x64_n100", "cam_farpose_64x48_n120", "cam_roll_64x48_n100")
+OWN_STAGE1 += CAMERA_SCENES
 OUTPUTS = ("points", "scales", "quaternions")
 E_REF = {"points": 2.171e-8, "scales": 4.687e-7, "quaternions": 3.790e-9}
 BOUND_RESTATEMENT = {k: 12 * v for k, v in E_REF.items()}
@@ -179,14 +183,17 @@ def _loss64(pre, lists, points, scales, quats, cam, W, tile, stops=None):
 
 
 def test_restatement_matches_central_differences_of_a_float64_forward():
+    central_differences("tile2_40x32_n80")
+
+
+def central_differences(name):
     """Every coordinate of FD_GAUSSIANS Gaussians (10 numbers each) perturbed by +-h: the central difference of the
     float64 forward against the restatement's gradient.  Tile lists and depth order are held fixed, so no rectangle can
     flip; a coordinate whose perturbation changes any pixel's stop decision is dropped, at most 10 % of them."""
     from oracle import cpu_ref
 
-    name = "tile2_40x32_n80"
     gg, base = fixture_inputs(name)
-    fwd = load_golden(name)
+    fwd = forward_fixture(name)
     pre, cam = golden_preprocessed(fwd), oracle_camera(fwd)
     w, h, tile = int(base["width"]), int(base["height"]), int(base["tile"])
     W = base["W"]
@@ -235,8 +242,8 @@ def test_restatement_matches_central_differences_of_a_float64_forward():
                 scale = np.abs(grads[key][row]).max()
                 worst = max(worst, abs(fd - g) / scale)
                 assert abs(fd - g) <= FD_TOL * scale, (key, int(row), j, fd, g)
-    print("finite differences: %d coordinates, %d dropped for a stop flip, worst |fd - grad| / max|grad row| = %.3g" % (
-        tried, dropped, worst))
+    print("%s: finite differences: %d coordinates, %d dropped for a stop flip, worst |fd - grad| / max|grad row| = %.3g" % (
+        name, tried, dropped, worst))
     assert tried == FD_GAUSSIANS * 10 and dropped <= tried // 10
 
 

@@ -239,7 +239,11 @@ def test_world2view_grad_is_the_total_derivative_composed_by_hand(tmp_path):
 def test_sh_scene_adds_the_camera_centre_s_share(tmp_path):
     from test_hip_sh_active import _scene as _sh_scene
 
-    scene = _sh_scene(tmp_path, 300, 2)
+    camera_centre_share(_sh_scene(tmp_path, 300, 2))
+
+
+def camera_centre_share(scene):
+    """The check on any SH scene."""
     g, im = scene.gaussians, scene.images[1]
     with torch.no_grad():
         target = (scene.render_image_hip(1) * 0.5 + 0.1).clone()

@@ -163,9 +163,14 @@ def _grads(scene, W, want, geometry, idx=1):
 
 @pytest.mark.parametrize("degree", [0, 1, 2, 3])
 def test_sh_scene_gradients_are_the_rgb_scene_s_carried_one_link_further(tmp_path, degree):
+    scene, W = _sh_scene(tmp_path, degree)
+    carried_one_link_further(tmp_path, scene, W, degree)
+
+
+def carried_one_link_further(tmp_path, scene, W, degree):
+    """The check on any SH scene built in ``tmp_path`` (its COLMAP files are read again for the RGB scene)."""
     from intro_to_gaussian_splatting_amd import GaussianScene
 
-    scene, W = _sh_scene(tmp_path, degree)
     g = scene.gaussians
     n, k = g.points.shape[0], (degree + 1) ** 2
     with torch.no_grad():

@@ -34,11 +34,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from capture_geometry_grad_golden import OWN_STAGE1, _weight  # noqa: E402
+from capture_geometry_grad_golden import CAMERA_ENTRY_SCENES, OWN_STAGE1, _weight  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "rows3_48x48_n500", "tile2_40x32_n80", "small_64x48_n300", "tile20_64x64_n300",
           "cull_96x80_n400"]
+SCENES += CAMERA_ENTRY_SCENES       # fx != fy and far poses (tests/camera_cases.py)
 
 
 class _Leaves:

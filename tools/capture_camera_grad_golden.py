@@ -35,7 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from capture_geometry_grad_golden import BRANCHES, OWN_STAGE1, STANDALONE, _weight, branch_counts  # noqa: E402
+from capture_geometry_grad_golden import BRANCHES, CAMERA_ENTRY_SCENES, OWN_STAGE1, STANDALONE, _weight, branch_counts  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "tile2_40x32_n80", "small_64x48_n300", "cull_96x80_n400", "wide_64x64_n400",
@@ -43,6 +43,7 @@ SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "tile2_40x32_n80", "small_64x48_n3
           "tiny_48x48_n600",
           # three visible of 500: the small row class with culled rows around it
           "rows3_48x48_n500"]
+SCENES += CAMERA_ENTRY_SCENES       # fx != fy and far poses (tests/camera_cases.py)
 # Not in the set: the other geomgrad_ scenes.  The graph through the geometry needs minutes and many GB each (needle, 110
 # Gaussians: over 21 GB); the eight above hit every branch.  Name one on the command line on a machine with the memory and
 # the time.

@@ -37,12 +37,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from capture_geometry_grad_golden import OWN_STAGE1, STANDALONE, _weight  # noqa: E402
+from capture_geometry_grad_golden import CAMERA_ENTRY_SCENES, OWN_STAGE1, STANDALONE, _weight  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["tile2_40x32_n80", "tiny_48x48_n600", "small_64x48_n300", "cull_96x80_n400", "rows1_48x48_n1", "rows3_48x48_n3",
           # a tile of more than 256 pixels: the tile kernels take it in two chunks
           "tile20_64x64_n300"]
+SCENES += CAMERA_ENTRY_SCENES       # fx != fy and far poses (tests/camera_cases.py)
 # Not in the set: the other geomgrad_ scenes.  Each needs two graphs through the geometry, minutes and many GB apiece
 # (needle, 110 Gaussians: over 21 GB for one); name one on the command line on a machine with the memory and the time.
 EXTRA = ["small_80x64_n120_tile8", "tile12_dense_52x40_n900", "tile32_96x96_n400", "wide_64x64_n400", "needle_160x160_n110",

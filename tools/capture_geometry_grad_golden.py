@@ -14,6 +14,7 @@ their file also holds the scene arguments, W, the image, grad_colors and grad_op
 three visible Gaussians, each on a rendered tile) have no forward fixture either: the reference renders them a second
 time with its ORIGINAL compute_gaussian_weight under no_grad, the two images must be equal bit for bit, and their file
 also holds the reference's camera constants and PreprocessedScene arrays under the keys of oracle/capture_golden.py.
+The scenes of CAMERA_SCENES (unequal focal lengths, far poses: the cameras of tests/camera_cases.py) are treated likewise.
 
     python tools/capture_geometry_grad_golden.py            # all scenes
     python tools/capture_geometry_grad_golden.py tile2      # only those whose name contains "tile2"
@@ -53,6 +54,23 @@ OWN_STAGE1 = {
     "rows1_48x48_n500": dict(n=500, width=48, height=48, seed=41, tile=16, generator="few", visible=1),
     "rows3_48x48_n500": dict(n=500, width=48, height=48, seed=43, tile=16, generator="few", visible=3),
 }
+# The cameras of tests/camera_cases.py (unequal focal lengths, far poses); treated like OWN_STAGE1.  Each scene lies in its
+# camera's own frustum.  aniso: floored determinants (footprints of a quarter of the usual size); aniso_tall: the clamp
+# with limx != limy; farpose: the cull.  roll keeps the usual footprints: the central differences of tests/test_depth_host.py step by 5e-5 of
+# a world unit, which a footprint well below a pixel does not resolve to their 1e-7.
+CAMERA_SCENES = {
+    "cam_aniso_64x48_n120": dict(n=120, width=64, height=48, seed=75, tile=16, fx=40.0, fy=62.0, sigma_scale=0.25,
+                                 sigma_ln=0.8),
+    "cam_aniso_tall_48x64_n100": dict(n=100, width=48, height=64, seed=73, tile=16, fx=70.0, fy=30.0,
+                                      qvec=(0.8, 0.3, -0.45, 0.25), tvec=(-0.7, 0.2, 2.1), spread=2.0, sigma_scale=3.0),
+    "cam_farpose_64x48_n120": dict(n=120, width=64, height=48, seed=79, tile=16, fx=48.0, fy=48.0,
+                                   qvec=(0.35, 0.6, -0.55, 0.46), tvec=(0.4, -0.9, 1.5), behind_fraction=0.25),
+    "cam_roll_64x48_n100": dict(n=100, width=64, height=48, seed=89, tile=16, fx=36.0, fy=52.0,
+                                qvec=(0.05, 0.1, -0.08, 0.99), tvec=(-0.3, 0.5, 2.0)),
+}
+# the two of them that also get camera, depth, screen and abs fixtures (tools/capture_{camera,depth,screen,abs}_grad_golden.py)
+CAMERA_ENTRY_SCENES = ["cam_aniso_tall_48x64_n100", "cam_roll_64x48_n100"]
+OWN_STAGE1.update(CAMERA_SCENES)
 SCENES += list(OWN_STAGE1)
 BRANCHES = ("n_floored_det", "n_clamped", "n_culled")
 
@@ -182,10 +200,10 @@ def capture(name: str, GaussianScene, Gaussians, original_weight=None) -> None:
               np.abs(gq).max(), qdot, t_fwd, t_bwd, os.path.getsize(path) / 1024), flush=True)
 
 
-def check_branches() -> None:
-    """Every branch of the table must be hit by at least one committed file."""
+def check_branches(names=None) -> None:
+    """Every branch of the table must be hit by at least one committed file of ``names`` (all scenes unless given)."""
     total = dict.fromkeys(BRANCHES, 0)
-    for name in SCENES:
+    for name in names or SCENES:
         path = os.path.join(OUT_DIR, "geomgrad_" + name + ".npz")
         if os.path.exists(path):
             z = np.load(path)
@@ -210,6 +228,7 @@ def main() -> None:
                 capture(name, GaussianScene, Gaussians, original_weight)
     if only in ("", "--check"):
         check_branches()
+        check_branches(list(CAMERA_SCENES))         # the camera scenes hit every branch on their own
 
 
 if __name__ == "__main__":
