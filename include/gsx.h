@@ -546,6 +546,40 @@ GSX_API int gsx_render_backward_depth(const GsxCamera *camera, const float *mean
 GSX_API size_t gsx_backward_depth_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
 
 /*
+ * BUILD EXTENSION -- gradients of the GSX_SEM_STD_3DGS frame (the published rule set: 0.3 dilation, alpha clamped at 0.99,
+ * the 1/255 skip, stop before the pair with T (1 - alpha) < 1e-4, background behind the last Gaussian).
+ * params->semantics must be GSX_SEM_STD_3DGS; params->background and GSX_FLAG_PUBLISHED_RECTS are honoured as in
+ * gsx_render_forward, so the tile lists are that frame's.  image: the frame gsx_render_forward wrote for these inputs and
+ * params (whole frame, params->layout); grad_image: dL/dimage, same layout.  Per pixel the forward's walk is repeated with
+ * the forward's operations and its three decisions; with g = dL/dpixel and F the pixel (T_fin background included):
+ *     dL/dc_k = T_k alpha_k g        dL/dalpha_k = T_k (c_k . g) - (F - C_k) . g / (1 - alpha_k)
+ * and u_k = dL/dalpha_k alpha_k where the clamp is inactive (opacity exp(power) < 0.99f), 0 where it is active: a clamped
+ * pair reaches its colour only.  dL/dlogit = (sum u)(1 - opacity), opacity = sigmoid(logit) once.  dL/dbackground is not
+ * computed.
+ * grad_means3d, grad_scales, grad_quats: all three or all NULL (NULL: the colour-only kernel runs; grad_colors and
+ * grad_opacity_logit are the same bits either way).  With them the moments of u reach the inputs through the rule set's own
+ * stage 1: quaternion normalised once, the dilation a constant, conic = adj / det without a floor, p_w = 1 / (w + 1e-7),
+ * pixel = ((ndc + 1) dim - 1) / 2, the 1.3 tan(fov / 2) clamp decided on float32 values formed in stage 1's order.
+ * grad_means2d (n,2) and screen_radius (n): both or both NULL, and only with the geometry three: dL/d(NDC mean) =
+ * dL/d(pixel mean) * (width / 2, height / 2) and the published radius ceil(3 sqrt(lambda_max)) in pixels, as
+ * gsx_density_accumulate_screen reads them.
+ * Every output row is written: exact zeros for a Gaussian that is culled or on no tile list.  Projection, depth order and
+ * binning are run again; GsxParams.hints is not touched; synchronises `stream`.  Refused like gsx_render_backward: tile
+ * window, output window, substrips, GSX_FLAG_NO_SYNC, camera_device, params->sh -- and any semantics but
+ * GSX_SEM_STD_3DGS.  Bad arguments are refused by name before any HIP call.  No float atomics: same inputs, same bits.
+ * workspace: gsx_backward_std_workspace_bytes.
+ */
+GSX_API int gsx_render_backward_std(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                                    const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                                    const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                                    float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                                    float *screen_radius, const GsxParams *params, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+
+/* Bytes of device workspace gsx_render_backward_std needs, with or without the geometry outputs (0 on invalid arguments). */
+GSX_API size_t gsx_backward_std_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =
  * (R S)(R S)^T from linear scales (n,3) and quaternions (n,4) (w,x,y,z), the quaternion
  * normalised twice as the reference does.  The render entry points compute this inline; the

@@ -160,6 +160,9 @@ SIGNATURES = {
     "gsx_render_backward_depth": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 11 +
                                   [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
     "gsx_backward_depth_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),
+    "gsx_render_backward_std": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 9 +
+                                [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
+    "gsx_backward_std_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),
     "gsx_covariance_3d": (ctypes.c_int, [_FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_covariance_2d": (ctypes.c_int, [POINTER(GsxCamera), _FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_project_points": (ctypes.c_int, [POINTER(GsxCamera), _FP, c_int64, _FP, c_void_p, c_void_p]),

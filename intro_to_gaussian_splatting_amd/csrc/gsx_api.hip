@@ -516,6 +516,86 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
     return GSX_OK;
 }
 
+// gsx_render_backward_std: render_backward's order of work on the GSX_SEM_STD_3DGS frame.  The forward's chain leaves the
+// packed records the std tile kernels read (no raw projection); the workspace is the geometry entry's.
+int render_backward_std(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                        const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, const float *image,
+                        const float *grad_image, float *grad_colors, float *grad_opacity_logit, float *grad_means3d,
+                        float *grad_scales, float *grad_quats, float *grad_means2d, float *screen_radius,
+                        const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const char *entry = "gsx_render_backward_std";
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    if (!params) return fail(GSX_ERR_INVALID_ARGUMENT, "params is NULL: %s needs params->semantics = GSX_SEM_STD_3DGS", entry);
+    if (!image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
+    Plan p;
+    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
+    if (rc != GSX_OK) return rc;
+    if (p.semantics != GSX_SEM_STD_3DGS)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s: params->semantics must be GSX_SEM_STD_3DGS", entry);
+    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
+    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s renders the whole frame: no tile window", entry);
+    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes the whole frame: no output window", entry);
+    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take substrips", entry);
+    if (params->flags & GSX_FLAG_NO_SYNC) return fail(GSX_ERR_INVALID_ARGUMENT, "%s synchronises: no GSX_FLAG_NO_SYNC", entry);
+    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "%s reads the camera argument: no camera_device", entry);
+    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
+    if (rc != GSX_OK) return rc;
+    if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
+    const int n_geo = (grad_means3d != nullptr) + (grad_scales != nullptr) + (grad_quats != nullptr);
+    if (n_geo != 0 && n_geo != 3)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats: all three or none");
+    const bool geo = n_geo == 3;
+    if ((grad_means2d != nullptr) != (screen_radius != nullptr))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d / screen_radius: both or none");
+    if (grad_means2d && !geo)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d and screen_radius need grad_means3d, grad_scales and grad_quats");
+    Carve c;
+    int64_t cap;
+    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, kCarveGeometry);
+    if (rc != GSX_OK) return rc;
+    char *ws = (char *)workspace;
+    // every row of every output: a Gaussian on no tile list has zero gradients
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_colors, (size_t)n * 3, s));
+    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_opacity_logit, (size_t)n, s));
+    if (geo) {
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_means3d, (size_t)n * 3, s));
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_scales, (size_t)n * 3, s));
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_quats, (size_t)n * 4, s));
+        if (grad_means2d) {
+            GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_means2d, (size_t)n * 2, s));
+            GSX_HIP(gsx::launch_zero_words((uint32_t *)screen_radius, (size_t)n, s));
+        }
+    }
+    if (n == 0 || p.grid.count() == 0) {
+        GSX_HIP(hipStreamSynchronize(s));
+        return GSX_OK;
+    }
+    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
+    const uint32_t *order, *sorted_vals;
+    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
+    int64_t counts[3];
+    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
+    if (rc != GSX_OK) return rc;
+    const uint32_t m = (uint32_t)counts[2];
+    if (m == 0 || counts[1] == 0) return GSX_OK;
+    const gsx::Record *rec = (const gsx::Record *)(ws + c.rec);
+    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
+    float4 *slots = (float4 *)(ws + c.slots), *geo_slots = geo ? (float4 *)(ws + c.geo_slots) : nullptr;
+    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
+    const gsx::BackwardTiles bt{rec, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots,
+                                  geo_slots};
+    GSX_HIP(gsx::launch_backward_tiles_std(bt, p.grid, p.out, s));
+    GSX_HIP(gsx::launch_backward_sums_std(slots, prefix, order, rec, m, grad_colors, grad_opacity_logit, s));
+    if (geo)
+        GSX_HIP(gsx::launch_backward_geometry_std(*camera, geo_slots, prefix, order, m, means3d, scales, quats, grad_means3d,
+                                                  grad_scales, grad_quats, grad_means2d, screen_radius, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -721,6 +801,21 @@ int gsx_render_backward_screen_abs(const GsxCamera *camera, const float *means3d
     geo.means2d_abs = grad_means2d_abs;
     return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
                            grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+}
+
+size_t gsx_backward_std_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveGeometry);
+}
+
+int gsx_render_backward_std(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                            const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                            const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
+                            float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
+                            float *screen_radius, const GsxParams *params, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+    return render_backward_std(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
+                               grad_colors, grad_opacity_logit, grad_means3d, grad_scales, grad_quats, grad_means2d,
+                               screen_radius, params, workspace, workspace_bytes, stream);
 }
 
 size_t gsx_backward_camera_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {

@@ -162,6 +162,7 @@ __device__ __forceinline__ float wave_sum2(float a, float b, int lane) {
 
 // backward_tile_kernel, backward_tile_geometry_kernel, backward_tile_depth_kernel and backward_tile_abs_kernel: one text,
 // four instances (gsx_backward_tile.inc)
+#define GSX_TILE_STD 0
 #define GSX_TILE_KERNEL backward_tile_kernel
 #define GSX_TILE_GEOMETRY false
 #define GSX_TILE_DEPTH 0
@@ -198,6 +199,29 @@ __device__ __forceinline__ float wave_sum2(float a, float b, int lane) {
 #undef GSX_TILE_DEPTH
 #undef GSX_TILE_ABS
 #undef GSX_TILE_ATTR
+#undef GSX_TILE_STD
+// the two GSX_SEM_STD_3DGS instances (gsx_render_backward_std): colour-only, and geometry held to the geometry instance's
+// occupancy
+#define GSX_TILE_STD 1
+#define GSX_TILE_DEPTH 0
+#define GSX_TILE_ABS 0
+#define GSX_TILE_KERNEL backward_tile_std_kernel
+#define GSX_TILE_GEOMETRY false
+#define GSX_TILE_ATTR
+#include "gsx_backward_tile.inc"
+#undef GSX_TILE_KERNEL
+#undef GSX_TILE_GEOMETRY
+#undef GSX_TILE_ATTR
+#define GSX_TILE_KERNEL backward_tile_std_geometry_kernel
+#define GSX_TILE_GEOMETRY true
+#define GSX_TILE_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
+#include "gsx_backward_tile.inc"
+#undef GSX_TILE_KERNEL
+#undef GSX_TILE_GEOMETRY
+#undef GSX_TILE_DEPTH
+#undef GSX_TILE_ABS
+#undef GSX_TILE_ATTR
+#undef GSX_TILE_STD
 
 // gsx_render_depth: (D, A) = (sum T alpha z, sum T alpha) of every pixel of every window tile, by the backward's walk --
 // one wave per tile, four pixels per lane, 64 records staged per batch, a tile of more than 256 pixels in chunks,
@@ -305,6 +329,33 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// gsx_render_backward_std: backward_sum_kernel on the packed GSX_SEM_STD_3DGS record, b = (Q''11, op, r, g) with
+// op = sigmoid(logit) applied ONCE: dL/dlogit = (sum u) (1 - op).  The slots are summed in the same order.
+__global__ void __launch_bounds__(256)
+    backward_std_sum_kernel(const float4 *__restrict__ slots, const uint32_t *__restrict__ prefix,
+                            const uint32_t *__restrict__ order, const Record *__restrict__ rec, uint32_t m,
+                            float *__restrict__ grad_colors, float *__restrict__ grad_opacity_logit) {
+    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= m) return;
+    const uint32_t b = prefix[r], e = prefix[r + 1];
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
+        const float4 v = slots[i];
+        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
+    }
+    const float v = wave_sum4(a0, a1, a2, a3, lane);
+    const float g = __shfl(v, 16), bl = __shfl(v, 32), u = __shfl(v, 48);
+    if (lane == 0) {
+        const uint32_t row = order[r];
+        const float op = rec[row].b.y;
+        grad_colors[3 * (int64_t)row] = v;
+        grad_colors[3 * (int64_t)row + 1] = g;
+        grad_colors[3 * (int64_t)row + 2] = bl;
+        grad_opacity_logit[row] = u * (1.0f - op);
+    }
+}
+
 // ---- gsx_render_backward_geometry: from a Gaussian's moment sums to dL/dpoint, dL/dscale, dL/dquaternion.
 // What stage 1 computes (gsx_project.hip: project), differentiated by hand in float32.  With d = mean - pixel,
 // power = -1/2 d^T Q d and u = dL/dpower:
@@ -320,6 +371,12 @@ __global__ void __launch_bounds__(256)
 // The branch decisions of (1) and (2) are taken on float32 values computed by the forward's operations in the forward's
 // order (ewa_covariance and finish_projection of gsx_project.hip, rows class kRowsMany); the rest of the forward values
 // this needs are recomputed in whatever order is shortest: they enter the gradient as factors, not as decisions.
+// kStd (gsx_render_backward_std): the same chain through GSX_SEM_STD_3DGS's stage 1 (gsx_project.hip: project_std), which
+// differs in five places -- (4) the quaternion is normalised once; (2) cov00 += 0.3 and cov11 += 0.3, constants, and the one
+// off-diagonal entry c01 serves for both (c10 = c01), so its gradient is the sum of the two; (1) Q = adj / det with no floor;
+// (5) pixel mean = ((h_xy p_w + 1) dim - 1) / 2 with p_w = 1 / (h_w + 1e-7), so d pixel / d ndc = dim / 2 (cam.sx, cam.sy)
+// and the focal lengths are dim / (2 tan(fov / 2)) (cam.fx, cam.fy).  The packed record holds Q'' = -1/2 log2(e) Q, not Q:
+// the conic is formed here as project_std forms it, and so is the published radius ceil(3 sqrt(lambda_max)) (*rad).
 struct GeoCamera {
     float V[16], F[16];            // world2view, full_proj (row vector times matrix)
     float fx, fy, limx, limy, sx, sy;   // focal lengths, 1.3 tan(fov / 2), (width - 1) / 2, (height - 1) / 2
@@ -328,20 +385,23 @@ struct GeoCamera {
 // kCamera (gsx_render_backward_camera): also this Gaussian's 24 terms of dL/dworld2view and dL/dfull_proj into gc, the
 // chain's own g_t, dT and gh contracted with the point instead of with the matrices (kCamTerms, below).  The other
 // instance is the text it was: gc is never touched.
-template <bool kCamera>
+template <bool kCamera, bool kStd = false>
 __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float *__restrict__ p, const float *__restrict__ sc,
                                                const float *__restrict__ qin, const float4 QA, const float4 QB,
                                                float S1, float S2, float S3, float S4, float S5, float *__restrict__ gp,
                                                float *__restrict__ gs, float *__restrict__ gq, float *__restrict__ gn,
-                                               float *__restrict__ gc) {
+                                               float *__restrict__ gc, float *__restrict__ rad = nullptr) {
     const float *V = cam.V, *F = cam.F;
     const float p0 = p[0], p1 = p[1], p2 = p[2];
     // ---- forward values
     // rotation, as covariance3d (gsx_project.hip) forms it
     const float n1 = fmaxf(sqrtf(((qin[0] * qin[0] + qin[1] * qin[1]) + qin[2] * qin[2]) + qin[3] * qin[3]), 1e-12f);
     const float a0 = qin[0] / n1, a1 = qin[1] / n1, a2 = qin[2] / n1, a3 = qin[3] / n1;
-    const float n2 = sqrtf(((a0 * a0 + a1 * a1) + a2 * a2) + a3 * a3);
-    const float w = a0 / n2, x = a1 / n2, y = a2 / n2, z = a3 / n2;
+    float n2 = 1.0f, w = a0, x = a1, y = a2, z = a3;
+    if constexpr (!kStd) {
+        n2 = sqrtf(((a0 * a0 + a1 * a1) + a2 * a2) + a3 * a3);
+        w = a0 / n2; x = a1 / n2; y = a2 / n2; z = a3 / n2;
+    }
     float R[3][3], M[3][3], Sg[3][3];
     R[0][0] = 1.0f - 2.0f * (y * y + z * z);
     R[0][1] = 2.0f * (x * y - w * z);
@@ -388,13 +448,28 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             C[i][j] = __builtin_fmaf(B[i][2], V[2 * 4 + j], __builtin_fmaf(B[i][1], V[1 * 4 + j], B[i][0] * V[0 * 4 + j]));
-    const float ca = C[0][0] * j00 + C[0][2] * j02, cb = C[0][1] * j11 + C[0][2] * j12;
-    const float cc = C[1][0] * j00 + C[1][2] * j02, cd = C[1][1] * j11 + C[1][2] * j12;
+    float ca = C[0][0] * j00 + C[0][2] * j02, cb = C[0][1] * j11 + C[0][2] * j12;
+    float cc = C[1][0] * j00 + C[1][2] * j02, cd = C[1][1] * j11 + C[1][2] * j12;
+    if constexpr (kStd) {
+        ca = ca + 0.3f;
+        cd = cd + 0.3f;
+        cc = cb;
+    }
     const float det_raw = ca * cd - cb * cc;
-    const float det = fmaxf(det_raw, 1e-3f);
-    const bool floored = det_raw < 1e-3f;
+    const float det = kStd ? det_raw : fmaxf(det_raw, 1e-3f);
+    const bool floored = !kStd && det_raw < 1e-3f;
     // ---- compositing: dL/dQ and dL/dmean (Q as the record stores it)
-    const float q00 = QA.z, q01 = QA.w, q10 = QB.x, q11 = QB.y;
+    float q00 = QA.z, q01 = QA.w, q10 = QB.x, q11 = QB.y;
+    if constexpr (kStd) {       // the conic and the radius as project_std forms them
+        const float det_inv = 1.0f / det;
+        q00 = cd * det_inv;
+        q01 = -cb * det_inv;
+        q10 = q01;
+        q11 = ca * det_inv;
+        const float mid = 0.5f * (ca + cd);
+        const float root = sqrtf(fmaxf(0.1f, mid * mid - det));
+        *rad = ceilf(3.0f * sqrtf(fmaxf(mid + root, mid - root)));
+    }
     const float gq00 = -0.5f * S3, gq01 = -0.5f * S4, gq11 = -0.5f * S5;       // gq10 = gq01
     const float gmx = -0.5f * (2.0f * q00 * S1 + (q01 + q10) * S2);
     const float gmy = -0.5f * ((q01 + q10) * S1 + 2.0f * q11 * S2);
@@ -406,6 +481,10 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
         g_cd += g_det * ca;
         g_cb -= g_det * cc;
         g_cc -= g_det * cb;
+    }
+    if constexpr (kStd) {       // c10 = c01: one entry carries both
+        g_cb += g_cc;
+        g_cc = 0.0f;
     }
     // ---- (2): G = [[g_ca, g_cb], [g_cc, g_cd]]
     float GT[2][3], GtT[2][3];             // G T and G^T T
@@ -475,7 +554,8 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
     // ---- (5), (6)
     const float h0 = __builtin_fmaf(p2, F[8], __builtin_fmaf(p1, F[4], p0 * F[0])) + F[12];
     const float h1 = __builtin_fmaf(p2, F[9], __builtin_fmaf(p1, F[5], p0 * F[1])) + F[13];
-    const float h3 = __builtin_fmaf(p2, F[11], __builtin_fmaf(p1, F[7], p0 * F[3])) + F[15];
+    float h3 = __builtin_fmaf(p2, F[11], __builtin_fmaf(p1, F[7], p0 * F[3])) + F[15];
+    if constexpr (kStd) h3 = h3 + 0.0000001f;
     const float gn0 = gmx * cam.sx, gn1 = gmy * cam.sy;     // dL/d(NDC mean): gsx_render_backward_screen's grad_means2d
     gn[0] = gn0;
     gn[1] = gn1;
@@ -559,6 +639,38 @@ __global__ void __launch_bounds__(256)
         grad_means2d[2 * row] = gn[0];
         grad_means2d[2 * row + 1] = gn[1];
         if (screen_radius) screen_radius[row] = rec.c.w;
+    }
+}
+
+// gsx_render_backward_std: backward_geometry_chain_kernel with the chain's kStd variant.  The packed record has no raw
+// conic and no radius: the chain forms both (QA, QB are not read).
+__global__ void __launch_bounds__(256)
+    backward_std_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                              const uint32_t *__restrict__ order, uint32_t m, GeoCamera cam, const float *__restrict__ means3d,
+                              const float *__restrict__ scales, const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                              float *__restrict__ grad_scales, float *__restrict__ grad_quats, float *__restrict__ grad_means2d,
+                              float *__restrict__ screen_radius) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t b = prefix[r];
+    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
+    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
+    const int64_t row = order[r];
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float gp[3], gs[3], gq[4], gn[2], rad;
+    geometry_chain<false, true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, none, none, S.x, S.y, S.z, S.w, S5.x, gp,
+                                gs, gq, gn, nullptr, &rad);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        grad_means3d[3 * row + k] = gp[k];
+        grad_scales[3 * row + k] = gs[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
+    if (grad_means2d) {
+        grad_means2d[2 * row] = gn[0];
+        grad_means2d[2 * row + 1] = gn[1];
+        screen_radius[row] = rad;
     }
 }
 
@@ -764,6 +876,15 @@ hipError_t launch_backward_tiles(const BackwardTiles &bt, const TileGrid &grid, 
     return hipGetLastError();
 }
 
+hipError_t launch_backward_tiles_std(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s) {
+    if (grid.count() <= 0) return hipSuccess;
+    if (bt.geo_slots)
+        backward_tile_std_geometry_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
+    else
+        backward_tile_std_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_backward_tiles_abs(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s) {
     if (grid.count() <= 0) return hipSuccess;
     backward_tile_abs_kernel<<<(unsigned)grid.count(), 64, 0, s>>>(bt, grid, out);
@@ -829,6 +950,32 @@ hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, 
     }
     backward_geometry_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,
                                                           grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_sums_std(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *rec,
+                                    uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    backward_std_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(slots, prefix, order, rec, m, grad_colors,
+                                                                              grad_opacity_logit);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                        const uint32_t *order, uint32_t m, const float *means3d, const float *scales,
+                                        const float *quats, float *grad_means3d, float *grad_scales, float *grad_quats,
+                                        float *grad_means2d, float *screen_radius, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    GeoCamera cam = geo_camera(camera);
+    // project_std's focal lengths and d pixel / d ndc
+    cam.fx = (float)camera.width / (2.0f * camera.tan_fovx);
+    cam.fy = (float)camera.height / (2.0f * camera.tan_fovy);
+    cam.sx = (float)camera.width * 0.5f;
+    cam.sy = (float)camera.height * 0.5f;
+    backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
+    backward_std_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
+        geo_slots, prefix, order, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
+        screen_radius);
     return hipGetLastError();
 }
 

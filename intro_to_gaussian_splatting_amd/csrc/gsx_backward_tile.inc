@@ -1,8 +1,10 @@
-// The compositing backward's tile kernel, included four times by gsx_backward.hip (inside its anonymous namespace):
+// The compositing backward's tile kernel, included six times by gsx_backward.hip (inside its anonymous namespace):
 //   GSX_TILE_KERNEL = backward_tile_kernel,          GSX_TILE_GEOMETRY = false: gsx_render_backward's, the colour-only instance
 //   GSX_TILE_KERNEL = backward_tile_geometry_kernel, GSX_TILE_GEOMETRY = true:  gsx_render_backward_geometry's
 //   GSX_TILE_KERNEL = backward_tile_depth_kernel,    GSX_TILE_GEOMETRY = true, GSX_TILE_DEPTH = 1: gsx_render_backward_depth's
 //   GSX_TILE_KERNEL = backward_tile_abs_kernel,      GSX_TILE_GEOMETRY = true, GSX_TILE_ABS = 1: gsx_render_backward_screen_abs'
+//   GSX_TILE_KERNEL = backward_tile_std_kernel,      GSX_TILE_GEOMETRY = false, GSX_TILE_STD = 1: gsx_render_backward_std's, colour-only
+//   GSX_TILE_KERNEL = backward_tile_std_geometry_kernel, GSX_TILE_GEOMETRY = true, GSX_TILE_STD = 1: gsx_render_backward_std's
 // Plain kernels from one text rather than a template or a shared device function: the colour-only kernel keeps its
 // name and compiles to the instructions it had before the geometry instance existed, and both keep theirs beside the
 // depth instance, whose text sits in #if GSX_TILE_DEPTH blocks, and beside the abs instance, whose text sits in
@@ -28,6 +30,16 @@
 // Ty = sum |fmaf(q01 + q10, u d0, (2 q11) (u d1))|, u d0 and u d1 the very products S1 and S2 add up, into the free words of
 // the second float4: (S5, 0, Tx, Ty).  The factor 1/2 is left to backward_geometry_abs_sum_kernel.  Every other sum takes the
 // geometry instance's operations in its order.
+// STD (gsx_render_backward_std; GSX_TILE_STD = 1, text in #if GSX_TILE_STD blocks): backward_tile_std_kernel (colour-only)
+// and backward_tile_std_geometry_kernel walk the packed GSX_SEM_STD_3DGS records -- a = (x, y, Q''00, Qs''), b = (Q''11,
+// opacity, r, g), c.x = b, exponent in log2 units -- under that rule set.  Per (pixel, record): pw and alpha =
+// fminf(0.99f, op exp2(pw)) by the forward's operations (std_exponent), the forward's three decisions (std_tests: skip when
+// pw > 0, skip when alpha < 1/255, stop BEFORE accumulating when T - T alpha < 1e-4), C_k by the forward's fmafs and
+// T <- T - T alpha: the composited pairs are the forward's.  F is the forward's pixel, T_fin background included, so the
+// background's share of dL/dalpha = T (c . g) - (F - C_k) . g / (1 - alpha) needs no code (alpha <= 0.99: the division is
+// safe).  u = dL/dalpha alpha where the clamp is inactive (op exp2(pw) < 0.99f) and 0 where it is active: a clamped pair
+// adds to dL/dc only.  u = dL/d(natural exponent); the moments are formed from it and d = mean - pixel as in GEO.  Pixels
+// beyond the frame's width or height (partial edge tiles) start dead and read nothing.
 #if GSX_TILE_DEPTH
 __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTiles bt, TileGrid grid, OutDesc out, DepthTiles dt) {
 #else
@@ -65,7 +77,11 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
 #pragma unroll
         for (int j = 0; j < kNpx; ++j) {
             const int64_t p = chunk + j * 64 + lane;
+#if GSX_TILE_STD
+            live[j] = p < npx && tx * T + (int)(p % T) < grid.width && ty * T + (int)(p / T) < grid.height;
+#else
             live[j] = p < npx;
+#endif
             const int x = live[j] ? (int)(p % T) : 0, y = live[j] ? (int)(p / T) : 0;
             fx[j] = ox + (float)x;
             fy[j] = oy + (float)y;
@@ -126,6 +142,40 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
 #pragma unroll
                     for (int j = 0; j < kNpx; ++j) {
                         if (!live[j]) continue;
+#if GSX_TILE_STD
+                        const float e0 = A.x - fx[j], e1 = A.y - fy[j];
+                        const float pw = std_exponent(e0, e1, A.z, A.w, B.x);
+                        const float raw = B.y * __builtin_amdgcn_exp2f(pw);
+                        const float alpha = fminf(kStdAlphaMax, raw);
+                        float ta;
+                        bool use, stop;
+                        std_tests(pw, alpha, kStdAlphaMin, Tr[j], ta, use, stop);
+                        if (stop) {                     // the pixel stops before this record
+                            live[j] = false;
+                            continue;
+                        }
+                        if (!use) continue;             // skipped by one of the two skip rules
+                        C0[j] = __builtin_fmaf(ta, B.z, C0[j]);
+                        C1[j] = __builtin_fmaf(ta, B.w, C1[j]);
+                        C2[j] = __builtin_fmaf(ta, Cc.x, C2[j]);
+                        const float cg = (B.z * G0[j] + B.w * G1[j]) + Cc.x * G2[j];
+                        const float rest = ((F0[j] - C0[j]) * G0[j] + (F1[j] - C1[j]) * G1[j]) + (F2[j] - C2[j]) * G2[j];
+                        const float da = Tr[j] * cg - rest / (1.0f - alpha);
+                        d0 = __builtin_fmaf(ta, G0[j], d0);
+                        d1 = __builtin_fmaf(ta, G1[j], d1);
+                        d2 = __builtin_fmaf(ta, G2[j], d2);
+                        const float u = raw < kStdAlphaMax ? da * alpha : 0.0f;     // a clamped alpha is a constant
+                        du += u;
+                        if constexpr (GEO) {
+                            const float u0 = u * e0, u1 = u * e1;
+                            m1 += u0;
+                            m2 += u1;
+                            m3 = __builtin_fmaf(u0, e0, m3);
+                            m4 = __builtin_fmaf(u0, e1, m4);
+                            m5 = __builtin_fmaf(u1, e1, m5);
+                        }
+                        Tr[j] = Tr[j] - ta;
+#else
                         const float alpha = alpha_ref(A.x, A.y, A.z, A.w, B.x, B.y, B.z, fx[j], fy[j]);
                         const float ta = Tr[j] * alpha;
                         const float test = Tr[j] - ta;
@@ -168,6 +218,7 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
 #endif
                         }
                         Tr[j] = test;
+#endif
                     }
                 }
                 const float v = wave_sum4(d0, d1, d2, du, lane);

@@ -1350,13 +1350,12 @@ __global__ void __launch_bounds__(64)
 // the pixel is live, +inf once it has stopped (or lies outside the frame), so "alpha < thr" skips
 // everything for a dead pixel without a separate flag.  A skipped or stopping pair composites with
 // weight 0 -- fma(0, c, C) = C and T - 0 = T exactly -- which keeps the loop free of control flow.
-constexpr float kStdAlphaMin = 1.0f / 255.0f, kStdStop = 0.0001f;
-
+// (kStdAlphaMin, kStdStop and the three tests: std_tests in gsx_internal.h, shared with the backward's std instances.)
 __device__ __forceinline__ void std_composite(float pw, float alpha, float cr, float cg, float cb, float &thr, float &T,
                                               float &c0, float &c1, float &c2) {
-    const bool use = !(pw > 0.0f) && !(alpha < thr);
-    const float ta = T * alpha;
-    const bool stop = use && (T - ta < kStdStop);
+    bool use, stop;
+    float ta;
+    std_tests(pw, alpha, thr, T, ta, use, stop);
     const float w = (use && !stop) ? ta : 0.0f;
     thr = stop ? __builtin_inff() : thr;
     c0 = __builtin_fmaf(w, cr, c0);

@@ -99,6 +99,24 @@ __device__ __forceinline__ float alpha_ref_tail(float x, float y, float q00, flo
     return p2 < -100.0f ? (__builtin_amdgcn_exp2f(p2 + 64.0f) * op) * 0x1p-64f : alpha;
 }
 
+// GSX_SEM_STD_3DGS, one (pixel, Gaussian) pair: the exponent in log2 units from the packed record (x, y, Q''00, Qs'',
+// Q''11), the rule set's two constants and its three decisions.  The forward's compositing kernels (gsx_blend.hip:
+// std_composite) and the backward's std instances (gsx_backward_tile.inc) evaluate these same operations, so the set of
+// composited pairs is one set.
+constexpr float kStdAlphaMin = 1.0f / 255.0f, kStdStop = 0.0001f, kStdAlphaMax = 0.99f;
+
+__device__ __forceinline__ float std_exponent(float e_x, float e_y, float Q00, float Qs, float Q11) {
+    return __builtin_fmaf(e_y, __builtin_fmaf(e_y, Q11, e_x * Qs), (e_x * e_x) * Q00);
+}
+
+// `thr`: the pixel's alpha threshold, 1/255 while it is live.  use: neither skip rule applies; ta = T alpha; stop: the
+// pixel ends BEFORE this pair.
+__device__ __forceinline__ void std_tests(float pw, float alpha, float thr, float T, float &ta, bool &use, bool &stop) {
+    use = !(pw > 0.0f) && !(alpha < thr);
+    ta = T * alpha;
+    stop = use && (T - ta < kStdStop);
+}
+
 // Tiles whose list is much longer than the frame's average are composited by FOUR waves (a quarter of the
 // tile's pixels each, one pixel per lane, eight records per trip) instead of one: a lone wave walks its list
 // at ~430 cycles per record, so one 20 000-entry tile would outlast the rest of the frame several times over.
@@ -592,5 +610,16 @@ hipError_t launch_backward_geometry_depth(const GsxCamera &camera, float4 *geo_s
                                           const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
                                           const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
                                           float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s);
+// gsx_render_backward_std (GSX_SEM_STD_3DGS): the tile kernel's two std instances on the PACKED records of the forward's own
+// projection (bt.raw = the frame's records, a = (x, y, Q''00, Qs''), b = (Q''11, opacity, r, g), c.x = b; geo_slots null:
+// the colour-only instance), the colour sums with dL/dlogit = (sum u)(1 - op), and the geometry sums followed by the
+// chain's std variant, which forms conic and radius itself (grad_means2d and screen_radius: both or neither).
+hipError_t launch_backward_tiles_std(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
+hipError_t launch_backward_sums_std(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *rec,
+                                    uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
+hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
+                                        const uint32_t *order, uint32_t m, const float *means3d, const float *scales,
+                                        const float *quats, float *grad_means3d, float *grad_scales, float *grad_quats,
+                                        float *grad_means2d, float *screen_radius, hipStream_t s);
 
 }  // namespace gsx

@@ -41,6 +41,13 @@ the "densify" event of step 7 runs ``density.relocate(generator)``, and "opacity
 returned stays the photometric one: the regularisers enter through their gradients only.  With ``strategy="adaptive"``, the
 default, every call is the one above.
 
+With ``semantics="std_3dgs"`` (and ``background=(r, g, b)``) step 2 passes the two to ``render_image_hip``: the frame is
+the published rule set's and step 4 runs gsx_render_backward_std; the loss of step 3 covers the whole frame (that rule set
+renders partial edge tiles) and ``evaluate()`` renders with the same rules.  ``statistic="screen"`` and ``strategy="mcmc"``
+work as above.  ``refine_poses``, ``depth_targets`` and ``statistic="screen_abs"`` are refused together with it: the std_3dgs
+backward has no pose gradient, no depth image and no absolute statistic.  With ``semantics="ref_cpu"``, the default, every
+call is the one above.
+
 The coefficients keep ONE learning rate: a second rate for the higher bands, as published, needs an Adam group over a strided
 part of ``sh`` and is not built.
 """
@@ -171,7 +178,11 @@ class Trainer:
     ``strategy``: ``"adaptive"`` (default: ``DensityControl``, every call and every bit as without the argument) or
     ``"mcmc"``: fixed-budget densification, ``density`` is then an ``MCMCControl`` built with the keywords of ``mcmc`` (a
     dict; ``cap_max`` is required there).  The "densify" event runs ``relocate()`` and there is no opacity reset: an explicit
-    ``opacity_reset_every``, ``density=`` or ``statistic=`` is refused together with ``"mcmc"``, as is ``mcmc=`` without it."""
+    ``opacity_reset_every``, ``density=`` or ``statistic=`` is refused together with ``"mcmc"``, as is ``mcmc=`` without it.
+    ``semantics``: ``"ref_cpu"`` (default: every call and every bit as without the argument) or ``"std_3dgs"``: the frames
+    are rendered, differentiated and evaluated under the published rule set over ``background`` (r, g, b), and the loss
+    covers the whole frame.  ``refine_poses``, ``depth_targets`` and ``statistic="screen_abs"`` are refused together with it;
+    a ``background`` other than black is refused without it (the ref_cpu frame has none)."""
 
     def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
                  tile_size: int = 16, statistic: Optional[str] = None, density: Optional[dict] = None,
@@ -180,8 +191,23 @@ class Trainer:
                  opacity_reset_logit: float = DEFAULT_OPACITY_RESET_LOGIT, seed: int = 0,
                  refine_poses: Optional[dict] = None, depth_targets: Optional[Dict[int, torch.Tensor]] = None,
                  lambda_depth: float = 0.0, masks: Optional[Dict[int, torch.Tensor]] = None,
-                 exposure: Optional[dict] = None, strategy: str = "adaptive", mcmc: Optional[dict] = None) -> None:
+                 exposure: Optional[dict] = None, strategy: str = "adaptive", mcmc: Optional[dict] = None,
+                 semantics: str = "ref_cpu", background: Tuple[float, float, float] = (0.0, 0.0, 0.0)) -> None:
         g = scene.gaussians
+        if semantics not in ("ref_cpu", "std_3dgs"):
+            raise ValueError("semantics = %r is neither 'ref_cpu' nor 'std_3dgs': no other frame is differentiable" % (semantics,))
+        background = tuple(float(v) for v in background)
+        if len(background) != 3:
+            raise ValueError("background = %r is not (r, g, b)" % (background,))
+        if semantics == "ref_cpu" and any(background):
+            raise ValueError("background = %r needs semantics='std_3dgs': the ref_cpu frame has no background" % (background,))
+        if semantics == "std_3dgs":
+            for name, given in (("refine_poses", refine_poses is not None), ("depth_targets", depth_targets is not None),
+                                ("statistic='screen_abs'", statistic == "screen_abs")):
+                if given:
+                    raise ValueError("%s cannot be combined with semantics='std_3dgs': gsx_render_backward_std has no pose "
+                                     "gradient, no depth image and no absolute statistic" % name)
+        self.semantics, self.background = semantics, background
         if strategy not in STRATEGIES:
             raise ValueError("strategy = %r is neither 'adaptive' nor 'mcmc'" % (strategy,))
         if strategy == "mcmc":
@@ -272,7 +298,13 @@ class Trainer:
         scene, g = self.scene, self.gaussians
         idx = self._next_view()
         depth = None
-        if self.depth_targets is not None:
+        region_kw = {}
+        if self.semantics == "std_3dgs":
+            frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
+                                           screen_statistics=self.statistic == "screen", semantics=self.semantics,
+                                           background=self.background)
+            region_kw = dict(semantics=self.semantics)
+        elif self.depth_targets is not None:
             frame, depth = scene.render_image_depth_hip(idx, tile_size=self.tile_size,
                                                         screen_statistics=self.statistic == "screen")
         elif self.statistic == "screen_abs":
@@ -285,7 +317,7 @@ class Trainer:
                                            screen_statistics=self.statistic == "screen", camera_gradients=True)
         terms: dict = {}
         loss = scene.photometric_loss(idx, frame, self.targets[idx], tile_size=self.tile_size,
-                                      lambda_dssim=self.lambda_dssim, terms=terms, **self._weighting(idx))
+                                      lambda_dssim=self.lambda_dssim, terms=terms, **self._weighting(idx), **region_kw)
         if depth is not None and idx in self.depth_targets:
             loss = loss + self.lambda_depth * depth_loss(depth, self.depth_targets[idx],
                                                          scene.rendered_region(idx, self.tile_size))
@@ -330,12 +362,18 @@ class Trainer:
         with torch.no_grad():
             for idx in (self._views if indices is None else indices):
                 target = self.targets[idx]
-                frame = self.scene.render_image_hip(idx, tile_size=self.tile_size)
+                std = self.semantics == "std_3dgs"
+                if std:
+                    frame = self.scene.render_image_hip(idx, tile_size=self.tile_size, semantics=self.semantics,
+                                                        background=self.background)
+                else:
+                    frame = self.scene.render_image_hip(idx, tile_size=self.tile_size)
                 terms: dict = {}
                 kw = self._weighting(idx)
+                region_kw = dict(semantics=self.semantics) if std else {}
                 self.scene.photometric_loss(idx, frame, target, tile_size=self.tile_size, lambda_dssim=self.lambda_dssim,
-                                            terms=terms, **kw)
-                a, b = self.scene.rendered_region(idx, self.tile_size)
+                                            terms=terms, **kw, **region_kw)
+                a, b = self.scene.rendered_region(idx, self.tile_size, **region_kw)
                 if not kw:
                     mse = ((frame[:a, :b] - target[:a, :b]) ** 2).mean()
                 else:

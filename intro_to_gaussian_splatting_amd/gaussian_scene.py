@@ -293,6 +293,13 @@ def _refuse_with_grad(what: str) -> None:
                      "requires_grad" % what)
 
 
+def _refuse_std_with_grad(what: str) -> None:
+    raise ValueError("gradients of the std_3dgs frame (gsx_render_backward_std) are not available with %s: they reach "
+                     "colors / sh, opacity and, with geometry_gradients=True, points, scales and quaternions, with "
+                     "screen_statistics=True the signed screen statistic -- no pose, no absolute statistic, no "
+                     "dL/dbackground; call it under torch.no_grad() or without requires_grad" % what)
+
+
 _ROW_ARRAYS = ("points", "scales", "quaternions", "opacity")
 # what a differentiable frame's forward saw of the state its backward reads again (_pending_snapshot / _check_pending)
 _PendingState = namedtuple("_PendingState", "scene image_idx image pose_version gaussians bands arrays original_index "
@@ -374,7 +381,10 @@ class _RenderImageFunction(torch.autograd.Function):
     (RuntimeError) before anything is launched.  Frames of other views, tile sizes or scenes rendered in between change
     nothing.  ``world2view`` (None unless ``camera_gradients=True``
     and the view's tensor requires grad) gets the total derivative of the pose: gsx_render_backward_camera's
-    dL/dworld2view + dL/dfull_proj @ projection_matrix^T, plus, on an SH scene, the camera centre's share."""
+    dL/dworld2view + dL/dfull_proj @ projection_matrix^T, plus, on an SH scene, the camera centre's share.
+    ``semantics="std_3dgs"`` in ``kw`` (with its ``background`` and ``published_rects``): the frame is the std_3dgs frame and
+    the backward is one gsx_render_backward_std call for the same outputs, the screen statistics included; no pose and no
+    absolute statistic there."""
 
     @staticmethod
     def forward(ctx, scene, image_idx, tile_size, layout, kw, points, scales, quaternions, opacity, colors, sh,
@@ -384,6 +394,9 @@ class _RenderImageFunction(torch.autograd.Function):
         ctx.geometry = bool(kw.pop("geometry_gradients", False)) or ctx.camera
         mode = kw.pop("screen_statistics", False)
         ctx.screen, ctx.screen_abs = bool(mode), mode == "abs"
+        # semantics="std_3dgs": the frame's rules, background and rectangles, which gsx_render_backward_std is told again
+        ctx.std = (tuple(float(v) for v in kw.get("background", (0.0, 0.0, 0.0))), bool(kw.get("published_rects", False))) \
+            if kw.get("semantics", "ref_cpu") == "std_3dgs" else None
         user_stats, st = kw.pop("stats", None), {}
         frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
         if user_stats is not None:
@@ -406,7 +419,7 @@ class _RenderImageFunction(torch.autograd.Function):
         geometry = ctx.geometry and (ctx.screen or camera or any(want[5:8]))
         grads = scene._render_backward(ctx.image_idx, ctx.tile_size, ctx.layout, frame, grad_frame,
                                        ctx.n_instances, ctx.n_visible, geometry=geometry, screen=ctx.screen, camera=camera,
-                                       screen_abs=ctx.screen_abs)
+                                       screen_abs=ctx.screen_abs, std=ctx.std)
         gc, go = grads[:2]
         gp, gs, gq = grads[2:5] if geometry else (None, None, None)
         if ctx.screen_abs:
@@ -737,6 +750,14 @@ class GaussianScene:
         Gaussian gradients and the frame are the same bits either way.  The frame is rendered from the ``GsxCamera`` baked
         by the image: editing ``world2view`` in place does NOT move the camera, ``GaussianImage.set_world2view`` does
         (``CameraRefiner`` steps the pose that way).  The refusals are those of the other gradient paths.
+        ``semantics="std_3dgs"`` with gradients: the frame is the std_3dgs frame rendered without them, bit for bit, over
+        ``background`` and with ``published_rects`` as given, and ``backward()`` is one gsx_render_backward_std call: dL/dcolors
+        (or dL/dsh through gsx_sh_backward) and dL/dopacity, with ``geometry_gradients=True`` dL/dpoints, dL/dscales and
+        dL/dquaternions through that rule set's own stage 1, with ``screen_statistics=True`` ``scene.screen_statistics`` as
+        above (dL/d(NDC mean) and the published radius).  A clamped alpha (0.99) passes gradient to its colour only.  Refused
+        by name there (ValueError; all of them run under ``torch.no_grad()``): ``camera_gradients=True``,
+        ``screen_statistics="abs"``, a ``background`` that requires grad (dL/dbackground is not computed), and the arguments
+        the ref_cpu gradient path refuses; ``semantics="ref_cuda"`` has no gradient.
         """
         screen_statistics = _screen_mode(screen_statistics)
         if screen_statistics and not geometry_gradients:
@@ -750,13 +771,24 @@ class GaussianScene:
         w2v = self.images[image_idx].world2view if _private is None and \
             _camera_wants_grad(self.images[image_idx], camera_gradients) else None
         if _private is None and (w2v is not None or _wants_grad(g, bool(geometry_gradients))):
-            # gradients (gsx_render_backward, gsx_render_backward_geometry, gsx_sh_backward): the whole ref_cpu frame only
-            for what, bad in _refusals(g, semantics, tile_window, out, substrips, no_sync, camera_buffer):
+            # gradients (gsx_render_backward, gsx_render_backward_geometry, gsx_sh_backward): the whole ref_cpu frame, or
+            # (gsx_render_backward_std) the whole std_3dgs frame -- decided here, the other arguments go through _refusals
+            std = semantics == "std_3dgs"
+            if std:
+                for what, bad in (("camera_gradients=True", bool(camera_gradients)),
+                                  ("screen_statistics='abs'", screen_statistics == "abs"),
+                                  ("a background that requires grad",
+                                   any(getattr(v, "requires_grad", False) for v in (background, *tuple(background))))):
+                    if bad:
+                        _refuse_std_with_grad(what)
+            for what, bad in _refusals(g, "ref_cpu" if std else semantics, tile_window, out, substrips, no_sync, camera_buffer):
                 if bad:
                     _refuse_with_grad(what)
             kw = dict(stats=stats, timing=timing, generic_kernels=generic_kernels, tile_counts=tile_counts,
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
                       geometry_gradients=bool(geometry_gradients), screen_statistics=screen_statistics)
+            if std:
+                kw.update(semantics=semantics, background=background, published_rects=published_rects)
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
                                               g.opacity, g.colors, getattr(g, "sh", None), w2v)
         own = _OwnedFrame.of(_private)
@@ -966,7 +998,8 @@ class GaussianScene:
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
                          n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False,
                          screen: bool = False, camera: bool = False, depth: Optional[torch.Tensor] = None,
-                         grad_depth: Optional[torch.Tensor] = None, screen_abs: bool = False) -> Tuple[torch.Tensor, ...]:
+                         grad_depth: Optional[torch.Tensor] = None, screen_abs: bool = False,
+                         std: Optional[tuple] = None) -> Tuple[torch.Tensor, ...]:
         """gsx_render_backward: (dL/dcolors (N,3), dL/dopacity (N,1)) of the ref_cpu frame ``frame`` for dL/dframe =
         ``grad_frame``; with ``geometry`` gsx_render_backward_geometry: those two and (dL/dpoints (N,3), dL/dscales (N,3),
         dL/dquaternions (N,4)); with ``screen`` besides gsx_render_backward_screen: those five and (dL/d(NDC mean) (N,2),
@@ -976,6 +1009,8 @@ class GaussianScene:
         ``screen`` the seven -- for L(frame, depth image), ``depth`` the image ``_render_depth`` returned and ``grad_depth``
         dL/d(that image).  With ``screen_abs`` (needs ``geometry`` and ``screen``, excludes ``camera`` and ``depth``)
         gsx_render_backward_screen_abs: the seven and (the absolute screen statistic (N,2)).
+        With ``std`` = (background, published_rects) (excludes ``camera``, ``depth`` and ``screen_abs``) ``frame`` is the
+        std_3dgs frame rendered with those two and the one call is gsx_render_backward_std: the two, the five or the seven.
         The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
@@ -984,8 +1019,14 @@ class GaussianScene:
             dev, n, tensors = self._inputs(image_idx)
             tensors = [t.detach() for t in tensors]
             cam = self.images[image_idx].gsx_camera()
-            params, _ = self._frame_params(dev, n, layout, "ref_cpu")
-            params.flags |= _ffi.rows_flag(n, n_visible) | int(flags)     # the row class the forward ended up with
+            params, _ = self._frame_params(dev, n, layout, "ref_cpu" if std is None else "std_3dgs")
+            if std is None:
+                params.flags |= _ffi.rows_flag(n, n_visible) | int(flags)     # the row class the forward ended up with
+            else:
+                if camera or depth is not None or screen_abs:
+                    raise ValueError("std excludes camera, depth and screen_abs: gsx_render_backward_std has none of them")
+                params.background[0], params.background[1], params.background[2] = [float(v) for v in std[0]]
+                params.flags |= int(flags) | (_ffi.GSX_FLAG_PUBLISHED_RECTS if std[1] else 0)
             gf = _check_f32("grad_frame", grad_frame.detach(), dev)
             img = _check_f32("frame", frame.detach(), dev)
             if tuple(gf.shape) != tuple(img.shape):
@@ -1024,6 +1065,9 @@ class GaussianScene:
             if depth is not None:
                 args = outs + ([] if screen else [None, None]) + [dimg, gd]     # grad_means2d, screen_radius: NULL
                 size_fn, entry = lib.gsx_backward_depth_workspace_bytes, lib.gsx_render_backward_depth
+            if std is not None:     # one entry: NULL for the outputs that were not asked for
+                args = outs + [None] * (7 - len(outs))
+                size_fn, entry = lib.gsx_backward_std_workspace_bytes, lib.gsx_render_backward_std
             with torch.cuda.device(dev):
                 nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
                 if nbytes == 0:
@@ -1331,24 +1375,32 @@ class GaussianScene:
 
     render = render_image  # the name BASELINE.json's north star uses
 
-    def rendered_region(self, image_idx: int, tile_size: int = 16, layout: str = "wh3") -> Tuple[int, int]:
+    def rendered_region(self, image_idx: int, tile_size: int = 16, layout: str = "wh3",
+                        semantics: str = "ref_cpu") -> Tuple[int, int]:
         """Extent (a, b) of what a ``ref_cpu`` frame of this camera renders, in the order of the frame's two leading axes:
         whole tiles from the origin, the last tile row and column left out (``strips.tiles_along``).  Everything outside is
-        the zeros the frame was cleared to -- not a rendering of black."""
+        the zeros the frame was cleared to -- not a rendering of black.  ``semantics="std_3dgs"``: the whole frame (that
+        rule set renders partial edge tiles)."""
         if layout not in ("wh3", "hw3"):
             raise ValueError("layout must be 'wh3' or 'hw3', got %r" % (layout,))
         cam = self.images[image_idx].gsx_camera()
+        if semantics == "std_3dgs":
+            return (int(cam.width), int(cam.height)) if layout == "wh3" else (int(cam.height), int(cam.width))
+        if semantics != "ref_cpu":
+            raise ValueError("rendered_region knows the ref_cpu and std_3dgs frames, not semantics=%r" % (semantics,))
         w = tiles_along(int(cam.width), int(tile_size)) * int(tile_size)
         h = tiles_along(int(cam.height), int(tile_size)) * int(tile_size)
         return (w, h) if layout == "wh3" else (h, w)
 
     def photometric_loss(self, image_idx: int, frame: torch.Tensor, target: torch.Tensor, tile_size: int = 16,
                          lambda_dssim: float = 0.2, layout: str = "wh3", terms: Optional[dict] = None,
-                         weight: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         weight: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None,
+                         semantics: str = "ref_cpu") -> torch.Tensor:
         """``loss.photometric_loss`` of a ``ref_cpu`` frame of this camera against ``target`` over ``rendered_region``: the
         rim no tile covers takes no part and receives an exact zero gradient.  ``weight`` (a per-pixel weight of the frame's
-        two leading axes) and ``exposure`` (a (3, 4) colour transform of the frame) are passed through as they are."""
-        region = self.rendered_region(image_idx, tile_size, layout)
+        two leading axes) and ``exposure`` (a (3, 4) colour transform of the frame) are passed through as they are.
+        ``semantics="std_3dgs"``: the frame is a std_3dgs frame and the region is all of it."""
+        region = self.rendered_region(image_idx, tile_size, layout, semantics)
         if region[0] <= 0 or region[1] <= 0:
             raise ValueError("a %s frame of camera %r has no rendered tile at tile_size %d (extent <= tile)" % (
                 layout, image_idx, tile_size))

@@ -1,6 +1,6 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth] [--screen-abs]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth] [--screen-abs] [--std]
                                                      [--workloads c3] [--sh [--active-degree A]]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
@@ -25,6 +25,11 @@ GSX_FLAG_TIMING stages of both, medians of `steps` calls.
 backward ("backward_z").  "fused_render_side_ms" = frame + depth_forward + fused against "composed_render_side_ms" =
 frame + frame_z + screen + backward_z, the medians added; "stages" holds the GSX_FLAG_TIMING stages of the screen and the
 fused backward (stage chain again; raw records, prefix and the tile kernel; sums and chain), medians of `steps` calls.
+
+--std (key "std") takes gsx_render_backward_std -- the std_3dgs frame of the same scene (black background, tight
+rectangles), its colour-only call ("std_colour_only") and its geometry call ("std_geometry") -- in turns with the ref_cpu
+geometry entry ("geometry") and the two forward frames ("frame", "std_frame") in one session: every median with its
+minimum and maximum, "std_geometry_over_geometry", and both frames' pair counts (the std lists are the shorter ones).
 
 --sh times the differentiable SH scene INSTEAD: the trained-like 1M scene with degree-3 coefficients (bench.py's
 c3_trainedlike).  Its backward is gsx_render_backward on this camera's evaluated colours (gsx_sh_to_rgb runs again) and
@@ -81,7 +86,7 @@ def _in_turns(calls, steps, warmup):
     return {k: (round(statistics.median(v), 4), [round(min(v), 4), round(max(v), 4)]) for k, v in turns.items()}
 
 
-def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False, screen_abs=False):
+def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False, screen_abs=False, std=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -160,6 +165,22 @@ def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, dept
                     stages.append(list(ms))
                 d["stages"][key] = [round(statistics.median(s[i] for s in stages), 4) for i in range(3)]
             out["screen_abs"] = d
+        if std:
+            st_std = {}
+            render_std = lambda **kw: scene.render_image_hip(1, semantics="std_3dgs", **kw)  # noqa: E731
+            frame_std = render_std(stats=st_std).clone()
+            back_std = lambda geo: scene._render_backward(1, 16, "wh3", frame_std, W, st_std["n_instances"],  # noqa: E731
+                                                          st_std["n_visible"], geometry=geo, std=((0.0, 0.0, 0.0), False))
+            t = _in_turns(dict(geometry=lambda: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"],
+                                                                       st["n_visible"], geometry=True),
+                               std_geometry=lambda: back_std(True), std_colour_only=lambda: back_std(False),
+                               frame=lambda: scene.render_image_hip(1), std_frame=render_std), steps, warmup)
+            d = {k + "_ms": v[0] for k, v in t.items()}
+            d.update({k + "_min_max": v[1] for k, v in t.items()})
+            d["std_geometry_over_geometry"] = round(t["std_geometry"][0] / t["geometry"][0], 4)
+            d["n_instances"] = int(st["n_instances"])
+            d["std_n_instances"] = int(st_std["n_instances"])
+            out["std"] = d
         if depth:
             back = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
                                                        geometry=True, **kw)
@@ -314,6 +335,8 @@ def main():
                     "with the screen entry and with the composed path's two frames and two backwards")
     ap.add_argument("--screen-abs", action="store_true", help="also time gsx_render_backward_screen_abs, in turns with the "
                     "screen entry")
+    ap.add_argument("--std", action="store_true", help="also time gsx_render_backward_std (colour-only and geometry), in turns "
+                    "with the ref_cpu geometry entry and the two forward frames")
     ap.add_argument("--workloads", default="c2,c3", help="comma-separated: which of c2, c3 to run (not with --sh)")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     ap.add_argument("--active-degree", type=int, default=None, help="with --sh: Gaussians.active_sh_degree (0..3), the "
@@ -326,7 +349,8 @@ def main():
                                                                        active=args.active_degree, camera=args.camera))))
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
-    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera, args.depth, args.screen_abs)
+    out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera, args.depth, args.screen_abs,
+                     args.std)
            for name, n in WORKLOADS.items() if name in args.workloads.split(",")}
     print(json.dumps(dict(metric="backward_ms", results=out)))
 
