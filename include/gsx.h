@@ -580,6 +580,39 @@ GSX_API int gsx_render_backward_std(const GsxCamera *camera, const float *means3
 GSX_API size_t gsx_backward_std_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
 
 /*
+ * Build extension: what every Gaussian contributes to one frame.  For a (record k, pixel) pair that the walk composites,
+ * w = T_k alpha_k is the record's blend weight in that pixel -- the factor its colour enters the pixel with.  Per row:
+ *   weight_max (n)  the largest w over the frame's pixels        (RadSplat's prune score, maximised over the views)
+ *   weight_sum (n)  the sum of w over the frame's pixels         (the score LightGaussian and Mini-Splatting rank on)
+ *   pixels     (n)  the number of pixels that composited the row
+ *   views      (n)  1 where the frame listed the row on a tile; may be NULL
+ * Projection, depth order, binning and the emission prefix run again exactly as for gsx_render_backward /
+ * gsx_render_backward_std: hints are neither read nor written, the row classes (GSX_FLAG_ONE_VISIBLE / _SMALL_BATCH) and
+ * the one synchronisation are theirs, GSX_FLAG_PUBLISHED_RECTS is honoured under GSX_SEM_STD_3DGS (the background changes
+ * nothing here).  params->semantics is GSX_SEM_REF_CPU (NULL params: that) or GSX_SEM_STD_3DGS; GSX_SEM_REF_CUDA is
+ * refused, and so is everything the gradient entries refuse: tile window, output window, substrips, GSX_FLAG_NO_SYNC,
+ * camera_device, params->sh.
+ * The walk is the GRADIENT entries' walk, not the forward's.  GSX_SEM_REF_CPU: the reference's alpha on every listed record
+ * (no 2^-26 skip), the pixel stopped before the record that would take its transmittance below 1e-6; the last row and
+ * column of tiles are not walked.  GSX_SEM_STD_3DGS: that rule set's exponent, two skips and stop on the packed records,
+ * alpha = min(0.99, ..); pixels beyond the frame's width or height are never walked.  w is the very value those entries
+ * multiply dL/dpixel with: weight_sum equals grad_colors[:, 0] of gsx_render_backward (gsx_render_backward_std) under
+ * dL/dframe = 1 bit for bit.  No float atomics: same inputs, same bits.
+ * accumulate == 0: every row of the arrays is written -- the call clears them on `stream` first, so a row the frame did
+ * not list reads +0 / 0 -- and views = 1 where listed.  accumulate == 1: a listed row is merged into what the arrays hold
+ * (max, +=, +=, views += 1) and an unlisted row is not touched: a sweep over the training views is one call per view.
+ * workspace: gsx_contribution_workspace_bytes.
+ */
+GSX_API int gsx_render_contribution(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                                    const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
+                                    float *weight_max /* (n) */, float *weight_sum /* (n) */, uint32_t *pixels /* (n) */,
+                                    uint32_t *views /* (n), may be NULL */, int32_t accumulate, const GsxParams *params,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bytes of device workspace gsx_render_contribution needs (0 on invalid arguments). */
+GSX_API size_t gsx_contribution_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances);
+
+/*
  * Replaces Gaussians.get_3d_covariance_matrix (splat/gaussians.py:54-69): covariance_out (n,3,3) =
  * (R S)(R S)^T from linear scales (n,3) and quaternions (n,4) (w,x,y,z), the quaternion
  * normalised twice as the reference does.  The render entry points compute this inline; the
@@ -879,6 +912,14 @@ GSX_API int gsx_density_plan_screen(const float *grad_sum, const uint32_t *seen,
                                     const float *radius_max /* may be NULL */, float prune_radius, int64_t n,
                                     const GsxDensityRules *rules, void *workspace, size_t workspace_bytes,
                                     int64_t *counts_host /* 4 */, void *stream);
+/* gsx_density_plan_contribution: a plan of KEEP and PRUNE alone from gsx_render_contribution's arrays, in gsx_density_plan's
+ * workspace format, so that the unchanged gsx_density_apply rewrites every array from it.  PRUNE iff weight_max[i] <
+ * threshold in float32 -- a NaN weight fails the comparison and is kept, a weight exactly equal is kept -- or, with `views`,
+ * views[i] == 0 (no view listed the row), whatever its weight.  A NaN or negative threshold is refused; the other
+ * refusals, the alignment rule, counts_host = (n_out, n_pruned, 0, 0) and the one synchronisation are gsx_density_plan's. */
+GSX_API int gsx_density_plan_contribution(const float *weight_max, const uint32_t *views /* may be NULL */, float threshold,
+                                          int64_t n, void *workspace, size_t workspace_bytes, int64_t *counts_host /* 4 */,
+                                          void *stream);
 GSX_API int gsx_density_apply(const GsxDensityGroup *groups /* host */, int32_t n_groups, int64_t n, int64_t n_out,
                               const float *noise /* (n,2,3), may be NULL without a POINTS group */,
                               int32_t *source_row /* (n_out), may be NULL */, void *workspace, size_t workspace_bytes,

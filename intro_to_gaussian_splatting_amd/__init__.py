@@ -2,7 +2,7 @@
 dcaustin33/intro_to_gaussian_splatting (``splat.GaussianScene``): PyTorch-ROCm tensors hold the
 Gaussians, hand-written HIP kernels (libgsx.so, C ABI in include/gsx.h) do the work."""
 from .gaussians import Gaussians
-from .gaussian_scene import GaussianScene, NativeExtension, render_preprocessed
+from .gaussian_scene import Contribution, GaussianScene, NativeExtension, render_preprocessed
 from .image import GaussianImage
 from .loss import depth_loss, photometric_loss
 from .optim import GaussianAdam, expon_lr
@@ -17,4 +17,4 @@ from .schema import PreprocessedScene
 __all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
            "NativeExtension", "photometric_loss", "depth_loss", "GaussianAdam", "expon_lr", "DensityControl", "MCMCControl",
            "nearest3",
-           "Trainer", "events_at", "CameraRefiner", "ExposureRefiner"]
+           "Trainer", "events_at", "CameraRefiner", "ExposureRefiner", "Contribution"]

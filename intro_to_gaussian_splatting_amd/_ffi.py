@@ -163,6 +163,9 @@ SIGNATURES = {
     "gsx_render_backward_std": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32] + [_FP] * 9 +
                                 [POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
     "gsx_backward_std_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),
+    "gsx_render_contribution": (ctypes.c_int, [POINTER(GsxCamera)] + [_FP] * 5 + [c_int64, c_int32, _FP, _FP, c_void_p, c_void_p,
+                                c_int32, POINTER(GsxParams), c_void_p, c_size_t, c_void_p]),
+    "gsx_contribution_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64]),
     "gsx_covariance_3d": (ctypes.c_int, [_FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_covariance_2d": (ctypes.c_int, [POINTER(GsxCamera), _FP, _FP, c_int64, _FP, c_void_p]),
     "gsx_project_points": (ctypes.c_int, [POINTER(GsxCamera), _FP, c_int64, _FP, c_void_p, c_void_p]),
@@ -186,6 +189,8 @@ SIGNATURES = {
     "gsx_density_accumulate_screen": (ctypes.c_int, [_FP, _FP, c_int64, _FP, c_void_p, _FP, c_void_p]),
     "gsx_density_plan_screen": (ctypes.c_int, [_FP, c_void_p, _FP, _FP, _FP, c_float, c_int64, POINTER(GsxDensityRules), c_void_p,
                                                c_size_t, POINTER(c_int64), c_void_p]),
+    "gsx_density_plan_contribution": (ctypes.c_int, [_FP, c_void_p, c_float, c_int64, c_void_p, c_size_t, POINTER(c_int64),
+                                                     c_void_p]),
     "gsx_density_apply": (ctypes.c_int, [POINTER(GsxDensityGroup), c_int32, c_int64, c_int64, _FP, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
     "gsx_mcmc_regularize": (ctypes.c_int, [_FP, _FP, c_int64, c_float, c_float, _FP, _FP, c_void_p]),

@@ -596,6 +596,71 @@ int render_backward_std(const GsxCamera *camera, const float *means3d, const flo
     return GSX_OK;
 }
 
+// gsx_render_contribution: the gradient entries' chain (lists_again) and walk on either rule set, with no frame and no
+// gradient: per row the largest T alpha, their sum and the pixel count (gsx_contribution.hip).  The workspace is
+// gsx_render_backward's.
+int render_contribution(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                        const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *weight_max,
+                        float *weight_sum, uint32_t *pixels, uint32_t *views, int32_t accumulate, const GsxParams *params,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const char *entry = "gsx_render_contribution";
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    if (!weight_max || !weight_sum || !pixels) return fail(GSX_ERR_INVALID_ARGUMENT, "weight_max / weight_sum / pixels is NULL");
+    if (accumulate != 0 && accumulate != 1) return fail(GSX_ERR_INVALID_ARGUMENT, "accumulate = %d is neither 0 nor 1", accumulate);
+    Plan p;
+    // (weight_max stands in for the frame the plan describes: this entry has none and writes no pixel)
+    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, weight_max, params, p);
+    if (rc != GSX_OK) return rc;
+    if (p.semantics == GSX_SEM_REF_CUDA)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s: GSX_SEM_REF_CUDA is not supported (GSX_SEM_REF_CPU or GSX_SEM_STD_3DGS)", entry);
+    const bool std_rules = p.semantics == GSX_SEM_STD_3DGS;
+    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
+    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s renders the whole frame: no tile window", entry);
+    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes the whole frame: no output window", entry);
+    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take substrips", entry);
+    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "%s synchronises: no GSX_FLAG_NO_SYNC", entry);
+    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "%s reads the camera argument: no camera_device", entry);
+    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
+    if (rc != GSX_OK) return rc;
+    Carve c;
+    int64_t cap;
+    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, kCarveBackward);
+    if (rc != GSX_OK) return rc;
+    char *ws = (char *)workspace;
+    if (!accumulate) {      // every row: a Gaussian on no tile list reads +0 / 0
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)weight_max, (size_t)n, s));
+        GSX_HIP(gsx::launch_zero_words((uint32_t *)weight_sum, (size_t)n, s));
+        GSX_HIP(gsx::launch_zero_words(pixels, (size_t)n, s));
+        if (views) GSX_HIP(gsx::launch_zero_words(views, (size_t)n, s));
+    }
+    if (n == 0 || p.grid.count() == 0) {
+        GSX_HIP(hipStreamSynchronize(s));
+        return GSX_OK;
+    }
+    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
+    const uint32_t *order, *sorted_vals;
+    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
+    int64_t counts[3];
+    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
+    if (rc != GSX_OK) return rc;
+    const uint32_t m = (uint32_t)counts[2];
+    if (m == 0 || counts[1] == 0) return GSX_OK;
+    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
+    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
+    float4 *slots = (float4 *)(ws + c.slots);
+    if (!std_rules) GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
+    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
+    const gsx::ContributionTiles ct{std_rules ? (const gsx::Record *)(ws + c.rec) : raw, sorted_vals, (const uint2 *)(ws + c.ranges),
+                                    rank_of, prefix, rrect, slots};
+    GSX_HIP(gsx::launch_contribution_tiles(ct, p.grid, std_rules, s));
+    GSX_HIP(gsx::launch_contribution_sums(slots, prefix, order, m, weight_max, weight_sum, pixels, views, accumulate != 0, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -816,6 +881,18 @@ int gsx_render_backward_std(const GsxCamera *camera, const float *means3d, const
     return render_backward_std(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
                                grad_colors, grad_opacity_logit, grad_means3d, grad_scales, grad_quats, grad_means2d,
                                screen_radius, params, workspace, workspace_bytes, stream);
+}
+
+size_t gsx_contribution_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveBackward);
+}
+
+int gsx_render_contribution(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
+                            const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *weight_max,
+                            float *weight_sum, uint32_t *pixels, uint32_t *views, int32_t accumulate, const GsxParams *params,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    return render_contribution(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, weight_max, weight_sum, pixels,
+                               views, accumulate, params, workspace, workspace_bytes, stream);
 }
 
 size_t gsx_backward_camera_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
@@ -1212,6 +1289,23 @@ int gsx_density_plan_screen(const float *grad_sum, const uint32_t *seen, const f
                             size_t workspace_bytes, int64_t *counts_host, void *stream) {
     return density_plan(grad_sum, seen, scales, opacity_logit, radius_max, prune_radius, true, n, rules, workspace,
                         workspace_bytes, counts_host, stream);
+}
+
+int gsx_density_plan_contribution(const float *weight_max, const uint32_t *views, float threshold, int64_t n, void *workspace,
+                                  size_t workspace_bytes, int64_t *counts_host, void *stream) {
+    if (!counts_host) return fail(GSX_ERR_INVALID_ARGUMENT, "counts_host is NULL");
+    if (!(threshold >= 0.0f)) return fail(GSX_ERR_INVALID_ARGUMENT, "threshold %g is NaN or negative", (double)threshold);
+    DensityCarve c;
+    const int rc = check_density_workspace(n, workspace, workspace_bytes, c);
+    if (rc != GSX_OK) return rc;
+    if (n > 0 && !weight_max) return fail(GSX_ERR_INVALID_ARGUMENT, "weight_max is NULL");
+    for (int i = 0; i < 4; ++i) counts_host[i] = 0;
+    if (n == 0) return GSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GSX_HIP(gsx::launch_density_plan_contribution(weight_max, views, threshold, n, (char *)workspace, c, s));
+    GSX_HIP(hipMemcpyAsync(counts_host, (const char *)workspace + 8, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
 }
 
 int gsx_density_apply(const GsxDensityGroup *groups, int32_t n_groups, int64_t n, int64_t n_out, const float *noise,

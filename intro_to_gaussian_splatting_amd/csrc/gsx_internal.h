@@ -622,4 +622,23 @@ hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slo
                                         const float *quats, float *grad_means3d, float *grad_scales, float *grad_quats,
                                         float *grad_means2d, float *screen_radius, hipStream_t s);
 
+// ---- gsx_contribution.hip (gsx_render_contribution): the gradient entries' walk with no image and no gradient
+struct ContributionTiles {
+    const Record *raw;            // GSX_SEM_REF_CPU: launch_project_raw, by row; GSX_SEM_STD_3DGS: the frame's packed records
+    const uint32_t *vals;         // sorted pair list: row of each entry, tile by tile
+    const uint2 *ranges;          // [first, last) of every window tile's list
+    const uint32_t *rank_of, *prefix;
+    const TileRect *rrect;
+    float4 *slots;                // one per pair, in emission order: (max T alpha, sum T alpha, bits of the pixel count, 0)
+};
+hipError_t launch_contribution_tiles(const ContributionTiles &ct, const TileGrid &grid, bool std_rules, hipStream_t s);
+// slots of each rank reduced in emission order and written to row order[r] of the three arrays (views: or null), or --
+// accumulate -- merged into it: max, +, +, views + 1
+hipError_t launch_contribution_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, uint32_t m,
+                                    float *weight_max, float *weight_sum, uint32_t *pixels, uint32_t *views, bool accumulate,
+                                    hipStream_t s);
+// gsx_density_plan_contribution behind its argument checks (views may be null); the workspace is gsx_density_plan's
+hipError_t launch_density_plan_contribution(const float *weight_max, const uint32_t *views, float threshold, int64_t n, char *ws,
+                                            const DensityCarve &c, hipStream_t s);
+
 }  // namespace gsx

@@ -6,7 +6,9 @@ After every ``backward()`` ``accumulate()`` adds the norm of each Gaussian's ``p
 hundred steps ``densify_and_prune()`` gives every Gaussian one action -- prune, clone, split or keep -- and rewrites every
 array of the container and both moment arrays of the optimiser in ONE library call: a survivor keeps the bits of its
 parameters and of its Adam moments, a new Gaussian starts with zero moments, and rows stay in source order with the children
-beside their parent.  There is no torch composition behind it and no CPU path.
+beside their parent.  ``prune_contribution()`` prunes by what a Gaussian shows instead -- the largest blend weight it reaches
+in any pixel of the views ``GaussianScene.contribution()`` swept (gsx_density_plan_contribution) -- through the same rewrite.
+There is no torch composition behind it and no CPU path.
 """
 from __future__ import annotations
 
@@ -199,6 +201,16 @@ class DensityControl:
         """One round: plan, rewrite every array and moment, install, reset the statistic and the scene's caches.  Returns
         ``n_out``, ``n_pruned``, ``n_cloned``, ``n_split``.  The split positions draw ``torch.randn((n, 2, 3))`` from
         ``generator`` (a generator of the container's device): the same seed gives the same container."""
+        n, dev = self._check_round()
+        counts = self._plan(n, self.grad_threshold, dev)
+        if self.max_gaussians is not None and counts["n_out"] > self.max_gaussians:
+            counts = self._plan(n, math.inf, dev)           # prune only
+        noise = torch.randn((n, 2, 3), generator=generator, device=dev, dtype=torch.float32)
+        self._apply(n, counts["n_out"], noise, dev)
+        return counts
+
+    def _check_round(self):
+        """What a round checks before it plans: the arrays, the statistic's length, the optimiser's moments.  (n, device)."""
         self._check_arrays()
         g, opt = self.gaussians, self.optimizer
         n = len(g)
@@ -214,14 +226,17 @@ class DensityControl:
                     m = getattr(opt, key)[name]
                     if tuple(m.shape) != tuple(getattr(g, name).shape) or m.device != dev or not m.is_contiguous():
                         raise ValueError("optimizer.%s[%r] is not of the shape and device of %s" % (key, name, name))
-        counts = self._plan(n, self.grad_threshold, dev)
-        if self.max_gaussians is not None and counts["n_out"] > self.max_gaussians:
-            counts = self._plan(n, math.inf, dev)           # prune only
-        n_out = counts["n_out"]
-        noise = torch.randn((n, 2, 3), generator=generator, device=dev, dtype=torch.float32)
+        return n, dev
+
+    def _apply(self, n: int, n_out: int, noise: Optional[torch.Tensor], dev) -> None:
+        """gsx_density_apply on the plan the workspace holds: every array of the container and both moment arrays rewritten
+        and installed, the statistic reset to ``n_out`` rows of zeros, the scene's caches dropped."""
+        g, opt = self.gaussians, self.optimizer
 
         names = self._names()
-        jobs = [(name, getattr(g, name), _ROLES.get(name, _ffi.GSX_DENSITY_COPY)) for name in names]
+        # (noise None: a plan of KEEP and PRUNE alone -- no row is split, every array is a plain copy and needs no noise)
+        roles = _ROLES if noise is not None else {}
+        jobs = [(name, getattr(g, name), roles.get(name, _ffi.GSX_DENSITY_COPY)) for name in names]
         if opt is not None:
             jobs += [((key, name), getattr(opt, key)[name], _ffi.GSX_DENSITY_ZERO_NEW)
                      for name in opt.names for key in ("exp_avg", "exp_avg_sq")]
@@ -236,7 +251,7 @@ class DensityControl:
             grp.width = src.numel() // n if n else max(1, math.prod(src.shape[1:]))
             grp.role = role
         with torch.cuda.device(dev):
-            rc = _ffi.load().gsx_density_apply(self._groups, len(jobs), n, n_out, noise.data_ptr(), None,
+            rc = _ffi.load().gsx_density_apply(self._groups, len(jobs), n, n_out, None if noise is None else noise.data_ptr(), None,
                                                self._workspace.data_ptr(), self._workspace.numel(), _stream_handle(dev))
         _ffi.check(rc)
 
@@ -252,7 +267,46 @@ class DensityControl:
             self.radius_max = torch.zeros(n_out, dtype=torch.float32, device=dev)
         if self.scene is not None:
             self.scene.gaussians_changed()
-        return counts
+
+    def prune_contribution(self, contribution, threshold: float = 0.01, require_seen: bool = True) -> Dict[str, int]:
+        """Prunes by what the Gaussians show (gsx_density_plan_contribution, then the gsx_density_apply of a round): a row
+        goes where ``contribution.weight_max`` -- the largest blend weight it reaches in any pixel of the views
+        ``scene.contribution(...)`` swept -- is below ``threshold`` (float32; exactly equal is kept, a NaN weight is kept)
+        and, with ``require_seen``, where no view listed it (``contribution.views == 0``), whatever its weight.  The
+        published threshold is 0.01 (RadSplat); the rules of ``densify_and_prune`` ask nothing of the kind: an opaque
+        Gaussian buried behind a surface passes all of them.  Survivors keep the bits of their parameters and Adam moments,
+        in order; the accumulated densification statistic is dropped and ``scene.gaussians_changed()`` called exactly as by
+        ``densify_and_prune``.  Returns its counts (``n_cloned`` = ``n_split`` = 0).  Refused: a ``contribution`` that is
+        not of this container's length or device, a NaN or negative ``threshold``."""
+        n, dev = self._check_round()
+        threshold = float(threshold)
+        if not threshold >= 0.0:
+            raise ValueError("threshold = %r is NaN or negative" % (threshold,))
+        wmax, views = getattr(contribution, "weight_max", None), getattr(contribution, "views", None)
+        if not isinstance(wmax, torch.Tensor) or not isinstance(views, torch.Tensor):
+            raise TypeError("contribution must be a Contribution (scene.contribution(...)), got %s" % type(contribution).__name__)
+        for name, t, dtype in (("weight_max", wmax, torch.float32), ("views", views, torch.int32)):
+            if t.dim() != 1 or t.shape[0] != n:
+                raise ValueError("contribution.%s has shape %s, the container %d rows: it was measured on other rows -- sweep the "
+                                 "views again (scene.contribution) after the rows changed" % (name, tuple(t.shape), n))
+            if t.device.type != "cuda" or t.device != dev:
+                raise ValueError("contribution.%s is on %s, the container on %s; there is no CPU fallback" % (name, t.device, dev))
+            if t.dtype != dtype or not t.is_contiguous():
+                raise ValueError("contribution.%s must be a contiguous %s tensor" % (name, dtype))
+        need = int(_ffi.load().gsx_density_workspace_bytes(n))
+        if need == 0:
+            raise ValueError("%d Gaussians are more than density control takes (2^30)" % n)
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        counts = (ctypes.c_int64 * 4)()
+        with torch.cuda.device(dev):
+            rc = _ffi.load().gsx_density_plan_contribution(wmax.data_ptr(), views.data_ptr() if require_seen else None, threshold,
+                                                           n, self._workspace.data_ptr(), self._workspace.numel(), counts,
+                                                           _stream_handle(dev))
+        _ffi.check(rc)
+        out = dict(zip(COUNT_NAMES, (int(c) for c in counts)))
+        self._apply(n, out["n_out"], None, dev)
+        return out
 
     def reset_opacity(self, cap_logit: float) -> None:
         """The published trainer's opacity reset, on the logit: ``opacity.clamp_(max=cap_logit)`` in place and zeros in the

@@ -16,7 +16,8 @@ it.  One step, numbered from 1:
    the host, then ``set_world2view``) runs right here, after ``opt.zero_grad()`` and before the events: the Gaussians and
    the camera both step along gradients of the SAME frame;
 7. the events ``events_at`` names for this step, in this order: ``density.densify_and_prune(generator)``,
-   ``density.reset_opacity(opacity_reset_logit)``, ``gaussians.oneup_sh_degree()``.
+   ``density.reset_opacity(opacity_reset_logit)``, ``gaussians.oneup_sh_degree()`` and, at the steps of
+   ``prune_contribution_at``, ``density.prune_contribution(scene.contribution(indices, semantics, tile_size), threshold)``.
 
 With ``depth_targets`` (image index -> (W,H) depth map) step 2 is ``frame, depth = scene.render_image_depth_hip(idx,
 tile_size, screen_statistics=statistic == "screen")`` and step 3 adds ``lambda_depth * depth_loss(depth,
@@ -65,7 +66,7 @@ from .loss import depth_loss
 from .optim import GROUP_NAMES, GaussianAdam
 from .pose import CameraRefiner
 
-EVENT_NAMES = ("densify", "opacity_reset", "sh_oneup")
+EVENT_NAMES = ("densify", "opacity_reset", "sh_oneup", "prune_contribution")
 # the published rates (Kerbl et al. 2023); the position rate is per unit of scene extent there: scale it for the scene, or
 # move the scene into those units once, before the fit: GaussianScene.normalize()
 DEFAULT_LR = {"points": 1.6e-4, "scales": 5e-3, "quaternions": 1e-3, "opacity": 5e-2, "colors": 2.5e-3, "sh": 2.5e-3}
@@ -88,12 +89,24 @@ def _period(name: str, value) -> int:
     return int(value)
 
 
+def _steps(name: str, value) -> Tuple[int, ...]:
+    if isinstance(value, (str, bytes)) or not isinstance(value, Iterable):
+        raise ValueError("%s = %r is not a sequence of steps" % (name, value))
+    out = tuple(value)
+    for v in out:
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError("%s names %r, which is not a positive integer (the first step is 1)" % (name, v))
+    return tuple(int(v) for v in out)
+
+
 def events_at(step: int, sh_degree_every: Optional[int] = 1000, densify_from: int = 500, densify_every: Optional[int] = 100,
-              densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000) -> Tuple[str, ...]:
+              densify_until: int = 15000, opacity_reset_every: Optional[int] = 3000,
+              prune_contribution_at: Optional[Iterable[int]] = None) -> Tuple[str, ...]:
     """The events due after the optimiser step of ``step`` (1 for the first), in the order they run -- a pure function:
     "densify"        ``densify_from < step <= densify_until`` and ``step`` a multiple of ``densify_every``;
     "opacity_reset"  ``step <= densify_until`` and ``step`` a multiple of ``opacity_reset_every``;
-    "sh_oneup"       ``step`` a multiple of ``sh_degree_every``.
+    "sh_oneup"       ``step`` a multiple of ``sh_degree_every``;
+    "prune_contribution"  ``step`` is one of ``prune_contribution_at`` (None, the default: never).
     A period of 0 or None switches its event off."""
     if isinstance(step, bool) or int(step) != step or int(step) < 1:
         raise ValueError("step = %r is not a positive integer (the first step is 1)" % (step,))
@@ -107,6 +120,8 @@ def events_at(step: int, sh_degree_every: Optional[int] = 1000, densify_from: in
         due.append("opacity_reset")
     if sh_every and step % sh_every == 0:
         due.append("sh_oneup")
+    if prune_contribution_at is not None and step in _steps("prune_contribution_at", prune_contribution_at):
+        due.append("prune_contribution")
     return tuple(due)
 
 
@@ -182,7 +197,13 @@ class Trainer:
     ``semantics``: ``"ref_cpu"`` (default: every call and every bit as without the argument) or ``"std_3dgs"``: the frames
     are rendered, differentiated and evaluated under the published rule set over ``background`` (r, g, b), and the loss
     covers the whole frame.  ``refine_poses``, ``depth_targets`` and ``statistic="screen_abs"`` are refused together with it;
-    a ``background`` other than black is refused without it (the ref_cpu frame has none)."""
+    a ``background`` other than black is refused without it (the ref_cpu frame has none).
+    ``prune_contribution_at``: None (every call and every bit as without it), or the steps after which the fit prunes by
+    contribution: ``scene.contribution(indices)`` sweeps the views (``prune_contribution["indices"]``; None: every view of
+    the scene) under the Trainer's ``semantics`` and tile size -- the background changes no blend weight -- and
+    ``density.prune_contribution(...)`` drops what shows below ``prune_contribution["threshold"]`` (0.01) in all of them.
+    ``prune_contribution`` (None: ``dict(threshold=0.01, indices=None)``) is read by that event alone.
+    Refused with ``strategy="mcmc"``: a fixed budget relocates and does not prune."""
 
     def __init__(self, scene, targets: Dict[int, torch.Tensor], lr: Optional[dict] = None, lambda_dssim: float = 0.2,
                  tile_size: int = 16, statistic: Optional[str] = None, density: Optional[dict] = None,
@@ -192,8 +213,25 @@ class Trainer:
                  refine_poses: Optional[dict] = None, depth_targets: Optional[Dict[int, torch.Tensor]] = None,
                  lambda_depth: float = 0.0, masks: Optional[Dict[int, torch.Tensor]] = None,
                  exposure: Optional[dict] = None, strategy: str = "adaptive", mcmc: Optional[dict] = None,
-                 semantics: str = "ref_cpu", background: Tuple[float, float, float] = (0.0, 0.0, 0.0)) -> None:
+                 semantics: str = "ref_cpu", background: Tuple[float, float, float] = (0.0, 0.0, 0.0),
+                 prune_contribution_at: Optional[Iterable[int]] = None, prune_contribution: Optional[dict] = None) -> None:
         g = scene.gaussians
+        if prune_contribution_at is not None:
+            prune_contribution_at = _steps("prune_contribution_at", prune_contribution_at)
+            if strategy == "mcmc":
+                raise ValueError("prune_contribution_at cannot be combined with strategy='mcmc': a fixed budget relocates "
+                                 "and does not prune (MCMCControl has no prune_contribution)")
+        pc = dict(threshold=0.01, indices=None)                 # (without prune_contribution_at no step reads it)
+        for key, value in dict(prune_contribution or {}).items():
+            if key not in pc:
+                raise ValueError("prune_contribution names %r: it takes threshold and indices" % (key,))
+            pc[key] = value
+        if pc["indices"] is not None:
+            pc["indices"] = list(pc["indices"])
+            for idx in pc["indices"]:
+                if idx not in scene.images:
+                    raise ValueError("prune_contribution['indices'] names image %r, which the scene does not have" % (idx,))
+        self.prune_contribution = pc
         if semantics not in ("ref_cpu", "std_3dgs"):
             raise ValueError("semantics = %r is neither 'ref_cpu' nor 'std_3dgs': no other frame is differentiable" % (semantics,))
         background = tuple(float(v) for v in background)
@@ -249,6 +287,8 @@ class Trainer:
             raise ValueError("exposure needs an lr: ExposureRefiner has no default rate")
         self._schedule = dict(sh_degree_every=sh_degree_every, densify_from=int(densify_from), densify_every=densify_every,
                               densify_until=int(densify_until), opacity_reset_every=opacity_reset_every)
+        if prune_contribution_at is not None:                   # (without it the schedule is the one it always was)
+            self._schedule["prune_contribution_at"] = prune_contribution_at
         events_at(1, **self._schedule)                          # refuses a bad period here, not at step 1000
         for name in lr:
             if getattr(g, name, None) is not None:
@@ -342,6 +382,10 @@ class Trainer:
                 self.density.densify_and_prune(generator=self._split_generator)
             elif event == "opacity_reset":
                 self.density.reset_opacity(self.opacity_reset_logit)
+            elif event == "prune_contribution":
+                pc = self.prune_contribution
+                con = scene.contribution(pc["indices"], semantics=self.semantics, tile_size=self.tile_size)
+                self.density.prune_contribution(con, threshold=pc["threshold"])
             else:
                 g.oneup_sh_degree()
         return torch.stack((loss.detach(), terms["l1"], terms["ssim"])), idx
