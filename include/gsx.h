@@ -279,6 +279,20 @@ typedef struct GsxParams {
  * (GSX_ERR_INVALID_ARGUMENT): the caller MUST be able to read it. */
 #define GSX_FLAG_PLAIN_FOOTPRINTS 1024
 
+/* GSX_SEM_STD_3DGS only: the anti-aliased variant of the published rule set (Mip-Splatting's 2D filter, the published
+ * rasteriser's `antialiasing` switch, gsplat's rasterize_mode="antialiased").  Stage 1 still adds 0.3 to the diagonal of
+ * the 2D covariance, and now multiplies the opacity by
+ *     rho = sqrt(max(0.000025, det0 / det1)),   det0 = ca cd - cb cb before the dilation, det1 after it,
+ * so that the widened Gaussian carries the energy of the original: alpha = min(0.99, sigmoid(logit) rho exp(exponent)),
+ * and the 1/255 skip, the 0.99 clamp and the stop rule all see that product.  Conic, radius and tile rectangles are the
+ * flag-clear call's (the rectangles are sized by sigmoid(logit): the same pairs are listed, more of them are skipped).
+ * Where det0 / det1 <= 0.000025 -- a float32 det0 <= 0 included -- rho is the constant 0.005 and carries no gradient.
+ * Honoured by gsx_render_forward, gsx_render_backward_std (dL/dlogit = (sum u)(1 - sigmoid(logit)), and dL/drho reaches
+ * scales, quaternions and points through the 2D covariance) and gsx_render_contribution.  GSX_ERR_INVALID_ARGUMENT under
+ * the other two semantics and from every entry that does not take GSX_SEM_STD_3DGS.  With the flag clear every output
+ * of every entry keeps its bits. */
+#define GSX_FLAG_ANTIALIASED 2048
+
 /* Indices into GsxFrameStats.stage_ms (milliseconds). */
 enum {
     GSX_STAGE_PROJECT = 0,    /* projection, depth keys, record packing         */
@@ -548,7 +562,8 @@ GSX_API size_t gsx_backward_depth_workspace_bytes(int64_t n, int32_t width, int3
 /*
  * BUILD EXTENSION -- gradients of the GSX_SEM_STD_3DGS frame (the published rule set: 0.3 dilation, alpha clamped at 0.99,
  * the 1/255 skip, stop before the pair with T (1 - alpha) < 1e-4, background behind the last Gaussian).
- * params->semantics must be GSX_SEM_STD_3DGS; params->background and GSX_FLAG_PUBLISHED_RECTS are honoured as in
+ * params->semantics must be GSX_SEM_STD_3DGS; params->background, GSX_FLAG_PUBLISHED_RECTS and GSX_FLAG_ANTIALIASED (the
+ * frame's opacity is sigmoid(logit) rho: dL/dlogit and the geometry gradients follow it, see the flag) are honoured as in
  * gsx_render_forward, so the tile lists are that frame's.  image: the frame gsx_render_forward wrote for these inputs and
  * params (whole frame, params->layout); grad_image: dL/dimage, same layout.  Per pixel the forward's walk is repeated with
  * the forward's operations and its three decisions; with g = dL/dpixel and F the pixel (T_fin background included):
@@ -588,8 +603,8 @@ GSX_API size_t gsx_backward_std_workspace_bytes(int64_t n, int32_t width, int32_
  *   views      (n)  1 where the frame listed the row on a tile; may be NULL
  * Projection, depth order, binning and the emission prefix run again exactly as for gsx_render_backward /
  * gsx_render_backward_std: hints are neither read nor written, the row classes (GSX_FLAG_ONE_VISIBLE / _SMALL_BATCH) and
- * the one synchronisation are theirs, GSX_FLAG_PUBLISHED_RECTS is honoured under GSX_SEM_STD_3DGS (the background changes
- * nothing here).  params->semantics is GSX_SEM_REF_CPU (NULL params: that) or GSX_SEM_STD_3DGS; GSX_SEM_REF_CUDA is
+ * the one synchronisation are theirs, GSX_FLAG_PUBLISHED_RECTS and GSX_FLAG_ANTIALIASED (the weights of the anti-aliased
+ * frame) are honoured under GSX_SEM_STD_3DGS (the background changes nothing here).  params->semantics is GSX_SEM_REF_CPU (NULL params: that) or GSX_SEM_STD_3DGS; GSX_SEM_REF_CUDA is
  * refused, and so is everything the gradient entries refuse: tile window, output window, substrips, GSX_FLAG_NO_SYNC,
  * camera_device, params->sh.
  * The walk is the GRADIENT entries' walk, not the forward's.  GSX_SEM_REF_CPU: the reference's alpha on every listed record

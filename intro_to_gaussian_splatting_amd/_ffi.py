@@ -38,6 +38,7 @@ GSX_FLAG_HINTS_VALID = 128
 GSX_FLAG_SMALL_BATCH = 256
 GSX_FLAG_ONE_VISIBLE = 512
 GSX_FLAG_PLAIN_FOOTPRINTS = 1024
+GSX_FLAG_ANTIALIASED = 2048
 GSX_BOUNDS_ROWS = 256
 GSX_ADAM_MAX_GROUPS = 8
 GSX_ADAM_LINEAR = 0

@@ -162,7 +162,7 @@ int project_and_sort(const Plan &p, const Carve &c, char *ws, const GsxCamera &c
     gsx::SampleHint presample;
     if (sampled && !sh.use && gsx::knob("GSX_PRESAMPLE", 1) != 0)
         presample = gsx::depth_presample(route, ws + c.temp, n, gsx::emit_chunk_sums(ws + c.temp, n, cap), row_of);
-    GSX_HIP(gsx::launch_project_pack(camera, p.camera_device, in, n, p.grid, p.semantics, p.tight, p.small_batch, p.sh_degree, k0, (gsx::Record *)(ws + c.rec),
+    GSX_HIP(gsx::launch_project_pack(camera, p.camera_device, in, n, p.grid, p.semantics, p.tight, p.antialiased, p.small_batch, p.sh_degree, k0, (gsx::Record *)(ws + c.rec),
                                      (gsx::TileRect *)(ws + c.rect), counters,
                                      p.semantics != GSX_SEM_STD_3DGS ? (float4 *)(ws + c.bbox) : nullptr, sched_hint,
                                      c.temp_bytes >= (size_t)(n / GSX_BOUNDS_ROWS + 1) ? (uint8_t *)(ws + c.temp) : nullptr, s, presample));
@@ -392,6 +392,7 @@ struct GeometryGrads {
 
 // What the gradient entries and gsx_render_depth cover: the reference's own frame, whole, RGB colours.
 int check_whole_ref_cpu(const Plan &p, const GsxCamera *camera, const GsxParams *params, const char *entry) {
+    if (p.antialiased) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take GSX_FLAG_ANTIALIASED: it supports GSX_SEM_REF_CPU only", entry);
     if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "%s supports GSX_SEM_REF_CPU only", entry);
     if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
     if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
@@ -588,10 +589,16 @@ int render_backward_std(const GsxCamera *camera, const float *means3d, const flo
     const gsx::BackwardTiles bt{rec, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots,
                                   geo_slots};
     GSX_HIP(gsx::launch_backward_tiles_std(bt, p.grid, p.out, s));
-    GSX_HIP(gsx::launch_backward_sums_std(slots, prefix, order, rec, m, grad_colors, grad_opacity_logit, s));
-    if (geo)
-        GSX_HIP(gsx::launch_backward_geometry_std(*camera, geo_slots, prefix, order, m, means3d, scales, quats, grad_means3d,
-                                                  grad_scales, grad_quats, grad_means2d, screen_radius, s));
+    if (p.antialiased) {
+        GSX_HIP(gsx::launch_backward_std_antialiased(*camera, slots, geo_slots, prefix, order, m, means3d, scales, quats,
+                                                     opacity_logit, grad_colors, grad_opacity_logit, grad_means3d, grad_scales,
+                                                     grad_quats, grad_means2d, screen_radius, s));
+    } else {
+        GSX_HIP(gsx::launch_backward_sums_std(slots, prefix, order, rec, m, grad_colors, grad_opacity_logit, s));
+        if (geo)
+            GSX_HIP(gsx::launch_backward_geometry_std(*camera, geo_slots, prefix, order, m, means3d, scales, quats, grad_means3d,
+                                                      grad_scales, grad_quats, grad_means2d, screen_radius, s));
+    }
     GSX_HIP(hipStreamSynchronize(s));
     return GSX_OK;
 }
@@ -697,6 +704,8 @@ int gsx_preprocess(const GsxCamera *camera, const float *means3d, const float *s
     hipStream_t s = (hipStream_t)stream;
     if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
     if (n < 0 || n >= (int64_t)1 << 31) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld out of range", (long long)n);
+    if (params && (params->flags & GSX_FLAG_ANTIALIASED))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_preprocess does not take GSX_FLAG_ANTIALIASED: it is the reference's stage 1, not GSX_SEM_STD_3DGS's");
     const int small_batch = !params ? 0 : ((params->flags & GSX_FLAG_ONE_VISIBLE) ? 1 : ((params->flags & GSX_FLAG_SMALL_BATCH) ? 2 : 0));
     if (n_visible_host) *n_visible_host = 0;
     if (n == 0) return GSX_OK;
@@ -749,6 +758,8 @@ int gsx_render_preprocessed(int32_t image_height, int32_t image_width, int32_t t
     Plan p;
     int rc = make_plan_or_fail(image_width, image_height, tile_size, out_image, params, p);
     if (rc != GSX_OK) return rc;
+    if (p.antialiased)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "gsx_render_preprocessed does not take GSX_FLAG_ANTIALIASED: GSX_SEM_STD_3DGS has its own stage 1, use gsx_render_forward");
     if (p.semantics == GSX_SEM_STD_3DGS)
         return fail(GSX_ERR_UNSUPPORTED, "GSX_SEM_STD_3DGS has its own stage 1: use gsx_render_forward");
     if (n < 0 || n >= (int64_t)1 << 31) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld out of range", (long long)n);

@@ -356,6 +356,38 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// GSX_FLAG_ANTIALIASED: the record holds op_eff = sigmoid(logit) * rho (std_aa_factor), and alpha = op_eff G, so the fourth
+// sum U = sum u is dL/d ln op_eff: dL/dlogit = U (1 - sigmoid(logit)), the sigmoid formed from the opacity input by stage 1's
+// own operations (std_sigmoid).  The chain after this kernel needs U for dL/drho: lane 0 leaves it in the free second word
+// of the Gaussian's first geometry slot pair, which backward_geometry_sum_kernel -- launched BEFORE this kernel on that
+// path -- has already rewritten as (S5, 0, 0, 0).  No extra pass, no atomics.  geo_slots null: the colour-only call.
+__global__ void __launch_bounds__(256)
+    backward_std_aa_sum_kernel(const float4 *__restrict__ slots, const uint32_t *__restrict__ prefix,
+                               const uint32_t *__restrict__ order, const float *__restrict__ opacity_logit, uint32_t m,
+                               float *__restrict__ grad_colors, float *__restrict__ grad_opacity_logit,
+                               float4 *__restrict__ geo_slots) {
+    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= m) return;
+    const uint32_t b = prefix[r], e = prefix[r + 1];
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
+        const float4 v = slots[i];
+        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
+    }
+    const float v = wave_sum4(a0, a1, a2, a3, lane);
+    const float g = __shfl(v, 16), bl = __shfl(v, 32), u = __shfl(v, 48);
+    if (lane == 0) {
+        const uint32_t row = order[r];
+        const float sg = std_sigmoid(opacity_logit[row]);
+        grad_colors[3 * (int64_t)row] = v;
+        grad_colors[3 * (int64_t)row + 1] = g;
+        grad_colors[3 * (int64_t)row + 2] = bl;
+        grad_opacity_logit[row] = u * (1.0f - sg);
+        if (geo_slots && b != e) geo_slots[2 * (size_t)b + 1].y = u;
+    }
+}
+
 // ---- gsx_render_backward_geometry: from a Gaussian's moment sums to dL/dpoint, dL/dscale, dL/dquaternion.
 // What stage 1 computes (gsx_project.hip: project), differentiated by hand in float32.  With d = mean - pixel,
 // power = -1/2 d^T Q d and u = dL/dpower:
@@ -377,6 +409,11 @@ __global__ void __launch_bounds__(256)
 // (5) pixel mean = ((h_xy p_w + 1) dim - 1) / 2 with p_w = 1 / (h_w + 1e-7), so d pixel / d ndc = dim / 2 (cam.sx, cam.sy)
 // and the focal lengths are dim / (2 tan(fov / 2)) (cam.fx, cam.fy).  The packed record holds Q'' = -1/2 log2(e) Q, not Q:
 // the conic is formed here as project_std forms it, and so is the published radius ceil(3 sqrt(lambda_max)) (*rad).
+// kAa (GSX_FLAG_ANTIALIASED, with kStd): alpha = sigmoid(logit) rho G with rho = sqrt(det0 / det1) of the covariance before
+// and after the dilation (std_aa_factor: the forward's own float32 decision), so U = sum u = dL/d ln rho and step (1) gains
+//     ln rho = 1/2 (ln det0 - ln det1):   g_ca += 1/2 U (cd0 / det0 - cd1 / det1),   g_cd += 1/2 U (ca0 / det0 - ca1 / det1),
+//     off-diagonal total -U cb (1 / det0 - 1 / det1)
+// before the c10 = c01 merge; where rho is clamped to its floor nothing is added.  The other instances' text is what it was.
 struct GeoCamera {
     float V[16], F[16];            // world2view, full_proj (row vector times matrix)
     float fx, fy, limx, limy, sx, sy;   // focal lengths, 1.3 tan(fov / 2), (width - 1) / 2, (height - 1) / 2
@@ -385,12 +422,13 @@ struct GeoCamera {
 // kCamera (gsx_render_backward_camera): also this Gaussian's 24 terms of dL/dworld2view and dL/dfull_proj into gc, the
 // chain's own g_t, dT and gh contracted with the point instead of with the matrices (kCamTerms, below).  The other
 // instance is the text it was: gc is never touched.
-template <bool kCamera, bool kStd = false>
+template <bool kCamera, bool kStd = false, bool kAa = false>
 __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float *__restrict__ p, const float *__restrict__ sc,
                                                const float *__restrict__ qin, const float4 QA, const float4 QB,
                                                float S1, float S2, float S3, float S4, float S5, float *__restrict__ gp,
                                                float *__restrict__ gs, float *__restrict__ gq, float *__restrict__ gn,
-                                               float *__restrict__ gc, float *__restrict__ rad = nullptr) {
+                                               float *__restrict__ gc, float *__restrict__ rad = nullptr, float U = 0.0f) {
+    static_assert(kStd || !kAa, "the opacity compensation belongs to GSX_SEM_STD_3DGS");
     const float *V = cam.V, *F = cam.F;
     const float p0 = p[0], p1 = p[1], p2 = p[2];
     // ---- forward values
@@ -450,6 +488,7 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
             C[i][j] = __builtin_fmaf(B[i][2], V[2 * 4 + j], __builtin_fmaf(B[i][1], V[1 * 4 + j], B[i][0] * V[0 * 4 + j]));
     float ca = C[0][0] * j00 + C[0][2] * j02, cb = C[0][1] * j11 + C[0][2] * j12;
     float cc = C[1][0] * j00 + C[1][2] * j02, cd = C[1][1] * j11 + C[1][2] * j12;
+    const float ca0 = ca, cd0 = cd;         // (read by kAa only)
     if constexpr (kStd) {
         ca = ca + 0.3f;
         cd = cd + 0.3f;
@@ -481,6 +520,15 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
         g_cd += g_det * ca;
         g_cb -= g_det * cc;
         g_cc -= g_det * cb;
+    }
+    if constexpr (kAa) {
+        const StdAaFactor f = std_aa_factor(ca0, cb, cd0, det);
+        if (!f.clamped) {
+            const float hu = 0.5f * U;
+            g_ca += hu * (cd0 / f.det0 - cd / det);
+            g_cd += hu * (ca0 / f.det0 - ca / det);
+            g_cb += -(U * cb) * (1.0f / f.det0 - 1.0f / det);
+        }
     }
     if constexpr (kStd) {       // c10 = c01: one entry carries both
         g_cb += g_cc;
@@ -660,6 +708,38 @@ __global__ void __launch_bounds__(256)
     float gp[3], gs[3], gq[4], gn[2], rad;
     geometry_chain<false, true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, none, none, S.x, S.y, S.z, S.w, S5.x, gp,
                                 gs, gq, gn, nullptr, &rad);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        grad_means3d[3 * row + k] = gp[k];
+        grad_scales[3 * row + k] = gs[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
+    if (grad_means2d) {
+        grad_means2d[2 * row] = gn[0];
+        grad_means2d[2 * row + 1] = gn[1];
+        screen_radius[row] = rad;
+    }
+}
+
+// GSX_FLAG_ANTIALIASED: backward_std_chain_kernel with the chain's kAa variant; U = sum u is where
+// backward_std_aa_sum_kernel left it, beside S5.
+__global__ void __launch_bounds__(256)
+    backward_std_aa_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                 const uint32_t *__restrict__ order, uint32_t m, GeoCamera cam, const float *__restrict__ means3d,
+                                 const float *__restrict__ scales, const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                                 float *__restrict__ grad_scales, float *__restrict__ grad_quats, float *__restrict__ grad_means2d,
+                                 float *__restrict__ screen_radius) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t b = prefix[r];
+    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
+    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
+    const int64_t row = order[r];
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float gp[3], gs[3], gq[4], gn[2], rad;
+    geometry_chain<false, true, true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, none, none, S.x, S.y, S.z, S.w, S5.x,
+                                      gp, gs, gq, gn, nullptr, &rad, S5.y);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         grad_means3d[3 * row + k] = gp[k];
@@ -976,6 +1056,31 @@ hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slo
     backward_std_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
         geo_slots, prefix, order, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
         screen_radius);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_std_antialiased(const GsxCamera &camera, const float4 *slots, float4 *geo_slots,
+                                           const uint32_t *prefix, const uint32_t *order, uint32_t m, const float *means3d,
+                                           const float *scales, const float *quats, const float *opacity_logit,
+                                           float *grad_colors, float *grad_opacity_logit, float *grad_means3d,
+                                           float *grad_scales, float *grad_quats, float *grad_means2d, float *screen_radius,
+                                           hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    const unsigned waves = (unsigned)(((uint64_t)m + 3) / 4);
+    // the geometry sums first: they rewrite each Gaussian's first slot pair, whose free word then takes U from the colour sums
+    if (geo_slots) backward_geometry_sum_kernel<<<waves, 256, 0, s>>>(geo_slots, prefix, m);
+    backward_std_aa_sum_kernel<<<waves, 256, 0, s>>>(slots, prefix, order, opacity_logit, m, grad_colors, grad_opacity_logit,
+                                                     geo_slots);
+    if (geo_slots) {
+        GeoCamera cam = geo_camera(camera);
+        cam.fx = (float)camera.width / (2.0f * camera.tan_fovx);        // (launch_backward_geometry_std)
+        cam.fy = (float)camera.height / (2.0f * camera.tan_fovy);
+        cam.sx = (float)camera.width * 0.5f;
+        cam.sy = (float)camera.height * 0.5f;
+        backward_std_aa_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
+            geo_slots, prefix, order, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
+            screen_radius);
+    }
     return hipGetLastError();
 }
 

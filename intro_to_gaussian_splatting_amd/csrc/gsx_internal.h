@@ -117,6 +117,29 @@ __device__ __forceinline__ void std_tests(float pw, float alpha, float thr, floa
     stop = use && (T - ta < kStdStop);
 }
 
+// GSX_FLAG_ANTIALIASED (GSX_SEM_STD_3DGS): the opacity compensation of one Gaussian from its EWA covariance (ca0, cb, cd0)
+// as ewa_covariance leaves it, BEFORE the 0.3 dilation, and det1, the determinant project_std forms AFTER it (the one its
+// conic divides by).  rho = sqrt(max(0.000025, det0 / det1)); where the ratio does not exceed the floor -- a float32
+// det0 <= 0 and a NaN included -- rho is the constant 0.005 and carries no gradient (clamped).  Stage 1 (gsx_project.hip:
+// project_std) and the backward chain (gsx_backward.hip: geometry_chain) both call this on the same float32 values, so both
+// take the same branch; every file is compiled with -ffp-contract=off: two rounded products, one difference, one quotient.
+constexpr float kStdAaFloor = 0.000025f;
+struct StdAaFactor {
+    float det0, rho;
+    bool clamped;
+};
+__device__ __forceinline__ StdAaFactor std_aa_factor(float ca0, float cb, float cd0, float det1) {
+    StdAaFactor f;
+    f.det0 = ca0 * cd0 - cb * cb;
+    const float ratio = f.det0 / det1;
+    f.clamped = !(ratio > kStdAaFloor);
+    f.rho = f.clamped ? 0.005f : sqrtf(ratio);    // (sqrtf(fmaxf(0.000025f, ratio)), its floor spelled as the constant it is)
+    return f;
+}
+// sigmoid(logit) as GSX_SEM_STD_3DGS's stage 1 forms it (gsx_project.hip: sigmoidf, the same operations): the anti-aliased
+// record holds sigmoid(logit) * rho, and dL/dlogit needs the first factor alone.
+__device__ __forceinline__ float std_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
 // Tiles whose list is much longer than the frame's average are composited by FOUR waves (a quarter of the
 // tile's pixels each, one pixel per lane, eight records per trip) instead of one: a lone wave walks its list
 // at ~430 cycles per record, so one 20 000-entry tile would outlast the rest of the frame several times over.
@@ -186,6 +209,7 @@ hipError_t launch_project_stage(const GsxCamera &cam, const GaussiansIn &in, int
 // bbox (REF_CUDA only, else may be null): (min_x, max_x, min_y, max_y) per Gaussian for the
 // per-pixel cull of splat/c/render.cu:55-60.
 // tight_rects: GSX_SEM_STD_3DGS without GSX_FLAG_PUBLISHED_RECTS (see include/gsx.h).
+// antialiased: GSX_FLAG_ANTIALIASED (GSX_SEM_STD_3DGS): the record's opacity is sigmoid(logit) * rho (std_aa_factor).
 // cam_device (may be null): GsxParams.camera_device, read by the kernel instead of `cam`.
 // sh_degree >= 0: in.colors holds spherical-harmonics coefficients, evaluated inline (GsxParams.sh).
 // counters: 4 words this kernel zeroes for the depth sort (culled count, kept count, ...).
@@ -199,7 +223,7 @@ struct SampleHint {
     const uint32_t *row_of = nullptr;      // GsxParams.row_of_index: sample index (an original index) -> row
 };
 hipError_t launch_project_pack(const GsxCamera &cam, const GsxCamera *cam_device, const GaussiansIn &in, int64_t n,
-                               const TileGrid &grid, int semantics, bool tight_rects, int visible_rows, int sh_degree,
+                               const TileGrid &grid, int semantics, bool tight_rects, bool antialiased, int visible_rows, int sh_degree,
                                uint32_t *keys, Record *rec, TileRect *rect, uint32_t *counters, float4 *bbox,
                                const ScheduleHint &sched, uint8_t *block_scratch, hipStream_t s,
                                const SampleHint &sample = SampleHint());
@@ -621,6 +645,16 @@ hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slo
                                         const uint32_t *order, uint32_t m, const float *means3d, const float *scales,
                                         const float *quats, float *grad_means3d, float *grad_scales, float *grad_quats,
                                         float *grad_means2d, float *screen_radius, hipStream_t s);
+// GSX_FLAG_ANTIALIASED: what the two launches above do on records that hold sigmoid(logit) * rho (std_aa_factor) -- the
+// geometry sums, then the colour sums with dL/dlogit = (sum u)(1 - sigmoid(logit)) from the opacity input, which also hand
+// sum u to the chain's anti-aliased variant through a free word of the Gaussian's first geometry slot pair.  geo_slots
+// null: the colour-only call (the five geometry outputs are not touched).
+hipError_t launch_backward_std_antialiased(const GsxCamera &camera, const float4 *slots, float4 *geo_slots,
+                                           const uint32_t *prefix, const uint32_t *order, uint32_t m, const float *means3d,
+                                           const float *scales, const float *quats, const float *opacity_logit,
+                                           float *grad_colors, float *grad_opacity_logit, float *grad_means3d,
+                                           float *grad_scales, float *grad_quats, float *grad_means2d, float *screen_radius,
+                                           hipStream_t s);
 
 // ---- gsx_contribution.hip (gsx_render_contribution): the gradient entries' walk with no image and no gradient
 struct ContributionTiles {

@@ -384,6 +384,7 @@ struct Plan {
     bool tight;    // GSX_SEM_STD_3DGS without GSX_FLAG_PUBLISHED_RECTS
     bool split;    // long tiles on four waves (not GSX_FLAG_NO_LONG_TILE_SPLIT)
     bool plain;         // GSX_FLAG_PLAIN_FOOTPRINTS
+    bool antialiased;   // GSX_FLAG_ANTIALIASED (GSX_SEM_STD_3DGS): stage 1 packs sigmoid(logit) * rho (gsx_internal.h: std_aa_factor)
     size_t stats_bytes; // how far GsxFrameStats is written: GsxParams.stats_size, 64 when the caller did not state it
     int small_batch;    // 1: GSX_FLAG_ONE_VISIBLE, 2: GSX_FLAG_SMALL_BATCH, 0: neither
     int schedule;  // tiles handed out by list length: 1 GSX_FLAG_TILE_SCHEDULE, 0 GSX_FLAG_NO_TILE_SCHEDULE, -1 by size
@@ -454,6 +455,9 @@ inline int make_plan(int32_t width, int32_t height, int32_t tile, float *out_ima
     p.tight = d.semantics == GSX_SEM_STD_3DGS && (d.flags & GSX_FLAG_PUBLISHED_RECTS) == 0;
     p.split = (d.flags & GSX_FLAG_NO_LONG_TILE_SPLIT) == 0;
     p.plain = (d.flags & GSX_FLAG_PLAIN_FOOTPRINTS) != 0;
+    p.antialiased = (d.flags & GSX_FLAG_ANTIALIASED) != 0;
+    if (p.antialiased && d.semantics != GSX_SEM_STD_3DGS)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "GSX_FLAG_ANTIALIASED needs GsxParams.semantics = GSX_SEM_STD_3DGS");
     if (d.stats_size == 0) d.stats_size = GSX_FRAME_STATS_BYTES_ABI300;     // (a zeroed struct: not stated)
     if (d.stats_size != GSX_FRAME_STATS_BYTES_ABI300 && (d.stats_size < (int32_t)sizeof(GsxFrameStats) || (d.stats_size & 7) != 0))
         return fail(GSX_ERR_INVALID_ARGUMENT, "GsxParams.stats_size %d is neither %d nor >= %zu", d.stats_size,

@@ -36,6 +36,7 @@ struct Projected {
     float q00, q01, q10, q11;
     float radius, depth;
     float min_x, max_x, min_y, max_y;
+    float rho;             // GSX_FLAG_ANTIALIASED: the opacity compensation (project_std; 1 otherwise)
 };
 
 // Column `col` of [p,1] @ M as torch's (N,4) @ (4,4) executes it: one sgemm, a sequential FMA chain over k
@@ -212,6 +213,8 @@ __device__ __forceinline__ void project(const GsxCamera &cam, float p0, float p1
 
 // GSX_SEM_STD_3DGS stage 1 (published 3DGS forward pass; see include/gsx.h).  Returns false when
 // the Gaussian is dropped (det == 0).  o.q00, o.q01 = o.q10, o.q11 = the symmetric conic.
+// AA (GSX_FLAG_ANTIALIASED): o.rho = std_aa_factor of the covariance before and after the dilation, else 1.
+template <bool AA>
 __device__ __forceinline__ bool project_std(const GsxCamera &cam, float p0, float p1, float p2, float tz,
                                             float s0, float s1, float s2, float qw, float qx, float qy, float qz,
                                             Projected &o) {
@@ -224,11 +227,13 @@ __device__ __forceinline__ bool project_std(const GsxCamera &cam, float p0, floa
     o.y = ((ndcy + 1.0f) * (float)cam.height - 1.0f) * 0.5f;
     float fx = (float)cam.width / (2.0f * cam.tan_fovx), fy = (float)cam.height / (2.0f * cam.tan_fovy);
     ewa_covariance(cam, fx, fy, p0, p1, p2, tz, S, o, kRowsMany);
+    const float ca0 = o.ca, cd0 = o.cd;
     o.ca = o.ca + 0.3f;
     o.cd = o.cd + 0.3f;
     o.cc = o.cb;
     float det = o.ca * o.cd - o.cb * o.cb;
     if (det == 0.0f) return false;
+    o.rho = AA ? std_aa_factor(ca0, o.cb, cd0, det).rho : 1.0f;
     float det_inv = 1.0f / det;
     o.q00 = o.cd * det_inv;
     o.q01 = -o.cb * det_inv;
@@ -476,7 +481,8 @@ __device__ __forceinline__ void presample_depths(const GsxCamera &cam, const Gau
 // together with everything else (pre_op, cr / cg / cb) -- a survivor of the window test nearly always needs them, and
 // fetched here, behind the arithmetic, they are two more dependent trips to memory.  SHDEG >= 0: cr / cg / cb hold the
 // colour evaluated from spherical harmonics.  Shared by both kernels: same operations, same bits.
-template <int SHDEG, bool CULL, bool PRE>
+// AA: GSX_FLAG_ANTIALIASED (GSX_SEM_STD_3DGS): the record's opacity is sigmoid(logit) * rho; AA = false is the text it was.
+template <int SHDEG, bool CULL, bool PRE, bool AA>
 __device__ __forceinline__ void project_one(const GsxCamera &cam, const GaussiansIn &in, int64_t g, int64_t slot, bool remapped,
                                             int64_t n, const TileGrid &grid, int semantics, bool tight, int vis, float cr,
                                             float cg, float cb, float pre_op, float p0, float p1, float p2, float s0, float s1,
@@ -496,7 +502,7 @@ __device__ __forceinline__ void project_one(const GsxCamera &cam, const Gaussian
     Projected o;
     bool keep = true;
     if (std3dgs)
-        keep = project_std(cam, p0, p1, p2, tz, s0, s1, s2, q0, q1, q2, q3, o);
+        keep = project_std<AA>(cam, p0, p1, p2, tz, s0, s1, s2, q0, q1, q2, q3, o);
     else
         project(cam, p0, p1, p2, tz, s0, s1, s2, q0, q1, q2, q3, o, vis);
     TileRect tr;
@@ -536,6 +542,9 @@ __device__ __forceinline__ void project_one(const GsxCamera &cam, const Gaussian
         return;
     }
     keys[slot] = __float_as_uint(tz);
+    // GSX_FLAG_ANTIALIASED: the record's opacity is sigmoid(logit) * rho (the rectangle above was sized by sigmoid(logit):
+    // rho <= 1 up to rounding, so every pixel the product can still reach lies inside it)
+    if (AA && std3dgs) op = op * o.rho;
     if (SHDEG < 0 && !PRE) {
         const float *c = in.colors + 3 * g;
         cr = c[0]; cg = c[1]; cb = c[2];
@@ -559,13 +568,15 @@ __device__ __forceinline__ void project_one(const GsxCamera &cam, const Gaussian
 // degree (gsx_sh_device.h: the workgroup streams its 256 Gaussians' coefficients through LDS) with the camera
 // centre of the GsxCamera the kernel reads -- no colour array, no colour launch, and a captured frame follows
 // a moving camera with SH colours too.  SHDEG = -1: in.colors holds RGB, as in the reference.
-template <bool DEVICE_CAMERA, int SHDEG>
-__global__ void __launch_bounds__(kBlock)
-    project_pack_kernel(GsxCamera cam_arg, const GsxCamera *__restrict__ cam_dev, GaussiansIn in, int64_t n,
-                        TileGrid grid, int semantics, bool tight, int vis,
-                        uint32_t *__restrict__ keys, Record *__restrict__ rec,
-                        TileRect *__restrict__ rect, uint32_t *__restrict__ counters, float4 *__restrict__ bbox,
-                        bool sh_vec, SchedJob sched_job, SampleJob sample_job) {
+// AA: GSX_FLAG_ANTIALIASED -- an instance of its own (project_pack_aa_kernel, below), so that the kernel every other frame
+// runs is the code it was.
+template <bool DEVICE_CAMERA, int SHDEG, bool AA>
+__device__ __forceinline__ void
+    project_pack_body(const GsxCamera &cam_arg, const GsxCamera *__restrict__ cam_dev, const GaussiansIn &in, int64_t n,
+                      const TileGrid &grid, int semantics, bool tight, int vis,
+                      uint32_t *__restrict__ keys, Record *__restrict__ rec,
+                      TileRect *__restrict__ rect, uint32_t *__restrict__ counters, float4 *__restrict__ bbox,
+                      bool sh_vec, const SchedJob &sched_job, const SampleJob &sample_job) {
     constexpr int DEG = SHDEG >= 0 ? SHDEG : 0;
     using L = sh::Layout<DEG>;
     // (the spare workgroups' sample lives where the others stage spherical harmonics: kSortSamples + 4 words at least)
@@ -615,9 +626,22 @@ __global__ void __launch_bounds__(kBlock)
 
     // ---- the exact projection (project_one: shared with the windowed kernel)
     const float *p = in.means3d + 3 * g, *sc = in.scales + 3 * g, *q = in.quats + 4 * g;
-    project_one<SHDEG, true, false>(cam, in, g, remap ? (int64_t)remap[g] : g, remap != nullptr, n, grid, semantics, tight, vis, cr, cg,
-                                    cb, 0.0f, p[0], p[1], p[2], sc[0], sc[1], sc[2], q[0], q[1], q[2], q[3], keys, rec, rect, bbox);
+    project_one<SHDEG, true, false, AA>(cam, in, g, remap ? (int64_t)remap[g] : g, remap != nullptr, n, grid, semantics, tight, vis, cr, cg,
+                                        cb, 0.0f, p[0], p[1], p[2], sc[0], sc[1], sc[2], q[0], q[1], q[2], q[3], keys, rec, rect, bbox);
 }
+#define GSX_PROJECT_PACK_KERNEL(NAME, AA)                                                                                 \
+    template <bool DEVICE_CAMERA, int SHDEG>                                                                              \
+    __global__ void __launch_bounds__(kBlock)                                                                             \
+        NAME(GsxCamera cam_arg, const GsxCamera *__restrict__ cam_dev, GaussiansIn in, int64_t n, TileGrid grid,          \
+             int semantics, bool tight, int vis, uint32_t *__restrict__ keys, Record *__restrict__ rec,                    \
+             TileRect *__restrict__ rect, uint32_t *__restrict__ counters, float4 *__restrict__ bbox, bool sh_vec,         \
+             SchedJob sched_job, SampleJob sample_job) {                                                                  \
+        project_pack_body<DEVICE_CAMERA, SHDEG, AA>(cam_arg, cam_dev, in, n, grid, semantics, tight, vis, keys, rec, rect, \
+                                                    counters, bbox, sh_vec, sched_job, sample_job);                       \
+    }
+GSX_PROJECT_PACK_KERNEL(project_pack_kernel, false)
+GSX_PROJECT_PACK_KERNEL(project_pack_aa_kernel, true)
+#undef GSX_PROJECT_PACK_KERNEL
 
 // GsxParams.block_bounds: may the windowed kernel drop the block (lo.xyz .. hi.xyz = box of its means, lo.w = its largest
 // |scale|) unread?  Only if every row of it would fail the row test of phase 1 WITHOUT being culled: all eight corners
@@ -669,13 +693,13 @@ __device__ __forceinline__ bool block_misses_window(const GsxCamera &cam, const 
 // strip of 5M Gaussians, 73 VGPRs: the kernel never waited for its loads but for its partial-line stores)
 constexpr int kWinPer = 1, kWinRows = kBlock * kWinPer;
 static_assert(kWinRows == GSX_BOUNDS_ROWS, "a workgroup of the windowed kernel takes one block of GsxParams.block_bounds");
-template <bool DEVICE_CAMERA, int SHDEG>
-__global__ void __launch_bounds__(kBlock)
-    project_window_kernel(GsxCamera cam_arg, const GsxCamera *__restrict__ cam_dev, GaussiansIn in, int64_t n,
-                          TileGrid grid, int semantics, bool tight, int vis,
-                          uint32_t *__restrict__ keys, Record *__restrict__ rec,
-                          TileRect *__restrict__ rect, uint32_t *__restrict__ counters, float4 *__restrict__ bbox,
-                          bool sh_vec, SchedJob sched_job, const uint8_t *__restrict__ block_dropped, SampleJob sample_job) {
+template <bool DEVICE_CAMERA, int SHDEG, bool AA>
+__device__ __forceinline__ void
+    project_window_body(const GsxCamera &cam_arg, const GsxCamera *__restrict__ cam_dev, const GaussiansIn &in, int64_t n,
+                        const TileGrid &grid, int semantics, bool tight, int vis,
+                        uint32_t *__restrict__ keys, Record *__restrict__ rec,
+                        TileRect *__restrict__ rect, uint32_t *__restrict__ counters, float4 *__restrict__ bbox,
+                        bool sh_vec, const SchedJob &sched_job, const uint8_t *__restrict__ block_dropped, const SampleJob &sample_job) {
     constexpr int DEG = SHDEG >= 0 ? SHDEG : 0;
     using L = sh::Layout<DEG>;
     constexpr int kShWords = SHDEG >= 0 ? L::kRows * L::STRIDE : 1;
@@ -808,10 +832,23 @@ __global__ void __launch_bounds__(kBlock)
             }
         }
         if (active)
-            project_one<SHDEG, false, true>(cam, in, g, slot, remap != nullptr, n, grid, semantics, tight, vis, cr, cg, cb, lg, p0,
-                                            p1, p2, s0, s1, s2, q0, q1, q2, q3, keys, rec, rect, bbox);
+            project_one<SHDEG, false, true, AA>(cam, in, g, slot, remap != nullptr, n, grid, semantics, tight, vis, cr, cg, cb, lg, p0,
+                                                p1, p2, s0, s1, s2, q0, q1, q2, q3, keys, rec, rect, bbox);
     }
 }
+#define GSX_PROJECT_WINDOW_KERNEL(NAME, AA)                                                                                 \
+    template <bool DEVICE_CAMERA, int SHDEG>                                                                                \
+    __global__ void __launch_bounds__(kBlock)                                                                               \
+        NAME(GsxCamera cam_arg, const GsxCamera *__restrict__ cam_dev, GaussiansIn in, int64_t n, TileGrid grid,            \
+             int semantics, bool tight, int vis, uint32_t *__restrict__ keys, Record *__restrict__ rec,                      \
+             TileRect *__restrict__ rect, uint32_t *__restrict__ counters, float4 *__restrict__ bbox, bool sh_vec,           \
+             SchedJob sched_job, const uint8_t *__restrict__ block_dropped, SampleJob sample_job) {                         \
+        project_window_body<DEVICE_CAMERA, SHDEG, AA>(cam_arg, cam_dev, in, n, grid, semantics, tight, vis, keys, rec, rect, \
+                                                      counters, bbox, sh_vec, sched_job, block_dropped, sample_job);        \
+    }
+GSX_PROJECT_WINDOW_KERNEL(project_window_kernel, false)
+GSX_PROJECT_WINDOW_KERNEL(project_window_aa_kernel, true)
+#undef GSX_PROJECT_WINDOW_KERNEL
 
 // GsxParams.original_index, before the projection: the keys start out as kEmptyKey ("reaches no tile": the projection then
 // stores only the keys of culled and kept Gaussians, under their original index), and -- GsxParams.block_bounds, a call that
@@ -958,7 +995,7 @@ hipError_t launch_project_stage(const GsxCamera &cam, const GaussiansIn &in, int
 
 template <int SHDEG>
 static void launch_project_pack_deg(const GsxCamera &cam, const GsxCamera *cam_device, const GaussiansIn &in, int64_t n,
-                                    const TileGrid &grid, int semantics, bool tight_rects, int visible_rows, uint32_t *keys,
+                                    const TileGrid &grid, int semantics, bool tight_rects, bool antialiased, int visible_rows, uint32_t *keys,
                                     Record *rec, TileRect *rect, uint32_t *counters, float4 *bbox, const ScheduleHint &sh,
                                     uint8_t *block_scratch, hipStream_t s, const SampleHint &sample) {
     const SchedJob job{sh.lens, sh.sched, sh.header, sh.ntiles, sh.nwy, sched_cap(sh.ntiles, sh.nwy)};
@@ -979,16 +1016,22 @@ static void launch_project_pack_deg(const GsxCamera &cam, const GsxCamera *cam_d
         else
             prepare_reordered_kernel<false><<<blocks, kBlock, 0, s>>>(cam, cam_device, grid, keys, n, in.block_bounds, nblocks, dropped);
     }
-#define GSX_LAUNCH_PP(DC)                                                                                             \
+#define GSX_LAUNCH_PP(DC, WINDOW, PACK)                                                                                \
     do {                                                                                                              \
         if (windowed)                                                                                                 \
-            project_window_kernel<DC, SHDEG><<<(unsigned)((n + kWinRows - 1) / kWinRows) + spare, kBlock, 0, s>>>(     \
+            WINDOW<DC, SHDEG><<<(unsigned)((n + kWinRows - 1) / kWinRows) + spare, kBlock, 0, s>>>(                    \
                 cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows ? visible_rows : rows_class(n), keys, rec, rect, counters, bbox, vec, job, dropped, sjob); \
         else                                                                                                          \
-            project_pack_kernel<DC, SHDEG><<<blocks_for(n) + spare, kBlock, 0, s>>>(                                   \
+            PACK<DC, SHDEG><<<blocks_for(n) + spare, kBlock, 0, s>>>(                                                  \
                 cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows ? visible_rows : rows_class(n), keys, rec, rect, counters, bbox, vec, job, sjob); \
     } while (0)
-    if (cam_device) GSX_LAUNCH_PP(true); else GSX_LAUNCH_PP(false);
+    if (antialiased && semantics == GSX_SEM_STD_3DGS) {
+        if (cam_device) GSX_LAUNCH_PP(true, project_window_aa_kernel, project_pack_aa_kernel);
+        else GSX_LAUNCH_PP(false, project_window_aa_kernel, project_pack_aa_kernel);
+    } else {
+        if (cam_device) GSX_LAUNCH_PP(true, project_window_kernel, project_pack_kernel);
+        else GSX_LAUNCH_PP(false, project_window_kernel, project_pack_kernel);
+    }
 #undef GSX_LAUNCH_PP
 }
 
@@ -1028,16 +1071,16 @@ __global__ void __launch_bounds__(kBlock)
 
 // sh_degree < 0: in.colors is (n,3) RGB; 0..3: in.colors is (n, (degree+1)^2, 3) spherical harmonics.
 hipError_t launch_project_pack(const GsxCamera &cam, const GsxCamera *cam_device, const GaussiansIn &in, int64_t n,
-                               const TileGrid &grid, int semantics, bool tight_rects, int visible_rows, int sh_degree,
+                               const TileGrid &grid, int semantics, bool tight_rects, bool antialiased, int visible_rows, int sh_degree,
                                uint32_t *keys, Record *rec, TileRect *rect, uint32_t *counters, float4 *bbox,
                                const ScheduleHint &sched, uint8_t *block_scratch, hipStream_t s, const SampleHint &sample) {
     if (n == 0) return hipSuccess;
     switch (sh_degree) {
-        case 0: launch_project_pack_deg<0>(cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
-        case 1: launch_project_pack_deg<1>(cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
-        case 2: launch_project_pack_deg<2>(cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
-        case 3: launch_project_pack_deg<3>(cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
-        default: launch_project_pack_deg<-1>(cam, cam_device, in, n, grid, semantics, tight_rects, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
+        case 0: launch_project_pack_deg<0>(cam, cam_device, in, n, grid, semantics, tight_rects, antialiased, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
+        case 1: launch_project_pack_deg<1>(cam, cam_device, in, n, grid, semantics, tight_rects, antialiased, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
+        case 2: launch_project_pack_deg<2>(cam, cam_device, in, n, grid, semantics, tight_rects, antialiased, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
+        case 3: launch_project_pack_deg<3>(cam, cam_device, in, n, grid, semantics, tight_rects, antialiased, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
+        default: launch_project_pack_deg<-1>(cam, cam_device, in, n, grid, semantics, tight_rects, antialiased, visible_rows, keys, rec, rect, counters, bbox, sched, block_scratch, s, sample); break;
     }
     return hipGetLastError();
 }

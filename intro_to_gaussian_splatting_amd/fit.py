@@ -46,7 +46,9 @@ With ``semantics="std_3dgs"`` (and ``background=(r, g, b)``) step 2 passes the t
 the published rule set's and step 4 runs gsx_render_backward_std; the loss of step 3 covers the whole frame (that rule set
 renders partial edge tiles) and ``evaluate()`` renders with the same rules.  ``statistic="screen"`` and ``strategy="mcmc"``
 work as above.  ``refine_poses``, ``depth_targets`` and ``statistic="screen_abs"`` are refused together with it: the std_3dgs
-backward has no pose gradient, no depth image and no absolute statistic.  With ``semantics="ref_cpu"``, the default, every
+backward has no pose gradient, no depth image and no absolute statistic.  With ``antialiased=True`` besides, the frames of
+step 2, of ``evaluate()`` and of the "prune_contribution" event are the anti-aliased variant of that rule set
+(``render_image_hip(..., antialiased=True)``: opacity times rho).  With ``semantics="ref_cpu"``, the default, every
 call is the one above.
 
 The coefficients keep ONE learning rate: a second rate for the higher bands, as published, needs an Adam group over a strided
@@ -198,6 +200,9 @@ class Trainer:
     are rendered, differentiated and evaluated under the published rule set over ``background`` (r, g, b), and the loss
     covers the whole frame.  ``refine_poses``, ``depth_targets`` and ``statistic="screen_abs"`` are refused together with it;
     a ``background`` other than black is refused without it (the ref_cpu frame has none).
+    ``antialiased`` (``semantics="std_3dgs"`` only; ValueError otherwise): every frame the Trainer renders -- ``step()``,
+    ``evaluate()`` and the contribution sweep -- is the anti-aliased variant (``render_image_hip(..., antialiased=True)``).
+    False, the default: every call and every bit as without the argument.
     ``prune_contribution_at``: None (every call and every bit as without it), or the steps after which the fit prunes by
     contribution: ``scene.contribution(indices)`` sweeps the views (``prune_contribution["indices"]``; None: every view of
     the scene) under the Trainer's ``semantics`` and tile size -- the background changes no blend weight -- and
@@ -214,7 +219,8 @@ class Trainer:
                  lambda_depth: float = 0.0, masks: Optional[Dict[int, torch.Tensor]] = None,
                  exposure: Optional[dict] = None, strategy: str = "adaptive", mcmc: Optional[dict] = None,
                  semantics: str = "ref_cpu", background: Tuple[float, float, float] = (0.0, 0.0, 0.0),
-                 prune_contribution_at: Optional[Iterable[int]] = None, prune_contribution: Optional[dict] = None) -> None:
+                 prune_contribution_at: Optional[Iterable[int]] = None, prune_contribution: Optional[dict] = None,
+                 antialiased: bool = False) -> None:
         g = scene.gaussians
         if prune_contribution_at is not None:
             prune_contribution_at = _steps("prune_contribution_at", prune_contribution_at)
@@ -245,7 +251,12 @@ class Trainer:
                 if given:
                     raise ValueError("%s cannot be combined with semantics='std_3dgs': gsx_render_backward_std has no pose "
                                      "gradient, no depth image and no absolute statistic" % name)
-        self.semantics, self.background = semantics, background
+        if antialiased and semantics != "std_3dgs":
+            raise ValueError("antialiased=True needs semantics='std_3dgs', got semantics=%r: the opacity compensation is a "
+                             "variant of the published rule set" % (semantics,))
+        self.semantics, self.background, self.antialiased = semantics, background, bool(antialiased)
+        # (passed only when set: without it every call is the one it was)
+        self._std_kw = dict(antialiased=True) if self.antialiased else {}
         if strategy not in STRATEGIES:
             raise ValueError("strategy = %r is neither 'adaptive' nor 'mcmc'" % (strategy,))
         if strategy == "mcmc":
@@ -342,7 +353,7 @@ class Trainer:
         if self.semantics == "std_3dgs":
             frame = scene.render_image_hip(idx, tile_size=self.tile_size, geometry_gradients=True,
                                            screen_statistics=self.statistic == "screen", semantics=self.semantics,
-                                           background=self.background)
+                                           background=self.background, **self._std_kw)
             region_kw = dict(semantics=self.semantics)
         elif self.depth_targets is not None:
             frame, depth = scene.render_image_depth_hip(idx, tile_size=self.tile_size,
@@ -384,7 +395,7 @@ class Trainer:
                 self.density.reset_opacity(self.opacity_reset_logit)
             elif event == "prune_contribution":
                 pc = self.prune_contribution
-                con = scene.contribution(pc["indices"], semantics=self.semantics, tile_size=self.tile_size)
+                con = scene.contribution(pc["indices"], semantics=self.semantics, tile_size=self.tile_size, **self._std_kw)
                 self.density.prune_contribution(con, threshold=pc["threshold"])
             else:
                 g.oneup_sh_degree()
@@ -409,7 +420,7 @@ class Trainer:
                 std = self.semantics == "std_3dgs"
                 if std:
                     frame = self.scene.render_image_hip(idx, tile_size=self.tile_size, semantics=self.semantics,
-                                                        background=self.background)
+                                                        background=self.background, **self._std_kw)
                 else:
                     frame = self.scene.render_image_hip(idx, tile_size=self.tile_size)
                 terms: dict = {}

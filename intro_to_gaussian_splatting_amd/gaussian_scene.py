@@ -300,6 +300,23 @@ def _refuse_with_grad(what: str) -> None:
                      "requires_grad" % what)
 
 
+def _check_antialiased(antialiased, semantics: str, camera_gradients=False, screen_statistics=False) -> None:
+    """``antialiased=True`` belongs to the std_3dgs rule set and to what that rule set computes: refused by name otherwise,
+    with or without gradients."""
+    if not antialiased:
+        return
+    if semantics != "std_3dgs":
+        raise ValueError("antialiased=True needs semantics='std_3dgs', got semantics=%r: the opacity compensation "
+                         "(GSX_FLAG_ANTIALIASED) is a variant of the published rule set, ref_cpu and ref_cuda have none"
+                         % (semantics,))
+    if camera_gradients:
+        raise ValueError("antialiased=True cannot be combined with camera_gradients=True: the std_3dgs frame has no pose "
+                         "gradient (gsx_render_backward_std)")
+    if _screen_mode(screen_statistics) == "abs":
+        raise ValueError("antialiased=True cannot be combined with screen_statistics='abs': the std_3dgs frame has no "
+                         "absolute statistic (gsx_render_backward_std); pass screen_statistics=True")
+
+
 def _refuse_std_with_grad(what: str) -> None:
     raise ValueError("gradients of the std_3dgs frame (gsx_render_backward_std) are not available with %s: they reach "
                      "colors / sh, opacity and, with geometry_gradients=True, points, scales and quaternions, with "
@@ -389,7 +406,7 @@ class _RenderImageFunction(torch.autograd.Function):
     nothing.  ``world2view`` (None unless ``camera_gradients=True``
     and the view's tensor requires grad) gets the total derivative of the pose: gsx_render_backward_camera's
     dL/dworld2view + dL/dfull_proj @ projection_matrix^T, plus, on an SH scene, the camera centre's share.
-    ``semantics="std_3dgs"`` in ``kw`` (with its ``background`` and ``published_rects``): the frame is the std_3dgs frame and
+    ``semantics="std_3dgs"`` in ``kw`` (with its ``background``, ``published_rects`` and ``antialiased``): the frame is the std_3dgs frame and
     the backward is one gsx_render_backward_std call for the same outputs, the screen statistics included; no pose and no
     absolute statistic there."""
 
@@ -402,8 +419,8 @@ class _RenderImageFunction(torch.autograd.Function):
         mode = kw.pop("screen_statistics", False)
         ctx.screen, ctx.screen_abs = bool(mode), mode == "abs"
         # semantics="std_3dgs": the frame's rules, background and rectangles, which gsx_render_backward_std is told again
-        ctx.std = (tuple(float(v) for v in kw.get("background", (0.0, 0.0, 0.0))), bool(kw.get("published_rects", False))) \
-            if kw.get("semantics", "ref_cpu") == "std_3dgs" else None
+        ctx.std = (tuple(float(v) for v in kw.get("background", (0.0, 0.0, 0.0))), bool(kw.get("published_rects", False)),
+                   bool(kw.get("antialiased", False))) if kw.get("semantics", "ref_cpu") == "std_3dgs" else None
         user_stats, st = kw.pop("stats", None), {}
         frame = scene.render_image_hip(image_idx, tile_size=tile_size, layout=layout, stats=st, **kw)
         if user_stats is not None:
@@ -689,7 +706,8 @@ class GaussianScene:
                          tile_schedule: Optional[bool] = None, use_hints: bool = True,
                          substrips: Optional[Sequence[int]] = None, substrip_events: Optional[list] = None,
                          _private: Optional[dict] = None, geometry_gradients: bool = False,
-                         screen_statistics: bool = False, camera_gradients: bool = False) -> torch.Tensor:
+                         screen_statistics: bool = False, camera_gradients: bool = False,
+                         antialiased: bool = False) -> torch.Tensor:
         """Full forward render in libgsx (gsx_render_forward).
 
         semantics: "ref_cpu" (the reference's ``render_image``), "ref_cuda" (its CUDA kernel's rules
@@ -765,7 +783,17 @@ class GaussianScene:
         by name there (ValueError; all of them run under ``torch.no_grad()``): ``camera_gradients=True``,
         ``screen_statistics="abs"``, a ``background`` that requires grad (dL/dbackground is not computed), and the arguments
         the ref_cpu gradient path refuses; ``semantics="ref_cuda"`` has no gradient.
+        ``antialiased`` (``semantics="std_3dgs"`` only, GSX_FLAG_ANTIALIASED): the anti-aliased variant of that rule set --
+        Mip-Splatting's 2D filter, the published rasteriser's ``antialiasing`` switch, gsplat's
+        ``rasterize_mode="antialiased"``.  The 0.3 dilation stays and the opacity is multiplied by
+        rho = sqrt(max(0.000025, det(cov2d) / det(cov2d + 0.3 I))), so a widened Gaussian keeps the energy of the original;
+        the 1/255 skip, the 0.99 clamp and the stop rule see the product.  With gradients the same one backward call, with
+        dL/dopacity through sigmoid * rho and dL/drho on to points, scales and quaternions (a rho on its floor, 0.005,
+        passes none).  ``antialiased=True`` under any other semantics is refused (ValueError), and so is what std_3dgs
+        refuses: ``camera_gradients=True``, ``screen_statistics="abs"``, the depth image (``render_image_depth_hip`` renders
+        the ref_cpu frame and has no such argument; gsx_render_depth refuses the flag by name).
         """
+        _check_antialiased(antialiased, semantics, camera_gradients, screen_statistics)
         screen_statistics = _screen_mode(screen_statistics)
         if screen_statistics and not geometry_gradients:
             raise ValueError("screen_statistics=%r needs geometry_gradients=True: the statistic comes out of the geometry "
@@ -795,14 +823,15 @@ class GaussianScene:
                       split_long_tiles=split_long_tiles, tile_schedule=tile_schedule, use_hints=use_hints,
                       geometry_gradients=bool(geometry_gradients), screen_statistics=screen_statistics)
             if std:
-                kw.update(semantics=semantics, background=background, published_rects=published_rects)
+                kw.update(semantics=semantics, background=background, published_rects=published_rects,
+                          antialiased=bool(antialiased))
             return _RenderImageFunction.apply(self, image_idx, tile_size, layout, kw, g.points, g.scales, g.quaternions,
                                               g.opacity, g.colors, getattr(g, "sh", None), w2v)
         own = _OwnedFrame.of(_private)
         speculative = bool(no_sync and not timing)
         plan = self._plan_frame(image_idx, tile_size, layout, tile_window, out, out_origin, timing, semantics, background,
                                 generic_kernels, published_rects, camera_buffer, tile_counts, split_long_tiles,
-                                tile_schedule, substrips, substrip_events)
+                                tile_schedule, substrips, substrip_events, bool(antialiased))
         cap, hint_slot = self._view_state(plan, own, tile_size, tile_window, semantics, generic_kernels, use_hints)
         pinned, st = self._issue(plan, own, cap, tile_size, semantics, speculative)
         if hint_slot is not None:
@@ -817,7 +846,7 @@ class GaussianScene:
                 out_origin=out_origin, semantics=semantics, background=background,
                 generic_kernels=generic_kernels, published_rects=published_rects, camera_buffer=camera_buffer,
                 tile_counts=tile_counts, split_long_tiles=split_long_tiles, tile_schedule=tile_schedule,
-                use_hints=use_hints)))
+                use_hints=use_hints, antialiased=bool(antialiased))))
         elif own is None:
             self._note_count(plan.cap_key, int(st.n_instances), int(st.n_kept), int(st.n_redo))
         if stats is not None:
@@ -826,7 +855,7 @@ class GaussianScene:
 
     def _plan_frame(self, image_idx, tile_size, layout, tile_window, out, out_origin, timing, semantics, background,
                     generic_kernels, published_rects, camera_buffer, tile_counts, split_long_tiles, tile_schedule,
-                    substrips, substrip_events):
+                    substrips, substrip_events, antialiased=False):
         """Validates the arguments of ``render_image_hip`` and fills GsxParams: all but the per-view state (``_view_state``)."""
         _ffi.load()         # (a missing library is reported before anything about the arguments)
         truncated = self._sh_truncated()
@@ -862,6 +891,8 @@ class GaussianScene:
             params.flags |= _ffi.GSX_FLAG_TILE_SCHEDULE if tile_schedule else _ffi.GSX_FLAG_NO_TILE_SCHEDULE
         if published_rects:     # std_3dgs: bin with the published 3-sigma squares (same pixels, longer lists)
             params.flags |= _ffi.GSX_FLAG_PUBLISHED_RECTS
+        if antialiased:         # std_3dgs: the opacity compensation of the dilation (sigmoid * rho in the record)
+            params.flags |= _ffi.GSX_FLAG_ANTIALIASED
         if camera_buffer is not None:   # GsxParams.camera_device: the kernels read the camera from this buffer
             if camera_buffer.device != dev or camera_buffer.dtype != torch.uint8 or \
                     camera_buffer.numel() != ctypes.sizeof(_ffi.GsxCamera):
@@ -889,7 +920,7 @@ class GaussianScene:
             ow, oh = (out.shape[0], out.shape[1]) if layout == "wh3" else (out.shape[1], out.shape[0])
             params.out_x0, params.out_y0, params.out_w, params.out_h = int(out_origin[0]), int(out_origin[1]), int(ow), int(oh)
         cap_key = (image_idx, tile_size, None if tile_window is None else tuple(int(v) for v in tile_window),
-                   semantics + ("/published" if published_rects else ""))
+                   semantics + ("/published" if published_rects else "") + ("/antialiased" if antialiased else ""))
         return _FramePlan(dev, n, cam, tensors, params, out, cap_key, owned_inputs, keep_alive)
 
     def _block_bounds(self, dev, n: int) -> Optional[torch.Tensor]:
@@ -1016,8 +1047,8 @@ class GaussianScene:
         ``screen`` the seven -- for L(frame, depth image), ``depth`` the image ``_render_depth`` returned and ``grad_depth``
         dL/d(that image).  With ``screen_abs`` (needs ``geometry`` and ``screen``, excludes ``camera`` and ``depth``)
         gsx_render_backward_screen_abs: the seven and (the absolute screen statistic (N,2)).
-        With ``std`` = (background, published_rects) (excludes ``camera``, ``depth`` and ``screen_abs``) ``frame`` is the
-        std_3dgs frame rendered with those two and the one call is gsx_render_backward_std: the two, the five or the seven.
+        With ``std`` = (background, published_rects, antialiased) (excludes ``camera``, ``depth`` and ``screen_abs``) ``frame`` is the
+        std_3dgs frame rendered with those three and the one call is gsx_render_backward_std: the two, the five or the seven.
         The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
@@ -1033,7 +1064,8 @@ class GaussianScene:
                 if camera or depth is not None or screen_abs:
                     raise ValueError("std excludes camera, depth and screen_abs: gsx_render_backward_std has none of them")
                 params.background[0], params.background[1], params.background[2] = [float(v) for v in std[0]]
-                params.flags |= int(flags) | (_ffi.GSX_FLAG_PUBLISHED_RECTS if std[1] else 0)
+                params.flags |= int(flags) | (_ffi.GSX_FLAG_PUBLISHED_RECTS if std[1] else 0) | \
+                    (_ffi.GSX_FLAG_ANTIALIASED if len(std) > 2 and std[2] else 0)
             gf = _check_f32("grad_frame", grad_frame.detach(), dev)
             img = _check_f32("frame", frame.detach(), dev)
             if tuple(gf.shape) != tuple(img.shape):
@@ -1147,7 +1179,8 @@ class GaussianScene:
             return frame, self._render_depth(image_idx, tile_size, layout, int(st["n_instances"]), int(st["n_visible"]))
 
     def _render_contribution(self, image_idx: int, tile_size: int, semantics: str, n_instances: int, n_visible: int,
-                             out: Optional[Contribution] = None, published_rects: bool = False) -> Contribution:
+                             out: Optional[Contribution] = None, published_rects: bool = False,
+                             antialiased: bool = False) -> Contribution:
         """gsx_render_contribution on view ``image_idx``: a new ``Contribution`` (every row written), or ``out`` with the
         view merged into it (accumulate).  ``n_instances`` and ``n_visible`` are the counts of the view's frame under
         ``semantics`` (the workspace and the row class), as for ``_render_backward``."""
@@ -1161,6 +1194,8 @@ class GaussianScene:
                 params.flags |= _ffi.rows_flag(n, n_visible)
             elif published_rects:
                 params.flags |= _ffi.GSX_FLAG_PUBLISHED_RECTS
+            if antialiased:
+                params.flags |= _ffi.GSX_FLAG_ANTIALIASED
             if out is None:
                 con = Contribution(torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
                                    torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
@@ -1185,12 +1220,13 @@ class GaussianScene:
 
     def render_contribution_hip(self, image_idx: int, semantics: str = "ref_cpu", tile_size: int = 16,
                                 out: Optional[Contribution] = None, tile_window=None,
-                                published_rects: bool = False) -> Contribution:
+                                published_rects: bool = False, antialiased: bool = False) -> Contribution:
         """What every Gaussian contributes to the frame of view ``image_idx`` (gsx_render_contribution): a ``Contribution``
         of device tensors, one row per row of the container -- ``weight_max``, the largest blend weight ``T alpha`` the
         Gaussian reaches in any pixel (RadSplat's prune score), ``weight_sum``, the sum of its weights (the score
         LightGaussian and Mini-Splatting rank on), ``pixels``, the number of pixels that composited it, and ``views``, 1
-        where the frame listed it on a tile.  ``semantics``: "ref_cpu" or "std_3dgs" (``published_rects`` as for the frame;
+        where the frame listed it on a tile.  ``semantics``: "ref_cpu" or "std_3dgs" (``published_rects`` and ``antialiased`` as for
+        the frame -- the weights of the anti-aliased frame are T alpha with alpha = sigmoid * rho * G --;
         the background changes no weight).  The walk is the gradient entries' own: ``weight_sum`` is, bit for bit, what
         ``colors.grad[:, 0]`` is after ``frame.sum().backward()``.  ``out``: a ``Contribution`` of this container; the view
         is merged into it (max, +=, +=, views += 1; rows the view does not list are not touched) and it is returned.
@@ -1198,6 +1234,7 @@ class GaussianScene:
         ``tile_window``.  The view's frame is rendered first, under ``no_grad``, for its counts -- the pair count that sizes the
         workspace and the visible count that names the row class, which reach the host as every frame's counts do -- so a
         call costs that frame (0.43 ms at 1080p and 1M Gaussians) on top of the pass; no tensor is read back."""
+        _check_antialiased(antialiased, semantics)
         _require_gpu(self.gaussians.points.device)
         if semantics == "ref_cuda":
             raise ValueError("semantics='ref_cuda' has no contribution pass: gsx_render_contribution walks the gradient "
@@ -1211,13 +1248,14 @@ class GaussianScene:
             raise TypeError("out must be a Contribution, got %s" % type(out).__name__)
         with torch.no_grad():
             st: dict = {}
-            kw = dict(semantics=semantics, published_rects=published_rects) if semantics == "std_3dgs" else {}
+            kw = dict(semantics=semantics, published_rects=published_rects, antialiased=bool(antialiased)) \
+                if semantics == "std_3dgs" else {}
             self.render_image_hip(image_idx, tile_size=tile_size, stats=st, **kw)
             return self._render_contribution(image_idx, tile_size, semantics, int(st["n_instances"]), int(st["n_visible"]),
-                                             out=out, published_rects=published_rects)
+                                             out=out, published_rects=published_rects, antialiased=bool(antialiased))
 
     def contribution(self, indices=None, semantics: str = "ref_cpu", tile_size: int = 16,
-                     published_rects: bool = False) -> Contribution:
+                     published_rects: bool = False, antialiased: bool = False) -> Contribution:
         """``render_contribution_hip`` swept over the views ``indices`` (default: every view of the scene, in the order of
         ``scene.images``): the maximum, the sums and the view count over all of them, one library call per view merging
         into the first view's arrays.  No tensor is read back to the host: per view, the frame rendered for its counts delivers
@@ -1231,7 +1269,7 @@ class GaussianScene:
         con = None
         for idx in views:
             con = self.render_contribution_hip(idx, semantics=semantics, tile_size=tile_size, out=con,
-                                               published_rects=published_rects)
+                                               published_rects=published_rects, antialiased=antialiased)
         return con
 
     def _sh_backward(self, image_idx: int, grad_colors: torch.Tensor,
@@ -1390,7 +1428,7 @@ class GaussianScene:
 
     def capture_frame(self, image_idx: int, tile_size: int = 16, layout: str = "wh3",
                       semantics: str = "ref_cpu", movable_camera: bool = False,
-                      headroom: float = 1.1) -> "CapturedFrame":
+                      headroom: float = 1.1, antialiased: bool = False) -> "CapturedFrame":
         """Records one whole frame of this camera (every launch, clear and the asynchronous count
         copy) into a hipGraph.  ``frame.replay()`` then re-renders it with ONE graph launch (~20 us
         of host time instead of ~120 us for ~30 separate launches) from the CURRENT contents of the
@@ -1400,7 +1438,9 @@ class GaussianScene:
         (same frame size; SH scenes too: the colour is evaluated inside the projection kernel with the
         camera centre of that buffer).  The graph holds room for ``headroom`` x the pair count of the captured view; a replay
         that needs more (another camera may) is reported by ``confirm()``.  Possible because the
-        no-sync frame has no host dependency at all."""
+        no-sync frame has no host dependency at all.  ``antialiased``: as in ``render_image_hip`` (std_3dgs only); the graph
+        bakes the mode in."""
+        _check_antialiased(antialiased, semantics)
         if _wants_grad(self.gaussians):
             _refuse_with_grad("capture_frame")
         if self._sh_truncated():
@@ -1417,6 +1457,8 @@ class GaussianScene:
         if movable_camera:
             cam_buf = torch.frombuffer(bytearray(bytes(cam)), dtype=torch.uint8).to(dev)
         kw = dict(tile_size=tile_size, layout=layout, out=out, semantics=semantics, camera_buffer=cam_buf)
+        if antialiased:
+            kw["antialiased"] = True
         st = {}
         self.render_image_hip(image_idx, stats=st, **kw)    # normal path: the pair count of this view
         # What the graph bakes in belongs to this frame alone: the pair capacity the recorded launches are

@@ -1,6 +1,6 @@
 """Backward pass timing (gsx_render_backward) at C2 and C3: one JSON line.
 
-    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth] [--screen-abs] [--std]
+    timeout -k 10 600 python tools/bench_backward.py [--steps 20] [--warmup 3] [--geometry] [--screen] [--camera] [--depth] [--screen-abs] [--std [--antialiased]]
                                                      [--workloads c3] [--sh [--active-degree A]]
 
 Per workload (SURVEY.md section 8(d) generator, seed 0, 1920x1080, tile 16): the forward frame (render_image_hip, no
@@ -30,6 +30,9 @@ fused backward (stage chain again; raw records, prefix and the tile kernel; sums
 rectangles), its colour-only call ("std_colour_only") and its geometry call ("std_geometry") -- in turns with the ref_cpu
 geometry entry ("geometry") and the two forward frames ("frame", "std_frame") in one session: every median with its
 minimum and maximum, "std_geometry_over_geometry", and both frames' pair counts (the std lists are the shorter ones).
+--antialiased (with --std) adds the anti-aliased frame and its two backward calls to the same turns ("std_aa_frame",
+"std_aa_geometry", "std_aa_colour_only"; GSX_FLAG_ANTIALIASED: the same pairs, opacity times rho) and
+"std_aa_geometry_over_std_geometry", "std_aa_frame_over_std_frame".
 
 --sh times the differentiable SH scene INSTEAD: the trained-like 1M scene with degree-3 coefficients (bench.py's
 c3_trainedlike).  Its backward is gsx_render_backward on this camera's evaluated colours (gsx_sh_to_rgb runs again) and
@@ -86,7 +89,8 @@ def _in_turns(calls, steps, warmup):
     return {k: (round(statistics.median(v), 4), [round(min(v), 4), round(max(v), 4)]) for k, v in turns.items()}
 
 
-def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False, screen_abs=False, std=False):
+def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, depth=False, screen_abs=False, std=False,
+        antialiased=False):
     import torch
 
     from intro_to_gaussian_splatting_amd import GaussianScene, Gaussians, _ffi
@@ -171,15 +175,27 @@ def run(name, n, steps, warmup, geometry=False, screen=False, camera=False, dept
             frame_std = render_std(stats=st_std).clone()
             back_std = lambda geo: scene._render_backward(1, 16, "wh3", frame_std, W, st_std["n_instances"],  # noqa: E731
                                                           st_std["n_visible"], geometry=geo, std=((0.0, 0.0, 0.0), False))
-            t = _in_turns(dict(geometry=lambda: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"],
-                                                                       st["n_visible"], geometry=True),
-                               std_geometry=lambda: back_std(True), std_colour_only=lambda: back_std(False),
-                               frame=lambda: scene.render_image_hip(1), std_frame=render_std), steps, warmup)
+            calls = dict(geometry=lambda: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"],
+                                                                 st["n_visible"], geometry=True),
+                         std_geometry=lambda: back_std(True), std_colour_only=lambda: back_std(False),
+                         frame=lambda: scene.render_image_hip(1), std_frame=render_std)
+            if antialiased:
+                st_aa = {}
+                frame_aa = render_std(stats=st_aa, antialiased=True).clone()
+                back_aa = lambda geo: scene._render_backward(1, 16, "wh3", frame_aa, W, st_aa["n_instances"],  # noqa: E731
+                                                             st_aa["n_visible"], geometry=geo, std=((0.0, 0.0, 0.0), False, True))
+                calls.update(std_aa_geometry=lambda: back_aa(True), std_aa_colour_only=lambda: back_aa(False),
+                             std_aa_frame=lambda: render_std(antialiased=True))
+            t = _in_turns(calls, steps, warmup)
             d = {k + "_ms": v[0] for k, v in t.items()}
             d.update({k + "_min_max": v[1] for k, v in t.items()})
             d["std_geometry_over_geometry"] = round(t["std_geometry"][0] / t["geometry"][0], 4)
             d["n_instances"] = int(st["n_instances"])
             d["std_n_instances"] = int(st_std["n_instances"])
+            if antialiased:
+                d["std_aa_geometry_over_std_geometry"] = round(t["std_aa_geometry"][0] / t["std_geometry"][0], 4)
+                d["std_aa_frame_over_std_frame"] = round(t["std_aa_frame"][0] / t["std_frame"][0], 4)
+                d["std_aa_n_instances"] = int(st_aa["n_instances"])
             out["std"] = d
         if depth:
             back = lambda **kw: scene._render_backward(1, 16, "wh3", frame, W, st["n_instances"], st["n_visible"],  # noqa: E731
@@ -337,11 +353,15 @@ def main():
                     "screen entry")
     ap.add_argument("--std", action="store_true", help="also time gsx_render_backward_std (colour-only and geometry), in turns "
                     "with the ref_cpu geometry entry and the two forward frames")
+    ap.add_argument("--antialiased", action="store_true", help="with --std: also the anti-aliased frame and its backward "
+                    "(GSX_FLAG_ANTIALIASED), in the same turns")
     ap.add_argument("--workloads", default="c2,c3", help="comma-separated: which of c2, c3 to run (not with --sh)")
     ap.add_argument("--sh", action="store_true", help="the differentiable SH scene instead: trained-like 1M, degree 3")
     ap.add_argument("--active-degree", type=int, default=None, help="with --sh: Gaussians.active_sh_degree (0..3), the "
                     "gsx_sh_*_active entries, and the degree-3 kernels timed in turns with them")
     args = ap.parse_args()
+    if args.antialiased and not args.std:
+        ap.error("--antialiased goes with --std: the opacity compensation belongs to the std_3dgs frame")
     from intro_to_gaussian_splatting_amd import _ffi
 
     if args.sh:
@@ -350,7 +370,7 @@ def main():
         return
     _ffi.use_test_library()     # gsx_debug_backward_stage_ms
     out = {name: run(name, n, args.steps, args.warmup, args.geometry, args.screen, args.camera, args.depth, args.screen_abs,
-                     args.std)
+                     args.std, args.antialiased)
            for name, n in WORKLOADS.items() if name in args.workloads.split(",")}
     print(json.dumps(dict(metric="backward_ms", results=out)))
 
