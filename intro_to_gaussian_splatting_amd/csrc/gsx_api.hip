@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "gsx_internal.h"
 #ifdef GSX_TEST_HOOKS
 #include "gsx_debug.h"
@@ -98,6 +100,20 @@ int check_workspace(void *workspace, size_t bytes, int64_t n, int64_t max_tiles,
         return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes cannot hold %lld Gaussians", bytes, (long long)n);
     c = carve(n, cap, max_tiles, binning_temp_bytes(n, cap), backward);
     return GSX_OK;
+}
+
+// The workspace of an entry whose size function gives the one size it takes (the losses, density, MCMC, kNN): `need` of
+// them; size_call, formatted with what follows it: that function's call as the message spells it.
+int check_sized_workspace(const void *workspace, size_t bytes, size_t need, const char *size_call, ...) {
+    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
+    if (bytes >= need) return GSX_OK;
+    char call[128];
+    va_list ap;
+    va_start(ap, size_call);
+    vsnprintf(call, sizeof call, size_call, ap);
+    va_end(ap);
+    return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, %s = %zu", bytes, call, need);
 }
 
 // gsx_workspace_bytes / gsx_backward_workspace_bytes / gsx_backward_geometry_workspace_bytes: 0 for sizes no call accepts.
@@ -390,103 +406,154 @@ struct GeometryGrads {
     float *means2d_abs = nullptr;                           // gsx_render_backward_screen_abs: (n,2); excludes the two lines above
 };
 
-// What the gradient entries and gsx_render_depth cover: the reference's own frame, whole, RGB colours.
-int check_whole_ref_cpu(const Plan &p, const GsxCamera *camera, const GsxParams *params, const char *entry) {
-    if (p.antialiased) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take GSX_FLAG_ANTIALIASED: it supports GSX_SEM_REF_CPU only", entry);
-    if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "%s supports GSX_SEM_REF_CPU only", entry);
-    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
-    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s renders the whole frame: no tile window", entry);
-    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes the whole frame: no output window", entry);
-    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take substrips", entry);
-    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "%s synchronises: no GSX_FLAG_NO_SYNC", entry);
-    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "%s reads the camera argument: no camera_device", entry);
+// ---- The entries that walk the forward's lists again: the gradient entries, gsx_render_depth, gsx_render_contribution.
+
+// The rule sets such an entry accepts: the reference's own frame, the published one, or either.
+enum { kRulesRefCpu = 1, kRulesStd3dgs = 2, kRulesEither = kRulesRefCpu | kRulesStd3dgs };
+
+int check_rules(const Plan &p, int rules, const char *entry) {
+    if (rules == kRulesRefCpu) {
+        if (p.antialiased) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take GSX_FLAG_ANTIALIASED: it supports GSX_SEM_REF_CPU only", entry);
+        if (p.semantics != GSX_SEM_REF_CPU) return fail(GSX_ERR_INVALID_ARGUMENT, "%s supports GSX_SEM_REF_CPU only", entry);
+    } else if (rules == kRulesStd3dgs) {
+        if (p.semantics != GSX_SEM_STD_3DGS)
+            return fail(GSX_ERR_INVALID_ARGUMENT, "%s: params->semantics must be GSX_SEM_STD_3DGS", entry);
+    } else if (p.semantics == GSX_SEM_REF_CUDA) {
+        return fail(GSX_ERR_INVALID_ARGUMENT, "%s: GSX_SEM_REF_CUDA is not supported (GSX_SEM_REF_CPU or GSX_SEM_STD_3DGS)", entry);
+    }
     return GSX_OK;
 }
 
-// The forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort and the
-// count read-back (which synchronises).  On GSX_OK: order, rrect, sorted_vals and counts = (n_visible, D, M).
-int lists_again(const Plan &p, const Carve &c, char *ws, const GsxCamera &camera, const gsx::GaussiansIn &in, int64_t n,
-                int64_t cap, hipStream_t s, const uint32_t *&order, const uint32_t *&sorted_vals, int64_t (&counts)[3]) {
-    bool sampled;
-    int rc = project_and_sort(p, c, ws, camera, in, n, cap, nullptr, nullptr, s, order, sampled);
+// The arguments all these entries share.
+struct WalkArgs {
+    const GsxCamera *camera;
+    const float *means3d, *scales, *quats, *opacity_logit, *colors;
+    int64_t n;
+    int32_t tile_size;
+    const GsxParams *params;
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+};
+
+// What the opening leaves: open_walk fills the first line, lists_again the second, launch_walk_prefix the third.
+struct Walk {
+    Plan p; Carve c; int64_t cap; char *ws; hipStream_t s;
+    gsx::GaussiansIn in; const uint32_t *order, *sorted_vals; const gsx::TileRect *rrect; uint32_t m; int64_t counts[3];
+    uint32_t *prefix, *rank_of; float4 *slots, *geo_slots;
+};
+
+// Validation, up to and including the workspace (a.camera is not NULL: the entry has said so, and whatever else it
+// says before there is a plan).  frame: the array the plan describes; rules: kRules*; outputs_fault: the entry's
+// complaint about its output arrays, or null -- it speaks here, between the inputs and the workspace; mode: kCarve*.
+int open_walk(const WalkArgs &a, const char *entry, int rules, float *frame, const char *outputs_fault, int mode, Walk &w) {
+    const int32_t width = a.camera->width, height = a.camera->height;
+    int rc = make_plan_or_fail(width, height, a.tile_size, frame, a.params, w.p);
     if (rc != GSX_OK) return rc;
-    uint32_t *counters = (uint32_t *)(ws + c.counters);
-    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
-    const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
-                              (uint32_t *)(ws + c.redo), counters + kCtrCulled, n};
-    const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(ws + c.longs), 0u};     // no long-tile split: plain [first, last)
-    sorted_vals = nullptr;
-    rc = bin_pairs(p, c, ws, n, cap, rrect, order, counters + kCtrKept, sampled, bcnt, lt, nullptr, s, sorted_vals);
+    rc = check_rules(w.p, rules, entry);
     if (rc != GSX_OK) return rc;
-    return read_counts(c, ws, cap, true, nullptr, counts, s);
+    char msg[256];
+    rc = check_whole_frame(w.p, width, height, a.params, entry, msg, sizeof msg);
+    if (rc != GSX_OK) return fail(rc, "%s", msg);
+    rc = check_inputs(w.p, a.n, a.means3d, a.scales, a.quats, a.opacity_logit, a.colors);
+    if (rc != GSX_OK) return rc;
+    if (outputs_fault) return fail(GSX_ERR_INVALID_ARGUMENT, "%s", outputs_fault);
+    rc = check_workspace(a.workspace, a.workspace_bytes, a.n, max_tiles_of(width, height, a.tile_size), w.c, w.cap, mode);
+    if (rc != GSX_OK) return rc;
+    w.ws = (char *)a.workspace;
+    w.s = (hipStream_t)a.stream;
+    return GSX_OK;
 }
+
+// An entry's outputs, zeroed in the order given: rows no tile lists, and frames that list nothing, read zero.
+struct ZeroFill {
+    void *ptr;      // null: not asked for, skipped
+    size_t words;
+};
+int zero_fill(std::initializer_list<ZeroFill> outputs, hipStream_t s) {
+    for (const ZeroFill &z : outputs)
+        if (z.ptr) GSX_HIP(gsx::launch_zero_words((uint32_t *)z.ptr, z.words, s));
+    return GSX_OK;
+}
+
+// Behind the entry's zero-fill.  Without a Gaussian or a tile the stream is synchronised and nothing more is done;
+// otherwise the forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
+// and the count read-back, which synchronises (tm: nullptr = no mark behind it).  That leaves in, order, rrect,
+// sorted_vals, counts = (n_visible, D, M) and m.  go: the frame lists something, there are pairs to walk -- false with
+// GSX_OK: the outputs stand as they were zero-filled.
+int lists_again(const WalkArgs &a, Walk &w, StageTimer *tm, bool &go) {
+    go = false;
+    if (a.n == 0 || w.p.grid.count() == 0) {
+        GSX_HIP(hipStreamSynchronize(w.s));
+        return GSX_OK;
+    }
+    w.in = gsx::GaussiansIn{a.means3d, a.scales, a.quats, a.opacity_logit, a.colors, w.p.original_index, nullptr};
+    w.rrect = (const gsx::TileRect *)(w.ws + w.c.rrect);
+    bool sampled;
+    int rc = project_and_sort(w.p, w.c, w.ws, *a.camera, w.in, a.n, w.cap, nullptr, nullptr, w.s, w.order, sampled);
+    if (rc == GSX_OK) {
+        uint32_t *counters = (uint32_t *)(w.ws + w.c.counters);
+        const gsx::BinCounts bcnt{(int64_t *)(counters + 4), nullptr, counters + kCtrPairs, counters + kCtrLong,
+                                  (uint32_t *)(w.ws + w.c.redo), counters + kCtrCulled, a.n};
+        const gsx::LongTiles lt{counters + kCtrLong, (uint32_t *)(w.ws + w.c.longs), 0u};     // no long-tile split: plain [first, last)
+        w.sorted_vals = nullptr;
+        rc = bin_pairs(w.p, w.c, w.ws, a.n, w.cap, w.rrect, w.order, counters + kCtrKept, sampled, bcnt, lt, nullptr, w.s, w.sorted_vals);
+    }
+    if (rc == GSX_OK) rc = read_counts(w.c, w.ws, w.cap, true, nullptr, w.counts, w.s);
+    if (tm) tm->mark();
+    if (rc != GSX_OK) return rc;
+    w.m = (uint32_t)w.counts[2];
+    go = w.m != 0 && w.counts[1] != 0;
+    return GSX_OK;
+}
+
+// For the bodies that leave sums per pair: every rank's first slot and every row's rank (launch_backward_prefix), and
+// where the slots are (geo: the second slot array of kCarveGeometry and up as well).
+int launch_walk_prefix(Walk &w, bool geo) {
+    w.prefix = (uint32_t *)(w.ws + w.c.prefix);
+    w.rank_of = (uint32_t *)(w.ws + w.c.rank_of);
+    w.slots = (float4 *)(w.ws + w.c.slots);
+    w.geo_slots = geo ? (float4 *)(w.ws + w.c.geo_slots) : nullptr;
+    GSX_HIP(gsx::launch_backward_prefix(w.rrect, w.order, w.m, w.prefix, w.rank_of, (uint32_t *)(w.ws + w.c.bsum), w.s));
+    return GSX_OK;
+}
+
+// What gsx_render_backward and gsx_render_backward_std say about a missing one of the three
+const char *const kNoGradArrays = "grad_image / grad_colors / grad_opacity_logit is NULL";
 
 // gsx_render_backward (geo == nullptr) and gsx_render_backward_geometry: one body.  The geometry call carves the third
 // workspace mode, runs the tile kernel's geometry instance and, after the colour sums, the per-Gaussian chain.
-int render_backward(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
-                    const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, const float *image,
-                    const float *grad_image, float *grad_colors, float *grad_opacity_logit, const GeometryGrads *geo,
-                    const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
-    Plan p;
-    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
+int render_backward(const WalkArgs &a, const float *image, const float *grad_image, float *grad_colors,
+                    float *grad_opacity_logit, const GeometryGrads *geo) {
+    if (!a.camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    Walk w;
+    int rc = open_walk(a, "gsx_render_backward", kRulesRefCpu, const_cast<float *>(image),
+                       !grad_image || !grad_colors || !grad_opacity_logit ? kNoGradArrays : nullptr,
+                       geo ? (geo->depth ? kCarveDepth : (geo->world2view ? kCarveCamera : kCarveGeometry)) : kCarveBackward, w);
     if (rc != GSX_OK) return rc;
-    rc = check_whole_ref_cpu(p, camera, params, "gsx_render_backward");
-    if (rc != GSX_OK) return rc;
-    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
-    if (rc != GSX_OK) return rc;
-    if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
-    Carve c;
-    int64_t cap;
-    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap,
-                         geo ? (geo->depth ? kCarveDepth : (geo->world2view ? kCarveCamera : kCarveGeometry)) : kCarveBackward);
-    if (rc != GSX_OK) return rc;
-    char *ws = (char *)workspace;
+    const Plan &p = w.p;
+    const int64_t n = a.n;
+    hipStream_t s = w.s;
     StageTimer tm;
     tm.begin(p.timing, s);
-    // every row of both outputs: a Gaussian on no tile list has zero gradients
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_colors, (size_t)n * 3, s));
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_opacity_logit, (size_t)n, s));
-    if (geo) {
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means3d, (size_t)n * 3, s));
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->scales, (size_t)n * 3, s));
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->quats, (size_t)n * 4, s));
-        if (geo->means2d) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means2d, (size_t)n * 2, s));
-        if (geo->radius) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->radius, (size_t)n, s));
-        if (geo->means2d_abs) GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->means2d_abs, (size_t)n * 2, s));
-        if (geo->world2view) {      // a frame that lists nothing leaves 32 exact +0
-            GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->world2view, 16, s));
-            GSX_HIP(gsx::launch_zero_words((uint32_t *)geo->full_proj, 16, s));
-        }
-    }
-    if (n == 0 || p.grid.count() == 0) {
-        GSX_HIP(hipStreamSynchronize(s));
-        return GSX_OK;
-    }
-    // ---- the forward's chain on the same inputs, without the hints buffer: projection, depth order, pairs, tile sort
-    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const uint32_t *order, *sorted_vals;
-    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
-    int64_t counts[3];
-    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
-    tm.mark();  // 1: the forward's stages
+    const GeometryGrads g = geo ? *geo : GeometryGrads{nullptr, nullptr, nullptr};
+    rc = zero_fill({{grad_colors, (size_t)n * 3}, {grad_opacity_logit, (size_t)n}, {g.means3d, (size_t)n * 3},
+                    {g.scales, (size_t)n * 3}, {g.quats, (size_t)n * 4}, {g.means2d, (size_t)n * 2}, {g.radius, (size_t)n},
+                    {g.means2d_abs, (size_t)n * 2}, {g.world2view, 16}, {g.full_proj, 16}}, s);   // (the two matrices: 32 exact +0)
     if (rc != GSX_OK) return rc;
-    const uint32_t m = (uint32_t)counts[2];
-    if (m == 0 || counts[1] == 0) return GSX_OK;
+    bool go;
+    rc = lists_again(a, w, &tm, go);     // mark 1: the forward's stages
+    if (rc != GSX_OK || !go) return rc;
     // ---- the backward kernels
-    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
-    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
-    float4 *slots = (float4 *)(ws + c.slots), *geo_slots = geo ? (float4 *)(ws + c.geo_slots) : nullptr;
-    GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
-    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
-    const gsx::BackwardTiles bt{raw, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots,
-                                  geo_slots};
+    gsx::Record *raw = (gsx::Record *)(w.ws + w.c.raw);
+    GSX_HIP(gsx::launch_project_raw(*a.camera, w.in, n, p.small_batch, raw, s));
+    rc = launch_walk_prefix(w, geo != nullptr);
+    if (rc != GSX_OK) return rc;
+    const gsx::BackwardTiles bt{raw, w.sorted_vals, (const uint2 *)(w.ws + w.c.ranges), w.rank_of, w.prefix, w.rrect, image,
+                                grad_image, w.slots, w.geo_slots};
     if (geo && geo->depth) {
-        float *zrow = (float *)(ws + c.zrow);
-        GSX_HIP(gsx::launch_project_depth(*camera, means3d, n, p.small_batch, zrow, s));
+        float *zrow = (float *)(w.ws + w.c.zrow);
+        GSX_HIP(gsx::launch_project_depth(*a.camera, a.means3d, n, p.small_batch, zrow, s));
         GSX_HIP(gsx::launch_backward_tiles_depth(bt, gsx::DepthTiles{zrow, geo->depth, geo->grad_depth}, p.grid, p.out, s));
     } else if (geo && geo->means2d_abs) {
         GSX_HIP(gsx::launch_backward_tiles_abs(bt, p.grid, p.out, s));
@@ -494,15 +561,17 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
     }
     tm.mark();  // 2: raw records, prefix, compositing backward
-    GSX_HIP(gsx::launch_backward_sums(slots, prefix, order, raw, m, grad_colors, grad_opacity_logit, s));
+    GSX_HIP(gsx::launch_backward_sums(w.slots, w.prefix, w.order, raw, w.m, grad_colors, grad_opacity_logit, s));
     if (geo && geo->depth) {
-        GSX_HIP(gsx::launch_backward_geometry_depth(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
-                                                    geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s));
+        GSX_HIP(gsx::launch_backward_geometry_depth(*a.camera, w.geo_slots, w.prefix, w.order, raw, w.m, a.means3d, a.scales,
+                                                    a.quats, geo->means3d, geo->scales, geo->quats, geo->means2d,
+                                                    geo->means2d ? geo->radius : nullptr, s));
     } else if (geo) {
-        const gsx::CameraGrads cg{geo->world2view, geo->full_proj, (float *)(ws + c.cam_partials)};
-        GSX_HIP(gsx::launch_backward_geometry(*camera, geo_slots, prefix, order, raw, m, means3d, scales, quats, geo->means3d,
-                                              geo->scales, geo->quats, geo->means2d, geo->means2d ? geo->radius : nullptr, s,
-                                              geo->world2view ? &cg : nullptr, geo->means2d_abs));
+        const gsx::CameraGrads cg{geo->world2view, geo->full_proj, (float *)(w.ws + w.c.cam_partials)};
+        GSX_HIP(gsx::launch_backward_geometry(*a.camera, w.geo_slots, w.prefix, w.order, raw, w.m, a.means3d, a.scales, a.quats,
+                                              geo->means3d, geo->scales, geo->quats, geo->means2d,
+                                              geo->means2d ? geo->radius : nullptr, s, geo->world2view ? &cg : nullptr,
+                                              geo->means2d_abs));
     }
     tm.mark();  // 3: sums (and the geometry chain)
     GSX_HIP(hipStreamSynchronize(s));
@@ -514,157 +583,6 @@ int render_backward(const GsxCamera *camera, const float *means3d, const float *
         for (int i = 0; i < 3; ++i) g_backward_ms[i] = st.stage_ms[i];
     }
 #endif
-    return GSX_OK;
-}
-
-// gsx_render_backward_std: render_backward's order of work on the GSX_SEM_STD_3DGS frame.  The forward's chain leaves the
-// packed records the std tile kernels read (no raw projection); the workspace is the geometry entry's.
-int render_backward_std(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
-                        const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, const float *image,
-                        const float *grad_image, float *grad_colors, float *grad_opacity_logit, float *grad_means3d,
-                        float *grad_scales, float *grad_quats, float *grad_means2d, float *screen_radius,
-                        const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const char *entry = "gsx_render_backward_std";
-    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
-    if (!params) return fail(GSX_ERR_INVALID_ARGUMENT, "params is NULL: %s needs params->semantics = GSX_SEM_STD_3DGS", entry);
-    if (!image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
-    Plan p;
-    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, const_cast<float *>(image), params, p);
-    if (rc != GSX_OK) return rc;
-    if (p.semantics != GSX_SEM_STD_3DGS)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s: params->semantics must be GSX_SEM_STD_3DGS", entry);
-    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
-    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s renders the whole frame: no tile window", entry);
-    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes the whole frame: no output window", entry);
-    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take substrips", entry);
-    if (params->flags & GSX_FLAG_NO_SYNC) return fail(GSX_ERR_INVALID_ARGUMENT, "%s synchronises: no GSX_FLAG_NO_SYNC", entry);
-    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "%s reads the camera argument: no camera_device", entry);
-    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
-    if (rc != GSX_OK) return rc;
-    if (!grad_image || !grad_colors || !grad_opacity_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_image / grad_colors / grad_opacity_logit is NULL");
-    const int n_geo = (grad_means3d != nullptr) + (grad_scales != nullptr) + (grad_quats != nullptr);
-    if (n_geo != 0 && n_geo != 3)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats: all three or none");
-    const bool geo = n_geo == 3;
-    if ((grad_means2d != nullptr) != (screen_radius != nullptr))
-        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d / screen_radius: both or none");
-    if (grad_means2d && !geo)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d and screen_radius need grad_means3d, grad_scales and grad_quats");
-    Carve c;
-    int64_t cap;
-    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, kCarveGeometry);
-    if (rc != GSX_OK) return rc;
-    char *ws = (char *)workspace;
-    // every row of every output: a Gaussian on no tile list has zero gradients
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_colors, (size_t)n * 3, s));
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_opacity_logit, (size_t)n, s));
-    if (geo) {
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_means3d, (size_t)n * 3, s));
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_scales, (size_t)n * 3, s));
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_quats, (size_t)n * 4, s));
-        if (grad_means2d) {
-            GSX_HIP(gsx::launch_zero_words((uint32_t *)grad_means2d, (size_t)n * 2, s));
-            GSX_HIP(gsx::launch_zero_words((uint32_t *)screen_radius, (size_t)n, s));
-        }
-    }
-    if (n == 0 || p.grid.count() == 0) {
-        GSX_HIP(hipStreamSynchronize(s));
-        return GSX_OK;
-    }
-    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const uint32_t *order, *sorted_vals;
-    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
-    int64_t counts[3];
-    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
-    if (rc != GSX_OK) return rc;
-    const uint32_t m = (uint32_t)counts[2];
-    if (m == 0 || counts[1] == 0) return GSX_OK;
-    const gsx::Record *rec = (const gsx::Record *)(ws + c.rec);
-    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
-    float4 *slots = (float4 *)(ws + c.slots), *geo_slots = geo ? (float4 *)(ws + c.geo_slots) : nullptr;
-    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
-    const gsx::BackwardTiles bt{rec, sorted_vals, (const uint2 *)(ws + c.ranges), rank_of, prefix, rrect, image, grad_image, slots,
-                                  geo_slots};
-    GSX_HIP(gsx::launch_backward_tiles_std(bt, p.grid, p.out, s));
-    if (p.antialiased) {
-        GSX_HIP(gsx::launch_backward_std_antialiased(*camera, slots, geo_slots, prefix, order, m, means3d, scales, quats,
-                                                     opacity_logit, grad_colors, grad_opacity_logit, grad_means3d, grad_scales,
-                                                     grad_quats, grad_means2d, screen_radius, s));
-    } else {
-        GSX_HIP(gsx::launch_backward_sums_std(slots, prefix, order, rec, m, grad_colors, grad_opacity_logit, s));
-        if (geo)
-            GSX_HIP(gsx::launch_backward_geometry_std(*camera, geo_slots, prefix, order, m, means3d, scales, quats, grad_means3d,
-                                                      grad_scales, grad_quats, grad_means2d, screen_radius, s));
-    }
-    GSX_HIP(hipStreamSynchronize(s));
-    return GSX_OK;
-}
-
-// gsx_render_contribution: the gradient entries' chain (lists_again) and walk on either rule set, with no frame and no
-// gradient: per row the largest T alpha, their sum and the pixel count (gsx_contribution.hip).  The workspace is
-// gsx_render_backward's.
-int render_contribution(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
-                        const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *weight_max,
-                        float *weight_sum, uint32_t *pixels, uint32_t *views, int32_t accumulate, const GsxParams *params,
-                        void *workspace, size_t workspace_bytes, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const char *entry = "gsx_render_contribution";
-    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
-    if (!weight_max || !weight_sum || !pixels) return fail(GSX_ERR_INVALID_ARGUMENT, "weight_max / weight_sum / pixels is NULL");
-    if (accumulate != 0 && accumulate != 1) return fail(GSX_ERR_INVALID_ARGUMENT, "accumulate = %d is neither 0 nor 1", accumulate);
-    Plan p;
-    // (weight_max stands in for the frame the plan describes: this entry has none and writes no pixel)
-    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, weight_max, params, p);
-    if (rc != GSX_OK) return rc;
-    if (p.semantics == GSX_SEM_REF_CUDA)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s: GSX_SEM_REF_CUDA is not supported (GSX_SEM_REF_CPU or GSX_SEM_STD_3DGS)", entry);
-    const bool std_rules = p.semantics == GSX_SEM_STD_3DGS;
-    if (p.sh) return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes RGB colours, not GsxParams.sh", entry);
-    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s renders the whole frame: no tile window", entry);
-    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != camera->width || p.out.h != camera->height)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "%s takes the whole frame: no output window", entry);
-    if (p.n_parts > 0) return fail(GSX_ERR_INVALID_ARGUMENT, "%s does not take substrips", entry);
-    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail(GSX_ERR_INVALID_ARGUMENT, "%s synchronises: no GSX_FLAG_NO_SYNC", entry);
-    if (p.camera_device) return fail(GSX_ERR_INVALID_ARGUMENT, "%s reads the camera argument: no camera_device", entry);
-    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
-    if (rc != GSX_OK) return rc;
-    Carve c;
-    int64_t cap;
-    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, kCarveBackward);
-    if (rc != GSX_OK) return rc;
-    char *ws = (char *)workspace;
-    if (!accumulate) {      // every row: a Gaussian on no tile list reads +0 / 0
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)weight_max, (size_t)n, s));
-        GSX_HIP(gsx::launch_zero_words((uint32_t *)weight_sum, (size_t)n, s));
-        GSX_HIP(gsx::launch_zero_words(pixels, (size_t)n, s));
-        if (views) GSX_HIP(gsx::launch_zero_words(views, (size_t)n, s));
-    }
-    if (n == 0 || p.grid.count() == 0) {
-        GSX_HIP(hipStreamSynchronize(s));
-        return GSX_OK;
-    }
-    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const uint32_t *order, *sorted_vals;
-    const gsx::TileRect *rrect = (const gsx::TileRect *)(ws + c.rrect);
-    int64_t counts[3];
-    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
-    if (rc != GSX_OK) return rc;
-    const uint32_t m = (uint32_t)counts[2];
-    if (m == 0 || counts[1] == 0) return GSX_OK;
-    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
-    uint32_t *prefix = (uint32_t *)(ws + c.prefix), *rank_of = (uint32_t *)(ws + c.rank_of);
-    float4 *slots = (float4 *)(ws + c.slots);
-    if (!std_rules) GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
-    GSX_HIP(gsx::launch_backward_prefix(rrect, order, m, prefix, rank_of, (uint32_t *)(ws + c.bsum), s));
-    const gsx::ContributionTiles ct{std_rules ? (const gsx::Record *)(ws + c.rec) : raw, sorted_vals, (const uint2 *)(ws + c.ranges),
-                                    rank_of, prefix, rrect, slots};
-    GSX_HIP(gsx::launch_contribution_tiles(ct, p.grid, std_rules, s));
-    GSX_HIP(gsx::launch_contribution_sums(slots, prefix, order, m, weight_max, weight_sum, pixels, views, accumulate != 0, s));
-    GSX_HIP(hipStreamSynchronize(s));
     return GSX_OK;
 }
 
@@ -692,7 +610,7 @@ size_t gsx_hints_bytes(int32_t width, int32_t height, int32_t tile) {
 }
 
 size_t gsx_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
-    return workspace_bytes(n, width, height, tile, max_instances, false);
+    return workspace_bytes(n, width, height, tile, max_instances, kCarveForward);
 }
 
 int gsx_preprocess(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
@@ -832,8 +750,8 @@ int gsx_render_backward(const GsxCamera *camera, const float *means3d, const flo
                         const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
                         const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
                         const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
-    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                           grad_colors, grad_opacity_logit, nullptr, params, workspace, workspace_bytes, stream);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    return render_backward(a, image, grad_image, grad_colors, grad_opacity_logit, nullptr);
 }
 
 int gsx_render_backward_geometry(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
@@ -844,8 +762,8 @@ int gsx_render_backward_geometry(const GsxCamera *camera, const float *means3d, 
     if (!grad_means3d || !grad_scales || !grad_quats)
         return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
     const GeometryGrads geo{grad_means3d, grad_scales, grad_quats};
-    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    return render_backward(a, image, grad_image, grad_colors, grad_opacity_logit, &geo);
 }
 
 int gsx_render_backward_screen(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
@@ -858,8 +776,8 @@ int gsx_render_backward_screen(const GsxCamera *camera, const float *means3d, co
         return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
     if (!grad_means2d) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d is NULL");
     const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
-    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    return render_backward(a, image, grad_image, grad_colors, grad_opacity_logit, &geo);
 }
 
 int gsx_render_backward_screen_abs(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
@@ -875,35 +793,108 @@ int gsx_render_backward_screen_abs(const GsxCamera *camera, const float *means3d
     if (!grad_means2d_abs) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means2d_abs is NULL");
     GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
     geo.means2d_abs = grad_means2d_abs;
-    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    return render_backward(a, image, grad_image, grad_colors, grad_opacity_logit, &geo);
 }
 
 size_t gsx_backward_std_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
     return workspace_bytes(n, width, height, tile, max_instances, kCarveGeometry);
 }
 
+// gsx_render_backward_std: render_backward's order of work on the GSX_SEM_STD_3DGS frame.  The forward's chain leaves the
+// packed records the std tile kernels read (no raw projection); the workspace is the geometry entry's.
 int gsx_render_backward_std(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
                             const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size,
                             const float *image, const float *grad_image, float *grad_colors, float *grad_opacity_logit,
                             float *grad_means3d, float *grad_scales, float *grad_quats, float *grad_means2d,
                             float *screen_radius, const GsxParams *params, void *workspace, size_t workspace_bytes,
                             void *stream) {
-    return render_backward_std(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                               grad_colors, grad_opacity_logit, grad_means3d, grad_scales, grad_quats, grad_means2d,
-                               screen_radius, params, workspace, workspace_bytes, stream);
+    const char *entry = "gsx_render_backward_std";
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    if (!params) return fail(GSX_ERR_INVALID_ARGUMENT, "params is NULL: %s needs params->semantics = GSX_SEM_STD_3DGS", entry);
+    if (!image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
+    const int n_geo = (grad_means3d != nullptr) + (grad_scales != nullptr) + (grad_quats != nullptr);
+    const bool geo = n_geo == 3;
+    const char *outputs_fault = nullptr;
+    if (!grad_image || !grad_colors || !grad_opacity_logit)
+        outputs_fault = kNoGradArrays;
+    else if (n_geo != 0 && n_geo != 3)
+        outputs_fault = "grad_means3d / grad_scales / grad_quats: all three or none";
+    else if ((grad_means2d != nullptr) != (screen_radius != nullptr))
+        outputs_fault = "grad_means2d / screen_radius: both or none";
+    else if (grad_means2d && !geo)
+        outputs_fault = "grad_means2d and screen_radius need grad_means3d, grad_scales and grad_quats";
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    Walk w;
+    int rc = open_walk(a, entry, kRulesStd3dgs, const_cast<float *>(image), outputs_fault, kCarveGeometry, w);
+    if (rc != GSX_OK) return rc;
+    hipStream_t s = w.s;
+    // (the three, and the two, are all there or all NULL)
+    rc = zero_fill({{grad_colors, (size_t)n * 3}, {grad_opacity_logit, (size_t)n}, {grad_means3d, (size_t)n * 3},
+                    {grad_scales, (size_t)n * 3}, {grad_quats, (size_t)n * 4}, {grad_means2d, (size_t)n * 2},
+                    {screen_radius, (size_t)n}}, s);
+    if (rc != GSX_OK) return rc;
+    bool go;
+    rc = lists_again(a, w, nullptr, go);
+    if (rc != GSX_OK || !go) return rc;
+    const gsx::Record *rec = (const gsx::Record *)(w.ws + w.c.rec);
+    rc = launch_walk_prefix(w, geo);
+    if (rc != GSX_OK) return rc;
+    const gsx::BackwardTiles bt{rec, w.sorted_vals, (const uint2 *)(w.ws + w.c.ranges), w.rank_of, w.prefix, w.rrect, image,
+                                grad_image, w.slots, w.geo_slots};
+    GSX_HIP(gsx::launch_backward_tiles_std(bt, w.p.grid, w.p.out, s));
+    if (w.p.antialiased) {
+        GSX_HIP(gsx::launch_backward_std_antialiased(*camera, w.slots, w.geo_slots, w.prefix, w.order, w.m, means3d, scales, quats,
+                                                     opacity_logit, grad_colors, grad_opacity_logit, grad_means3d, grad_scales,
+                                                     grad_quats, grad_means2d, screen_radius, s));
+    } else {
+        GSX_HIP(gsx::launch_backward_sums_std(w.slots, w.prefix, w.order, rec, w.m, grad_colors, grad_opacity_logit, s));
+        if (geo)
+            GSX_HIP(gsx::launch_backward_geometry_std(*camera, w.geo_slots, w.prefix, w.order, w.m, means3d, scales, quats,
+                                                      grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius, s));
+    }
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
 }
 
 size_t gsx_contribution_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
     return workspace_bytes(n, width, height, tile, max_instances, kCarveBackward);
 }
 
+// gsx_render_contribution: the gradient entries' chain (lists_again) and walk on either rule set, with no frame and no
+// gradient: per row the largest T alpha, their sum and the pixel count (gsx_contribution.hip).  The workspace is
+// gsx_render_backward's.
 int gsx_render_contribution(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
                             const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *weight_max,
                             float *weight_sum, uint32_t *pixels, uint32_t *views, int32_t accumulate, const GsxParams *params,
                             void *workspace, size_t workspace_bytes, void *stream) {
-    return render_contribution(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, weight_max, weight_sum, pixels,
-                               views, accumulate, params, workspace, workspace_bytes, stream);
+    if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
+    if (!weight_max || !weight_sum || !pixels) return fail(GSX_ERR_INVALID_ARGUMENT, "weight_max / weight_sum / pixels is NULL");
+    if (accumulate != 0 && accumulate != 1) return fail(GSX_ERR_INVALID_ARGUMENT, "accumulate = %d is neither 0 nor 1", accumulate);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    Walk w;
+    // (weight_max stands in for the frame the plan describes: this entry has none and writes no pixel)
+    int rc = open_walk(a, "gsx_render_contribution", kRulesEither, weight_max, nullptr, kCarveBackward, w);
+    if (rc != GSX_OK) return rc;
+    hipStream_t s = w.s;
+    const bool std_rules = w.p.semantics == GSX_SEM_STD_3DGS;
+    if (!accumulate) {      // every row: a Gaussian on no tile list reads +0 / 0
+        rc = zero_fill({{weight_max, (size_t)n}, {weight_sum, (size_t)n}, {pixels, (size_t)n}, {views, (size_t)n}}, s);
+        if (rc != GSX_OK) return rc;
+    }
+    bool go;
+    rc = lists_again(a, w, nullptr, go);
+    if (rc != GSX_OK || !go) return rc;
+    gsx::Record *raw = (gsx::Record *)(w.ws + w.c.raw);
+    if (!std_rules) GSX_HIP(gsx::launch_project_raw(*camera, w.in, n, w.p.small_batch, raw, s));
+    rc = launch_walk_prefix(w, false);
+    if (rc != GSX_OK) return rc;
+    const gsx::ContributionTiles ct{std_rules ? (const gsx::Record *)(w.ws + w.c.rec) : raw, w.sorted_vals,
+                                    (const uint2 *)(w.ws + w.c.ranges), w.rank_of, w.prefix, w.rrect, w.slots};
+    GSX_HIP(gsx::launch_contribution_tiles(ct, w.p.grid, std_rules, s));
+    GSX_HIP(gsx::launch_contribution_sums(w.slots, w.prefix, w.order, w.m, weight_max, weight_sum, pixels, views, accumulate != 0, s));
+    GSX_HIP(hipStreamSynchronize(s));
+    return GSX_OK;
 }
 
 size_t gsx_backward_camera_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
@@ -920,8 +911,8 @@ int gsx_render_backward_camera(const GsxCamera *camera, const float *means3d, co
         return fail(GSX_ERR_INVALID_ARGUMENT, "grad_means3d / grad_scales / grad_quats is NULL");
     if (!grad_world2view || !grad_full_proj) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_world2view / grad_full_proj is NULL");
     const GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius, grad_world2view, grad_full_proj};
-    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    return render_backward(a, image, grad_image, grad_colors, grad_opacity_logit, &geo);
 }
 
 size_t gsx_depth_workspace_bytes(int64_t n, int32_t width, int32_t height, int32_t tile, int64_t max_instances) {
@@ -935,38 +926,24 @@ size_t gsx_backward_depth_workspace_bytes(int64_t n, int32_t width, int32_t heig
 int gsx_render_depth(const GsxCamera *camera, const float *means3d, const float *scales, const float *quats,
                      const float *opacity_logit, const float *colors, int64_t n, int32_t tile_size, float *depth_out,
                      const GsxParams *params, void *workspace, size_t workspace_bytes, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
     if (!camera) return fail(GSX_ERR_INVALID_ARGUMENT, "camera is NULL");
     if (!depth_out) return fail(GSX_ERR_INVALID_ARGUMENT, "depth_out is NULL");
-    Plan p;
-    int rc = make_plan_or_fail(camera->width, camera->height, tile_size, depth_out, params, p);    // (the frame's descriptor: depth_index)
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    Walk w;
+    int rc = open_walk(a, "gsx_render_depth", kRulesRefCpu, depth_out, nullptr, kCarveDepth, w);   // (the frame's descriptor: depth_index)
     if (rc != GSX_OK) return rc;
-    rc = check_whole_ref_cpu(p, camera, params, "gsx_render_depth");
-    if (rc != GSX_OK) return rc;
-    rc = check_inputs(p, n, means3d, scales, quats, opacity_logit, colors);
-    if (rc != GSX_OK) return rc;
-    Carve c;
-    int64_t cap;
-    rc = check_workspace(workspace, workspace_bytes, n, max_tiles_of(camera->width, camera->height, tile_size), c, cap, kCarveDepth);
-    if (rc != GSX_OK) return rc;
-    char *ws = (char *)workspace;
+    hipStream_t s = w.s;
     // every pixel: zeros where the frame has zeros (the unrendered last row and column of tiles, a frame that lists nothing)
-    GSX_HIP(gsx::launch_zero_words((uint32_t *)depth_out, (size_t)camera->width * (size_t)camera->height * 2, s));
-    if (n == 0 || p.grid.count() == 0) {
-        GSX_HIP(hipStreamSynchronize(s));
-        return GSX_OK;
-    }
-    const gsx::GaussiansIn in{means3d, scales, quats, opacity_logit, colors, p.original_index, nullptr};
-    const uint32_t *order, *sorted_vals;
-    int64_t counts[3];
-    rc = lists_again(p, c, ws, *camera, in, n, cap, s, order, sorted_vals, counts);
+    rc = zero_fill({{depth_out, (size_t)camera->width * (size_t)camera->height * 2}}, s);
     if (rc != GSX_OK) return rc;
-    if (counts[2] == 0 || counts[1] == 0) return GSX_OK;
-    gsx::Record *raw = (gsx::Record *)(ws + c.raw);
-    float *zrow = (float *)(ws + c.zrow);
-    GSX_HIP(gsx::launch_project_raw(*camera, in, n, p.small_batch, raw, s));
-    GSX_HIP(gsx::launch_project_depth(*camera, means3d, n, p.small_batch, zrow, s));
-    GSX_HIP(gsx::launch_depth_tiles(raw, sorted_vals, (const uint2 *)(ws + c.ranges), zrow, p.grid, p.out, depth_out, s));
+    bool go;
+    rc = lists_again(a, w, nullptr, go);
+    if (rc != GSX_OK || !go) return rc;
+    gsx::Record *raw = (gsx::Record *)(w.ws + w.c.raw);
+    float *zrow = (float *)(w.ws + w.c.zrow);
+    GSX_HIP(gsx::launch_project_raw(*camera, w.in, n, w.p.small_batch, raw, s));
+    GSX_HIP(gsx::launch_project_depth(*camera, means3d, n, w.p.small_batch, zrow, s));
+    GSX_HIP(gsx::launch_depth_tiles(raw, w.sorted_vals, (const uint2 *)(w.ws + w.c.ranges), zrow, w.p.grid, w.p.out, depth_out, s));
     GSX_HIP(hipStreamSynchronize(s));
     return GSX_OK;
 }
@@ -983,8 +960,8 @@ int gsx_render_backward_depth(const GsxCamera *camera, const float *means3d, con
     GeometryGrads geo{grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
     geo.depth = depth;
     geo.grad_depth = grad_depth;
-    return render_backward(camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, image, grad_image,
-                           grad_colors, grad_opacity_logit, &geo, params, workspace, workspace_bytes, stream);
+    const WalkArgs a{camera, means3d, scales, quats, opacity_logit, colors, n, tile_size, params, workspace, workspace_bytes, stream};
+    return render_backward(a, image, grad_image, grad_colors, grad_opacity_logit, &geo);
 }
 
 #ifdef GSX_TEST_HOOKS
@@ -1055,32 +1032,42 @@ size_t gsx_photometric_loss_workspace_bytes(int32_t rows, int32_t cols, int32_t 
     return loss_carve(rows, cols, with_grad != 0, c) ? c.total : 0;
 }
 
+// What the two loss entries check alike: the images, the region and the strides, then -- behind whatever else the
+// weighted entry says about its arguments -- lambda_dssim.
+static int check_loss_images(const gsx::LossImages &im, const float *loss_out) {
+    if (!im.image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
+    if (!im.target) return fail(GSX_ERR_INVALID_ARGUMENT, "target is NULL");
+    if (!loss_out) return fail(GSX_ERR_INVALID_ARGUMENT, "loss_out is NULL");
+    if (im.rows <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "rows = %d is not positive", im.rows);
+    if (im.cols <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "cols = %d is not positive", im.cols);
+    const int64_t need = 3 * (int64_t)im.cols;
+    if (im.image_stride < need)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "image_row_stride %lld is below 3 cols = %lld", (long long)im.image_stride, (long long)need);
+    if (im.target_stride < need)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "target_row_stride %lld is below 3 cols = %lld", (long long)im.target_stride, (long long)need);
+    if (im.grad && im.grad_stride < need)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_row_stride %lld is below 3 cols = %lld", (long long)im.grad_stride, (long long)need);
+    return GSX_OK;
+}
+static int check_lambda_dssim(float lambda_dssim) {
+    if (!(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f))      // (a NaN fails both comparisons)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lambda_dssim %g is outside [0, 1]", (double)lambda_dssim);
+    return GSX_OK;
+}
+
 int gsx_photometric_loss(const float *image, int64_t image_row_stride, const float *target, int64_t target_row_stride,
                          int32_t rows, int32_t cols, float lambda_dssim, float *loss_out, float *grad_image,
                          int64_t grad_row_stride, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
-    if (!target) return fail(GSX_ERR_INVALID_ARGUMENT, "target is NULL");
-    if (!loss_out) return fail(GSX_ERR_INVALID_ARGUMENT, "loss_out is NULL");
-    if (rows <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "rows = %d is not positive", rows);
-    if (cols <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "cols = %d is not positive", cols);
-    const int64_t need = 3 * (int64_t)cols;
-    if (image_row_stride < need)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "image_row_stride %lld is below 3 cols = %lld", (long long)image_row_stride, (long long)need);
-    if (target_row_stride < need)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "target_row_stride %lld is below 3 cols = %lld", (long long)target_row_stride, (long long)need);
-    if (grad_image && grad_row_stride < need)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_row_stride %lld is below 3 cols = %lld", (long long)grad_row_stride, (long long)need);
-    if (!(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f))      // (a NaN fails both comparisons)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "lambda_dssim %g is outside [0, 1]", (double)lambda_dssim);
+    const gsx::LossImages im{image, target, grad_image, image_row_stride, target_row_stride, grad_row_stride, rows, cols};
+    int rc = check_loss_images(im, loss_out);
+    if (rc == GSX_OK) rc = check_lambda_dssim(lambda_dssim);
+    if (rc != GSX_OK) return rc;
     LossCarve c;
     if (!loss_carve(rows, cols, grad_image != nullptr, c))
         return fail(GSX_ERR_INVALID_ARGUMENT, "rows x cols = %d x %d is more than 2^31 - 1 tiles of %d x %d", rows, cols, kLossTile, kLossTile);
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    if (workspace_bytes < c.total)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_photometric_loss_workspace_bytes(%d, %d, %d) = %zu",
-                    workspace_bytes, rows, cols, grad_image ? 1 : 0, c.total);
-    const gsx::LossImages im{image, target, grad_image, image_row_stride, target_row_stride, grad_row_stride, rows, cols};
+    rc = check_sized_workspace(workspace, workspace_bytes, c.total, "gsx_photometric_loss_workspace_bytes(%d, %d, %d)", rows, cols,
+                               grad_image ? 1 : 0);
+    if (rc != GSX_OK) return rc;
     GSX_HIP(gsx::launch_photometric_loss(im, lambda_dssim, loss_out, (char *)workspace, c, (hipStream_t)stream));
     return GSX_OK;
 }
@@ -1094,33 +1081,21 @@ int gsx_photometric_loss_weighted(const float *image, int64_t image_row_stride, 
                                   const float *weight, int64_t weight_row_stride, const float *exposure, int32_t rows,
                                   int32_t cols, float lambda_dssim, float *loss_out, float *grad_image, int64_t grad_row_stride,
                                   float *grad_exposure, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!image) return fail(GSX_ERR_INVALID_ARGUMENT, "image is NULL");
-    if (!target) return fail(GSX_ERR_INVALID_ARGUMENT, "target is NULL");
-    if (!loss_out) return fail(GSX_ERR_INVALID_ARGUMENT, "loss_out is NULL");
-    if (rows <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "rows = %d is not positive", rows);
-    if (cols <= 0) return fail(GSX_ERR_INVALID_ARGUMENT, "cols = %d is not positive", cols);
-    const int64_t need = 3 * (int64_t)cols;
-    if (image_row_stride < need)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "image_row_stride %lld is below 3 cols = %lld", (long long)image_row_stride, (long long)need);
-    if (target_row_stride < need)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "target_row_stride %lld is below 3 cols = %lld", (long long)target_row_stride, (long long)need);
-    if (grad_image && grad_row_stride < need)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "grad_row_stride %lld is below 3 cols = %lld", (long long)grad_row_stride, (long long)need);
+    const gsx::LossImages im{image, target, grad_image, image_row_stride, target_row_stride, grad_row_stride, rows, cols};
+    int rc = check_loss_images(im, loss_out);
+    if (rc != GSX_OK) return rc;
     if (weight && weight_row_stride < (int64_t)cols)
         return fail(GSX_ERR_INVALID_ARGUMENT, "weight_row_stride %lld is below cols = %d", (long long)weight_row_stride, cols);
     if (grad_exposure && !exposure) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_exposure without exposure");
     if (grad_exposure && !grad_image) return fail(GSX_ERR_INVALID_ARGUMENT, "grad_exposure without grad_image");
-    if (!(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f))      // (a NaN fails both comparisons)
-        return fail(GSX_ERR_INVALID_ARGUMENT, "lambda_dssim %g is outside [0, 1]", (double)lambda_dssim);
+    rc = check_lambda_dssim(lambda_dssim);
+    if (rc != GSX_OK) return rc;
     LossWeightedCarve c;
     if (!loss_weighted_carve(rows, cols, grad_image != nullptr, c))
         return fail(GSX_ERR_INVALID_ARGUMENT, "rows x cols = %d x %d is more than 2^31 - 1 tiles of %d x %d", rows, cols, kLossTile, kLossTile);
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    if (workspace_bytes < c.total)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_photometric_loss_weighted_workspace_bytes(%d, %d, %d) = %zu",
-                    workspace_bytes, rows, cols, grad_image ? 1 : 0, c.total);
-    const gsx::LossImages im{image, target, grad_image, image_row_stride, target_row_stride, grad_row_stride, rows, cols};
+    rc = check_sized_workspace(workspace, workspace_bytes, c.total, "gsx_photometric_loss_weighted_workspace_bytes(%d, %d, %d)", rows,
+                               cols, grad_image ? 1 : 0);
+    if (rc != GSX_OK) return rc;
     if (!weight && !exposure) {     // the kernels and the bits of gsx_photometric_loss; the carve starts with its carve
         GSX_HIP(gsx::launch_photometric_loss(im, lambda_dssim, loss_out, (char *)workspace, c.base, (hipStream_t)stream));
         GSX_HIP(gsx::launch_loss_weight_sum(rows, cols, loss_out, (hipStream_t)stream));
@@ -1248,12 +1223,7 @@ namespace {
 // n and the workspace of gsx_density_plan / gsx_density_apply
 int check_density_workspace(int64_t n, const void *workspace, size_t workspace_bytes, DensityCarve &c) {
     if (!density_carve(n, c)) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    if (workspace_bytes < c.total)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_density_workspace_bytes(%lld) = %zu", workspace_bytes,
-                    (long long)n, c.total);
-    return GSX_OK;
+    return check_sized_workspace(workspace, workspace_bytes, c.total, "gsx_density_workspace_bytes(%lld)", (long long)n);
 }
 
 // gsx_density_plan (radius_max == nullptr, prune_radius = +inf) and gsx_density_plan_screen: one body
@@ -1449,11 +1419,8 @@ int gsx_mcmc_plan(const float *opacity, int64_t n, float dead_logit, int64_t n_o
         return fail(GSX_ERR_INVALID_ARGUMENT, "n_out = %lld is outside n = %lld .. 2^30", (long long)n_out, (long long)n);
     if (dead_logit != dead_logit) return fail(GSX_ERR_INVALID_ARGUMENT, "dead_logit is NaN");
     if (!counts_host) return fail(GSX_ERR_INVALID_ARGUMENT, "counts_host is NULL");
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    if (workspace_bytes < c.total)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_mcmc_workspace_bytes(%lld) = %zu", workspace_bytes,
-                    (long long)n, c.total);
+    const int rc = check_sized_workspace(workspace, workspace_bytes, c.total, "gsx_mcmc_workspace_bytes(%lld)", (long long)n);
+    if (rc != GSX_OK) return rc;
     if (n > 0) {
         if (!opacity) return fail(GSX_ERR_INVALID_ARGUMENT, "opacity is NULL");
         if (!uniforms) return fail(GSX_ERR_INVALID_ARGUMENT, "uniforms is NULL");
@@ -1538,11 +1505,8 @@ int gsx_knn3(const float *points, int64_t n, const int32_t *order, int32_t rule,
         return GSX_OK;
     }
     if (!points) return fail(GSX_ERR_INVALID_ARGUMENT, "points is NULL");
-    if (!workspace) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace is NULL");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0) return fail(GSX_ERR_INVALID_ARGUMENT, "workspace must be 256-byte aligned");
-    if (workspace_bytes < c.total)
-        return fail(GSX_ERR_WORKSPACE_TOO_SMALL, "workspace of %zu bytes, gsx_knn3_workspace_bytes(%lld) = %zu", workspace_bytes,
-                    (long long)n, c.total);
+    const int rc = check_sized_workspace(workspace, workspace_bytes, c.total, "gsx_knn3_workspace_bytes(%lld)", (long long)n);
+    if (rc != GSX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (candidates) GSX_HIP(hipMemsetAsync(workspace, 0, sizeof(uint64_t), s));
     GSX_HIP(gsx::launch_knn3(points, n, order, rule, dist3, scale, (char *)workspace, c, candidates != nullptr, s));

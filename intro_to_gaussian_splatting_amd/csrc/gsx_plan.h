@@ -532,6 +532,26 @@ inline int make_plan(int32_t width, int32_t height, int32_t tile, float *out_ima
     return GSX_OK;
 }
 
+// What every entry that walks the forward's lists again covers (the gradient entries, gsx_render_depth,
+// gsx_render_contribution): the whole width x height frame of RGB colours, in one synchronous call that reads the host
+// camera.  p: make_plan's plan of `params`; entry: the exported name, which every message starts with.
+inline int check_whole_frame(const Plan &p, int32_t width, int32_t height, const GsxParams *params, const char *entry,
+                             char *msg, size_t msg_bytes) {
+    auto fail = [&](const char *what) {
+        snprintf(msg, msg_bytes, "%s %s", entry, what);
+        return GSX_ERR_INVALID_ARGUMENT;
+    };
+    if (p.sh) return fail("takes RGB colours, not GsxParams.sh");
+    if (p.grid.wx0 != 0 || p.grid.wy0 != 0 || p.grid.wx1 != p.grid.ntx || p.grid.wy1 != p.grid.nty)
+        return fail("renders the whole frame: no tile window");
+    if (p.out.x0 != 0 || p.out.y0 != 0 || p.out.w != width || p.out.h != height)
+        return fail("takes the whole frame: no output window");
+    if (p.n_parts > 0) return fail("does not take substrips");
+    if (params && (params->flags & GSX_FLAG_NO_SYNC)) return fail("synchronises: no GSX_FLAG_NO_SYNC");   // (p.no_sync is off under GSX_FLAG_TIMING)
+    if (p.camera_device) return fail("reads the camera argument: no camera_device");
+    return GSX_OK;
+}
+
 // The pixels of the output buffer that no tile of the window covers (the compositing kernel writes every
 // pixel of every tile it owns, empty tiles included): up to four rectangles, zeroed by extra workgroups
 // of the compositing launch instead of a whole-frame memset (25 MB at 1080p).  whole = true: the entire

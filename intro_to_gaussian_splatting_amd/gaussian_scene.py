@@ -1033,6 +1033,32 @@ class GaussianScene:
         _ffi.check(rc)
         return pinned, st
 
+    def _walk_lists(self, image_idx: int, tile_size: int, layout: str, semantics: str, n_instances: int, prepare):
+        """The frame of every call that walks the forward's lists again (``_render_backward``, ``_render_depth``,
+        ``_render_contribution``): the scene's inputs, detached, the view's camera and the frame's params; then
+        ``prepare(lib, dev, n, cam, params)``, which sets the call's flags, checks and makes what is the call's own and
+        returns (size function, what to say when it returns 0, entry, its arguments between ``tile_size`` and ``params``
+        -- tensors, None or ints --, the result); then the workspace for ``n_instances + 4096`` pairs, the call, its
+        check.  Returns the result."""
+        lib = _ffi.load()
+        with torch.no_grad():
+            dev, n, tensors = self._inputs(image_idx)
+            tensors = [t.detach() for t in tensors]
+            cam = self.images[image_idx].gsx_camera()
+            params, _ = self._frame_params(dev, n, layout, semantics)
+            size_fn, rejected, entry, args, result = prepare(lib, dev, n, cam, params)
+            cap = int(n_instances) + 4096
+            with torch.cuda.device(dev):
+                nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
+                if nbytes == 0:
+                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, rejected)
+                ws = _WORKSPACE.get(dev, nbytes)
+                rc = entry(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size,
+                           *[a if isinstance(a, int) else _ptr(a) for a in args], ctypes.byref(params), _ptr(ws), nbytes,
+                           _stream_handle(dev))
+            _ffi.check(rc)
+        return result
+
     def _render_backward(self, image_idx: int, tile_size: int, layout: str, frame: torch.Tensor, grad_frame: torch.Tensor,
                          n_instances: int, n_visible: int, flags: int = 0, geometry: bool = False,
                          screen: bool = False, camera: bool = False, depth: Optional[torch.Tensor] = None,
@@ -1052,12 +1078,7 @@ class GaussianScene:
         The projection, depth order and binning run again in the library (the same lists as the
         forward's); the scene's hints buffers are not touched.  ``flags``: GSX_FLAG_* added to the call's own (the test
         library's stage times: GSX_FLAG_TIMING, tools/bench_backward.py)."""
-        lib = _ffi.load()
-        with torch.no_grad():
-            dev, n, tensors = self._inputs(image_idx)
-            tensors = [t.detach() for t in tensors]
-            cam = self.images[image_idx].gsx_camera()
-            params, _ = self._frame_params(dev, n, layout, "ref_cpu" if std is None else "std_3dgs")
+        def prepare(lib, dev, n, cam, params):
             if std is None:
                 params.flags |= _ffi.rows_flag(n, n_visible) | int(flags)     # the row class the forward ended up with
             else:
@@ -1089,7 +1110,6 @@ class GaussianScene:
                 if tuple(gd.shape) != tuple(dimg.shape) or tuple(dimg.shape) != tuple(img.shape[:2]) + (2,):
                     raise ValueError("depth has shape %s and grad_depth %s, the frame %s" % (tuple(dimg.shape), tuple(gd.shape),
                                                                                           tuple(img.shape)))
-            cap = int(n_instances) + 4096
             size_fn = lib.gsx_backward_geometry_workspace_bytes if geometry else lib.gsx_backward_workspace_bytes
             entry = (lib.gsx_render_backward_screen if screen else lib.gsx_render_backward_geometry) if geometry \
                 else lib.gsx_render_backward
@@ -1107,38 +1127,20 @@ class GaussianScene:
             if std is not None:     # one entry: NULL for the outputs that were not asked for
                 args = outs + [None] * (7 - len(outs))
                 size_fn, entry = lib.gsx_backward_std_workspace_bytes, lib.gsx_render_backward_std
-            with torch.cuda.device(dev):
-                nbytes = size_fn(n, cam.width, cam.height, tile_size, cap)
-                if nbytes == 0:
-                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "the backward workspace function rejected the sizes")
-                ws = _WORKSPACE.get(dev, nbytes)
-                rc = entry(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(img), _ptr(gf),
-                           *[_ptr(t) for t in args], ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
-            _ffi.check(rc)
-        return tuple(outs)
+            return size_fn, "the backward workspace function rejected the sizes", entry, [img, gf] + args, tuple(outs)
+
+        return self._walk_lists(image_idx, tile_size, layout, "ref_cpu" if std is None else "std_3dgs", n_instances, prepare)
 
     def _render_depth(self, image_idx: int, tile_size: int, layout: str, n_instances: int, n_visible: int) -> torch.Tensor:
         """gsx_render_depth: the (D, A) image of the whole ref_cpu frame, (W,H,2) for ``layout`` "wh3" and (H,W,2) for "hw3";
         ``n_instances`` and ``n_visible`` are the frame's counts (its workspace and row class)."""
-        lib = _ffi.load()
-        with torch.no_grad():
-            dev, n, tensors = self._inputs(image_idx)
-            tensors = [t.detach() for t in tensors]
-            cam = self.images[image_idx].gsx_camera()
-            params, _ = self._frame_params(dev, n, layout, "ref_cpu")
+        def prepare(lib, dev, n, cam, params):
             params.flags |= _ffi.rows_flag(n, n_visible)
             shape = (cam.width, cam.height, 2) if layout == "wh3" else (cam.height, cam.width, 2)
             out = torch.empty(shape, dtype=torch.float32, device=dev)
-            cap = int(n_instances) + 4096
-            with torch.cuda.device(dev):
-                nbytes = lib.gsx_depth_workspace_bytes(n, cam.width, cam.height, tile_size, cap)
-                if nbytes == 0:
-                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_depth_workspace_bytes rejected the sizes")
-                ws = _WORKSPACE.get(dev, nbytes)
-                rc = lib.gsx_render_depth(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size, _ptr(out),
-                                          ctypes.byref(params), _ptr(ws), nbytes, _stream_handle(dev))
-            _ffi.check(rc)
-        return out
+            return lib.gsx_depth_workspace_bytes, "gsx_depth_workspace_bytes rejected the sizes", lib.gsx_render_depth, [out], out
+
+        return self._walk_lists(image_idx, tile_size, layout, "ref_cpu", n_instances, prepare)
 
     def render_image_depth_hip(self, image_idx: int, tile_size: int = 16, layout: str = "wh3",
                                screen_statistics: bool = False, stats: Optional[dict] = None):
@@ -1184,12 +1186,7 @@ class GaussianScene:
         """gsx_render_contribution on view ``image_idx``: a new ``Contribution`` (every row written), or ``out`` with the
         view merged into it (accumulate).  ``n_instances`` and ``n_visible`` are the counts of the view's frame under
         ``semantics`` (the workspace and the row class), as for ``_render_backward``."""
-        lib = _ffi.load()
-        with torch.no_grad():
-            dev, n, tensors = self._inputs(image_idx)
-            tensors = [t.detach() for t in tensors]
-            cam = self.images[image_idx].gsx_camera()
-            params, _ = self._frame_params(dev, n, "wh3", semantics)
+        def prepare(lib, dev, n, cam, params):
             if semantics == "ref_cpu":
                 params.flags |= _ffi.rows_flag(n, n_visible)
             elif published_rects:
@@ -1206,17 +1203,10 @@ class GaussianScene:
                             or not t.is_contiguous():
                         raise ValueError("out.%s must be a contiguous %s tensor of shape (%d,) on %s: a Contribution of this "
                                          "container" % (name, dtype, n, dev))
-            cap = int(n_instances) + 4096
-            with torch.cuda.device(dev):
-                nbytes = lib.gsx_contribution_workspace_bytes(n, cam.width, cam.height, tile_size, cap)
-                if nbytes == 0:
-                    raise _ffi.GsxError(_ffi.GSX_ERR_INVALID_ARGUMENT, "gsx_contribution_workspace_bytes rejected the sizes")
-                ws = _WORKSPACE.get(dev, nbytes)
-                rc = lib.gsx_render_contribution(ctypes.byref(cam), *[_ptr(t) for t in tensors], n, tile_size,
-                                                 *[_ptr(t) for t in con], 0 if out is None else 1, ctypes.byref(params),
-                                                 _ptr(ws), nbytes, _stream_handle(dev))
-            _ffi.check(rc)
-        return con
+            return (lib.gsx_contribution_workspace_bytes, "gsx_contribution_workspace_bytes rejected the sizes",
+                    lib.gsx_render_contribution, list(con) + [0 if out is None else 1], con)
+
+        return self._walk_lists(image_idx, tile_size, "wh3", semantics, n_instances, prepare)
 
     def render_contribution_hip(self, image_idx: int, semantics: str = "ref_cpu", tile_size: int = 16,
                                 out: Optional[Contribution] = None, tile_window=None,

@@ -155,6 +155,64 @@ static void check_plan(int32_t w, int32_t h, int32_t tile, int sem, int layout, 
     CHECK(all == (int64_t)p.out.w * p.out.h);
 }
 
+// check_whole_frame, the refusals every entry that walks the forward's lists again shares: the default plan passes, and
+// one plan per refusal is refused with a message that names the entry and fits its buffer, however small that is.
+static void check_whole_frame_refusals(int32_t w, int32_t h, int32_t tile, int sem, int layout) {
+    float dummy = 0.0f;
+    GsxCamera cam_dev;
+    int32_t bounds[3];
+    void *events[2] = {&dummy, &dummy};
+    const char *entry = "gsx_render_backward_geometry";
+    auto run = [&](const GsxParams &prm, int want, const char *word) {
+        Plan p;
+        char plan_msg[256] = "";
+        if (make_plan(w, h, tile, &dummy, &prm, p, plan_msg, sizeof plan_msg) != GSX_OK) return;   // (a frame no call accepts)
+        char msg[96] = "", tiny[8] = "";
+        CHECK(check_whole_frame(p, w, h, &prm, entry, msg, sizeof msg) == want);
+        CHECK(check_whole_frame(p, w, h, &prm, entry, tiny, sizeof tiny) == want);
+        CHECK(strlen(msg) < sizeof msg && strlen(tiny) < sizeof tiny);
+        if (want == GSX_OK) {
+            CHECK(msg[0] == '\0' && tiny[0] == '\0');
+            CHECK(check_whole_frame(p, w, h, nullptr, entry, msg, sizeof msg) == GSX_OK);
+        } else {
+            CHECK(strncmp(msg, entry, strlen(entry)) == 0 && strstr(msg, word) != nullptr);
+            CHECK(strncmp(tiny, entry, sizeof tiny - 1) == 0);
+        }
+    };
+    GsxParams base;
+    default_params(&base);
+    base.semantics = sem;
+    base.layout = layout;
+    run(base, GSX_OK, "");
+    GsxParams prm = base;
+    prm.sh = &dummy;
+    run(prm, GSX_ERR_INVALID_ARGUMENT, "GsxParams.sh");
+    if (tiles_along(w, tile, sem) >= 1) {      // (without a tile along x every window is the whole frame)
+        prm = base;
+        prm.tile_x0 = 1;
+        run(prm, GSX_ERR_INVALID_ARGUMENT, "no tile window");
+    }
+    if (w < INT32_MAX) {
+        prm = base;
+        prm.out_w = w + 1;
+        prm.out_h = h;
+        run(prm, GSX_ERR_INVALID_ARGUMENT, "no output window");
+    }
+    prm = base;
+    bounds[0] = bounds[1] = 0;
+    bounds[2] = tiles_along(w, tile, sem);
+    prm.n_substrips = 2;
+    prm.substrip_bounds = bounds;
+    prm.substrip_events = events;
+    run(prm, GSX_ERR_INVALID_ARGUMENT, "substrips");
+    prm = base;
+    prm.flags = GSX_FLAG_NO_SYNC | GSX_FLAG_TIMING;      // (the plan's own no_sync is off under GSX_FLAG_TIMING: the flag is what counts)
+    run(prm, GSX_ERR_INVALID_ARGUMENT, "GSX_FLAG_NO_SYNC");
+    prm = base;
+    prm.camera_device = &cam_dev;
+    run(prm, GSX_ERR_INVALID_ARGUMENT, "camera_device");
+}
+
 int main() {
     // ---- workspace carving and capacity, hand-picked edges and a random sweep up to the 2^31 limits
     const int64_t big = ((int64_t)1 << 31) - 1;
@@ -215,6 +273,7 @@ int main() {
         const bool huge = (int64_t)w * h > (int64_t)1 << 40;   // rectangle areas still fit int64; nothing else is formed
         (void)huge;
         check_plan(w, h, tile, sem, layout, win, rnd() % 2 == 0);
+        check_whole_frame_refusals(w, h, tile, sem, layout);
     }
     // an empty window that starts at tile 0 renders nothing (it used to mean "to the end")
     {
