@@ -517,6 +517,8 @@ int launch_walk_prefix(Walk &w, bool geo) {
     GSX_HIP(gsx::launch_backward_prefix(w.rrect, w.order, w.m, w.prefix, w.rank_of, (uint32_t *)(w.ws + w.c.bsum), w.s));
     return GSX_OK;
 }
+// ... and what the per-Gaussian launches behind the tile kernels take of it
+gsx::RankSlots rank_slots(const Walk &w) { return gsx::RankSlots{w.slots, w.geo_slots, w.prefix, w.order, w.m}; }
 
 // What gsx_render_backward and gsx_render_backward_std say about a missing one of the three
 const char *const kNoGradArrays = "grad_image / grad_colors / grad_opacity_logit is NULL";
@@ -561,17 +563,15 @@ int render_backward(const WalkArgs &a, const float *image, const float *grad_ima
         GSX_HIP(gsx::launch_backward_tiles(bt, p.grid, p.out, s));
     }
     tm.mark();  // 2: raw records, prefix, compositing backward
-    GSX_HIP(gsx::launch_backward_sums(w.slots, w.prefix, w.order, raw, w.m, grad_colors, grad_opacity_logit, s));
+    const gsx::RankSlots rk = rank_slots(w);
+    GSX_HIP(gsx::launch_backward_sums(rk, raw, grad_colors, grad_opacity_logit, s));
+    const gsx::GeometryRows rows{a.means3d, a.scales, a.quats, g.means3d, g.scales, g.quats, g.means2d,
+                                 g.means2d ? g.radius : nullptr};
     if (geo && geo->depth) {
-        GSX_HIP(gsx::launch_backward_geometry_depth(*a.camera, w.geo_slots, w.prefix, w.order, raw, w.m, a.means3d, a.scales,
-                                                    a.quats, geo->means3d, geo->scales, geo->quats, geo->means2d,
-                                                    geo->means2d ? geo->radius : nullptr, s));
+        GSX_HIP(gsx::launch_backward_geometry_depth(*a.camera, rk, raw, rows, s));
     } else if (geo) {
         const gsx::CameraGrads cg{geo->world2view, geo->full_proj, (float *)(w.ws + w.c.cam_partials)};
-        GSX_HIP(gsx::launch_backward_geometry(*a.camera, w.geo_slots, w.prefix, w.order, raw, w.m, a.means3d, a.scales, a.quats,
-                                              geo->means3d, geo->scales, geo->quats, geo->means2d,
-                                              geo->means2d ? geo->radius : nullptr, s, geo->world2view ? &cg : nullptr,
-                                              geo->means2d_abs));
+        GSX_HIP(gsx::launch_backward_geometry(*a.camera, rk, raw, rows, s, geo->world2view ? &cg : nullptr, geo->means2d_abs));
     }
     tm.mark();  // 3: sums (and the geometry chain)
     GSX_HIP(hipStreamSynchronize(s));
@@ -843,15 +843,13 @@ int gsx_render_backward_std(const GsxCamera *camera, const float *means3d, const
     const gsx::BackwardTiles bt{rec, w.sorted_vals, (const uint2 *)(w.ws + w.c.ranges), w.rank_of, w.prefix, w.rrect, image,
                                 grad_image, w.slots, w.geo_slots};
     GSX_HIP(gsx::launch_backward_tiles_std(bt, w.p.grid, w.p.out, s));
+    const gsx::RankSlots rk = rank_slots(w);
+    const gsx::GeometryRows rows{means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius};
     if (w.p.antialiased) {
-        GSX_HIP(gsx::launch_backward_std_antialiased(*camera, w.slots, w.geo_slots, w.prefix, w.order, w.m, means3d, scales, quats,
-                                                     opacity_logit, grad_colors, grad_opacity_logit, grad_means3d, grad_scales,
-                                                     grad_quats, grad_means2d, screen_radius, s));
+        GSX_HIP(gsx::launch_backward_std_antialiased(*camera, rk, rows, opacity_logit, grad_colors, grad_opacity_logit, s));
     } else {
-        GSX_HIP(gsx::launch_backward_sums_std(w.slots, w.prefix, w.order, rec, w.m, grad_colors, grad_opacity_logit, s));
-        if (geo)
-            GSX_HIP(gsx::launch_backward_geometry_std(*camera, w.geo_slots, w.prefix, w.order, w.m, means3d, scales, quats,
-                                                      grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius, s));
+        GSX_HIP(gsx::launch_backward_sums_std(rk, rec, grad_colors, grad_opacity_logit, s));
+        if (geo) GSX_HIP(gsx::launch_backward_geometry_std(*camera, rk, rows, s));
     }
     GSX_HIP(hipStreamSynchronize(s));
     return GSX_OK;

@@ -22,25 +22,29 @@
 // by column.  (2) backward_sum_kernel: one wave per Gaussian sums its contiguous slots (lane-strided, then the same
 // butterfly), applies the sigmoid chain and scatters to the Gaussian's row.  Same inputs, same bits.
 //
-// gsx_render_backward_geometry adds dL/dpoint, dL/dscale, dL/dquaternion -- the gradients the reference's graph gives once
-// its weight stays a tensor.  (1') backward_tile_geometry_kernel, the tile kernel's second instance
-// (gsx_backward_tile.inc), also sums five moments of u = dL/dalpha alpha per record into a second slot array;
-// (2') backward_geometry_sum_kernel sums them per Gaussian and backward_geometry_chain_kernel carries them through stage 1's
-// derivative (geometry_chain, below).  The colour-only kernels and their slots are the same code and layout either way.
-// gsx_render_backward_screen is the geometry call with two more per-Gaussian stores in the chain kernel: dL/d(NDC mean), which
-// the chain forms anyway on its way to dL/dpoint, and the radius project_raw_kernel left in the raw record's last word.
-// gsx_render_backward_camera is the screen call with the chain kernel's camera instance (backward_camera_chain_kernel): the
-// chain's g_t, dT and gh contracted with the point into 24 terms of dL/dworld2view and dL/dfull_proj per Gaussian, summed
-// per block with the butterflies above and LDS, and over the blocks by camera_reduce_kernel in a fixed order.
+// The file has two halves, each one text with an instance per entry.  Per pair: the tile walk (gsx_backward_tile.inc, six
+// instances).  Per Gaussian: three bodies -- colour_sums (2), geometry_sums, which sums a second slot array the same way,
+// and chain_rank, which carries those sums through stage 1's derivative (geometry_chain) -- behind one thin kernel per
+// variant.  What each entry adds to gsx_render_backward:
+// gsx_render_backward_geometry: dL/dpoint, dL/dscale, dL/dquaternion -- the gradients the reference's graph gives once its
+// weight stays a tensor.  (1') backward_tile_geometry_kernel also sums five moments of u = dL/dalpha alpha per record into
+// the second slot array; (2') backward_geometry_sum_kernel and backward_geometry_chain_kernel.  The colour-only kernels and
+// their slots are the same code and layout either way.
+// gsx_render_backward_screen: two more per-Gaussian stores in the chain: dL/d(NDC mean), which the chain forms anyway on its
+// way to dL/dpoint, and the radius project_raw_kernel left in the raw record's last word.
+// gsx_render_backward_camera: backward_camera_chain_kernel, the chain's g_t, dT and gh contracted with the point into 24
+// terms of dL/dworld2view and dL/dfull_proj per Gaussian, summed per block with the butterflies above and LDS, and over the
+// blocks by camera_reduce_kernel in a fixed order.
 // gsx_render_depth and gsx_render_backward_depth: expected depth D = sum T alpha z and coverage A = sum T alpha per pixel
 // (depth_tile_kernel, the backward's walk on the raw records plus one float per row, the view-space depth), and their
-// gradients fused into the one backward walk: the tile kernel's third instance (backward_tile_depth_kernel) adds depth's
-// term to dL/dalpha before u is formed and sums dL/dz per record beside the five moments; backward_depth_sum_kernel and
-// backward_depth_chain_kernel are the geometry kernels with that sixth sum, which reaches dL/dpoint through world2view's
-// third column.
-// gsx_render_backward_screen_abs: the screen call with the tile kernel's fourth instance (backward_tile_abs_kernel), which
-// also sums the ABSOLUTE value of every pixel's term of dL/dmean per record, and backward_geometry_abs_sum_kernel, the
-// geometry sum with those two sums beside the five moments and one more store per Gaussian; the chain kernel is the same.
+// gradients fused into the one backward walk: backward_tile_depth_kernel adds depth's term to dL/dalpha before u is formed
+// and sums dL/dz per record beside the five moments; backward_depth_sum_kernel and backward_depth_chain_kernel carry that
+// sixth sum, which reaches dL/dpoint through world2view's third column.
+// gsx_render_backward_screen_abs: backward_tile_abs_kernel also sums the ABSOLUTE value of every pixel's term of dL/dmean per
+// record, and backward_geometry_abs_sum_kernel sums those two beside the five moments, with one more store per Gaussian; the
+// chain kernel is the geometry entry's.
+// gsx_render_backward_std (GSX_SEM_STD_3DGS, and GSX_FLAG_ANTIALIASED): the tile walk's two std instances and the std and
+// anti-aliased variants of the colour sums and of the chain.
 //
 // alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
@@ -301,91 +305,72 @@ __global__ void __launch_bounds__(64)
     }
 }
 
-// One wave per depth rank: its slots [prefix[r], prefix[r + 1]) summed lane-strided, then over the wave; lane 0 applies
-// the sigmoid chain and writes the Gaussian's row.
+// ---- The per-Gaussian half: one body per role (colour sums, geometry sums, chain), one thin kernel per variant.
+// The colour sums.  One wave per depth rank: its slots [prefix[r], prefix[r + 1]) summed lane-strided in rising order, then
+// over the wave by wave_sum4's fixed butterfly; lane 0 writes the Gaussian's row (order[r]): the three colour sums, and
+// dlogit(row, U, b, e) -- the rule set's way from the fourth sum U = sum u to dL/dlogit, the one thing the variants differ in.
+// The kernels keep their pointers as __restrict__ arguments of their own and hand them on: what the compiler makes of the
+// bodies rests on it (by-value structs in their place cost the chain kernels their register allocation).
+template <class Logit>
+__device__ __forceinline__ void colour_sums(const float4 *__restrict__ slots, const uint32_t *__restrict__ prefix,
+                                            const uint32_t *__restrict__ order, uint32_t m, float *__restrict__ grad_colors,
+                                            float *__restrict__ grad_opacity_logit, Logit dlogit) {
+    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= m) return;
+    const uint32_t b = prefix[r], e = prefix[r + 1];
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
+        const float4 v = slots[i];
+        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
+    }
+    const float v = wave_sum4(a0, a1, a2, a3, lane);
+    const float g = __shfl(v, 16), bl = __shfl(v, 32), u = __shfl(v, 48);
+    if (lane == 0) {
+        const uint32_t row = order[r];
+        const float dl = dlogit(row, u, b, e);
+        grad_colors[3 * (int64_t)row] = v;
+        grad_colors[3 * (int64_t)row + 1] = g;
+        grad_colors[3 * (int64_t)row + 2] = bl;
+        grad_opacity_logit[row] = dl;
+    }
+}
+
+// GSX_SEM_REF_CPU: the raw record's b = (Q10, Q11, op = sigmoid(s), s = sigmoid(logit)), the sigmoid applied twice.
 __global__ void __launch_bounds__(256)
     backward_sum_kernel(const float4 *__restrict__ slots, const uint32_t *__restrict__ prefix, const uint32_t *__restrict__ order,
                         const Record *__restrict__ raw, uint32_t m, float *__restrict__ grad_colors,
                         float *__restrict__ grad_opacity_logit) {
-    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (r >= m) return;
-    const uint32_t b = prefix[r], e = prefix[r + 1];
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
-        const float4 v = slots[i];
-        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
-    }
-    const float v = wave_sum4(a0, a1, a2, a3, lane);
-    const float g = __shfl(v, 16), bl = __shfl(v, 32), u = __shfl(v, 48);
-    if (lane == 0) {
-        const uint32_t row = order[r];
-        const float4 B = raw[row].b;        // (Q10, Q11, op = sigmoid(s), s = sigmoid(logit))
+    colour_sums(slots, prefix, order, m, grad_colors, grad_opacity_logit, [=](uint32_t row, float u, uint32_t, uint32_t) {
+        const float4 B = raw[row].b;
         const float ds = u * (1.0f - B.z);
-        grad_colors[3 * (int64_t)row] = v;
-        grad_colors[3 * (int64_t)row + 1] = g;
-        grad_colors[3 * (int64_t)row + 2] = bl;
-        grad_opacity_logit[row] = ds * (B.w * (1.0f - B.w));
-    }
+        return ds * (B.w * (1.0f - B.w));
+    });
 }
 
-// gsx_render_backward_std: backward_sum_kernel on the packed GSX_SEM_STD_3DGS record, b = (Q''11, op, r, g) with
-// op = sigmoid(logit) applied ONCE: dL/dlogit = (sum u) (1 - op).  The slots are summed in the same order.
+// gsx_render_backward_std: the packed GSX_SEM_STD_3DGS record, b = (Q''11, op, r, g) with op = sigmoid(logit) applied ONCE.
 __global__ void __launch_bounds__(256)
     backward_std_sum_kernel(const float4 *__restrict__ slots, const uint32_t *__restrict__ prefix,
                             const uint32_t *__restrict__ order, const Record *__restrict__ rec, uint32_t m,
                             float *__restrict__ grad_colors, float *__restrict__ grad_opacity_logit) {
-    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (r >= m) return;
-    const uint32_t b = prefix[r], e = prefix[r + 1];
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
-        const float4 v = slots[i];
-        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
-    }
-    const float v = wave_sum4(a0, a1, a2, a3, lane);
-    const float g = __shfl(v, 16), bl = __shfl(v, 32), u = __shfl(v, 48);
-    if (lane == 0) {
-        const uint32_t row = order[r];
-        const float op = rec[row].b.y;
-        grad_colors[3 * (int64_t)row] = v;
-        grad_colors[3 * (int64_t)row + 1] = g;
-        grad_colors[3 * (int64_t)row + 2] = bl;
-        grad_opacity_logit[row] = u * (1.0f - op);
-    }
+    colour_sums(slots, prefix, order, m, grad_colors, grad_opacity_logit,
+                [=](uint32_t row, float u, uint32_t, uint32_t) { return u * (1.0f - rec[row].b.y); });
 }
 
-// GSX_FLAG_ANTIALIASED: the record holds op_eff = sigmoid(logit) * rho (std_aa_factor), and alpha = op_eff G, so the fourth
-// sum U = sum u is dL/d ln op_eff: dL/dlogit = U (1 - sigmoid(logit)), the sigmoid formed from the opacity input by stage 1's
-// own operations (std_sigmoid).  The chain after this kernel needs U for dL/drho: lane 0 leaves it in the free second word
-// of the Gaussian's first geometry slot pair, which backward_geometry_sum_kernel -- launched BEFORE this kernel on that
-// path -- has already rewritten as (S5, 0, 0, 0).  No extra pass, no atomics.  geo_slots null: the colour-only call.
+// GSX_FLAG_ANTIALIASED: the record holds op_eff = sigmoid(logit) * rho (std_aa_factor), and alpha = op_eff G, so U is
+// dL/d ln op_eff: dL/dlogit = U (1 - sigmoid(logit)), the sigmoid formed from the opacity input by stage 1's own operations
+// (std_sigmoid).  The chain after this kernel needs U for dL/drho: lane 0 leaves it in the free second word of the Gaussian's
+// first geometry slot pair, which backward_geometry_sum_kernel -- launched BEFORE this kernel on that path -- has already
+// rewritten as (S5, 0, 0, 0).  No extra pass, no atomics.  geo_slots null: the colour-only call.
 __global__ void __launch_bounds__(256)
     backward_std_aa_sum_kernel(const float4 *__restrict__ slots, const uint32_t *__restrict__ prefix,
                                const uint32_t *__restrict__ order, const float *__restrict__ opacity_logit, uint32_t m,
                                float *__restrict__ grad_colors, float *__restrict__ grad_opacity_logit,
                                float4 *__restrict__ geo_slots) {
-    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (r >= m) return;
-    const uint32_t b = prefix[r], e = prefix[r + 1];
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
-        const float4 v = slots[i];
-        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
-    }
-    const float v = wave_sum4(a0, a1, a2, a3, lane);
-    const float g = __shfl(v, 16), bl = __shfl(v, 32), u = __shfl(v, 48);
-    if (lane == 0) {
-        const uint32_t row = order[r];
-        const float sg = std_sigmoid(opacity_logit[row]);
-        grad_colors[3 * (int64_t)row] = v;
-        grad_colors[3 * (int64_t)row + 1] = g;
-        grad_colors[3 * (int64_t)row + 2] = bl;
-        grad_opacity_logit[row] = u * (1.0f - sg);
+    colour_sums(slots, prefix, order, m, grad_colors, grad_opacity_logit, [=](uint32_t row, float u, uint32_t b, uint32_t e) {
         if (geo_slots && b != e) geo_slots[2 * (size_t)b + 1].y = u;
-    }
+        return u * (1.0f - std_sigmoid(opacity_logit[row]));
+    });
 }
 
 // ---- gsx_render_backward_geometry: from a Gaussian's moment sums to dL/dpoint, dL/dscale, dL/dquaternion.
@@ -632,33 +617,134 @@ __device__ __forceinline__ void geometry_chain(const GeoCamera &cam, const float
     }
 }
 
-// One wave per depth rank: the Gaussian's geometry slots [prefix[r], prefix[r + 1]) summed as backward_sum_kernel sums
-// the colour slots (lane-strided, then the fixed butterflies).  The five sums go back into the Gaussian's FIRST slot:
-// only this wave reads the slots of rank r, and it has read them all by then.
-__global__ void __launch_bounds__(256)
-    backward_geometry_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m) {
+// The geometry sums.  One wave per depth rank: the Gaussian's geometry slot pairs [prefix[r], prefix[r + 1]) summed as
+// colour_sums sums the colour slots (lane-strided in rising order, then the fixed butterflies: wave_sum4 for the first four
+// moments, wave_sum1 for S5).  The sums go back into the Gaussian's FIRST pair as (S1, S2, S3, S4), (S5, 0, 0, 0): only this
+// wave reads the slots of rank r, and it has read them all by then.  A rank on no tile list is left alone.  Every kind forms
+// the five moments in the same operations and the same order, so the chain behind any of them gives the same bits.
+//   kDepth (gsx_render_backward_depth): the sixth sum Sz of the pairs' second .y, summed like S5; the pair becomes (S5, Sz, 0, 0).
+//   kAbs (gsx_render_backward_screen_abs): the two absolute sums backward_tile_abs_kernel left in the pairs' second .z and .w,
+//     Tx and Ty, summed like the moments and then by wave_sum2's fixed exchange and butterfly -- no atomics --, and a store
+//     per Gaussian, grad_means2d_abs[row] = ((0.5f * Tx) * hx, (0.5f * Ty) * hy) with hx = |sx|, hy = |sy| the chain's half
+//     extents.  The pair's .z and .w are read and then written as zeros; a rank on no tile list keeps the +0 the launch stored.
+enum class GeoSums { kMoments, kDepth, kAbs };
+
+template <GeoSums kKind>
+__device__ __forceinline__ void geometry_sums(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m,
+                                              const uint32_t *__restrict__ order = nullptr, float hx = 0.0f, float hy = 0.0f,
+                                              float *__restrict__ grad_means2d_abs = nullptr) {
     const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (r >= m) return;
     const uint32_t b = prefix[r], e = prefix[r + 1];
     if (b == e) return;
-    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f;
+    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, a6 = 0.0f, ax = 0.0f, ay = 0.0f;
     for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
         const float4 v = geo_slots[2 * (size_t)i], v5 = geo_slots[2 * (size_t)i + 1];
         a1 += v.x; a2 += v.y; a3 += v.z; a4 += v.w; a5 += v5.x;
+        if constexpr (kKind == GeoSums::kDepth) a6 += v5.y;
+        if constexpr (kKind == GeoSums::kAbs) { ax += v5.z; ay += v5.w; }
     }
     const float v = wave_sum4(a1, a2, a3, a4, lane);
     const float S5 = wave_sum1(a5);
+    float Sz = 0.0f, Txy = 0.0f, Ty = 0.0f;
+    if constexpr (kKind == GeoSums::kDepth) Sz = wave_sum1(a6);
     const float S2 = __shfl(v, 16), S3 = __shfl(v, 32), S4 = __shfl(v, 48);
+    if constexpr (kKind == GeoSums::kAbs) {
+        Txy = wave_sum2(ax, ay, lane);
+        Ty = __shfl(Txy, 32);
+    }
     if (lane == 0) {
         geo_slots[2 * (size_t)b] = make_float4(v, S2, S3, S4);
-        geo_slots[2 * (size_t)b + 1] = make_float4(S5, 0.0f, 0.0f, 0.0f);
+        geo_slots[2 * (size_t)b + 1] = make_float4(S5, Sz, 0.0f, 0.0f);
+        if constexpr (kKind == GeoSums::kAbs) {
+            const int64_t row = order[r];
+            grad_means2d_abs[2 * row] = (0.5f * Txy) * hx;
+            grad_means2d_abs[2 * row + 1] = (0.5f * Ty) * hy;
+        }
     }
 }
 
-// One thread per depth rank: the chain on the sums backward_geometry_sum_kernel left, the Gaussian's three rows written.
-// gsx_render_backward_screen (grad_means2d not null) also gets the chain's dL/d(NDC mean) and (screen_radius, or null) the
-// radius project_raw_kernel left in the record's last word; the launch has zeroed both for the rows this kernel skips.
+__global__ void __launch_bounds__(256)
+    backward_geometry_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m) {
+    geometry_sums<GeoSums::kMoments>(geo_slots, prefix, m);
+}
+
+__global__ void __launch_bounds__(256)
+    backward_depth_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m) {
+    geometry_sums<GeoSums::kDepth>(geo_slots, prefix, m);
+}
+
+__global__ void __launch_bounds__(256)
+    backward_geometry_abs_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                     const uint32_t *__restrict__ order, uint32_t m, float hx, float hy,
+                                     float *__restrict__ grad_means2d_abs) {
+    geometry_sums<GeoSums::kAbs>(geo_slots, prefix, m, order, hx, hy, grad_means2d_abs);
+}
+
+// The chain, for one depth rank r on a tile list, its first slot pair at b: the sums the geometry sums left there carried
+// through geometry_chain, and the Gaussian's three rows (order[r]) written.  gsx_render_backward_screen (rows.grad_means2d not
+// null) also gets the chain's dL/d(NDC mean) and the radius; the launch has zeroed both for the rows no kernel reaches.
+//   kGeometry, kCamera (gc: the 24 camera terms, else not touched), kDepth: GSX_SEM_REF_CPU.  The conic comes from the raw
+//     record, and rows.screen_radius (or null) gets the radius project_raw_kernel left in the record's last word.
+//   kDepth (gsx_render_backward_depth): Sz world2view[k][2] added to dL/dpoint_k -- z = p . world2view[:3][2] + world2view[3][2]
+//     -- as a separate addend and only where it is not zero: with dL/ddepth = 0 every row holds the screen entry's bits, a -0
+//     included.
+//   kStd, kStdAa (gsx_render_backward_std): the chain's kStd variant.  The packed record has no raw conic and no radius: the
+//     chain forms both (no record is read), and rows.screen_radius is there whenever rows.grad_means2d is.  kStdAa
+//     (GSX_FLAG_ANTIALIASED) is the chain's kAa variant; U = sum u is where backward_std_aa_sum_kernel left it, beside S5.
+enum class Chain { kGeometry, kCamera, kDepth, kStd, kStdAa };
+
+template <Chain kKind>
+__device__ __forceinline__ void chain_rank(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ order,
+                                           const Record *__restrict__ raw, const GeoCamera &cam, const GeometryRows &rows,
+                                           uint32_t r, uint32_t b, float *__restrict__ gc) {
+    constexpr bool kStd = kKind == Chain::kStd || kKind == Chain::kStdAa;
+    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
+    const int64_t row = order[r];
+    float4 QA = make_float4(0.0f, 0.0f, 0.0f, 0.0f), QB = QA;
+    float rad = 0.0f;
+    if constexpr (!kStd) {
+        const Record rec = raw[row];
+        QA = rec.a;
+        QB = rec.b;
+        rad = rec.c.w;
+    }
+    float gp[3], gs[3], gq[4], gn[2];
+    geometry_chain<kKind == Chain::kCamera, kStd, kKind == Chain::kStdAa>(
+        cam, rows.means3d + 3 * row, rows.scales + 3 * row, rows.quats + 4 * row, QA, QB, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq, gn,
+        gc, &rad, kKind == Chain::kStdAa ? S5.y : 0.0f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if constexpr (kKind == Chain::kDepth) {
+            const float gz = S5.y * cam.V[k * 4 + 2];       // dL/dz dz/dp_k
+            rows.grad_means3d[3 * row + k] = gz != 0.0f ? gp[k] + gz : gp[k];
+        } else {
+            rows.grad_means3d[3 * row + k] = gp[k];
+        }
+        rows.grad_scales[3 * row + k] = gs[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rows.grad_quats[4 * row + k] = gq[k];
+    if (rows.grad_means2d) {
+        rows.grad_means2d[2 * row] = gn[0];
+        rows.grad_means2d[2 * row + 1] = gn[1];
+        if (kStd || rows.screen_radius) rows.screen_radius[row] = rad;
+    }
+}
+
+// One thread per depth rank; a rank past m or on no tile list is left alone: its rows keep their zeros.
+template <Chain kKind>
+__device__ __forceinline__ void chain_ranks(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                            const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m,
+                                            const GeoCamera &cam, const GeometryRows &rows) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t b = prefix[r];
+    if (b == prefix[r + 1]) return;
+    chain_rank<kKind>(geo_slots, order, raw, cam, rows, r, b, nullptr);
+}
+
 __global__ void __launch_bounds__(256)
     backward_geometry_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
                                    const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m, GeoCamera cam,
@@ -666,151 +752,8 @@ __global__ void __launch_bounds__(256)
                                    const float *__restrict__ quats, float *__restrict__ grad_means3d,
                                    float *__restrict__ grad_scales, float *__restrict__ grad_quats,
                                    float *__restrict__ grad_means2d, float *__restrict__ screen_radius) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= m) return;
-    const uint32_t b = prefix[r];
-    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
-    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
-    const int64_t row = order[r];
-    const Record rec = raw[row];
-    float gp[3], gs[3], gq[4], gn[2];
-    geometry_chain<false>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq,
-                          gn, nullptr);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        grad_means3d[3 * row + k] = gp[k];
-        grad_scales[3 * row + k] = gs[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
-    if (grad_means2d) {
-        grad_means2d[2 * row] = gn[0];
-        grad_means2d[2 * row + 1] = gn[1];
-        if (screen_radius) screen_radius[row] = rec.c.w;
-    }
-}
-
-// gsx_render_backward_std: backward_geometry_chain_kernel with the chain's kStd variant.  The packed record has no raw
-// conic and no radius: the chain forms both (QA, QB are not read).
-__global__ void __launch_bounds__(256)
-    backward_std_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
-                              const uint32_t *__restrict__ order, uint32_t m, GeoCamera cam, const float *__restrict__ means3d,
-                              const float *__restrict__ scales, const float *__restrict__ quats, float *__restrict__ grad_means3d,
-                              float *__restrict__ grad_scales, float *__restrict__ grad_quats, float *__restrict__ grad_means2d,
-                              float *__restrict__ screen_radius) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= m) return;
-    const uint32_t b = prefix[r];
-    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
-    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
-    const int64_t row = order[r];
-    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float gp[3], gs[3], gq[4], gn[2], rad;
-    geometry_chain<false, true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, none, none, S.x, S.y, S.z, S.w, S5.x, gp,
-                                gs, gq, gn, nullptr, &rad);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        grad_means3d[3 * row + k] = gp[k];
-        grad_scales[3 * row + k] = gs[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
-    if (grad_means2d) {
-        grad_means2d[2 * row] = gn[0];
-        grad_means2d[2 * row + 1] = gn[1];
-        screen_radius[row] = rad;
-    }
-}
-
-// GSX_FLAG_ANTIALIASED: backward_std_chain_kernel with the chain's kAa variant; U = sum u is where
-// backward_std_aa_sum_kernel left it, beside S5.
-__global__ void __launch_bounds__(256)
-    backward_std_aa_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
-                                 const uint32_t *__restrict__ order, uint32_t m, GeoCamera cam, const float *__restrict__ means3d,
-                                 const float *__restrict__ scales, const float *__restrict__ quats, float *__restrict__ grad_means3d,
-                                 float *__restrict__ grad_scales, float *__restrict__ grad_quats, float *__restrict__ grad_means2d,
-                                 float *__restrict__ screen_radius) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= m) return;
-    const uint32_t b = prefix[r];
-    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
-    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
-    const int64_t row = order[r];
-    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float gp[3], gs[3], gq[4], gn[2], rad;
-    geometry_chain<false, true, true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, none, none, S.x, S.y, S.z, S.w, S5.x,
-                                      gp, gs, gq, gn, nullptr, &rad, S5.y);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        grad_means3d[3 * row + k] = gp[k];
-        grad_scales[3 * row + k] = gs[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
-    if (grad_means2d) {
-        grad_means2d[2 * row] = gn[0];
-        grad_means2d[2 * row + 1] = gn[1];
-        screen_radius[row] = rad;
-    }
-}
-
-// ---- gsx_render_backward_screen_abs: backward_geometry_sum_kernel with the two absolute sums backward_tile_abs_kernel left
-// in the .z and .w of its pairs' second geometry float4 -- the five moments in the same operations and the same order, so
-// the chain after it gives the screen entry's bits; Tx and Ty lane-strided over [prefix[r], prefix[r + 1]) in rising order
-// like them, then wave_sum2's fixed exchange and butterfly: no atomics -- and a store per Gaussian,
-//     grad_means2d_abs[row] = ((0.5f * Tx) * hx, (0.5f * Ty) * hy),   hx = |sx|, hy = |sy|
-// the chain's half extents.  One pass over the slots and one launch for both; a rank on no tile list keeps the +0 the
-// launch stored.
-__global__ void __launch_bounds__(256)
-    backward_geometry_abs_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
-                                     const uint32_t *__restrict__ order, uint32_t m, float hx, float hy,
-                                     float *__restrict__ grad_means2d_abs) {
-    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (r >= m) return;
-    const uint32_t b = prefix[r], e = prefix[r + 1];
-    if (b == e) return;
-    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, ax = 0.0f, ay = 0.0f;
-    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
-        const float4 v = geo_slots[2 * (size_t)i], v5 = geo_slots[2 * (size_t)i + 1];
-        a1 += v.x; a2 += v.y; a3 += v.z; a4 += v.w; a5 += v5.x; ax += v5.z; ay += v5.w;
-    }
-    const float v = wave_sum4(a1, a2, a3, a4, lane);
-    const float S5 = wave_sum1(a5);
-    const float S2 = __shfl(v, 16), S3 = __shfl(v, 32), S4 = __shfl(v, 48);
-    const float Txy = wave_sum2(ax, ay, lane);
-    const float Ty = __shfl(Txy, 32);
-    if (lane == 0) {
-        geo_slots[2 * (size_t)b] = make_float4(v, S2, S3, S4);
-        geo_slots[2 * (size_t)b + 1] = make_float4(S5, 0.0f, 0.0f, 0.0f);
-        const int64_t row = order[r];
-        grad_means2d_abs[2 * row] = (0.5f * Txy) * hx;
-        grad_means2d_abs[2 * row + 1] = (0.5f * Ty) * hy;
-    }
-}
-
-// ---- gsx_render_backward_depth: backward_geometry_sum_kernel with the sixth sum -- the five in the same operations and the
-// same order, Sz like S5 -- and backward_geometry_chain_kernel with Sz world2view[k][2] added to dL/dpoint_k, as a
-// separate addend and only where it is not zero: with dL/ddepth = 0 every row holds the screen entry's bits, a -0 included.
-__global__ void __launch_bounds__(256)
-    backward_depth_sum_kernel(float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix, uint32_t m) {
-    const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (r >= m) return;
-    const uint32_t b = prefix[r], e = prefix[r + 1];
-    if (b == e) return;
-    float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, a6 = 0.0f;
-    for (uint32_t i = b + (uint32_t)lane; i < e; i += 64u) {
-        const float4 v = geo_slots[2 * (size_t)i], v5 = geo_slots[2 * (size_t)i + 1];
-        a1 += v.x; a2 += v.y; a3 += v.z; a4 += v.w; a5 += v5.x; a6 += v5.y;
-    }
-    const float v = wave_sum4(a1, a2, a3, a4, lane);
-    const float S5 = wave_sum1(a5), Sz = wave_sum1(a6);
-    const float S2 = __shfl(v, 16), S3 = __shfl(v, 32), S4 = __shfl(v, 48);
-    if (lane == 0) {
-        geo_slots[2 * (size_t)b] = make_float4(v, S2, S3, S4);
-        geo_slots[2 * (size_t)b + 1] = make_float4(S5, Sz, 0.0f, 0.0f);
-    }
+    chain_ranks<Chain::kGeometry>(geo_slots, prefix, order, raw, m, cam,
+                                  {means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius});
 }
 
 __global__ void __launch_bounds__(256)
@@ -820,29 +763,28 @@ __global__ void __launch_bounds__(256)
                                 const float *__restrict__ quats, float *__restrict__ grad_means3d,
                                 float *__restrict__ grad_scales, float *__restrict__ grad_quats,
                                 float *__restrict__ grad_means2d, float *__restrict__ screen_radius) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= m) return;
-    const uint32_t b = prefix[r];
-    if (b == prefix[r + 1]) return;         // on no tile list: its rows keep their zeros
-    const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
-    const int64_t row = order[r];
-    const Record rec = raw[row];
-    float gp[3], gs[3], gq[4], gn[2];
-    geometry_chain<false>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs, gq,
-                          gn, nullptr);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float gz = S5.y * cam.V[k * 4 + 2];       // dL/dz dz/dp_k
-        grad_means3d[3 * row + k] = gz != 0.0f ? gp[k] + gz : gp[k];
-        grad_scales[3 * row + k] = gs[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
-    if (grad_means2d) {
-        grad_means2d[2 * row] = gn[0];
-        grad_means2d[2 * row + 1] = gn[1];
-        if (screen_radius) screen_radius[row] = rec.c.w;
-    }
+    chain_ranks<Chain::kDepth>(geo_slots, prefix, order, raw, m, cam,
+                               {means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius});
+}
+
+__global__ void __launch_bounds__(256)
+    backward_std_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                              const uint32_t *__restrict__ order, uint32_t m, GeoCamera cam, const float *__restrict__ means3d,
+                              const float *__restrict__ scales, const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                              float *__restrict__ grad_scales, float *__restrict__ grad_quats, float *__restrict__ grad_means2d,
+                              float *__restrict__ screen_radius) {
+    chain_ranks<Chain::kStd>(geo_slots, prefix, order, nullptr, m, cam,
+                             {means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius});
+}
+
+__global__ void __launch_bounds__(256)
+    backward_std_aa_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
+                                 const uint32_t *__restrict__ order, uint32_t m, GeoCamera cam, const float *__restrict__ means3d,
+                                 const float *__restrict__ scales, const float *__restrict__ quats, float *__restrict__ grad_means3d,
+                                 float *__restrict__ grad_scales, float *__restrict__ grad_quats, float *__restrict__ grad_means2d,
+                                 float *__restrict__ screen_radius) {
+    chain_ranks<Chain::kStdAa>(geo_slots, prefix, order, nullptr, m, cam,
+                               {means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius});
 }
 
 // ---- gsx_render_backward_camera: dL/dworld2view and dL/dfull_proj, the 24 entries that are not exact zeros.
@@ -853,8 +795,8 @@ __global__ void __launch_bounds__(256)
 // order, and the stripes in stripe order.
 constexpr int kCamTerms = 24, kCamStripes = 8;
 
-// backward_geometry_chain_kernel with the camera terms: the same rows written with the same values, and no early
-// return -- every thread of the block takes part in the reduction, a rank past m or on no tile list with 24 zeros.
+// The chain with the camera terms: the geometry kernel's rows written with the same values, and no early return -- every
+// thread of the block takes part in the reduction, a rank past m or on no tile list with 24 zeros.
 __global__ void __launch_bounds__(256)
     backward_camera_chain_kernel(const float4 *__restrict__ geo_slots, const uint32_t *__restrict__ prefix,
                                  const uint32_t *__restrict__ order, const Record *__restrict__ raw, uint32_t m, GeoCamera cam,
@@ -874,26 +816,10 @@ __global__ void __launch_bounds__(256)
         b = prefix[r];
         e = prefix[r + 1];
     }
-    if (b != e) {
-        const float4 S = geo_slots[2 * (size_t)b], S5 = geo_slots[2 * (size_t)b + 1];
-        const int64_t row = order[r];
-        const Record rec = raw[row];
-        float gp[3], gs[3], gq[4], gn[2];
-        geometry_chain<true>(cam, means3d + 3 * row, scales + 3 * row, quats + 4 * row, rec.a, rec.b, S.x, S.y, S.z, S.w, S5.x, gp, gs,
-                             gq, gn, gc);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            grad_means3d[3 * row + k] = gp[k];
-            grad_scales[3 * row + k] = gs[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) grad_quats[4 * row + k] = gq[k];
-        if (grad_means2d) {
-            grad_means2d[2 * row] = gn[0];
-            grad_means2d[2 * row + 1] = gn[1];
-            if (screen_radius) screen_radius[row] = rec.c.w;
-        }
-    }
+    if (b != e)
+        chain_rank<Chain::kCamera>(geo_slots, order, raw, cam,
+                                   {means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius}, r, b,
+                                   gc);
 #pragma unroll
     for (int g = 0; g < kCamTerms / 4; ++g) {
         const float v = wave_sum4(gc[4 * g], gc[4 * g + 1], gc[4 * g + 2], gc[4 * g + 3], lane);
@@ -985,11 +911,18 @@ hipError_t launch_depth_tiles(const Record *raw, const uint32_t *vals, const uin
     return hipGetLastError();
 }
 
-hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *raw,
-                                uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s) {
-    if (m == 0) return hipSuccess;
-    backward_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(slots, prefix, order, raw, m, grad_colors,
-                                                                          grad_opacity_logit);
+// Grids of 256 threads over m depth ranks: one wave per rank (the sums), one thread per rank (the chain).
+static unsigned wave_blocks(uint32_t m) { return (unsigned)(((uint64_t)m + 3) / 4); }
+static unsigned thread_blocks(uint32_t m) { return (unsigned)(((uint64_t)m + 255) / 256); }
+// The eight rows as the chain kernels take them, one argument each
+#define GSX_ROWS(rows) \
+    (rows).means3d, (rows).scales, (rows).quats, (rows).grad_means3d, (rows).grad_scales, (rows).grad_quats, (rows).grad_means2d, \
+        (rows).screen_radius
+
+hipError_t launch_backward_sums(const RankSlots &rk, const Record *raw, float *grad_colors, float *grad_opacity_logit,
+                                hipStream_t s) {
+    if (rk.m == 0) return hipSuccess;
+    backward_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.slots, rk.prefix, rk.order, raw, rk.m, grad_colors, grad_opacity_logit);
     return hipGetLastError();
 }
 
@@ -1008,92 +941,71 @@ static GeoCamera geo_camera(const GsxCamera &camera) {
     return cam;
 }
 
-hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                    const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
-                                    const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
-                                    const CameraGrads *cg, float *grad_means2d_abs) {
-    if (m == 0) return hipSuccess;
-    const GeoCamera cam = geo_camera(camera);
-    if (grad_means2d_abs)
-        backward_geometry_abs_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(
-            geo_slots, prefix, order, m, fabsf(cam.sx), fabsf(cam.sy), grad_means2d_abs);
-    else
-        backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
-    const unsigned blocks = (unsigned)(((uint64_t)m + 255) / 256);
-    if (cg) {
-        backward_camera_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,
-                                                            grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius,
-                                                            cg->partials);
-        camera_reduce_kernel<<<1, kCamStripes * 32, 0, s>>>(cg->partials, blocks, cg->world2view, cg->full_proj);
-        return hipGetLastError();
-    }
-    backward_geometry_chain_kernel<<<blocks, 256, 0, s>>>(geo_slots, prefix, order, raw, m, cam, means3d, scales, quats,
-                                                          grad_means3d, grad_scales, grad_quats, grad_means2d, screen_radius);
-    return hipGetLastError();
-}
-
-hipError_t launch_backward_sums_std(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *rec,
-                                    uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s) {
-    if (m == 0) return hipSuccess;
-    backward_std_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(slots, prefix, order, rec, m, grad_colors,
-                                                                              grad_opacity_logit);
-    return hipGetLastError();
-}
-
-hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                        const uint32_t *order, uint32_t m, const float *means3d, const float *scales,
-                                        const float *quats, float *grad_means3d, float *grad_scales, float *grad_quats,
-                                        float *grad_means2d, float *screen_radius, hipStream_t s) {
-    if (m == 0) return hipSuccess;
+// GSX_SEM_STD_3DGS: project_std's focal lengths and d pixel / d ndc
+static GeoCamera geo_camera_std(const GsxCamera &camera) {
     GeoCamera cam = geo_camera(camera);
-    // project_std's focal lengths and d pixel / d ndc
     cam.fx = (float)camera.width / (2.0f * camera.tan_fovx);
     cam.fy = (float)camera.height / (2.0f * camera.tan_fovy);
     cam.sx = (float)camera.width * 0.5f;
     cam.sy = (float)camera.height * 0.5f;
-    backward_geometry_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
-    backward_std_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
-        geo_slots, prefix, order, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
-        screen_radius);
-    return hipGetLastError();
+    return cam;
 }
 
-hipError_t launch_backward_std_antialiased(const GsxCamera &camera, const float4 *slots, float4 *geo_slots,
-                                           const uint32_t *prefix, const uint32_t *order, uint32_t m, const float *means3d,
-                                           const float *scales, const float *quats, const float *opacity_logit,
-                                           float *grad_colors, float *grad_opacity_logit, float *grad_means3d,
-                                           float *grad_scales, float *grad_quats, float *grad_means2d, float *screen_radius,
-                                           hipStream_t s) {
-    if (m == 0) return hipSuccess;
-    const unsigned waves = (unsigned)(((uint64_t)m + 3) / 4);
-    // the geometry sums first: they rewrite each Gaussian's first slot pair, whose free word then takes U from the colour sums
-    if (geo_slots) backward_geometry_sum_kernel<<<waves, 256, 0, s>>>(geo_slots, prefix, m);
-    backward_std_aa_sum_kernel<<<waves, 256, 0, s>>>(slots, prefix, order, opacity_logit, m, grad_colors, grad_opacity_logit,
-                                                     geo_slots);
-    if (geo_slots) {
-        GeoCamera cam = geo_camera(camera);
-        cam.fx = (float)camera.width / (2.0f * camera.tan_fovx);        // (launch_backward_geometry_std)
-        cam.fy = (float)camera.height / (2.0f * camera.tan_fovy);
-        cam.sx = (float)camera.width * 0.5f;
-        cam.sy = (float)camera.height * 0.5f;
-        backward_std_aa_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
-            geo_slots, prefix, order, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
-            screen_radius);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_backward_geometry_depth(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                          const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
-                                          const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                          float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s) {
-    if (m == 0) return hipSuccess;
+hipError_t launch_backward_geometry(const GsxCamera &camera, const RankSlots &rk, const Record *raw, const GeometryRows &rows,
+                                    hipStream_t s, const CameraGrads *cg, float *grad_means2d_abs) {
+    if (rk.m == 0) return hipSuccess;
     const GeoCamera cam = geo_camera(camera);
-    backward_depth_sum_kernel<<<(unsigned)(((uint64_t)m + 3) / 4), 256, 0, s>>>(geo_slots, prefix, m);
-    backward_depth_chain_kernel<<<(unsigned)(((uint64_t)m + 255) / 256), 256, 0, s>>>(
-        geo_slots, prefix, order, raw, m, cam, means3d, scales, quats, grad_means3d, grad_scales, grad_quats, grad_means2d,
-        screen_radius);
+    if (grad_means2d_abs)
+        backward_geometry_abs_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.order, rk.m, fabsf(cam.sx),
+                                                                           fabsf(cam.sy), grad_means2d_abs);
+    else
+        backward_geometry_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.m);
+    const unsigned blocks = thread_blocks(rk.m);
+    if (cg) {
+        backward_camera_chain_kernel<<<blocks, 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.order, raw, rk.m, cam, GSX_ROWS(rows),
+                                                            cg->partials);
+        camera_reduce_kernel<<<1, kCamStripes * 32, 0, s>>>(cg->partials, blocks, cg->world2view, cg->full_proj);
+        return hipGetLastError();
+    }
+    backward_geometry_chain_kernel<<<blocks, 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.order, raw, rk.m, cam, GSX_ROWS(rows));
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_geometry_depth(const GsxCamera &camera, const RankSlots &rk, const Record *raw,
+                                          const GeometryRows &rows, hipStream_t s) {
+    if (rk.m == 0) return hipSuccess;
+    backward_depth_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.m);
+    backward_depth_chain_kernel<<<thread_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.order, raw, rk.m, geo_camera(camera),
+                                                                    GSX_ROWS(rows));
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_sums_std(const RankSlots &rk, const Record *rec, float *grad_colors, float *grad_opacity_logit,
+                                    hipStream_t s) {
+    if (rk.m == 0) return hipSuccess;
+    backward_std_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.slots, rk.prefix, rk.order, rec, rk.m, grad_colors, grad_opacity_logit);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_geometry_std(const GsxCamera &camera, const RankSlots &rk, const GeometryRows &rows, hipStream_t s) {
+    if (rk.m == 0) return hipSuccess;
+    backward_geometry_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.m);
+    backward_std_chain_kernel<<<thread_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.order, rk.m, geo_camera_std(camera),
+                                                                  GSX_ROWS(rows));
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_std_antialiased(const GsxCamera &camera, const RankSlots &rk, const GeometryRows &rows,
+                                           const float *opacity_logit, float *grad_colors, float *grad_opacity_logit,
+                                           hipStream_t s) {
+    if (rk.m == 0) return hipSuccess;
+    // the geometry sums first: they rewrite each Gaussian's first slot pair, whose free word then takes U from the colour sums
+    if (rk.geo_slots) backward_geometry_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.m);
+    backward_std_aa_sum_kernel<<<wave_blocks(rk.m), 256, 0, s>>>(rk.slots, rk.prefix, rk.order, opacity_logit, rk.m, grad_colors,
+                                                                 grad_opacity_logit, rk.geo_slots);
+    if (rk.geo_slots)
+        backward_std_aa_chain_kernel<<<thread_blocks(rk.m), 256, 0, s>>>(rk.geo_slots, rk.prefix, rk.order, rk.m,
+                                                                         geo_camera_std(camera), GSX_ROWS(rows));
     return hipGetLastError();
 }
 

@@ -606,54 +606,61 @@ hipError_t launch_backward_tiles_depth(const BackwardTiles &bt, const DepthTiles
 // record) and writes (D, A) of every pixel of its tile.  raw, vals, ranges as in BackwardTiles.
 hipError_t launch_depth_tiles(const Record *raw, const uint32_t *vals, const uint2 *ranges, const float *zrow,
                               const TileGrid &grid, const OutDesc &out, float *depth, hipStream_t s);
-// slots of each rank summed in emission order, the sigmoid chain applied, scattered to rows (order[r])
-hipError_t launch_backward_sums(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *raw,
-                                uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
-// gsx_render_backward_geometry: geometry slots of each rank summed in emission order (one wave per rank; the sums are
-// left in the rank's first slot), then one thread per rank runs the chain from dL/dQ and dL/dmean to the inputs
-// (gsx_backward.hip: geometry_chain) and scatters to rows (order[r]).  gsx_render_backward_screen: grad_means2d (n,2) gets
-// the chain's dL/d(NDC mean) and screen_radius (n, or null) the record's radius; null for gsx_render_backward_geometry
-// gsx_render_backward_camera (cg not null): the chain kernel's camera instance also leaves each block's 24 terms of
-// dL/dworld2view and dL/dfull_proj in a row of cg->partials (kCameraPartialBytes per 256 ranks, gsx_plan.h), and one
-// small kernel adds the rows in a fixed order into the two 4x4 outputs.
-// gsx_render_backward_screen_abs (grad_means2d_abs not null, cg null; after launch_backward_tiles_abs): the sum kernel's abs
-// instance adds Tx and Ty beside the five moments, in emission order and a fixed butterfly, and stores
-// (0.5 Tx |sx|, 0.5 Ty |sy|) to the Gaussian's row of grad_means2d_abs (n,2), which the caller has zeroed.
+// ---- The per-Gaussian half, behind the tile kernels: every launch below takes what the walk left per depth rank and, where
+// it runs the chain, the rows it reads and writes.
+struct RankSlots {
+    const float4 *slots;          // BackwardTiles::slots
+    float4 *geo_slots;            // BackwardTiles::geo_slots, or null: the colour-only calls
+    const uint32_t *prefix;       // launch_backward_prefix: rank r's pairs are slots [prefix[r], prefix[r + 1])
+    const uint32_t *order;        // row of rank r
+    uint32_t m;                   // ranks
+};
+struct GeometryRows {
+    const float *means3d, *scales, *quats;                  // (n,3), (n,3), (n,4): stage 1's inputs
+    float *grad_means3d, *grad_scales, *grad_quats;         // the same shapes, zeroed by the caller
+    // gsx_render_backward_screen: (n,2) the chain's dL/d(NDC mean), and (n) the radius -- GSX_SEM_REF_CPU: the raw record's, or
+    // null; GSX_SEM_STD_3DGS: the chain's own, both or neither.  Null: gsx_render_backward_geometry
+    float *grad_means2d, *screen_radius;
+};
 struct CameraGrads {
     float *world2view, *full_proj;   // device, 16 floats each
     float *partials;                 // workspace
 };
-hipError_t launch_backward_geometry(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                    const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
-                                    const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                    float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s,
-                                    const CameraGrads *cg = nullptr, float *grad_means2d_abs = nullptr);
-// gsx_render_backward_depth: the same with the sixth sum Sz beside S5 (backward_depth_sum_kernel, in the same order), and
-// the chain adds Sz world2view[0:3][2] to dL/dpoint: z = p . world2view[:3][2] + world2view[3][2] (no camera terms).
-hipError_t launch_backward_geometry_depth(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                          const uint32_t *order, const Record *raw, uint32_t m, const float *means3d,
-                                          const float *scales, const float *quats, float *grad_means3d, float *grad_scales,
-                                          float *grad_quats, float *grad_means2d, float *screen_radius, hipStream_t s);
-// gsx_render_backward_std (GSX_SEM_STD_3DGS): the tile kernel's two std instances on the PACKED records of the forward's own
-// projection (bt.raw = the frame's records, a = (x, y, Q''00, Qs''), b = (Q''11, opacity, r, g), c.x = b; geo_slots null:
-// the colour-only instance), the colour sums with dL/dlogit = (sum u)(1 - op), and the geometry sums followed by the
-// chain's std variant, which forms conic and radius itself (grad_means2d and screen_radius: both or neither).
+// The colour sums: slots of each rank summed in emission order (one wave per rank), the rule set's way from sum u to
+// dL/dlogit applied -- raw: the sigmoid applied twice; rec, the PACKED records of the forward's own projection
+// (a = (x, y, Q''00, Qs''), b = (Q''11, opacity, r, g), c.x = b): (sum u)(1 - op) --, scattered to rows (order[r]).
+hipError_t launch_backward_sums(const RankSlots &rk, const Record *raw, float *grad_colors, float *grad_opacity_logit,
+                                hipStream_t s);
+hipError_t launch_backward_sums_std(const RankSlots &rk, const Record *rec, float *grad_colors, float *grad_opacity_logit,
+                                    hipStream_t s);
+// The geometry sums and the chain: geometry slots of each rank summed in emission order (one wave per rank; the sums are
+// left in the rank's first slot pair), then one thread per rank runs the chain from dL/dQ and dL/dmean to the inputs
+// (gsx_backward.hip: geometry_chain) and scatters to rows (order[r]).
+// launch_backward_geometry: gsx_render_backward_geometry and _screen, and
+//   gsx_render_backward_camera (cg not null): the chain kernel's camera instance also leaves each block's 24 terms of
+//     dL/dworld2view and dL/dfull_proj in a row of cg->partials (kCameraPartialBytes per 256 ranks, gsx_plan.h), and one
+//     small kernel adds the rows in a fixed order into the two 4x4 outputs;
+//   gsx_render_backward_screen_abs (grad_means2d_abs not null, cg null; after launch_backward_tiles_abs): the sum kernel's abs
+//     instance adds Tx and Ty beside the five moments, in emission order and a fixed butterfly, and stores
+//     (0.5 Tx |sx|, 0.5 Ty |sy|) to the Gaussian's row of grad_means2d_abs (n,2), which the caller has zeroed.
+// launch_backward_geometry_depth (gsx_render_backward_depth): the sixth sum Sz beside S5, in the same order, and the chain
+//   adds Sz world2view[0:3][2] to dL/dpoint: z = p . world2view[:3][2] + world2view[3][2] (no camera terms).
+// launch_backward_geometry_std (gsx_render_backward_std, after launch_backward_sums_std): the chain's std variant, which forms
+//   conic and radius itself.
+hipError_t launch_backward_geometry(const GsxCamera &camera, const RankSlots &rk, const Record *raw, const GeometryRows &rows,
+                                    hipStream_t s, const CameraGrads *cg = nullptr, float *grad_means2d_abs = nullptr);
+hipError_t launch_backward_geometry_depth(const GsxCamera &camera, const RankSlots &rk, const Record *raw,
+                                          const GeometryRows &rows, hipStream_t s);
+hipError_t launch_backward_geometry_std(const GsxCamera &camera, const RankSlots &rk, const GeometryRows &rows, hipStream_t s);
+// gsx_render_backward_std's tile kernels, two std instances on the packed records (bt.raw = the frame's records; geo_slots
+// null: the colour-only instance)
 hipError_t launch_backward_tiles_std(const BackwardTiles &bt, const TileGrid &grid, const OutDesc &out, hipStream_t s);
-hipError_t launch_backward_sums_std(const float4 *slots, const uint32_t *prefix, const uint32_t *order, const Record *rec,
-                                    uint32_t m, float *grad_colors, float *grad_opacity_logit, hipStream_t s);
-hipError_t launch_backward_geometry_std(const GsxCamera &camera, float4 *geo_slots, const uint32_t *prefix,
-                                        const uint32_t *order, uint32_t m, const float *means3d, const float *scales,
-                                        const float *quats, float *grad_means3d, float *grad_scales, float *grad_quats,
-                                        float *grad_means2d, float *screen_radius, hipStream_t s);
-// GSX_FLAG_ANTIALIASED: what the two launches above do on records that hold sigmoid(logit) * rho (std_aa_factor) -- the
+// GSX_FLAG_ANTIALIASED: what the two std launches do on records that hold sigmoid(logit) * rho (std_aa_factor) -- the
 // geometry sums, then the colour sums with dL/dlogit = (sum u)(1 - sigmoid(logit)) from the opacity input, which also hand
-// sum u to the chain's anti-aliased variant through a free word of the Gaussian's first geometry slot pair.  geo_slots
-// null: the colour-only call (the five geometry outputs are not touched).
-hipError_t launch_backward_std_antialiased(const GsxCamera &camera, const float4 *slots, float4 *geo_slots,
-                                           const uint32_t *prefix, const uint32_t *order, uint32_t m, const float *means3d,
-                                           const float *scales, const float *quats, const float *opacity_logit,
-                                           float *grad_colors, float *grad_opacity_logit, float *grad_means3d,
-                                           float *grad_scales, float *grad_quats, float *grad_means2d, float *screen_radius,
+// sum u to the chain's anti-aliased variant through a free word of the Gaussian's first geometry slot pair.  rk.geo_slots
+// null: the colour-only call (rows is not read, the five geometry outputs are not touched).
+hipError_t launch_backward_std_antialiased(const GsxCamera &camera, const RankSlots &rk, const GeometryRows &rows,
+                                           const float *opacity_logit, float *grad_colors, float *grad_opacity_logit,
                                            hipStream_t s);
 
 // ---- gsx_contribution.hip (gsx_render_contribution): the gradient entries' walk with no image and no gradient
