@@ -1,6 +1,8 @@
 // What the kernels of gsx_loss.hip (gsx_photometric_loss) and gsx_loss_weighted.hip (gsx_photometric_loss_weighted) share:
-// the tiling constants, the window taps, the staging of a tile + halo into channel planes in LDS and the fixed-order
-// workgroup sum.  Everything sits in an anonymous namespace: each translation unit compiles its own copy, inlined.
+// the tiling constants, the window taps, the staging of a tile + halo into channel planes in LDS, the fixed-order
+// workgroup sum, the reduce kernels' double tree and what the launchers read off the carve.  The two big passages of the
+// tile kernels are text, not functions: gsx_loss_maps.inc and gsx_loss_grad_filter.inc.
+// Everything sits in an anonymous namespace: each translation unit compiles its own copy, inlined.
 #pragma once
 
 #include "gsx_internal.h"
@@ -74,6 +76,27 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
     return s;
 }
 
+// The reduce kernels' sum (one workgroup of 256 threads): `tiles` records of K floats, the K columns side by side, in
+// double and in a fixed order -- strided over the threads, then a halving tree.  Column k's sum is sa[k][0], for every thread.
+template <int K>
+__device__ __forceinline__ void sum_records(const float *__restrict__ rec, int64_t tiles, double (&sa)[K][256]) {
+    double a[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = 0.0;
+    for (int64_t i = threadIdx.x; i < tiles; i += 256)
+#pragma unroll
+        for (int k = 0; k < K; ++k) a[k] += (double)rec[i * K + k];
+#pragma unroll
+    for (int k = 0; k < K; ++k) sa[k][threadIdx.x] = a[k];
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half)
+#pragma unroll
+            for (int k = 0; k < K; ++k) sa[k][threadIdx.x] += sa[k][threadIdx.x + half];
+        __syncthreads();
+    }
+}
+
 constexpr int kMapsLds = 6 * kPlane + 5 * S * T;    // x, y planes of three channels + five row-filtered planes: 69 216 bytes
 constexpr int kGradLds = 3 * kPlane + 3 * S * T;    // one map's three planes + their row-filtered planes:       37 296 bytes
 static_assert(3 * T * kRowFloats <= 6 * kPlane && 3 * T * kRowFloats <= kGradLds, "the outgoing rows reuse the staging area");
@@ -81,6 +104,34 @@ static_assert(kMapsLds * sizeof(float) <= 80 * 1024, "two workgroups per CU");
 
 inline bool rows_aligned(const void *base, int64_t stride) {
     return (reinterpret_cast<uintptr_t>(base) & 15u) == 0 && (stride & 3) == 0;
+}
+
+// What both launchers read off the images and the plain carve (the weighted carve starts with it) and hand to their
+// kernels as plain arguments.
+struct LossLaunch {
+    float *mu, *mp, *mq;        // the three maps in the workspace; nullptr without a gradient
+    int64_t map_stride;
+    unsigned tiles, tiles_c;    // workgroups of a tile kernel; tiles per tile row
+    bool vx, vy, vg;            // rows_aligned: image, target, grad
+    int run;                    // test library only: which launches run, GSX_LOSS_KERNELS = 1 maps | 2 reduce | 4 gradient
+                                // (tools/bench_loss.py times them one by one)
+};
+
+inline LossLaunch loss_launch(const LossImages &im, char *ws, const plan::LossCarve &c) {
+    LossLaunch l{};
+    if (im.grad) {
+        l.mu = reinterpret_cast<float *>(ws + c.maps[0]);
+        l.mp = reinterpret_cast<float *>(ws + c.maps[1]);
+        l.mq = reinterpret_cast<float *>(ws + c.maps[2]);
+    }
+    l.map_stride = c.map_stride;
+    l.tiles = (unsigned)c.tiles;
+    l.tiles_c = (unsigned)c.tiles_c;
+    l.vx = rows_aligned(im.image, im.image_stride);
+    l.vy = rows_aligned(im.target, im.target_stride);
+    l.vg = rows_aligned(im.grad, im.grad_stride);
+    l.run = knob("GSX_LOSS_KERNELS", 7);
+    return l;
 }
 
 // g[i] = exp(-(i - 5)^2 / (2 1.5^2)) / sum, formed in double, rounded once.

@@ -1,22 +1,19 @@
 // The photometric loss with a per-pixel weight m and a per-view exposure E (gsx_photometric_loss_weighted, include/gsx.h):
 //   x'_i = ((E_i0 x_0 + E_i1 x_1) + E_i2 x_2) + E_i3 inside the region, 0 outside;  W = sum m
 //   loss = (1 - lambda) sum m |x' - y| / (3 W) + lambda (1 - sum m SSIM-map(x', y) / (3 W))
-// value, dL/dimage and dL/dE in one call.  The tiling, the staging and the filter are those of gsx_loss.hip
-// (gsx_loss_device.h); what differs is where the weight and the exposure enter, and that 1 / W is not known while the maps
-// are formed:
-//   wloss_maps_kernel             stages both tiles as gsx_loss.hip does, then turns the staged x into x' in place in LDS (a
-//                                 staged pixel inside the region: three reads, three writes by one thread; the zero padding
-//                                 stays zero, not E_i3); the weight of an output pixel is one 4-byte read into a register.
-//                                 Stores m Dmu, m Dp, m Dq UNSCALED and three sums per workgroup: sum m, sum m ssim-map,
-//                                 sum m |x' - y|
-//   wloss_reduce_kernel           one workgroup: the sums in double; loss_out = (loss, l1, ssim, W) and, for the gradient
-//                                 kernel, (1 - lambda) / (3 W) and -lambda / (3 W) in the workspace (+0 when W == 0): W never
-//                                 reaches the host
-//   wloss_grad_kernel             filters the three maps as gsx_loss.hip does; each thread then forms g' of its own pixels
-//                                 from the scales, m, x' and y, dL/dx = E[:, :3]^T g' (which leaves through LDS as whole
+// value, dL/dimage and dL/dE in one call.  The tiling, the staging, the filter and the maps are gsx_loss.hip's, from the
+// same texts (gsx_loss_device.h, gsx_loss_maps.inc, gsx_loss_grad_filter.inc); what is this file's own is where the weight
+// and the exposure enter, and that 1 / W is not known while the maps are formed:
+//   wloss_maps_kernel             gsx_loss_maps.inc, the instance with weight and exposure.  Stores m Dmu, m Dp, m Dq
+//                                 UNSCALED and three sums per workgroup: sum m, sum m ssim-map, sum m |x' - y|
+//   wloss_reduce_kernel           one workgroup: the sums in double (sum_records); loss_out = (loss, l1, ssim, W) and, for the
+//                                 gradient kernel, (1 - lambda) / (3 W) and -lambda / (3 W) in the workspace (+0 when W == 0):
+//                                 W never reaches the host
+//   wloss_grad_kernel             the three maps filtered (gsx_loss_grad_filter.inc); each thread then forms g' of its own
+//                                 pixels from the scales, m, x' and y, dL/dx = E[:, :3]^T g' (which leaves through LDS as whole
 //                                 interleaved rows), and its share of the twelve sums of dL/dE: down the lanes of a wave,
 //                                 then the waves in turn, twelve partials per workgroup
-//   wloss_exposure_reduce_kernel  one workgroup: the partials in double, in a fixed order
+//   wloss_exposure_reduce_kernel  one workgroup: the partials in double, in sum_records' order
 // No atomics; same inputs, same bits.  Compiled with -ffp-contract=off: x' is rounded product by product as written.
 #include "gsx_loss_device.h"
 
@@ -50,148 +47,16 @@ __global__ void __launch_bounds__(NT)
                       const float *__restrict__ exposure, int32_t R, int32_t C, Taps taps, float *__restrict__ map_mu,
                       float *__restrict__ map_p, float *__restrict__ map_q, int64_t map_stride, float *__restrict__ sums,
                       uint32_t tiles_c, bool vec_x, bool vec_y) {
-    __shared__ __attribute__((aligned(16))) float lds[kMapsLds];
-    float *px = lds, *py = lds + 3 * kPlane, *hp = lds + 6 * kPlane;
-    const uint32_t by = blockIdx.x / tiles_c, bx = blockIdx.x % tiles_c;
-    const int64_t r0 = (int64_t)by * T, c0 = (int64_t)bx * T, cf0 = 3 * c0;
-    stage_tile(image, image_stride, R, C, r0, cf0, px, vec_x);
-    stage_tile(target, target_stride, R, C, r0, cf0, py, vec_y);
-    __syncthreads();
-    if (EXPO) {
-        const Exposure E = load_exposure(exposure);
-        for (int idx = threadIdx.x; idx < kPlane; idx += NT) {
-            const int64_t rr = r0 - H + idx / S, cc = c0 - H + idx % S;
-            if (rr >= 0 && rr < R && cc >= 0 && cc < C) {
-                float xp[3];
-                expose(E, px[idx], px[kPlane + idx], px[2 * kPlane + idx], xp);
-                px[idx] = xp[0];
-                px[kPlane + idx] = xp[1];
-                px[2 * kPlane + idx] = xp[2];
-            }
-        }
-        __syncthreads();
-    }
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    const int tr = threadIdx.x / T, tc = threadIdx.x % T;
-    float mw[PX];
-    float sum_w = 0.0f, sum_m = 0.0f, sum_d = 0.0f;
-#pragma unroll
-    for (int m = 0; m < PX; ++m) {
-        const int64_t row = r0 + tr + (NT / T) * m, col = c0 + tc;
-        mw[m] = 0.0f;
-        if (row < R && col < C) mw[m] = weight ? weight[row * weight_stride + col] : 1.0f;
-        sum_w += mw[m];
-    }
-    float o[3][3][PX];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float *cx = px + ch * kPlane, *cy = py + ch * kPlane;
-        for (int idx = threadIdx.x; idx < S * T; idx += NT) {
-            const int i = idx / T, c = idx % T;
-            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kTaps; ++k) {
-                const float x = cx[i * S + c + k], y = cy[i * S + c + k], g = taps.g[k];
-                a0 = fmaf(g, x, a0);
-                a1 = fmaf(g, y, a1);
-                a2 = fmaf(g, x * x, a2);
-                a3 = fmaf(g, x * y, a3);
-                a4 = fmaf(g, y * y, a4);
-            }
-            hp[0 * S * T + idx] = a0;
-            hp[1 * S * T + idx] = a1;
-            hp[2 * S * T + idx] = a2;
-            hp[3 * S * T + idx] = a3;
-            hp[4 * S * T + idx] = a4;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < PX; ++m) {
-            const int r = tr + (NT / T) * m;
-            float mu1 = 0.0f, mu2 = 0.0f, p = 0.0f, q = 0.0f, rr = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kTaps; ++k) {
-                const float g = taps.g[k];
-                const int at = (r + k) * T + tc;
-                mu1 = fmaf(g, hp[0 * S * T + at], mu1);
-                mu2 = fmaf(g, hp[1 * S * T + at], mu2);
-                p = fmaf(g, hp[2 * S * T + at], p);
-                q = fmaf(g, hp[3 * S * T + at], q);
-                rr = fmaf(g, hp[4 * S * T + at], rr);
-            }
-            const bool inside = r0 + r < R && c0 + tc < C;
-            const float x = cx[(r + H) * S + tc + H], y = cy[(r + H) * S + tc + H];
-            const float mu1sq = mu1 * mu1, mu2sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s1 = p - mu1sq, s2 = rr - mu2sq, s12 = q - mu12;
-            const float A1 = 2.0f * mu12 + C1, A2 = 2.0f * s12 + C2;
-            const float B1 = mu1sq + mu2sq + C1, B2 = s1 + s2 + C2;
-            const float B12 = B1 * B2, A12 = A1 * A2;
-            const float mval = A12 / B12;
-            if (inside) {
-                sum_m += mw[m] * mval;
-                sum_d += mw[m] * fabsf(x - y);
-            }
-            if (GRAD) {
-                const float dmu = 2.0f * mu2 * (A2 - A1) / B12 - 2.0f * mu1 * A12 * (B2 - B1) / (B12 * B12);
-                const float dp = -A12 / (B12 * B2);
-                const float dq = 2.0f * A1 / B12;
-                o[0][ch][m] = inside ? mw[m] * dmu : 0.0f;
-                o[1][ch][m] = inside ? mw[m] * dp : 0.0f;
-                o[2][ch][m] = inside ? mw[m] * dq : 0.0f;
-            }
-        }
-        __syncthreads();     // the next channel overwrites hp
-    }
-    float *red = hp;
-    const float tot_w = block_sum(sum_w, red), tot_m = block_sum(sum_m, red), tot_d = block_sum(sum_d, red);
-    if (threadIdx.x == 0) {
-        float *dst = sums + (size_t)blockIdx.x * kSums;
-        dst[0] = tot_w;
-        dst[1] = tot_m;
-        dst[2] = tot_d;
-    }
-    if (!GRAD) return;
-    // the three maps leave as whole interleaved rows: obuf[map][r][3 c + ch] over the staging area, which nobody reads any more
-    float *obuf = lds;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-            for (int m = 0; m < PX; ++m) obuf[(k * T + tr + (NT / T) * m) * kRowFloats + 3 * tc + ch] = o[k][ch][m];
-    __syncthreads();
-    const int64_t lim = 3 * (int64_t)C;
-    for (int idx = threadIdx.x; idx < 3 * T * kRowQuads; idx += NT) {
-        const int k = idx / (T * kRowQuads), rem = idx % (T * kRowQuads), r = rem / kRowQuads, q = rem % kRowQuads;
-        const int64_t row = r0 + r, f0 = cf0 + 4 * q;
-        if (row >= R || f0 >= lim) continue;
-        float *dst = (k == 0 ? map_mu : (k == 1 ? map_p : map_q)) + row * map_stride + f0;   // 16-byte aligned: map_stride % 4 == 0
-        const float *src = obuf + (k * T + r) * kRowFloats + 4 * q;
-        if (f0 + 4 <= lim) {
-            *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
-        } else {
-            for (int e = 0; f0 + e < lim; ++e) dst[e] = src[e];
-        }
-    }
+#define GSX_LOSS_WEIGHTED 1
+#include "gsx_loss_maps.inc"
+#undef GSX_LOSS_WEIGHTED
 }
 
 __global__ void __launch_bounds__(256)
     wloss_reduce_kernel(const float *__restrict__ sums, int64_t tiles, float lambda, float *__restrict__ loss_out,
                         float *__restrict__ scale) {
     __shared__ double sa[kSums][256];
-    double a[kSums] = {0.0, 0.0, 0.0};
-    for (int64_t i = threadIdx.x; i < tiles; i += 256)
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) a[k] += (double)sums[i * kSums + k];
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) sa[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half)
-#pragma unroll
-            for (int k = 0; k < kSums; ++k) sa[k][threadIdx.x] += sa[k][threadIdx.x + half];
-        __syncthreads();
-    }
+    sum_records<kSums>(sums, tiles, sa);
     if (threadIdx.x == 0) {
         const double W = sa[0][0], lam = (double)lambda;
         float out[4] = {0.0f, 0.0f, 0.0f, 0.0f}, l1_weight = 0.0f, w = 0.0f;
@@ -221,36 +86,7 @@ __global__ void __launch_bounds__(NT)
                       Taps taps, const float *__restrict__ scale, const float *__restrict__ map_mu,
                       const float *__restrict__ map_p, const float *__restrict__ map_q, int64_t map_stride,
                       float *__restrict__ exposure_partials, uint32_t tiles_c, bool vec_g) {
-    __shared__ __attribute__((aligned(16))) float lds[kGradLds];
-    float *planes = lds, *hp = lds + 3 * kPlane;
-    const uint32_t by = blockIdx.x / tiles_c, bx = blockIdx.x % tiles_c;
-    const int64_t r0 = (int64_t)by * T, c0 = (int64_t)bx * T, cf0 = 3 * c0;
-    const int tr = threadIdx.x / T, tc = threadIdx.x % T;
-    float F[3][3][PX];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        stage_tile(k == 0 ? map_mu : (k == 1 ? map_p : map_q), map_stride, R, C, r0, cf0, planes, true);
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < 3 * S * T; idx += NT) {
-            const int ch = idx / (S * T), rem = idx % (S * T), i = rem / T, c = rem % T;
-            float a = 0.0f;
-#pragma unroll
-            for (int t = 0; t < kTaps; ++t) a = fmaf(taps.g[t], planes[ch * kPlane + i * S + c + t], a);
-            hp[idx] = a;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-            for (int m = 0; m < PX; ++m) {
-                const int r = tr + (NT / T) * m;
-                float a = 0.0f;
-#pragma unroll
-                for (int t = 0; t < kTaps; ++t) a = fmaf(taps.g[t], hp[ch * S * T + (r + t) * T + tc], a);
-                F[k][ch][m] = a;
-            }
-        __syncthreads();     // the next map overwrites planes and hp
-    }
+#include "gsx_loss_grad_filter.inc"
     // g' and dL/dx of this thread's own pixels; the rows leave through obuf[r][3 c + ch] over the staging area
     const float l1_weight = scale[0], w = scale[1];
     const bool dead = !(scale[2] > 0.0f);          // W == 0: every gradient is an exact +0
@@ -329,6 +165,8 @@ __global__ void __launch_bounds__(NT)
 __global__ void __launch_bounds__(256)
     wloss_exposure_reduce_kernel(const float *__restrict__ partials, int64_t tiles, float *__restrict__ grad_exposure) {
     __shared__ double sa[kTerms][256];
+    // sum_records<kTerms>, written out: through the function this kernel compiles to other address arithmetic in front of
+    // its loop, and the one timing it can be held to did not place it inside the parent's spread (docs/lab_notes/loss_shared_text.md)
     double a[kTerms];
 #pragma unroll
     for (int k = 0; k < kTerms; ++k) a[k] = 0.0;
@@ -361,22 +199,15 @@ hipError_t launch_loss_weight_sum(int32_t rows, int32_t cols, float *loss_out, h
 hipError_t launch_photometric_loss_weighted(const LossImages &im, const LossWeights &wt, float lambda, float *loss_out, char *ws,
                                             const plan::LossWeightedCarve &c, hipStream_t s) {
     const Taps taps = window_taps();
-    const bool vx = rows_aligned(im.image, im.image_stride), vy = rows_aligned(im.target, im.target_stride);
+    const LossLaunch l = loss_launch(im, ws, c.base);
     float *sums = reinterpret_cast<float *>(ws + c.sums), *scale = reinterpret_cast<float *>(ws + c.scale);
     float *partials = (im.grad && wt.grad_exposure) ? reinterpret_cast<float *>(ws + c.exposure) : nullptr;
-    float *mu = im.grad ? reinterpret_cast<float *>(ws + c.base.maps[0]) : nullptr;
-    float *mp = im.grad ? reinterpret_cast<float *>(ws + c.base.maps[1]) : nullptr;
-    float *mq = im.grad ? reinterpret_cast<float *>(ws + c.base.maps[2]) : nullptr;
-    const unsigned tiles = (unsigned)c.base.tiles, tiles_c = (unsigned)c.base.tiles_c;
-    const int64_t ms = c.base.map_stride;
-    // test library only: which of the launches run (tools/bench_loss.py times them one by one)
-    const int run = knob("GSX_LOSS_KERNELS", 7);
     hipError_t e = hipSuccess;
 #define GSX_WLOSS_MAPS(G, X)                                                                                                   \
-    wloss_maps_kernel<G, X><<<tiles, NT, 0, s>>>(im.image, im.image_stride, im.target, im.target_stride, wt.weight,            \
-                                                 wt.weight_stride, wt.exposure, im.rows, im.cols, taps, mu, mp, mq, ms, sums,   \
-                                                 tiles_c, vx, vy)
-    if (run & 1) {
+    wloss_maps_kernel<G, X><<<l.tiles, NT, 0, s>>>(im.image, im.image_stride, im.target, im.target_stride, wt.weight,          \
+                                                   wt.weight_stride, wt.exposure, im.rows, im.cols, taps, l.mu, l.mp, l.mq,     \
+                                                   l.map_stride, sums, l.tiles_c, l.vx, l.vy)
+    if (l.run & 1) {
         if (im.grad && wt.exposure) GSX_WLOSS_MAPS(true, true);
         else if (im.grad) GSX_WLOSS_MAPS(true, false);
         else if (wt.exposure) GSX_WLOSS_MAPS(false, true);
@@ -384,20 +215,21 @@ hipError_t launch_photometric_loss_weighted(const LossImages &im, const LossWeig
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
 #undef GSX_WLOSS_MAPS
-    if (run & 2) {
+    if (l.run & 2) {
         wloss_reduce_kernel<<<1, 256, 0, s>>>(sums, c.base.tiles, lambda, loss_out, scale);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (im.grad && (run & 4)) {
-        const bool vg = rows_aligned(im.grad, im.grad_stride);
+    if (im.grad && (l.run & 4)) {
         if (wt.exposure)
-            wloss_grad_kernel<true><<<tiles, NT, 0, s>>>(im.image, im.image_stride, im.target, im.target_stride, wt.weight,
-                                                         wt.weight_stride, wt.exposure, im.grad, im.grad_stride, im.rows, im.cols,
-                                                         taps, scale, mu, mp, mq, ms, partials, tiles_c, vg);
+            wloss_grad_kernel<true><<<l.tiles, NT, 0, s>>>(im.image, im.image_stride, im.target, im.target_stride, wt.weight,
+                                                           wt.weight_stride, wt.exposure, im.grad, im.grad_stride, im.rows,
+                                                           im.cols, taps, scale, l.mu, l.mp, l.mq, l.map_stride, partials,
+                                                           l.tiles_c, l.vg);
         else
-            wloss_grad_kernel<false><<<tiles, NT, 0, s>>>(im.image, im.image_stride, im.target, im.target_stride, wt.weight,
-                                                          wt.weight_stride, wt.exposure, im.grad, im.grad_stride, im.rows, im.cols,
-                                                          taps, scale, mu, mp, mq, ms, partials, tiles_c, vg);
+            wloss_grad_kernel<false><<<l.tiles, NT, 0, s>>>(im.image, im.image_stride, im.target, im.target_stride, wt.weight,
+                                                            wt.weight_stride, wt.exposure, im.grad, im.grad_stride, im.rows,
+                                                            im.cols, taps, scale, l.mu, l.mp, l.mq, l.map_stride, partials,
+                                                            l.tiles_c, l.vg);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (partials) {
             wloss_exposure_reduce_kernel<<<1, 256, 0, s>>>(partials, c.base.tiles, wt.grad_exposure);
