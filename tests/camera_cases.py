@@ -36,6 +36,22 @@ ENTRY_CAMERAS = ("aniso_tall", "roll")
 # a principal point off the frame centre, as a real COLMAP camera has one (pixels added to cx, cy)
 OFF_CENTRE = (5.25, -3.5)
 
+# The std_3dgs rule set at these cameras (tests/test_std3dgs_camera_cases_host.py, tests/test_hip_camera_cases.py):
+# name -> (camera, n, seed, make_scene keywords); every case at TILE over STD_BG, built with scene(camera, n, seed, **kw).
+# The first four carry culled rows; the two off-axis ones put centres up to 1.8 frustum half-widths off axis with
+# footprints that reach back into the frame, so the EWA clamp's gradient branch runs with limx != limy and fx != fy
+# (seeds 21 and 22 each give Gaussians clamped in x alone and in y alone that carry gradient: the host test asserts it).
+STD_BG = (0.25, 0.5, 0.75)
+STD_CAMERA_CASES = {
+    "std_aniso_64x48_n120": ("aniso", 120, 11, dict(behind_fraction=0.1)),
+    "std_aniso_tall_48x64_n100": ("aniso_tall", 100, 12, dict(behind_fraction=0.1)),
+    "std_farpose_64x48_n120": ("farpose", 120, 13, dict(behind_fraction=0.1)),
+    "std_roll_64x48_n100": ("roll", 100, 14, dict(behind_fraction=0.1)),
+    "std_offaxis_aniso_tall_48x64_n100": ("aniso_tall", 100, 21, dict(spread=1.8, sigma_scale=3.0)),
+    "std_offaxis_roll_64x48_n100": ("roll", 100, 22, dict(spread=1.8, sigma_scale=3.0)),
+}
+STD_OFFAXIS = tuple(k for k in STD_CAMERA_CASES if "offaxis" in k)
+
 
 def rotation(qvec):
     """R of a COLMAP qvec (camera = R world + t)."""

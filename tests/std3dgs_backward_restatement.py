@@ -216,9 +216,10 @@ def composite(R: rsr.Records, dec: Decisions, grad_frame_hw3, background, n: int
     return Composite(own, gc, (go * (one - op_row)).astype(dt), S, sc, so * (1.0 - op_row.astype(np.float64)), Sabs)
 
 
-def stage1_std(points, scales, quats, cam, dtype=np.float64) -> dict:
+def stage1_std(points, scales, quats, cam, dtype=np.float64, focal=None, limits=None) -> dict:
     """The rule set's stage 1 of every row given (no culling) in `dtype`, with the keys geometry_backward_restatement.chain
-    reads (b = a and n2 = 1: one normalisation; floored nowhere; h_w already holds the + 1e-7)."""
+    reads (b = a and n2 = 1: one normalisation; floored nowhere; h_w already holds the + 1e-7).  focal, limits: (fx, fy) and
+    (limx, limy) to take in place of the camera's own -- a seam for tests that hand the mirror deliberately wrong ones."""
     dt = np.dtype(dtype).type
     p, s, q = (np.asarray(a, np.float64).astype(dt) for a in (points, scales, quats))
     V, F = np.asarray(cam.world2view, np.float64).astype(dt), np.asarray(cam.full_proj, np.float64).astype(dt)
@@ -237,13 +238,13 @@ def stage1_std(points, scales, quats, cam, dtype=np.float64) -> dict:
     t = (ph @ V)[:, :3]
     tz = t[:, 2]
     tan_x, tan_y = dt(f32(cam.tan_fovx)), dt(f32(cam.tan_fovy))
-    limx, limy = dt(f32(1.3)) * tan_x, dt(f32(1.3)) * tan_y
+    limx, limy = (dt(f32(1.3)) * tan_x, dt(f32(1.3)) * tan_y) if limits is None else (dt(limits[0]), dt(limits[1]))
     with np.errstate(all="ignore"):
         rx, ry = t[:, 0] / tz, t[:, 1] / tz
         kx, ky = np.clip(rx, -limx, limx), np.clip(ry, -limy, limy)
         inx, iny = (rx >= -limx) & (rx <= limx), (ry >= -limy) & (ry <= limy)
         cx, cy = kx * tz, ky * tz
-        fx, fy = dt(W) / (dt(2.0) * tan_x), dt(H) / (dt(2.0) * tan_y)
+        fx, fy = (dt(W) / (dt(2.0) * tan_x), dt(H) / (dt(2.0) * tan_y)) if focal is None else (dt(focal[0]), dt(focal[1]))
         J = np.zeros((m, 2, 3), dt)
         J[:, 0, 0] = fx / tz; J[:, 0, 2] = -(fx * cx) / (tz * tz)
         J[:, 1, 1] = fy / tz; J[:, 1, 2] = -(fy * cy) / (tz * tz)

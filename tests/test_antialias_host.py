@@ -148,7 +148,12 @@ def forward_case(name):
 @functools.lru_cache(maxsize=None)
 def backward_case(name):
     """forward_case(name) and: the decisions, the gradient mask, dL/dframe, `ref` (float64) and `mirror` (float32)."""
-    case = dict(forward_case(name))
+    return build_backward(forward_case(name))
+
+
+def build_backward(case):
+    """backward_case's dict of any build_case dict."""
+    case = dict(case)
     fwd, sc = case["fwd"], case["sc"]
     dec = sbr.decide(fwd.R, case["W"], case["H"])
     mask = sbr.gradient_mask(fwd.wk, dec)
@@ -164,7 +169,10 @@ def backward_case(name):
 def test_the_mirrors_covariance_is_the_c_ports(name):
     """The dilated conic formed from the mirror's float32 covariance is the C port's stage-1 conic bit for bit: the mirror
     walks the operation order the port shares with gsx_project.hip."""
-    case = forward_case(name)
+    covariance_is_the_c_ports(forward_case(name))
+
+
+def covariance_is_the_c_ports(case):
     fac, rows = case["fwd"].fac32, case["rows0"]
     seen = ~np.isnan(rows[:, 0])
     assert seen.any()
@@ -181,7 +189,11 @@ def test_the_mirrors_covariance_is_the_c_ports(name):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_no_gaussian_lies_on_the_clamp(name):
-    case = forward_case(name)
+    no_gaussian_lies_on_the_clamp(name, forward_case(name))
+
+
+def no_gaussian_lies_on_the_clamp(name, case):
+    """The check on any build_case dict; returns the nearest ratio to the floor, in units of the floor."""
     sc, rows = case["sc"], case["rows0"]
     seen = np.nonzero(~np.isnan(rows[:, 0]))[0]
     st64 = sbr.stage1_std(sc["points"][seen], sc["scales"][seen], sc["quaternions"][seen], case["cam"], np.float64)
@@ -189,13 +201,14 @@ def test_no_gaussian_lies_on_the_clamp(name):
     r, delta = aar.ratio_bound(st64, fac64)
     band = aar.on_the_clamp_band(fac64, r, delta)
     fac32 = case["fwd"].fac32
+    nearest = float(np.min(np.maximum(fac64.ratio, 1e-300) / float(aar.FLOOR) + (fac64.ratio < float(aar.FLOOR)) * 1e9))
     print("%s: %d rows, %d clamped (float32), %d with float32 det0 <= 0, %d judged by the absolute bound; nearest ratio to "
           "the floor %.3g x" % (name, seen.size, int(fac32.clamped[seen].sum()), int((fac32.det0[seen] <= 0).sum()),
-                                int((r >= 1).sum()), float(np.min(np.maximum(fac64.ratio, 1e-300) / float(aar.FLOOR)
-                                                                  + (fac64.ratio < float(aar.FLOOR)) * 1e9))))
+                                int((r >= 1).sum()), nearest))
     assert not band.any(), (name, seen[band], fac64.ratio[band], r[band])
     # off the band, float32 and float64 take the same decision
     assert np.array_equal(fac32.clamped[seen], fac64.clamped), name
+    return nearest
 
 
 def test_the_new_scenes_hold_what_they_are_for():
@@ -304,7 +317,11 @@ def torch_gradients(case):
 
 @pytest.mark.parametrize("name", BACKWARD_CASES)
 def test_the_restatement_agrees_with_autograd_of_an_independent_forward(name):
-    case = backward_case(name)
+    agrees_with_autograd(name, backward_case(name))
+
+
+def agrees_with_autograd(name, case):
+    """The check on any build_backward dict (tests/test_std3dgs_camera_cases_host.py runs it on its own)."""
     fwd, sc = case["fwd"], case["sc"]
     rows = np.asarray(fwd.R.index, np.int64)
     auto, values, sigma = torch_gradients(case)

@@ -9,7 +9,8 @@ colour and a black background -- the pixel IS op_eff = rho.
 
 Backward: colors, opacity, points, scales, quaternions, means2d per Gaussian within BOUND_AA = 12 E_REF_AA of the float64
 restatement (tests/test_antialias_host.py measures E_REF_AA from the float32 mirror), dL/dframe the seeded random image times
-the gradient mask.
+the gradient mask.  Every case here has fx = fy and the Treehill or identity pose; unequal focal lengths and far poses are in
+tests/test_hip_camera_cases.py (STD_CAMERA_CASES, the four that are not off axis).
 
 Measured on an MI355X.  Frames: worst decided pixel 2.78e-07 (random_64x64_n800_t2; bound 5.39e-06), two ambiguous pixels in
 all the cases together (random_130x70_n1500_t8, 9.8e-08 from an alternative), nothing left out, no pixel beyond 1e-4; every

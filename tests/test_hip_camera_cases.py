@@ -35,6 +35,40 @@ That the file could have seen one, once and not committed: with cam.fx written f
 13 of the 24 tests fail -- every geometry, camera-entry and depth case at aniso, aniso_tall and roll (dL/dpoints off by 1.5e-04
 .. 1.2e-03 of its scale against a bound of 2.61e-07) -- the farpose cases (fx = fy) pass, and all 31 tests of
 tests/test_hip_geometry_backward.py pass as if nothing had happened.
+
+The std_3dgs rule set (second half of the file).  Its route shares no camera term with the one above: geo_camera_std and
+project_std derive fx = width / (2 tan_fovx), fy = height / (2 tan_fovy) themselves, and the kStd / kAa instances of
+geometry_chain add h3 + 1e-7, the c10 = c01 merge and the rho term.  The six cases of camera_cases.STD_CAMERA_CASES (3072
+pixels, at most 612 instances; two with the EWA clamp's gradient branch at limx != limy), the four that are not off axis also
+anti-aliased.  The checks and bounds are the sibling files' own and unchanged -- the frame by rule_set_restatement's classify
+at BOUND = 12 E_REF (tests/test_rule_sets_host.py), the gradients at BOUND = 12 E_REF (tests/test_std3dgs_backward_host.py)
+and BOUND_AA = 12 E_REF_AA (tests/test_antialias_host.py), the contribution at tests/test_hip_contribution.py's TOL, the SH
+link at tests/test_sh_backward_host.py's BOUND -- and tests/test_std3dgs_camera_cases_host.py asserts on the CPU that the
+float32 mirror's own error on these cases stays within the recorded E_REF / E_REF_AA.  The scene object rounds tan_fovx of
+aniso and roll one bit away from cpu_ref.build_camera: those cases are walked on the scene object's own camera.
+
+Measured on an MI355X (23 tests, 4.8 s in all), kernel vs restatement, worst error / scale per case; published rectangles
+give the same figures to the last printed digit:
+  std_3dgs                             frame      colors     opacity    points     scales     quaternions  means2d
+  std_aniso_64x48_n120                 1.47e-07   3.02e-08   5.69e-09   1.69e-09   8.26e-10   9.41e-11     3.83e-09
+  std_aniso_tall_48x64_n100            1.22e-07   2.73e-08   1.29e-08   3.35e-09   2.74e-09   1.24e-10     7.41e-09
+  std_farpose_64x48_n120               1.29e-07   2.95e-08   6.03e-09   2.34e-09   8.80e-10   4.67e-11     4.62e-09
+  std_roll_64x48_n100                  1.30e-07   2.47e-08   5.75e-09   2.91e-09   1.19e-09   5.92e-11     4.82e-09
+  std_offaxis_aniso_tall_48x64_n100    1.15e-07   6.27e-08   1.18e-08   6.57e-10   6.62e-10   4.23e-11     1.27e-08
+  std_offaxis_roll_64x48_n100          2.31e-07   6.34e-08   2.48e-09   9.72e-10   1.47e-09   4.84e-11     5.72e-09
+  BOUND = 12 E_REF                     5.39e-06   7.95e-06   1.91e-07   1.72e-07   7.37e-08   3.40e-09     3.12e-07
+  anti-aliased
+  std_aniso_64x48_n120                 1.29e-07   4.87e-08   1.36e-08   1.01e-09   5.75e-10   2.94e-11     4.98e-09
+  std_aniso_tall_48x64_n100            1.01e-07   3.05e-08   1.09e-08   3.90e-09   7.29e-10   6.25e-11     7.38e-09
+  std_farpose_64x48_n120               1.30e-07   2.72e-08   5.81e-09   1.93e-09   4.80e-10   4.00e-11     4.31e-09
+  std_roll_64x48_n100                  1.45e-07   3.30e-08   9.71e-09   4.49e-09   7.82e-10   2.22e-11     6.82e-09
+  BOUND_AA = 12 E_REF_AA               5.39e-06   4.68e-06   4.74e-07   2.96e-07   4.11e-06   8.23e-09     4.58e-07
+(frame: the worst decided pixel; no frame has an ambiguous pixel, nothing is left out.)  The twelve probes' pixels are the
+mirror's rho bit for bit, the four on the floor 0.005f.  Contribution: |weight_max - restatement| 6.84e-08 (roll), 7.78e-08
+(offaxis_aniso_tall), bound 1e-4; weight_sum the backward's bits.  SH link at the roll camera's centre: sh 3.86e-07 (bound
+8.31e-06), points 1.16e-07 (bound 4.61e-06).  Every figure is at least 14 times inside its bound: no kernel defect was found
+under this rule set at these cameras.  The deliberately wrong scratch builds these tests caught are in
+docs/lab_notes/std_camera_cases.md.
 """
 import numpy as np
 import pytest
@@ -43,12 +77,23 @@ import torch
 from conftest import load_golden
 
 import abs_gradient_restatement as agr
+import antialias_restatement as aar
 import backward_restatement
 import camera_cases as cc
+import contribution_restatement as cr
 import geometry_backward_restatement as gbr
 import screen_gradient_restatement as sgr
+import sh_backward_restatement as shr
+import std3dgs_backward_restatement as sbr
 import test_abs_statistic_host as abs_host
+import test_antialias_host as aa_host
+import test_hip_antialias as hip_aa
+import test_hip_contribution as hip_con
+import test_hip_std3dgs_backward as hip_std
 import test_screen_statistic_host as screen_host
+import test_sh_backward_host as sh_host
+import test_std3dgs_backward_host as std_host
+import test_std3dgs_camera_cases_host as std_cam
 from test_backward_host import REL, TOL
 from test_depth_host import depth_fixture
 from test_hip_abs_statistic import _abs_grads
@@ -59,8 +104,11 @@ from test_hip_depth import _check as _check_depth
 from test_hip_depth import _check_maps, _depth_grads
 from test_hip_geometry_backward import _W, _all_grads, _camera
 from test_hip_geometry_backward import _check as _check_geometry
+from test_hip_parity import _oracle_cam
+from test_hip_rule_sets import _judge, _same_camera
 from test_hip_screen_statistic import FIVE, _screen_grads
-from test_hip_sh_backward import carried_one_link_further
+from test_hip_sh_backward import _sh_for, carried_one_link_further
+from test_rule_sets_host import BOUND as FRAME_BOUND
 
 pytestmark = pytest.mark.gpu
 
@@ -331,3 +379,267 @@ def test_two_runs_at_roll_give_equal_bits_with_and_without_hints(tmp_path):
     _, first, _ = _entry(scene, W)
     _, again, _ = _entry(scene, W)
     assert len(first) == 9 and all(_same(x, y) for x, y in zip(first, again)) and first[-2].abs().max() > 0
+
+
+# ================================================================================================ the std_3dgs rule set
+# The cases of camera_cases.STD_CAMERA_CASES, the sibling files' own checks and bounds (module doc).
+
+STD_NAMES = list(std_cam.CAMERA_CASES)
+AA_NAMES = list(std_cam.CAMERA_CASES_AA)
+_OWN_CAMERA = {}         # (case, antialiased) -> the case again on the scene object's own camera, built once
+
+
+def _std_case(tmp_path, name, antialiased=False):
+    """(case dict, scene).  Where the scene object rounds its camera otherwise than cpu_ref.build_camera (tan_fovx of aniso
+    and roll, in the last bit), the case is the one walked on the arrays the kernels get."""
+    case = (std_cam.backward_case_aa if antialiased else std_cam.backward_case)(name)
+    scene = _scene(tmp_path, case["sc"], colors=case["colors"])
+    gcam = _oracle_cam(scene)
+    if _same_camera(case["cam"], gcam):
+        return case, scene
+    if (name, antialiased) not in _OWN_CAMERA:
+        print("%s: walking the scene object's own camera" % name)
+        args = (case["sc"], case["tile"], case["bg"])
+        if antialiased:
+            own = aa_host.build_backward(aa_host.build_case(*args, cam=gcam, colors=case["colors"]))
+            wk = own["fwd"].wk
+        else:
+            own = std_host.build_backward(std_host.build_tuple(*args, cam=gcam, colors=case["colors"]))
+            wk = own["wk"]
+        assert not wk.left_out and (~own["mask"]).sum() <= std_host.MAX_MASKED_SHARE * own["mask"].size
+        _OWN_CAMERA[(name, antialiased)] = own
+    return _OWN_CAMERA[(name, antialiased)], scene
+
+
+def _line(err, keys):
+    return "  ".join("%s %.3g" % (k, err[k]) for k in keys)
+
+
+# ---- the frame
+@pytest.mark.parametrize("name", STD_NAMES)
+def test_std3dgs_frame_is_decided_or_explained_on_every_route_and_ignores_the_principal_point(tmp_path, name):
+    case, scene = _std_case(tmp_path, name)
+    sc, tile, bg, w, h = case["sc"], case["tile"], case["bg"], case["W"], case["H"]
+    c = scene.images[1].gsx_camera()
+    camera = cc.CAMERAS[cc.STD_CAMERA_CASES[name][0]]
+    assert (c.fx, c.fy, c.width, c.height) == (np.float32(camera["fx"]), np.float32(camera["fy"]), w, h)
+    kw = dict(tile_size=tile, semantics="std_3dgs", background=bg)
+    st, tight = {}, {}
+    with torch.no_grad():
+        img = scene.render_image_hip(1, layout="hw3", published_rects=True, stats=st, **kw)
+        assert tuple(img.shape) == (h, w, 3)
+        assert st["n_visible"] == case["nvis"] and st["n_instances"] == case["inst"]
+        _judge("std_3dgs " + name, case["wk"], img.cpu().numpy(), FRAME_BOUND["std_3dgs"])
+        # every other route: the same frame, bit for bit
+        assert torch.equal(scene.render_image_hip(1, layout="hw3", stats=tight, **kw), img), "tight rectangles"
+        assert tight["n_visible"] == case["nvis"] and tight["n_instances"] <= case["inst"]
+        assert torch.equal(scene.render_image_hip(1, layout="hw3", generic_kernels=True, published_rects=True, **kw), img)
+        assert torch.equal(scene.render_image_hip(1, layout="hw3", generic_kernels=True, **kw), img)
+        assert torch.equal(scene.render_image_hip(1, layout="wh3", **kw).permute(1, 0, 2), img)
+        assert torch.equal(scene.render_image_hip(1, layout="wh3", generic_kernels=True, **kw).permute(1, 0, 2), img)
+        ntx, nty = (w + tile - 1) // tile, (h + tile - 1) // tile
+        acc = torch.zeros_like(img)
+        for x0, x1 in ((0, ntx // 2), (ntx // 2, ntx)):
+            for y0, y1 in ((0, nty // 2), (nty // 2, nty)):
+                acc += scene.render_image_hip(1, layout="hw3", tile_window=(x0, x1, y0, y1), **kw)
+        assert torch.equal(acc, img), "tile windows"
+        # a principal point off the centre: the render path reads none
+        (tmp_path / "off").mkdir()
+        moved = _scene(tmp_path / "off", cc.off_centre(sc), colors=case["colors"])
+        assert float(moved.images[1].c_x) != float(scene.images[1].c_x)
+        assert torch.equal(_bits(moved.render_image_hip(1, layout="hw3", published_rects=True, **kw)), _bits(img))
+
+
+# ---- the gradients
+@pytest.mark.parametrize("name", STD_NAMES)
+def test_std3dgs_gradients_match_the_restatement(tmp_path, name):
+    case, scene = _std_case(tmp_path, name)
+    gf = torch.from_numpy(case["g"]).to(DEV)
+    frame, st = hip_std._forward(scene, case)
+    outs = hip_std._backward(scene, case, frame, st, gf)
+    assert len(outs) == 7
+    err = hip_std._errors(case, outs)
+    print("%s: kernel vs restatement, max error / scale: %s" % (name, _line(err, hip_std.KEYS)))
+    # the radius is the stage-1 row's wherever the frame listed the Gaussian, 0 elsewhere; whoever has gradient is listed
+    radius, rows = outs[6].cpu().numpy().reshape(-1), case["rows"]
+    listed = radius > 0
+    assert listed.any() and np.array_equal(radius[listed], rows[listed, 5])
+    assert listed[case["ref"].scales["colors"] > 0].all() and not listed[np.isnan(rows[:, 0])].any()
+    for o in outs[:6]:
+        assert o.abs().max() > 0 and not o.cpu().numpy()[~listed].any()
+    # two runs: the same bits
+    again = hip_std._backward(scene, case, frame, st, gf)
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(again, outs))
+    # published rectangles: the same frame, other slots -- within the bound
+    frame_p, st_p = hip_std._forward(scene, case, published_rects=True)
+    assert torch.equal(frame_p, frame) and st_p["n_instances"] >= st["n_instances"]
+    outs_p = hip_std._backward(scene, case, frame_p, st_p, gf, published=True)
+    err_p = hip_std._errors(case, outs_p)
+    print("%s: published rectangles: %s" % (name, _line(err_p, hip_std.KEYS)))
+    radius_p = outs_p[6].cpu().numpy().reshape(-1)
+    assert np.array_equal(radius_p[radius_p > 0], rows[radius_p > 0, 5]) and (radius_p > 0)[listed].all()
+    for o in outs_p[:6]:
+        assert not o.cpu().numpy()[radius_p == 0].any()
+    for k in hip_std.KEYS:
+        assert err[k] <= std_host.BOUND[k], (name, k, err[k], std_host.BOUND[k])
+        assert err_p[k] <= std_host.BOUND[k], (name, "published", k, err_p[k], std_host.BOUND[k])
+    if name in cc.STD_OFFAXIS:      # the clamp's branch carried gradient on the GPU too
+        ewa = case["ref"].clamped_ewa & (case["ref"].scales["points"] > 0)
+        assert ewa.sum() >= 10 and np.abs(outs[2].cpu().numpy()[ewa]).max() > 0
+
+
+# ---- anti-aliased
+@pytest.mark.parametrize("name", AA_NAMES)
+def test_antialiased_frame_and_gradients_match_the_restatement_and_the_flag_clear_call_keeps_its_bits(tmp_path, name):
+    case, scene = _std_case(tmp_path, name, antialiased=True)
+    img, st_p = hip_aa._frame(scene, case, antialiased=True, published_rects=True)
+    assert tuple(img.shape) == (case["H"], case["W"], 3) and st_p["n_instances"] == case["inst"]
+    hip_aa._hold_frame("antialiased " + name, case, img, st_p)
+    plain, st0 = hip_aa._frame(scene, case)
+    frame, st = hip_aa._frame(scene, case, antialiased=True)
+    assert torch.equal(frame, img) and st["n_instances"] == st0["n_instances"] <= case["inst"]
+    assert not torch.equal(plain, img)
+    assert torch.equal(hip_aa._frame(scene, case, antialiased=True, generic_kernels=True)[0], img)
+    assert torch.equal(hip_aa._frame(scene, case, layout="wh3", antialiased=True)[0].permute(1, 0, 2), img)
+    # the gradients
+    gf = torch.from_numpy(case["g"]).to(DEV)
+    outs = hip_aa._backward(scene, case, frame, st, gf)
+    assert len(outs) == 7
+    got, err = hip_aa._errors(case["ref"], outs)
+    print("%s: antialiased: kernel vs restatement, max error / scale: %s" % (name, _line(err, aar.KEYS)))
+    radius, rows = outs[6].cpu().numpy().reshape(-1), case["rows0"]
+    listed = radius > 0
+    assert listed.any() and np.array_equal(radius[listed], rows[listed, 5])
+    assert listed[case["ref"].scales["colors"] > 0].all()
+    for o in outs[:6]:
+        assert o.abs().max() > 0 and not o.cpu().numpy()[~listed].any()
+    again = hip_aa._backward(scene, case, frame, st, gf)
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(again, outs))
+    # flag clear: the argument not passed, and passed as False -- the same bits, and not the anti-aliased ones
+    a = hip_aa._backward(scene, case, plain, st0, gf, std=(case["bg"], False))
+    b = hip_aa._backward(scene, case, plain, st0, gf, antialiased=False)
+    off, st_off = hip_aa._frame(scene, case, antialiased=False)
+    assert torch.equal(_bits(off), _bits(plain)) and st_off["n_instances"] == st0["n_instances"]
+    assert len(a) == len(b) == 7 and all(torch.equal(_bits(x), _bits(y)) for x, y in zip(a, b))
+    assert not torch.equal(outs[1], a[1]) and not torch.equal(outs[3], a[3])
+    for k in aar.KEYS:
+        assert err[k] <= aa_host.BOUND_AA[k], (name, k, err[k], aa_host.BOUND_AA[k])
+
+
+# scales in pixels at z = 4 along the Gaussian's own axes: an ordinary one, a needle, one on the floor of rho
+AA_PROBES = [(2.0, 0.7, 1.2), (3.0, 0.03, 0.03), (0.02, 0.03, 0.01)]
+PROBE_OFFSET = (9, -7)          # pixels from the frame centre: J's third column is not zero
+
+
+@pytest.mark.parametrize("camera", cc.NAMES)
+def test_antialiased_packed_opacity_is_the_mirrors_bit_for_bit(tmp_path, camera):
+    """tests/test_hip_antialias.py's probes at these cameras: one Gaussian, sigmoid(20) = 1 in float32, colour 1, black
+    background, so the pixel under its centre is op_eff exp(power) = rho exp(power).  At a far pose no float32 point
+    projects onto a pixel centre exactly; the point is placed there in float64 and rounded, which leaves |power| below
+    2^-26 (asserted from the C port's float32 stage 1): exp is 1 to the last bit and the pixel is rho's bits."""
+    from oracle import std3dgs_ref
+
+    c = cc.CAMERAS[camera]
+    w, h, z = c["width"], c["height"], 4.0
+    px, py = w // 2 + PROBE_OFFSET[0], h // 2 + PROBE_OFFSET[1]
+    R, t = cc.rotation(c["qvec"]), np.asarray(c["tvec"], np.float64)
+    p_cam = np.array([(px + 0.5 - w / 2) * z / c["fx"], (py + 0.5 - h / 2) * z / c["fy"], z])
+    point = (R.T @ (p_cam - t)).astype(np.float32)[None]
+    quat = (np.array([[0.7, 0.3, -0.5, 0.4]]) / np.linalg.norm([0.7, 0.3, -0.5, 0.4])).astype(np.float32)
+    for k, sigma in enumerate(AA_PROBES):
+        sc = dict(points=point, colors_0_255=np.full((1, 3), 256.0, np.float32),
+                  scales=(np.array([sigma]) * z / np.sqrt(c["fx"] * c["fy"])).astype(np.float32), quaternions=quat,
+                  opacity=np.array([[20.0]], np.float32), fx=np.float64(c["fx"]), fy=np.float64(c["fy"]), cx=np.float64(w / 2),
+                  cy=np.float64(h / 2), width=np.int64(w), height=np.int64(h), qvec=np.asarray(c["qvec"], np.float64),
+                  tvec=np.asarray(c["tvec"], np.float64))
+        (tmp_path / str(k)).mkdir()
+        scene = _scene(tmp_path / str(k), sc, colors=np.ones((1, 3), np.float32))
+        cam = _oracle_cam(scene)
+        st1 = std3dgs_ref.stage1(sc["points"], sc["scales"], sc["quaternions"], sc["opacity"], cam, 16)
+        assert st1.opacity[0] == np.float32(1.0)
+        dx, dy = float(st1.xy[0][0]) - px, float(st1.xy[0][1]) - py
+        A, B, C = (float(v) for v in st1.conic[0])
+        power = 0.5 * (A * dx * dx + C * dy * dy) + B * dx * dy
+        assert abs(dx) < 1e-3 and abs(dy) < 1e-3 and abs(power) < 2.0 ** -26, (camera, k, dx, dy, power)
+        fac = aar.factor(*aar.covariance32(sc["points"], sc["scales"], sc["quaternions"], cam))
+        rho = fac.rho[0]
+        assert np.float32(1.0 / 255.0) <= rho < np.float32(0.99)          # composited, and not the alpha clamp
+        assert bool(fac.clamped[0]) == (k == 2) and (not fac.clamped[0] or rho == np.float32(0.005))
+        with torch.no_grad():
+            img = scene.render_image_hip(1, layout="hw3", semantics="std_3dgs", antialiased=True)
+            plain = scene.render_image_hip(1, layout="hw3", semantics="std_3dgs")
+        got = img[py, px].cpu().numpy()
+        print("%s probe %d: rho mirror %.9g (det0 %.6g, ratio %.6g), kernel %.9g; centre %.2e, %.2e px off the pixel's" % (
+            camera, k, rho, fac.det0[0], fac.ratio[0], got[0], dx, dy))
+        assert (got.view(np.int32) == np.float32(rho).view(np.int32)).all(), (camera, k, got, rho)
+        assert (plain[py, px].cpu().numpy() == np.float32(0.99)).all()      # without the flag: sigmoid = 1, clamped at 0.99
+
+
+# ---- the contribution
+@pytest.mark.parametrize("name", ["std_roll_64x48_n100", "std_offaxis_aniso_tall_48x64_n100"])
+def test_std3dgs_contribution_sum_is_the_backward_s_bits_and_max_and_pixels_match_the_restatement(tmp_path, name):
+    case, scene = _std_case(tmp_path, name)
+    assert hip_con.BG == case["bg"]
+    n, tile = case["n"], case["tile"]
+    frame, st = hip_con._forward(scene, "std_3dgs", tile)
+    con = hip_con._contribution(scene, "std_3dgs", tile, st)
+    gc0 = hip_con._colour_gradient(scene, "std_3dgs", tile, frame, st)
+    assert gc0.abs().max() > 0 and torch.equal(_bits(con.weight_sum), _bits(gc0))
+    other = scene.render_contribution_hip(1, semantics="std_3dgs", tile_size=tile)
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(con, other))
+    ref = cr.std_3dgs(case["R"], case["W"], case["H"], n)
+    assert not ref.excluded.any()
+    wmax, wsum, pixels, views = (_np(x) for x in con)
+    err, bad = cr.compare(wmax, pixels, ref)
+    err_sum = float(np.abs(wsum - ref.weight_sum).max() / max(1.0, ref.weight_sum.max()))
+    print("%s: |weight_max - restatement| %.3g (bound %.3g), weight_sum vs restatement %.3g of its largest, %d rows composited"
+          % (name, err, hip_con.TOL, err_sum, int((pixels > 0).sum())))
+    assert (pixels > 0).sum() >= 50 and err <= hip_con.TOL and bad.size == 0 and err_sum <= hip_con.TOL, (name, err, bad[:10])
+    assert (views[pixels > 0] == 1).all() and not wsum[views == 0].any() and not wmax[views == 0].any()
+    # published rectangles: the same composited pairs
+    frame_p, st_p = hip_con._forward(scene, "std_3dgs", tile, published=True)
+    con_p = hip_con._contribution(scene, "std_3dgs", tile, st_p, published=True)
+    assert torch.equal(_bits(con_p.weight_max), _bits(con.weight_max)) and torch.equal(con_p.pixels, con.pixels)
+    assert torch.equal(_bits(con_p.weight_sum), _bits(hip_con._colour_gradient(scene, "std_3dgs", tile, frame_p, st_p, published=True)))
+
+
+# ---- through the public surface
+def test_std3dgs_autograd_gives_the_raw_call_s_bits_and_an_sh_copy_carries_them_on(tmp_path):
+    name = "std_offaxis_roll_64x48_n100"
+    case, scene = _std_case(tmp_path, name)
+    gf = torch.from_numpy(case["g"]).to(DEV)
+    plain, st = hip_std._forward(scene, case)
+    want = hip_std._backward(scene, case, plain, st, gf)
+    frame, grads = hip_std._autograd(scene, case, gf, geometry_gradients=True, screen_statistics=True)
+    assert frame.grad_fn is not None and torch.equal(frame.detach(), plain)
+    for key, ref in zip(("colors", "opacity", "points", "scales", "quaternions"), want):
+        assert grads[key].abs().max() > 0 and torch.equal(_bits(grads[key].reshape(-1)), _bits(ref.reshape(-1))), key
+    idx, g2d, radius = scene.screen_statistics
+    assert idx == 1 and torch.equal(_bits(g2d), _bits(want[5])) and torch.equal(_bits(radius), _bits(want[6].view(-1)))
+    # the SH copy: degree 2, the case's colours lifted to DC.  The view direction reads the camera centre -R^T t
+    g = scene.gaussians
+    g.sh = torch.from_numpy(_sh_for(case["colors"], 2, 3)).to(DEV).contiguous()
+    g.sh_degree = 2
+    centre = np.asarray(scene.images[1].camera_center_host, np.float64)
+    c = cc.CAMERAS["roll"]
+    assert np.abs(centre + cc.rotation(c["qvec"]).T @ np.asarray(c["tvec"])).max() <= 1e-5
+    plain_sh, st = hip_std._forward(scene, case)
+    assert not torch.equal(plain_sh, plain)
+    outs = hip_std._backward(scene, case, plain_sh, st, gf, screen=False)
+    gsh, gview = scene._sh_backward(1, outs[0], with_points=True)
+    frame, grads = hip_std._autograd(scene, case, gf, names=("points", "opacity", "sh"), geometry_gradients=True)
+    assert torch.equal(frame.detach(), plain_sh) and grads["colors"] is None
+    assert grads["sh"].abs().max() > 0 and torch.equal(_bits(grads["sh"].reshape(-1)), _bits(gsh.reshape(-1)))
+    assert torch.equal(_bits(grads["opacity"].reshape(-1)), _bits(outs[1].reshape(-1)))
+    assert gview.abs().max() > 0 and torch.equal(_bits(grads["points"]), _bits(outs[2] + gview))
+    # and the link itself against its float64 restatement at this camera centre (tests/test_hip_sh_backward.py's check)
+    pts, sh, gc = case["sc"]["points"], _np(g.sh), _np(outs[0])
+    pre, mask = shr.forward(pts, sh, 2, centre)[:2]
+    sure = np.abs(pre) >= shr.NEAR_ZERO
+    assert (~sure).mean() <= 0.01 and 0.01 <= (~mask).mean() <= 0.5
+    ref_sh, ref_mean, scale_sh, scale_mean = shr.backward(pts, sh, 2, centre, gc)
+    e_sh = shr.scaled_error(_np(gsh), ref_sh, scale_sh, keep=sure[:, None, :])
+    e_mean = shr.scaled_error(_np(gview), ref_mean, scale_mean, keep=sure.all(1)[:, None])
+    print("%s: SH link vs restatement, max error / scale: sh %.4g (bound %.3g), points %.4g (bound %.3g)" % (
+        name, e_sh, sh_host.BOUND["sh"], e_mean, sh_host.BOUND["points"]))
+    assert e_sh <= sh_host.BOUND["sh"] and e_mean <= sh_host.BOUND["points"], (e_sh, e_mean)

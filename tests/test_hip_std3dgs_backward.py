@@ -4,6 +4,7 @@ random image times the restatement's gradient mask (zero on the pixels whose dec
 
 Bounds (tests/test_std3dgs_backward_host.py): BOUND = 12 E_REF per output array, E_REF the float32 mirror's own error against
 float64 in the restatement's per-Gaussian norm.  The cases are the issue's seven of STD_CASES and that file's off-axis case.
+All of them have fx = fy; unequal focal lengths and far poses are in tests/test_hip_camera_cases.py (STD_CAMERA_CASES).
 
 Measured on an MI355X, kernel vs restatement, worst error / scale per case (tight rectangles; published_rects=True gives the
 same figures to the last printed digit except scales: 2.57e-09 and 2.06e-09 in the two cases marked *):

@@ -69,10 +69,15 @@ def case_tuple(name):
     if name in STD_CASES:
         return std_case(name)
     make, tile, bg = CASES[name]
-    sc = make()
+    return build_tuple(make(), tile, bg)
+
+
+def build_tuple(sc, tile, bg, cam=None, colors=None):
+    """std_case's tuple of any scene dict; cam, colors: the ones to walk in place of cpu_ref.build_camera's and the
+    scene's own / 256 (what a scene object hands its kernels, where that rounds differently)."""
     w, h = int(sc["width"]), int(sc["height"])
-    cam = cpu_ref.build_camera(sc["qvec"], sc["tvec"], sc["fx"], sc["fy"], w, h)
-    colors = (sc["colors_0_255"] / f32(256.0)).astype(f32)
+    cam = cpu_ref.build_camera(sc["qvec"], sc["tvec"], sc["fx"], sc["fy"], w, h) if cam is None else cam
+    colors = (sc["colors_0_255"] / f32(256.0)).astype(f32) if colors is None else colors
     return (sc, tile, bg, cam, colors) + std_reference(sc, cam, colors, tile, bg)
 
 
@@ -80,7 +85,14 @@ def case_tuple(name):
 def backward_case(name):
     """dict of one case, computed once: the std_case entries by name, the decisions, the gradient mask, dL/dframe (H, W, 3)
     float32, `ref` (float64 restatement at the float32 rows) and `mirror` (float32)."""
-    sc, tile, bg, cam, colors, img, nvis, inst, R, wk = case_tuple(name)
+    return build_backward(case_tuple(name), c_rows(name))
+
+
+def build_backward(tup, rows=None):
+    """backward_case's dict of any case tuple (rows: its C-port stage-1 rows, where they are at hand)."""
+    sc, tile, bg, cam, colors, img, nvis, inst, R, wk = tup
+    if rows is None:
+        rows = rows_of(tup)
     W, H = int(cam.width), int(cam.height)
     dec = sbr.decide(R, W, H)
     assert (dec.composited == wk.composited).all() and ((dec.stop_position >= 0) == wk.stopped).all()
@@ -89,16 +101,20 @@ def backward_case(name):
     args = (R, dec, sc["points"], sc["scales"], sc["quaternions"], cam, g, bg)
     ref = sbr.backward(*args, dtype=np.float64)
     mirror = sbr.backward(*args, dtype=np.float32)
-    rows = np.asarray(c_rows(name), f32)
+    rows = np.asarray(rows, f32)
     return dict(sc=sc, tile=tile, bg=bg, cam=cam, colors=colors, R=R, wk=wk, dec=dec, mask=mask, g=g, ref=ref, mirror=mirror,
-                W=W, H=H, n=int(sc["points"].shape[0]), rows=rows)
+                W=W, H=H, n=int(sc["points"].shape[0]), rows=rows, img=img, nvis=nvis, inst=inst)
 
 
 @functools.lru_cache(maxsize=None)
 def c_rows(name):
     """The (n, 8) float32 stage-1 rows of the C port (x, y, A, B, C, radius, depth, opacity; NaN where culled)."""
+    return rows_of(case_tuple(name))
+
+
+def rows_of(tup):
     from oracle import c_oracle
-    sc, tile, bg, cam, colors = case_tuple(name)[:5]
+    sc, tile, bg, cam, colors = tup[:5]
     return c_oracle.render_std3dgs(sc["points"], colors, sc["scales"], sc["quaternions"], sc["opacity"], cam, tile=tile,
                                    background=bg, nthreads=8)[3]
 
@@ -178,7 +194,11 @@ def torch_gradients(case):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_the_restatement_agrees_with_autograd_of_an_independent_forward(name):
-    case = backward_case(name)
+    agrees_with_autograd(name, backward_case(name))
+
+
+def agrees_with_autograd(name, case):
+    """The check on any case dict of backward_case's shape (tests/test_std3dgs_camera_cases_host.py runs it on its own)."""
     R, rows = case["R"], np.asarray(case["R"].index, np.int64)
     auto, values = torch_gradients(case)
     sc = case["sc"]
