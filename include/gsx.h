@@ -674,6 +674,12 @@ GSX_API int gsx_sh_to_rgb(const float *means3d, const float *sh, int32_t degree,
  * Every entry of both outputs is written (exact zeros for a clamped channel, and for grad_means3d at degree 0); grad_means3d
  * is written, not accumulated: a caller that also has gsx_render_backward_geometry's dL/dmeans3d adds the two.  No atomics:
  * same inputs, same bits.  Does not synchronise.  n == 0 is GSX_OK.
+ * The zero-row rule: a row whose grad_colors is zero in every channel the forward did not clamp (m_c grad_colors[i][c] = 0
+ * for all c) gets exact zeros in grad_sh and grad_means3d, whatever its mean and coefficients hold -- NaN, an infinity, a
+ * mean that IS the camera centre (no view direction).  Every Gaussian that is culled or on no tile list is such a row (its
+ * grad_colors is 0), so a row a fit has lost reaches neither the coefficients' gradient nor, through the sum of
+ * grad_means3d over all rows that the pose gradient of an SH scene takes, dL/dworld2view.  A row with a non-zero masked
+ * grad_colors holds the bits it held before the rule.
  */
 GSX_API int gsx_sh_backward(const float *means3d, const float *sh, int32_t degree, int64_t n,
                             const float *camera_center_host, const float *grad_colors,

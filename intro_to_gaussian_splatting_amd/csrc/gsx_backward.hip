@@ -46,7 +46,7 @@
 // gsx_render_backward_std (GSX_SEM_STD_3DGS, and GSX_FLAG_ANTIALIASED): the tile walk's two std instances and the std and
 // anti-aliased variants of the colour sums and of the chain.
 //
-// alpha is evaluated in the reference's operation order for every record (alpha_ref and kStopRefCpu, gsx_internal.h: the
+// alpha is evaluated in the reference's operation order for every record (alpha_ref_walk and kStopRefCpu, gsx_internal.h: the
 // forward's own) and without the forward's 2^-26 skip: the gradient sees every record the reference sees.
 #include "gsx_internal.h"
 
@@ -229,7 +229,7 @@ __device__ __forceinline__ float wave_sum2(float a, float b, int lane) {
 
 // gsx_render_depth: (D, A) = (sum T alpha z, sum T alpha) of every pixel of every window tile, by the backward's walk --
 // one wave per tile, four pixels per lane, 64 records staged per batch, a tile of more than 256 pixels in chunks,
-// alpha_ref on every listed record (no 2^-26 skip), the pixel stopped before the record that fails kStopRefCpu.  D takes
+// alpha_ref_walk on every listed record (no 2^-26 skip), the pixel stopped before the record that fails kStopRefCpu.  D takes
 // one fmaf per record and A one add: backward_tile_depth_kernel accumulates both the same way, so its D_fin - D_k and
 // A_fin - A_k are exact zeros behind a pixel's last record.
 __global__ void __launch_bounds__(64)
@@ -281,7 +281,7 @@ __global__ void __launch_bounds__(64)
 #pragma unroll
                     for (int j = 0; j < kNpx; ++j) {
                         if (!live[j]) continue;
-                        const float alpha = alpha_ref(Ra.x, Ra.y, Ra.z, Ra.w, Rb.x, Rb.y, Rb.z, fx[j], fy[j]);
+                        const float alpha = alpha_ref_walk(Ra.x, Ra.y, Ra.z, Ra.w, Rb.x, Rb.y, Rb.z, fx[j], fy[j]);
                         const float ta = Tr[j] * alpha;
                         const float test = Tr[j] - ta;
                         if (!(test >= kStopRefCpu)) {

@@ -176,7 +176,7 @@ __global__ void __launch_bounds__(64) GSX_TILE_ATTR GSX_TILE_KERNEL(BackwardTile
                         }
                         Tr[j] = Tr[j] - ta;
 #else
-                        const float alpha = alpha_ref(A.x, A.y, A.z, A.w, B.x, B.y, B.z, fx[j], fy[j]);
+                        const float alpha = alpha_ref_walk(A.x, A.y, A.z, A.w, B.x, B.y, B.z, fx[j], fy[j]);
                         const float ta = Tr[j] * alpha;
                         const float test = Tr[j] - ta;
                         if (!(test >= kStopRefCpu)) {   // the pixel stops before this record (the forward's rule; NaN stops too)

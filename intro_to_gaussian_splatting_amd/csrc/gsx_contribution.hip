@@ -2,7 +2,7 @@
 // in any pixel (weight_max), the sum of its weights (weight_sum) and the number of pixels that composited it (pixels).
 //
 // The walk is the gradient entries' walk (gsx_backward.hip, gsx_backward_tile.inc), not the forward's: under GSX_SEM_REF_CPU
-// alpha_ref on every listed record with no 2^-26 skip and the pixel stopped before the record that fails kStopRefCpu, the
+// alpha_ref_walk on every listed record with no 2^-26 skip and the pixel stopped before the record that fails kStopRefCpu, the
 // raw stage-1 records (launch_project_raw); under GSX_SEM_STD_3DGS std_exponent and std_tests on the packed records of
 // the frame's own projection, alpha = fminf(0.99, ..), pixels beyond the frame's width or height dead from the start.  For
 // a composited (record, pixel) w is the very `ta` the backward instances form.
@@ -62,7 +62,7 @@ __device__ __forceinline__ void store_batch(float4 *__restrict__ slots, const ui
 
 // One (pixel, record) pair under either rule set: whether the pixel composites the record; if so its weight ta = T alpha
 // goes into the lane's sum and max and T is updated.  live: the pixel has not stopped (cleared here when it stops BEFORE
-// this record).  kStd = false, GSX_SEM_REF_CPU: A = (x, y, Q00, Q01), B = (Q10, Q11, op, -) of the raw record, alpha_ref and
+// this record).  kStd = false, GSX_SEM_REF_CPU: A = (x, y, Q00, Q01), B = (Q10, Q11, op, -) of the raw record, alpha_ref_walk and
 // kStopRefCpu (a NaN stops too).  kStd = true, GSX_SEM_STD_3DGS: A = (x, y, Q''00, Qs''), B = (Q''11, opacity, ..) of the
 // packed record, std_exponent and std_tests' two skips and stop.  The operations are the backward instances'.
 template <bool kStd>
@@ -85,7 +85,7 @@ __device__ __forceinline__ bool composite_pair(const float4 &A, const float4 &B,
             used = true;
         }
     } else {
-        const float alpha = alpha_ref(A.x, A.y, A.z, A.w, B.x, B.y, B.z, px, py);
+        const float alpha = alpha_ref_walk(A.x, A.y, A.z, A.w, B.x, B.y, B.z, px, py);
         const float ta = T * alpha;
         const float test = T - ta;
         if (!(test >= kStopRefCpu)) {   // the pixel stops before this record

@@ -72,7 +72,7 @@ constexpr float kStopRefCpu = 0.000001f;
 // exp, times the opacity factor.  px, py: the pixel in FRAME coordinates (integers: exact as floats).  The exponential
 // is v_exp_f32 of power * log2(e): within 2 ulp of expf plus 6e-8 |power| log2(e), i.e. < 2e-6 of alpha wherever
 // alpha >= 1e-7 -- the one step that is not the reference's bit for bit.  The forward's compositing kernels
-// (gsx_blend.hip) and the backward's (gsx_backward.hip) both evaluate it.
+// (gsx_blend.hip) evaluate it; the kernels that walk the forward's lists evaluate alpha_ref_walk, below.
 __device__ __forceinline__ float alpha_ref(float x, float y, float q00, float q01, float q10, float q11, float op,
                                            float px, float py) {
     const float e0 = x - px, e1 = y - py;
@@ -81,6 +81,30 @@ __device__ __forceinline__ float alpha_ref(float x, float y, float q00, float q0
     const float t1 = __builtin_fmaf(d1, q11, d0 * q01);
     const float power = t0 * e0 + t1 * e1;
     return __builtin_amdgcn_exp2f(power * 1.44269504088896340736f) * op;
+}
+
+// alpha_ref for the kernels that WALK the forward's lists (the backward's tile kernels, gsx_render_depth,
+// gsx_render_contribution): the same operations up to `power`, the product power * log2(e) carried with its float32
+// residual.  Rounding that product costs 6e-8 |power| log2(e) of alpha, which the frame cannot see but a gradient can: a
+// Gaussian whose centre lies outside the rendered region is graded only on pixels several sigmas out, every term of its
+// sums is off the same way, and dL/dopacity of such a row was 8.5e-7 of its error scale away from float64 (the reference's
+// own float32 autograd: 3e-8).  p2 + lo is the product to 2^-48: lo = the product's own rounding error (one FMA) plus
+// power times what float32 drops of log2(e); exp2(p2 + lo) = exp2(p2) (1 + lo ln 2) to 1e-14.  What is left is v_exp_f32's
+// own 1 ulp, independent of |power|.
+__device__ __forceinline__ float alpha_ref_walk(float x, float y, float q00, float q01, float q10, float q11, float op,
+                                                float px, float py) {
+    constexpr float kLog2e = 1.44269504088896340736f;
+    constexpr float kLog2eLo = (float)(1.44269504088896340736 - (double)kLog2e);
+    const float e0 = x - px, e1 = y - py;
+    const float d0 = -0.5f * e0, d1 = -0.5f * e1;
+    const float t0 = __builtin_fmaf(d1, q10, d0 * q00);
+    const float t1 = __builtin_fmaf(d1, q11, d0 * q01);
+    const float power = t0 * e0 + t1 * e1;
+    const float p2 = power * kLog2e;
+    const float lo = __builtin_fmaf(power, kLog2eLo, __builtin_fmaf(power, kLog2e, -p2));
+    const float w = __builtin_amdgcn_exp2f(p2);
+    // (outside v_exp_f32's range -- an overflowed or NaN exponent included -- the value is alpha_ref's: lo is inf - inf there)
+    return (__builtin_fabsf(p2) < 126.0f ? __builtin_fmaf(w, lo * 0.693147180559945309417f, w) : w) * op;
 }
 
 // alpha_ref for the geometry moments.  v_exp_f32 returns zero where its result would be below 2^-126, so alpha_ref is
@@ -602,7 +626,7 @@ struct DepthTiles {
 // becomes (S5, Sz, 0, 0), Sz = sum T alpha dL/dD = dL/dz of the record over the tile.
 hipError_t launch_backward_tiles_depth(const BackwardTiles &bt, const DepthTiles &dt, const TileGrid &grid, const OutDesc &out,
                                        hipStream_t s);
-// gsx_render_depth: one wave per window tile walks its list as the backward does (alpha_ref, kStopRefCpu, every listed
+// gsx_render_depth: one wave per window tile walks its list as the backward does (alpha_ref_walk, kStopRefCpu, every listed
 // record) and writes (D, A) of every pixel of its tile.  raw, vals, ranges as in BackwardTiles.
 hipError_t launch_depth_tiles(const Record *raw, const uint32_t *vals, const uint2 *ranges, const float *zrow,
                               const TileGrid &grid, const OutDesc &out, float *depth, hipStream_t s);

@@ -73,6 +73,11 @@ __global__ void __launch_bounds__(sh::kBlock)
                 gx = (dgx - x * radial) * inv;
                 gy = (dgy - y * radial) * inv;
                 gz = (dgz - z * radial) * inv;
+                // The zero-row rule (include/gsx.h): without a non-zero masked dL/dcolour nothing of the row's own reaches
+                // dL/dmean.  A row the frame listed nowhere has gm = 0, and its mean may be NaN, infinite or the camera
+                // centre itself, or a coefficient NaN: 0 * NaN above is NaN, and the caller sums every row's share into
+                // the pose's gradient.  (A select on a wave mask: no register is held for it.)
+                if (gm[0] == 0.0f && gm[1] == 0.0f && gm[2] == 0.0f) gx = gy = gz = 0.0f;
             }
             grad_means3d[3 * i] = gx;
             grad_means3d[3 * i + 1] = gy;

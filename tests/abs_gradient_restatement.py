@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import geometry_backward_restatement as gbr
 from backward_restatement import _alpha32
 from oracle import cpu_ref
 from screen_gradient_restatement import half_extents
@@ -27,6 +28,7 @@ def abs_gradient(pre, n: int, frame, grad_frame, width: int, height: int, tile: 
     """(abs (n,2), signed (n,2)) float64 in NDC units and ORIGINAL row order; rows that are culled or on no composited pixel
     are zero.  with_scale: also the per-Gaussian error scale (n,) of screen_gradient_restatement.screen_gradient -- its
     construction (geometry_backward_restatement.moments' Sabs1, Sabs2 through from_moments) from this one walk."""
+    pre, _ = gbr.listed_only(pre, width, height, tile, tiles)        # the conic of a row on no list may be NaN
     m = pre.points_xy.shape[0]
     mean32 = np.asarray(pre.points_xy, f32)
     inv32 = np.asarray(pre.inverse_covariance_2d, f32)

@@ -89,8 +89,11 @@ def camera_backward(pre, points, scales, quats, cam, frame, grad_frame, width: i
     """(gV (4,4), gF (4,4)) float64: dL/dworld2view and dL/dfull_proj of the frame of `pre` (the depth-sorted float32 stage
     1: its means and conics enter the compositing, as in the reference).  absolute: the sum of |terms| per entry instead.
     moments: (S, Sabs) of gbr.moments when the caller has them already."""
+    pre, on = gbr.listed_only(pre, width, height, tile)         # a row on no list adds 32 exact zeros, whatever it holds
     order = np.asarray(pre.order, np.int64)
     S, Sabs = gbr.moments(pre, frame, grad_frame, width, height, tile) if moments is None else moments
+    if len(S) != order.size:                                    # the caller's moments are of all the visible rows
+        S, Sabs = S[on], Sabs[on]
     pts = np.asarray(points)[order]
     st = gbr.stage1(pts, np.asarray(scales)[order], np.asarray(quats)[order], cam)
     Q = np.asarray(pre.inverse_covariance_2d, np.float64)

@@ -198,6 +198,7 @@ def depth_backward(pre, points, scales, quats, cam, frame, grad_frame, depth, gr
     the reference); points, scales, quats the float32 inputs; frame, depth the forward's images (the reference's float32
     ones for a fixture)."""
     n = np.asarray(points).shape[0]
+    pre, _ = gbr.listed_only(pre, width, height, tile, tiles)
     order = np.asarray(pre.order, np.int64)
     sm = sums(pre, frame, grad_frame, depth, grad_depth, width, height, tile, tiles=tiles)
     st = gbr.stage1(np.asarray(points)[order], np.asarray(scales)[order], np.asarray(quats)[order], cam)

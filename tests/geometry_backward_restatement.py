@@ -217,12 +217,26 @@ def moments(pre, frame, grad_frame, width: int, height: int, tile: int, tiles=No
     return S, Sabs
 
 
+def listed_only(pre, width: int, height: int, tile: int, tiles=None):
+    """(the rows of `pre` that are on at least one tile list, in their order; on, bool (m,): which rows those are).  The
+    lists of the result are the lists of `pre` (cpu_ref.tile_list compares a row's own box with the tile), so every sum over
+    composited (record, pixel) pairs is the same sum.  A row on no list has zero moments and a zero gradient whatever its
+    stage 1 holds -- a NaN box is how a non-finite row gets there -- so no float64 stage 1 is formed for it at all."""
+    on = np.zeros(np.asarray(pre.points_xy).shape[0], bool)
+    if tiles is None:
+        tiles = [(x0, y0) for x0 in cpu_ref.tile_origins(width, tile) for y0 in cpu_ref.tile_origins(height, tile)]
+    for x0, y0 in tiles:
+        on[cpu_ref.tile_list(pre, x0, y0, tile)] = True
+    return type(pre)(*[np.asarray(a)[on] for a in pre]), on
+
+
 def geometry_backward(pre, points, scales, quats, cam, frame, grad_frame, width: int, height: int, tile: int, tiles=None,
                       with_scale: bool = False):
     """(dL/dpoints (n,3), dL/dscales (n,3), dL/dquaternions (n,4)) in ORIGINAL row order; rows that are culled or on no
     composited pixel are zero.  pre: the depth-sorted float32 stage 1 (its means and conics enter the compositing, as in
     the reference); points, scales, quats: the float32 inputs.  with_scale: also (scale_p, scale_s, scale_q), each (n,)."""
     n = np.asarray(points).shape[0]
+    pre, _ = listed_only(pre, width, height, tile, tiles)
     order = np.asarray(pre.order, np.int64)
     S, Sabs = moments(pre, frame, grad_frame, width, height, tile, tiles)
     st = stage1(np.asarray(points)[order], np.asarray(scales)[order], np.asarray(quats)[order], cam)

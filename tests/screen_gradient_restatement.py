@@ -51,7 +51,10 @@ def listed(pre, width: int, height: int, tile: int) -> np.ndarray:
 def screen_gradient(pre, n: int, frame, grad_frame, width: int, height: int, tile: int, tiles=None, moments=None):
     """(grad_means2d (n,2) float64, scale (n,)) in ORIGINAL row order; rows that are culled or on no composited pixel are
     zero.  moments: (S, Sabs) of geometry_backward_restatement.moments if the caller has them already."""
+    pre, on = gbr.listed_only(pre, width, height, tile, tiles)      # the conic of a row on no list may be NaN
     S, Sabs = gbr.moments(pre, frame, grad_frame, width, height, tile, tiles) if moments is None else moments
+    if len(S) != len(pre.order):                                    # the caller's moments are of all the visible rows
+        S, Sabs = S[on], Sabs[on]
     gn, scale = from_moments(pre.inverse_covariance_2d, S, Sabs, width, height)
     order = np.asarray(pre.order, np.int64)
     full, full_scale = np.zeros((n, 2)), np.zeros(n)

@@ -92,9 +92,20 @@ def colors(points, sh, degree, center):
 
 
 def backward(points, sh, degree, center, grad_colors):
-    """(dL/dsh (n,K,3), dL/dmean (n,3), scale of dL/dsh (n,K,3), scale of dL/dmean (n,3)) in float64."""
+    """(dL/dsh (n,K,3), dL/dmean (n,3), scale of dL/dsh (n,K,3), scale of dL/dmean (n,3)) in float64.
+    The zero-row rule (include/gsx.h, gsx_sh_backward): a row whose dL/dcolour is zero in all three channels -- every row
+    the frame listed nowhere -- gets exact zeros in all four, whatever its mean and coefficients hold; no view direction is
+    formed for it (a NaN mean, or a mean on the camera centre, has none)."""
     sh = np.asarray(sh, np.float64)
     g = np.asarray(grad_colors, np.float64)
+    live = g.any(1)
+    if not live.all():
+        n, k = sh.shape[0], sh.shape[1]
+        out = [np.zeros((n, k, 3)), np.zeros((n, 3)), np.zeros((n, k, 3)), np.zeros((n, 3))]
+        if live.any():
+            for full, part in zip(out, backward(np.asarray(points)[live], sh[live], degree, center, g[live])):
+                full[live] = part
+        return tuple(out)
     pre, mask, d, norm, Y = forward(points, sh, degree, center)
     gm = np.where(mask, g, 0.0)
     grad_sh = Y[:, :, None] * gm[:, None, :]

@@ -45,6 +45,8 @@ ABS_SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "rows3_48x48_n500", "tile2_40x
               "cull_96x80_n400"]
 # at the cameras of tests/camera_cases.py; tests/test_camera_cases_host.py holds them to the reference
 CAMERA_ABS_SCENES = ["cam_aniso_tall_48x64_n100", "cam_roll_64x48_n100"]
+# the clean twins of tests/bad_row_cases.py; tests/test_bad_rows_host.py holds them to the reference
+BAD_ROW_ABS_SCENES = ["badrow_base_twin_64x48_n300", "badrow_roll_twin_64x48_n300"]
 RATIO_SCENES = ABS_SCENES[:5]       # the five scenes the statistic's gain was checked on
 E_REF_ABS = 2.942e-8
 BOUND_RESTATEMENT = 12 * E_REF_ABS
@@ -167,14 +169,14 @@ def test_python_surface_keywords_and_refusals(tmp_path):
 
 # ---- the float64 restatement
 def test_every_abs_fixture_is_data_only():
-    for name in ABS_SCENES + CAMERA_ABS_SCENES:
+    for name in ABS_SCENES + CAMERA_ABS_SCENES + BAD_ROW_ABS_SCENES:
         path = os.path.join(ROOT, "tests", "golden", "absgrad_%s.npz" % name)
         assert os.path.getsize(path) <= 16 * 1024, path
         z = np.load(path)
         assert sorted(z.files) == ["grad_points_xy_abs", "reference_backward_seconds", "reference_forward_seconds"], name
         assert z["grad_points_xy_abs"].dtype == np.float64 and (z["grad_points_xy_abs"] >= 0).all()
     have = sorted(f for f in os.listdir(os.path.join(ROOT, "tests", "golden")) if f.startswith("absgrad_"))
-    assert have == sorted("absgrad_%s.npz" % name for name in ABS_SCENES + CAMERA_ABS_SCENES)
+    assert have == sorted("absgrad_%s.npz" % name for name in ABS_SCENES + CAMERA_ABS_SCENES + BAD_ROW_ABS_SCENES)
 
 
 @pytest.mark.parametrize("name", ABS_SCENES)

@@ -41,6 +41,9 @@ OWN_STAGE1 = ("rows1_48x48_n1", "rows3_48x48_n3", "rows1_48x48_n500", "rows3_48x
 # their own E_REF_CAM, so they are not in GEOM_SCENES
 CAMERA_SCENES = ("cam_aniso_64x48_n120", "cam_aniso_tall_48x64_n100", "cam_farpose_64x48_n120", "cam_roll_64x48_n100")
 OWN_STAGE1 += CAMERA_SCENES
+# likewise the clean twins of tests/bad_row_cases.py's RGB cases; tests/test_bad_rows_host.py holds them to their own E_REF_BAD
+BAD_ROW_TWINS = ("badrow_base_twin_64x48_n300", "badrow_roll_twin_64x48_n300")
+OWN_STAGE1 += BAD_ROW_TWINS
 OUTPUTS = ("points", "scales", "quaternions")
 E_REF = {"points": 2.171e-8, "scales": 4.687e-7, "quaternions": 3.790e-9}
 BOUND_RESTATEMENT = {k: 12 * v for k, v in E_REF.items()}

@@ -35,11 +35,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from capture_geometry_grad_golden import CAMERA_ENTRY_SCENES, OWN_STAGE1, _weight  # noqa: E402
+from capture_geometry_grad_golden import BAD_ROW_TWINS, reference_colors, scene_arrays  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "rows3_48x48_n500", "tile2_40x32_n80", "small_64x48_n300", "tile20_64x64_n300",
           "cull_96x80_n400"]
 SCENES += CAMERA_ENTRY_SCENES       # fx != fy and far poses (tests/camera_cases.py)
+SCENES += list(BAD_ROW_TWINS)       # the clean twins of tests/bad_row_cases.py
 
 
 class _Leaves:
@@ -63,17 +65,14 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
 
     from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
 
-    spec = dict(OWN_STAGE1[name] if name in OWN_STAGE1 else FIXTURES[name])
-    tile = spec.pop("tile")
-    assert not spec.pop("defaults", False)
-    sc = _generate(spec)
+    sc, tile, _ = scene_arrays(name)
     with tempfile.TemporaryDirectory() as tmp:
         write_colmap_text(os.path.join(tmp, "colmap"), sc)
         g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
         g.points = torch.from_numpy(sc["points"]).float().clone().requires_grad_(True)
         g.scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
         g.quaternions = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
-        g.colors = g.colors.detach().clone().requires_grad_(True)
+        g.colors = reference_colors(sc, g).requires_grad_(True)
         g.opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone().requires_grad_(True)
         scene = GaussianScene(os.path.join(tmp, "colmap"), g)
         kept = []

@@ -36,6 +36,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from capture_geometry_grad_golden import BRANCHES, CAMERA_ENTRY_SCENES, OWN_STAGE1, STANDALONE, _weight, branch_counts  # noqa: E402
+from capture_geometry_grad_golden import BAD_ROW_TWINS, reference_colors, scene_arrays  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "tile2_40x32_n80", "small_64x48_n300", "cull_96x80_n400", "wide_64x64_n400",
@@ -44,6 +45,7 @@ SCENES = ["rows1_48x48_n1", "rows3_48x48_n3", "tile2_40x32_n80", "small_64x48_n3
           # three visible of 500: the small row class with culled rows around it
           "rows3_48x48_n500"]
 SCENES += CAMERA_ENTRY_SCENES       # fx != fy and far poses (tests/camera_cases.py)
+SCENES += list(BAD_ROW_TWINS)       # the clean twins of tests/bad_row_cases.py
 # Not in the set: the other geomgrad_ scenes.  The graph through the geometry needs minutes and many GB each (needle, 110
 # Gaussians: over 21 GB); the eight above hit every branch.  Name one on the command line on a machine with the memory and
 # the time.
@@ -56,11 +58,7 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
 
     from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
 
-    own = name in OWN_STAGE1
-    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
-    tile = spec.pop("tile")
-    assert not spec.pop("defaults", False)
-    sc = _generate(spec)
+    sc, tile, own = scene_arrays(name)
     gg = np.load(os.path.join(OUT_DIR, "geomgrad_" + name + ".npz"))
     base = gg if (own or name in STANDALONE) else np.load(os.path.join(OUT_DIR, "grad_" + name + ".npz"))
     with tempfile.TemporaryDirectory() as tmp:
@@ -70,7 +68,7 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
         scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
         quats = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
         g.points, g.scales, g.quaternions = points, scales, quats
-        g.colors = g.colors.detach().clone()
+        g.colors = reference_colors(sc, g)
         g.opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone()
         scene = GaussianScene(os.path.join(tmp, "colmap"), g)
         counts = branch_counts(scene, g)

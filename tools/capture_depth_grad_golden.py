@@ -38,12 +38,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from capture_geometry_grad_golden import CAMERA_ENTRY_SCENES, OWN_STAGE1, STANDALONE, _weight  # noqa: E402
+from capture_geometry_grad_golden import BAD_ROW_TWINS, reference_colors, scene_arrays  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
 SCENES = ["tile2_40x32_n80", "tiny_48x48_n600", "small_64x48_n300", "cull_96x80_n400", "rows1_48x48_n1", "rows3_48x48_n3",
           # a tile of more than 256 pixels: the tile kernels take it in two chunks
           "tile20_64x64_n300"]
 SCENES += CAMERA_ENTRY_SCENES       # fx != fy and far poses (tests/camera_cases.py)
+SCENES += list(BAD_ROW_TWINS)       # the clean twins of tests/bad_row_cases.py
 # Not in the set: the other geomgrad_ scenes.  Each needs two graphs through the geometry, minutes and many GB apiece
 # (needle, 110 Gaussians: over 21 GB for one); name one on the command line on a machine with the memory and the time.
 EXTRA = ["small_80x64_n120_tile8", "tile12_dense_52x40_n900", "tile32_96x96_n400", "wide_64x64_n400", "needle_160x160_n110",
@@ -55,18 +57,14 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
 
     from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
 
-    own = name in OWN_STAGE1
-    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
-    tile = spec.pop("tile")
-    assert not spec.pop("defaults", False)
-    sc = _generate(spec)
+    sc, tile, own = scene_arrays(name)
     with tempfile.TemporaryDirectory() as tmp:
         write_colmap_text(os.path.join(tmp, "colmap"), sc)
         g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
         points = torch.from_numpy(sc["points"]).float().clone().requires_grad_(True)
         scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
         quats = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
-        colors = g.colors.detach().clone().requires_grad_(True)
+        colors = reference_colors(sc, g).requires_grad_(True)
         opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone().requires_grad_(True)
         g.points, g.scales, g.quaternions, g.colors, g.opacity = points, scales, quats, colors, opacity
         scene = GaussianScene(os.path.join(tmp, "colmap"), g)

@@ -72,6 +72,11 @@ CAMERA_SCENES = {
 CAMERA_ENTRY_SCENES = ["cam_aniso_tall_48x64_n100", "cam_roll_64x48_n100"]
 OWN_STAGE1.update(CAMERA_SCENES)
 SCENES += list(OWN_STAGE1)
+# The clean twins of tests/bad_row_cases.py's RGB cases (every non-finite row replaced by a culled finite one; the
+# degenerate rows -- zero scales, logits of +-80, colours of 0 and 4, quaternions times 1e-18 and 1e18 -- stay): the
+# reference runs on finite rows only.  fixture -> case; the arrays come from that module, treated like OWN_STAGE1.
+BAD_ROW_TWINS = {"badrow_base_twin_64x48_n300": "base", "badrow_roll_twin_64x48_n300": "roll"}
+SCENES += list(BAD_ROW_TWINS)
 BRANCHES = ("n_floored_det", "n_clamped", "n_culled")
 
 
@@ -81,6 +86,28 @@ def _weight(pixel_coord, point_mean, inverse_covariance):
 
     d = point_mean - pixel_coord
     return torch.exp(-0.5 * d @ inverse_covariance @ d.T)
+
+
+def scene_arrays(name: str):
+    """(scene dict, tile, own) of a scene of any of the gradient capture tools.  own: the scene has no forward fixture
+    and no grad_ fixture (OWN_STAGE1, BAD_ROW_TWINS): its geomgrad_ file carries its inputs and the reference's stage 1."""
+    own = name in OWN_STAGE1 or name in BAD_ROW_TWINS
+    if name in BAD_ROW_TWINS:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import bad_row_cases
+
+        return dict(bad_row_cases.rgb_case(BAD_ROW_TWINS[name])[1]), bad_row_cases.TILE, own
+    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
+    tile = spec.pop("tile")
+    assert not spec.pop("defaults", False)
+    return _generate(spec), tile, own
+
+
+def reference_colors(sc, g):
+    """The colour array the reference renders: its own (colors_0_255 / 256) unless the scene dict carries one."""
+    import torch
+
+    return (torch.from_numpy(sc["colors"]) if "colors" in sc else g.colors.detach()).clone()
 
 
 def branch_counts(scene, g) -> dict:
@@ -130,18 +157,14 @@ def capture(name: str, GaussianScene, Gaussians, original_weight=None) -> None:
 
     from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
 
-    own = name in OWN_STAGE1
-    spec = dict(OWN_STAGE1[name] if own else FIXTURES[name])
-    tile = spec.pop("tile")
-    assert not spec.pop("defaults", False)
-    sc = _generate(spec)
+    sc, tile, own = scene_arrays(name)
     with tempfile.TemporaryDirectory() as tmp:
         write_colmap_text(os.path.join(tmp, "colmap"), sc)
         g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
         points = torch.from_numpy(sc["points"]).float().clone().requires_grad_(True)
         scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
         quats = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
-        colors = g.colors.detach().clone().requires_grad_(True)
+        colors = reference_colors(sc, g).requires_grad_(True)
         opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone().requires_grad_(True)
         g.points, g.scales, g.quaternions, g.colors, g.opacity = points, scales, quats, colors, opacity
         scene = GaussianScene(os.path.join(tmp, "colmap"), g)

@@ -29,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from capture_geometry_grad_golden import CAMERA_ENTRY_SCENES, CAMERA_SCENES, OWN_STAGE1, _weight  # noqa: E402
+from capture_geometry_grad_golden import BAD_ROW_TWINS, reference_colors, scene_arrays  # noqa: E402
 from capture_geometry_grad_golden import SCENES as GEOMETRY_SCENES  # noqa: E402
 from oracle.capture_golden import FIXTURES, OUT_DIR, _generate, _import_reference  # noqa: E402
 
@@ -41,10 +42,7 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
 
     from intro_to_gaussian_splatting_amd.synthetic import write_colmap_text
 
-    spec = dict(OWN_STAGE1[name] if name in OWN_STAGE1 else FIXTURES[name])
-    tile = spec.pop("tile")
-    assert not spec.pop("defaults", False)
-    sc = _generate(spec)
+    sc, tile, _ = scene_arrays(name)
     with tempfile.TemporaryDirectory() as tmp:
         write_colmap_text(os.path.join(tmp, "colmap"), sc)
         g = Gaussians(torch.from_numpy(sc["points"]), torch.from_numpy(sc["colors_0_255"]), model_path=tmp)
@@ -52,7 +50,7 @@ def capture(name: str, GaussianScene, Gaussians) -> None:
         g.points = points
         g.scales = torch.from_numpy(sc["scales"]).float().clone().requires_grad_(True)
         g.quaternions = torch.from_numpy(sc["quaternions"]).float().clone().requires_grad_(True)
-        g.colors = g.colors.detach().clone().requires_grad_(True)
+        g.colors = reference_colors(sc, g).requires_grad_(True)
         g.opacity = torch.from_numpy(np.ascontiguousarray(sc["opacity"], dtype=np.float32)).clone().requires_grad_(True)
         scene = GaussianScene(os.path.join(tmp, "colmap"), g)
         kept = []
