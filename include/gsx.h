@@ -1113,6 +1113,66 @@ GSX_API int gsx_transform_gaussians(float *points /* (n,3) */, float *scales /* 
                                     float *sh /* (n, (sh_degree+1)^2, 3), may be NULL when sh_degree == 0 */, int32_t sh_degree,
                                     int64_t n, const GsxTransform *transform /* host */, void *stream);
 
+/*
+ * Build extension: photo rectification.  One photograph (uint8 RGB, as a decoder leaves it) is resampled, under the lens
+ * model COLMAP estimated for it, into the pinhole camera a rule set renders: the float32 target a fit compares its frames
+ * with, and the per-pixel weight of gsx_photometric_loss_weighted (1 where the photo covers the pixel, 0 on the
+ * undistortion border).  Box-filtered over S x S sub-samples (S = samples) so that a multi-megapixel photo can be brought
+ * down to the training size without aliasing.  ONE kernel launch, one thread per output pixel; no workspace, no
+ * synchronisation, no atomics, no hints: a pure function of its arguments, the same bits on every run.
+ *
+ * lens   (HOST) the photo's camera: COLMAP's model id, size and params in COLMAP's order --
+ *          GSX_LENS_SIMPLE_PINHOLE f, cx, cy            GSX_LENS_PINHOLE fx, fy, cx, cy
+ *          GSX_LENS_SIMPLE_RADIAL  f, cx, cy, k         GSX_LENS_RADIAL  f, cx, cy, k1, k2
+ *          GSX_LENS_OPENCV         fx, fy, cx, cy, k1, k2, p1, p2
+ *        (f: fx_s = fy_s = f; a coefficient the model lacks is 0).  COLMAP's image coordinates: the centre of pixel 0 is
+ *        at 0.5.  The fisheye models, FOV and FULL_OPENCV (ids 5..10) are refused by name with GSX_ERR_UNSUPPORTED.
+ * target (HOST) the pinhole to resample to, in OUTPUT PIXEL-INDEX coordinates (index i sits at i): the view-space direction
+ *        of index (i, j) is ((i - cx) / fx, (j - cy) / fy, 1).  Which (fx, cx) a rule set's frame has for a given camera is
+ *        the caller's business (intro_to_gaussian_splatting_amd/capture.py: rectified_camera).
+ * photo  (DEVICE) (lens.height, lens.width, 3) bytes, rows photo_row_stride bytes apart, only read.
+ * image_out (DEVICE) (target.width, target.height, 3) float32, the frame's default layout GSX_LAYOUT_WH3; weight_out
+ *        (DEVICE, may be NULL) (target.width, target.height) float32.  Every element of both is written.
+ *
+ * Per output pixel (i, j), every float32 operation rounded on its own (no fused multiply-add; divide correctly rounded), in
+ * exactly this order; sub-samples b = 0 .. S-1 (outer, along y), a = 0 .. S-1 (inner, along x):
+ *   y  = (((float) j + (((float) b + 0.5f) / (float) S - 0.5f)) - cy) / fy
+ *   x  = (((float) i + (((float) a + 0.5f) / (float) S - 0.5f)) - cx) / fx
+ *   xx = x x;  yy = y y;  xy = x y;  r2 = xx + yy;  rho = (k1 + k2 r2) r2                     (= k1 r^2 + k2 r^4)
+ *   xd = ((x + x rho) + (2 p1) xy) + p2 (r2 + 2 xx)
+ *   yd = ((y + y rho) + p1 (r2 + 2 yy)) + (2 p2) xy
+ *   g  = 1 + rho;  gp = k1 + (2 k2) r2                                                        (gp = d rho / d r2)
+ *   jxx = ((g + (2 xx) gp) + (2 p1) y) + (6 p2) x;   jyy = ((g + (2 yy) gp) + (6 p1) y) + (2 p2) x
+ *   jxy = ((2 xy) gp + (2 p1) x) + (2 p2) y;          det = jxx jyy - jxy jxy     (the Jacobian of (x, y) -> (xd, yd))
+ *   u  = fx_s xd + (cx_s - 0.5f);   v = fy_s yd + (cy_s - 0.5f)                    (source INDEX coordinates)
+ *   valid:  0 <= u <= W_s - 1  and  0 <= v <= H_s - 1  (all four bilinear taps inside the photo)  and  det > 0 (the
+ *           model has not folded back, as a barrel lens does far outside its field); a NaN is not valid.
+ *   a valid sample:  x0 = floor(u), x1 = min(x0 + 1, W_s - 1), tx = u - (float) x0, the same along y; per channel, with
+ *           the four bytes converted to float:  top = p00 + tx (p01 - p00);  bot = p10 + tx (p11 - p10);
+ *           value = top + ty (bot - top);  sum_c = sum_c + value (in sample order);  count = count + 1
+ *   image_out[i][j][c] = sum_c / (255.0f (float) count), or +0 when count == 0;  weight_out[i][j] = (float) count / (float)(S S)
+ * With the pinhole models every coefficient is 0: xd = x and det = 1 exactly.
+ *
+ * Refused (gsx_last_error names the argument) before any HIP call, GSX_ERR_INVALID_ARGUMENT unless stated: photo, lens,
+ * target or image_out NULL; samples outside 1..8; a size of either camera outside 1 .. 65536; photo_row_stride below
+ * 3 lens.width; an unsupported model (GSX_ERR_UNSUPPORTED) or an unknown one; a focal length of either side that is not
+ * positive and finite; a lens parameter the model reads, or a target principal point, that is not finite.
+ */
+enum { GSX_LENS_SIMPLE_PINHOLE = 0, GSX_LENS_PINHOLE = 1, GSX_LENS_SIMPLE_RADIAL = 2, GSX_LENS_RADIAL = 3, GSX_LENS_OPENCV = 4 };
+typedef struct GsxLens {
+    int32_t model;        /* GSX_LENS_*: COLMAP's camera model id */
+    int32_t width, height;
+    float params[8];      /* COLMAP's params in COLMAP's order; entries the model does not have are not read */
+} GsxLens;
+typedef struct GsxPinhole {
+    int32_t width, height;
+    float fx, fy, cx, cy; /* output pixel-index coordinates: index i sits at i */
+} GsxPinhole;
+GSX_API int gsx_rectify_photo(const uint8_t *photo /* device, (lens.height, lens.width, 3) */, int64_t photo_row_stride,
+                              const GsxLens *lens /* host */, const GsxPinhole *target /* host */, int32_t samples /* 1..8 */,
+                              float *image_out /* device (W', H', 3) */, float *weight_out /* device (W', H'), may be NULL */,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,8 +13,9 @@ from .fit import Trainer, events_at
 from .pose import CameraRefiner
 from .exposure import ExposureRefiner
 from .schema import PreprocessedScene
+from .capture import load_capture, read_photo, rectified_camera, rectify
 
-__all__ = ["Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
+__all__ = ["load_capture", "read_photo", "rectified_camera", "rectify","Gaussians", "GaussianScene", "GaussianImage", "PreprocessedScene", "render_preprocessed",
            "NativeExtension", "photometric_loss", "depth_loss", "GaussianAdam", "expon_lr", "DensityControl", "MCMCControl",
            "nearest3",
            "Trainer", "events_at", "CameraRefiner", "ExposureRefiner", "Contribution"]

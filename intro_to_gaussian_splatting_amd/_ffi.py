@@ -57,6 +57,7 @@ GSX_MCMC_OPACITY = 2
 GSX_MCMC_SCALES = 3
 GSX_KNN_RULE_REFERENCE = 0
 GSX_KNN_RULE_PUBLISHED = 1
+GSX_LENS_SIMPLE_PINHOLE, GSX_LENS_PINHOLE, GSX_LENS_SIMPLE_RADIAL, GSX_LENS_RADIAL, GSX_LENS_OPENCV = 0, 1, 2, 3, 4
 
 
 def visible_rows_flag(n: int, n_visible: int, flags: int) -> int:
@@ -125,6 +126,14 @@ class GsxDensityRules(ctypes.Structure):
 class GsxTransform(ctypes.Structure):
     _fields_ = [("R", c_float * 9), ("s", c_float), ("t", c_float * 3), ("q_R", c_float * 4),
                 ("M1", c_float * 9), ("M2", c_float * 25), ("M3", c_float * 49)]
+
+
+class GsxLens(ctypes.Structure):
+    _fields_ = [("model", c_int32), ("width", c_int32), ("height", c_int32), ("params", c_float * 8)]
+
+
+class GsxPinhole(ctypes.Structure):
+    _fields_ = [("width", c_int32), ("height", c_int32), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float)]
 
 
 # name -> (restype, argtypes); every symbol include/gsx.h declares.
@@ -204,6 +213,7 @@ SIGNATURES = {
     "gsx_knn3_workspace_bytes": (c_size_t, [c_int64]),
     "gsx_knn3": (ctypes.c_int, [_FP, c_int64, c_void_p, c_int32, _FP, _FP, POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
     "gsx_transform_gaussians": (ctypes.c_int, [_FP, _FP, _FP, _FP, c_int32, c_int64, POINTER(GsxTransform), c_void_p]),
+    "gsx_rectify_photo": (ctypes.c_int, [c_void_p, c_int64, POINTER(GsxLens), POINTER(GsxPinhole), c_int32, _FP, _FP, c_void_p]),
 }
 
 # csrc/gsx_debug.h

@@ -1,4 +1,4 @@
-"""Minimal COLMAP sparse-model reader: cameras and images, text or binary.
+"""Minimal COLMAP sparse-model reader: cameras, images and 3D points, text or binary.
 
 Counterpart of what ``GaussianScene.__init__`` needs from the reference's
 ``splat/read_colmap.py:87-239`` and ``splat/utils.py:269-290`` (``.bin`` preferred over ``.txt``).
@@ -6,6 +6,8 @@ Same record fields as the reference's namedtuples (``Camera``: id, model, width,
 ``Image``: id, qvec, tvec, camera_id, name, xys, point3D_ids); the render path reads camera model /
 size / params and image pose / camera id / name.  Both readers are held against the reference's own
 parse of a committed model (tests/golden/colmap_model*, captured by oracle/capture_golden.py).
+The point readers (``Point3D``: id, xyz, rgb, error, image_ids, point2D_idxs; splat/read_colmap.py:242-309) are held the same
+way against tests/golden/colmap_points* (tools/capture_points3d_golden.py).
 """
 from __future__ import annotations
 
@@ -32,6 +34,15 @@ class Image(NamedTuple):
     name: str
     xys: np.ndarray = np.zeros((0, 2))            # 2D keypoints (n, 2)
     point3D_ids: np.ndarray = np.zeros(0, dtype=np.int64)
+
+
+class Point3D(NamedTuple):
+    id: int
+    xyz: np.ndarray            # (3,) float64
+    rgb: np.ndarray            # (3,) integers 0..255
+    error: float
+    image_ids: np.ndarray      # the track: the images that see the point ...
+    point2D_idxs: np.ndarray   # ... and the keypoint of each that is the point
 
 
 # COLMAP camera model id -> (name, number of params)
@@ -120,6 +131,33 @@ def read_images_binary(path: str) -> Dict[int, Image]:
     return out
 
 
+def read_points3D_text(path: str) -> Dict[int, Point3D]:
+    out = {}
+    for line in _data_lines(path):
+        tok = line.split()
+        pid = int(tok[0])
+        out[pid] = Point3D(pid, np.array([float(v) for v in tok[1:4]]), np.array([int(v) for v in tok[4:7]], dtype=np.int64),
+                           float(tok[7]), np.array([int(v) for v in tok[8::2]], dtype=np.int64),
+                           np.array([int(v) for v in tok[9::2]], dtype=np.int64))
+    return out
+
+
+def read_points3D_binary(path: str) -> Dict[int, Point3D]:
+    out = {}
+    with open(path, "rb") as fid:
+        (count,) = _unpack(fid, "Q")
+        for _ in range(count):
+            rec = _unpack(fid, "QdddBBBd")
+            (length,) = _unpack(fid, "Q")
+            raw = fid.read(8 * length)             # (image_id, point2D_idx) pairs: int32, int32
+            if len(raw) != 8 * length:
+                raise ValueError("truncated COLMAP binary file")
+            track = np.frombuffer(raw, dtype="<i4").reshape(-1, 2).astype(np.int64)
+            out[rec[0]] = Point3D(rec[0], np.array(rec[1:4]), np.array(rec[4:7], dtype=np.int64), float(rec[7]),
+                                  track[:, 0].copy(), track[:, 1].copy())
+    return out
+
+
 def read_camera_file(colmap_path: str) -> Dict[int, Camera]:
     binary, text = os.path.join(colmap_path, "cameras.bin"), os.path.join(colmap_path, "cameras.txt")
     if os.path.exists(binary):
@@ -136,3 +174,12 @@ def read_image_file(colmap_path: str) -> Dict[int, Image]:
     if os.path.exists(text):
         return read_images_text(text)
     raise ValueError("no images.bin / images.txt under %s" % colmap_path)
+
+
+def read_points3D_file(colmap_path: str) -> Dict[int, Point3D]:
+    binary, text = os.path.join(colmap_path, "points3D.bin"), os.path.join(colmap_path, "points3D.txt")
+    if os.path.exists(binary):
+        return read_points3D_binary(binary)
+    if os.path.exists(text):
+        return read_points3D_text(text)
+    raise ValueError("no points3D.bin / points3D.txt under %s" % colmap_path)

@@ -1185,6 +1185,65 @@ int gsx_transform_gaussians(float *points, float *scales, float *quaternions, fl
     return GSX_OK;
 }
 
+int gsx_rectify_photo(const uint8_t *photo, int64_t photo_row_stride, const GsxLens *lens, const GsxPinhole *target,
+                      int32_t samples, float *image_out, float *weight_out, void *stream) {
+    if (!photo) return fail(GSX_ERR_INVALID_ARGUMENT, "photo is NULL");
+    if (!lens) return fail(GSX_ERR_INVALID_ARGUMENT, "lens is NULL");
+    if (!target) return fail(GSX_ERR_INVALID_ARGUMENT, "target is NULL");
+    if (!image_out) return fail(GSX_ERR_INVALID_ARGUMENT, "image_out is NULL");
+    if (samples < 1 || samples > 8) return fail(GSX_ERR_INVALID_ARGUMENT, "samples = %d is outside 1..8", samples);
+    if (lens->width < 1 || lens->height < 1 || lens->width > kRectifyMaxSize || lens->height > kRectifyMaxSize)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lens size %d x %d is outside 1..%d", lens->width, lens->height, kRectifyMaxSize);
+    if (target->width < 1 || target->height < 1 || target->width > kRectifyMaxSize || target->height > kRectifyMaxSize)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "target size %d x %d is outside 1..%d", target->width, target->height, kRectifyMaxSize);
+    if (photo_row_stride < (int64_t)3 * lens->width)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "photo_row_stride = %lld is below 3 * width = %lld", (long long)photo_row_stride,
+                    (long long)3 * lens->width);
+    static const char *const refused[] = {"OPENCV_FISHEYE", "FULL_OPENCV", "FOV", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE",
+                                          "THIN_PRISM_FISHEYE"};
+    if (lens->model > GSX_LENS_OPENCV && lens->model <= GSX_LENS_OPENCV + 6)
+        return fail(GSX_ERR_UNSUPPORTED, "lens model %d (%s) is not supported: SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV",
+                    lens->model, refused[lens->model - GSX_LENS_OPENCV - 1]);
+    if (lens->model < GSX_LENS_SIMPLE_PINHOLE || lens->model > GSX_LENS_OPENCV)
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lens model %d is unknown", lens->model);
+    RectifyArgs a;
+    memset(&a, 0, sizeof a);
+    const float *p = lens->params;
+    int used = 0;       // params the model reads, COLMAP's order
+    switch (lens->model) {
+        case GSX_LENS_SIMPLE_PINHOLE: a.fxs = a.fys = p[0]; a.cxs = p[1]; a.cys = p[2]; used = 3; break;
+        case GSX_LENS_PINHOLE: a.fxs = p[0]; a.fys = p[1]; a.cxs = p[2]; a.cys = p[3]; used = 4; break;
+        case GSX_LENS_SIMPLE_RADIAL: a.fxs = a.fys = p[0]; a.cxs = p[1]; a.cys = p[2]; a.k1 = p[3]; used = 4; break;
+        case GSX_LENS_RADIAL: a.fxs = a.fys = p[0]; a.cxs = p[1]; a.cys = p[2]; a.k1 = p[3]; a.k2 = p[4]; used = 5; break;
+        default: a.fxs = p[0]; a.fys = p[1]; a.cxs = p[2]; a.cys = p[3]; a.k1 = p[4]; a.k2 = p[5]; a.p1 = p[6]; a.p2 = p[7]; used = 8; break;
+    }
+    const auto positive = [](float v) { return v > 0.0f && v <= FLT_MAX; };     // (a NaN fails both)
+    if (!positive(a.fxs) || !positive(a.fys))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "lens focal length (%g, %g) is not positive and finite", (double)a.fxs, (double)a.fys);
+    for (int i = 0; i < used; ++i)
+        if (!(p[i] >= -FLT_MAX && p[i] <= FLT_MAX))
+            return fail(GSX_ERR_INVALID_ARGUMENT, "lens->params[%d] = %g is not finite", i, (double)p[i]);
+    if (!positive(target->fx) || !positive(target->fy))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "target focal length (%g, %g) is not positive and finite", (double)target->fx, (double)target->fy);
+    if (!(target->cx >= -FLT_MAX && target->cx <= FLT_MAX && target->cy >= -FLT_MAX && target->cy <= FLT_MAX))
+        return fail(GSX_ERR_INVALID_ARGUMENT, "target principal point (%g, %g) is not finite", (double)target->cx, (double)target->cy);
+    a.photo = photo;
+    a.row_stride = photo_row_stride;
+    a.image = image_out;
+    a.weight = weight_out;
+    a.src_w = lens->width;
+    a.src_h = lens->height;
+    a.out_w = target->width;
+    a.out_h = target->height;
+    a.samples = samples;
+    a.fx = target->fx;
+    a.fy = target->fy;
+    a.cx = target->cx;
+    a.cy = target->cy;
+    GSX_HIP(gsx::launch_rectify(a, (hipStream_t)stream));
+    return GSX_OK;
+}
+
 int gsx_density_accumulate(const float *grad, int32_t width, int64_t n, float *grad_sum, uint32_t *seen, void *stream) {
     if (n < 0 || n > kDensityMaxRows) return fail(GSX_ERR_INVALID_ARGUMENT, "n = %lld is outside 0 .. 2^30", (long long)n);
     if (width < 1 || width > kDensityMaxWidth)

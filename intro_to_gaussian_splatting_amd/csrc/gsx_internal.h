@@ -436,6 +436,22 @@ struct TransformArgs {
 };
 hipError_t launch_transform(const TransformArgs &args, int degree, hipStream_t s);
 
+// ---- gsx_rectify.hip
+// gsx_rectify_photo behind its argument checks.  One thread per output pixel, kRectifyJ along the output's contiguous axis j
+// by kRectifyI along i; the whole struct is the kernel's argument.  k1, k2, p1, p2: the lens model's coefficients, zero where
+// the model has none (a pinhole is the OPENCV body with four zeros: the same operations, exact).
+constexpr int kRectifyJ = 8, kRectifyI = 32;
+constexpr int kRectifyMaxSize = 1 << 16;        // of either image, per axis
+struct RectifyArgs {
+    const uint8_t *photo;
+    int64_t row_stride;
+    float *image, *weight;                      // weight: or null
+    int32_t src_w, src_h, out_w, out_h, samples;
+    float fxs, fys, cxs, cys, k1, k2, p1, p2;   // the photo's camera
+    float fx, fy, cx, cy;                       // the target, in output index coordinates
+};
+hipError_t launch_rectify(const RectifyArgs &args, hipStream_t s);
+
 // ---- gsx_density.hip
 // gsx_density_accumulate / _plan / _apply behind their argument checks.  The workspace of n rows (DensityCarve):
 //   header  kDensityHeader bytes: int64 n, n_out, n_pruned, n_cloned, n_split; float split_shrink at kDensityShrinkAt

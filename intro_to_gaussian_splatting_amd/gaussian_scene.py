@@ -533,8 +533,19 @@ class _RenderImageDepthFunction(torch.autograd.Function):
 
 class GaussianScene:
     def __init__(self, colmap_path: str, gaussians: Gaussians) -> None:
-        cameras = read_camera_file(colmap_path)
-        images = read_image_file(colmap_path)
+        self._init_from_views(read_camera_file(colmap_path), read_image_file(colmap_path), gaussians)
+
+    @classmethod
+    def from_views(cls, cameras, images, gaussians: Gaussians) -> "GaussianScene":
+        """The scene of ``cameras`` (id -> ``colmap.Camera``) and ``images`` (id -> ``colmap.Image``), the two dicts the
+        constructor reads from disk: ``GaussianScene(colmap_path, g)`` is ``from_views(read_camera_file(colmap_path),
+        read_image_file(colmap_path), g)``, one body.  For cameras that are not on disk as they are wanted
+        (``capture.load_capture``: the rectified pinholes of a capture's lens-distorted cameras)."""
+        scene = cls.__new__(cls)
+        scene._init_from_views(cameras, images, gaussians)
+        return scene
+
+    def _init_from_views(self, cameras, images, gaussians: Gaussians) -> None:
         self.images: Dict[int, GaussianImage] = {}
         for idx, image in images.items():
             self.images[idx] = GaussianImage(camera=cameras[image.camera_id], image=image,

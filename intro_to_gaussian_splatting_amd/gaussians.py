@@ -299,6 +299,22 @@ class Gaussians:
         return g
 
     @classmethod
+    def from_colmap_points(cls, points3D, min_track_length: int = 2, device=None) -> "Gaussians":
+        """A container from COLMAP's sparse points (``colmap.read_points3D_file``: id -> ``Point3D``): the points seen by at
+        least ``min_track_length`` images (the filter of the reference's notebook), one row each, in ASCENDING POINT ID --
+        whatever order the file or the dict had, so the container is a pure function of the model -- and then the
+        constructor's own arithmetic (``colors = rgb / 256``, the default scales, quaternions and opacity).  Scales from the
+        neighbours (``initialize_scale``) and SH (``init_sh``) stay the caller's lines."""
+        import numpy as np
+
+        if isinstance(min_track_length, bool) or int(min_track_length) != min_track_length or int(min_track_length) < 0:
+            raise ValueError("min_track_length = %r is not a non-negative integer" % (min_track_length,))
+        kept = [points3D[k] for k in sorted(points3D) if len(points3D[k].image_ids) >= int(min_track_length)]
+        xyz = np.array([p.xyz for p in kept], dtype=np.float64).reshape(-1, 3)
+        rgb = np.array([p.rgb for p in kept], dtype=np.float64).reshape(-1, 3)
+        return cls(torch.from_numpy(xyz), torch.from_numpy(rgb), device=device)
+
+    @classmethod
     def from_ply(cls, path: str, device=None) -> "Gaussians":
         """Loads a ``.ply``: a trained 3D Gaussian Splatting checkpoint (log-scales -> linear, SH
         coefficients, logit opacity) or a plain xyz+rgb point cloud (then the reference's
