@@ -85,10 +85,11 @@ def terms(st: dict, points, Q, S, absolute: bool = False):
 
 
 def camera_backward(pre, points, scales, quats, cam, frame, grad_frame, width: int, height: int, tile: int,
-                    absolute: bool = False, moments=None):
+                    absolute: bool = False, moments=None, per_gaussian: bool = False):
     """(gV (4,4), gF (4,4)) float64: dL/dworld2view and dL/dfull_proj of the frame of `pre` (the depth-sorted float32 stage
     1: its means and conics enter the compositing, as in the reference).  absolute: the sum of |terms| per entry instead.
-    moments: (S, Sabs) of gbr.moments when the caller has them already."""
+    moments: (S, Sabs) of gbr.moments when the caller has them already.  per_gaussian: (gV, gF, tV (m,4,4), tF (m,4,4))
+    instead, the terms the two sums are over, one per listed Gaussian in depth-rank order."""
     pre, on = gbr.listed_only(pre, width, height, tile)         # a row on no list adds 32 exact zeros, whatever it holds
     order = np.asarray(pre.order, np.int64)
     S, Sabs = gbr.moments(pre, frame, grad_frame, width, height, tile) if moments is None else moments
@@ -98,6 +99,8 @@ def camera_backward(pre, points, scales, quats, cam, frame, grad_frame, width: i
     st = gbr.stage1(pts, np.asarray(scales)[order], np.asarray(quats)[order], cam)
     Q = np.asarray(pre.inverse_covariance_2d, np.float64)
     tV, tF = terms(st, pts, Q, Sabs if absolute else S, absolute)
+    if per_gaussian:
+        return tV.sum(0), tF.sum(0), tV, tF
     return tV.sum(0), tF.sum(0)
 
 

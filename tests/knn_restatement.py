@@ -5,6 +5,8 @@ q = (dx dx + dy dy) + dz dz, every operation rounded to float32 on its own; the 
 correctly rounded, +inf where there is no neighbour.  Only the values of the three smallest q enter, so neither ties nor
 the order of the candidates matter.  numpy's float32 arithmetic rounds every operation and fuses nothing.
 
+``nearest3_sq_torch`` is the same brute force in torch, for the sizes at which numpy's takes minutes.
+
 Also the point clouds the knn tests share (``cloud``): the capture tool makes the reference's fixtures of them.
 """
 import functools
@@ -74,6 +76,31 @@ def nearest3_sq(points, chunk=512):
         part = np.partition(q, k - 1, axis=1)[:, :k] if n > k else q
         out[i0:i1, :k] = np.sort(part, axis=1)[:, :k]
     return out
+
+
+def nearest3_sq_torch(points, device, chunk=1024):
+    """nearest3_sq in torch float32 on `device`, for the sizes at which numpy's brute force takes minutes: the same n^2
+    pairs in the same operation order, 1024 queries x n per step, every operation an eager elementwise op of its own (each
+    rounds on its own; nothing is there to contract), the query's own row set to +inf, the three smallest by topk.  An oracle
+    only where tests/test_hip_knn.py has first held it to nearest3_sq bit for bit."""
+    import torch
+
+    p = torch.from_numpy(np.array(points, dtype=F)).to(device)           # (a copy: the shared cases are read only)
+    n = p.shape[0]
+    out = torch.full((n, 3), float("inf"), dtype=torch.float32, device=device)
+    x, y, z = p[:, 0].contiguous(), p[:, 1].contiguous(), p[:, 2].contiguous()
+    k = min(3, n)
+    for i0 in range(0, n, chunk):
+        i1 = min(i0 + chunk, n)
+        dx = x[None, :] - x[i0:i1, None]
+        dy = y[None, :] - y[i0:i1, None]
+        dz = z[None, :] - z[i0:i1, None]
+        xx, yy, zz = dx * dx, dy * dy, dz * dz
+        q = (xx + yy) + zz
+        assert q.dtype == torch.float32 and q.shape == (i1 - i0, n)
+        q[torch.arange(i1 - i0, device=device), torch.arange(i0, i1, device=device)] = float("inf")    # exclusion by row
+        out[i0:i1, :k] = torch.topk(q, k, dim=1, largest=False, sorted=True).values
+    return out.cpu().numpy()
 
 
 def scale_of(q3, rule):

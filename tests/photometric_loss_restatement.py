@@ -107,11 +107,35 @@ CASES = [
 ]
 CASE_IDS = [c[0] for c in CASES]
 
+# ---- the smallest shapes at which the one-workgroup reduce over the tile partials (loss_reduce_kernel, sum_records:
+# `for (i = threadIdx.x; i < tiles; i += 256)`) takes its second step, and at which a tile has neighbours on all eight sides.
+# Same format as CASES.  They do not feed E_REF (tests/test_photometric_loss_host.py holds the float32 reference to
+# E_REF x E_REF_WINDOW at each of them instead).
+LARGE_CASES = [
+    ("tiles_3x3_vector", (3 * T, 3 * T), (3 * T, 3 * T), 0),                # stride 288: the 16-byte path; one interior tile
+    ("tiles_4x4_scalar", (97, 103), (97, 103), 0),                          # stride 309: the scalar path; partial far tiles
+    ("tiles_256", (512, 512), (512, 512), 0),                               # 16 x 16 tiles: one record per reduce thread
+    ("tiles_289_scalar", (513, 513), (513, 513), 0),                        # 17 x 17: threads 0..32 take a second; stride 1539
+    ("tiles_289_vector_cropped", (520, 516), (513, 514), 0),                # stride 1548: 16-byte path, a row ends inside an access
+]
+LARGE_CASE_IDS = [c[0] for c in LARGE_CASES]
+_ALL_CASES = CASES + LARGE_CASES
+_ALL_IDS = CASE_IDS + LARGE_CASE_IDS
+
+
+def case_of(name):
+    """The (name, tensor shape, region, base shift) entry of a case of CASES or LARGE_CASES."""
+    return _ALL_CASES[_ALL_IDS.index(name)]
+
+
+def tiles_of(region):
+    return -(-region[0] // TILE) * -(-region[1] // TILE)
+
 
 def case_inputs(name):
     """(frame, target) float32 (A, B, 3) in [0, 1] of the named case: a smooth-ish random frame and a noisy copy of it."""
-    idx = CASE_IDS.index(name)
-    shape = CASES[idx][1]
+    idx = _ALL_IDS.index(name)
+    shape = _ALL_CASES[idx][1]
     rs = np.random.RandomState(100 + idx)
     x = rs.uniform(size=shape + (3,)).astype(np.float32)
     y = np.clip(x + rs.normal(0, 0.15, size=x.shape), 0.0, 1.0).astype(np.float32)

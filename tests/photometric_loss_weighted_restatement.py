@@ -124,19 +124,33 @@ CASE_IDS = [c[0] for c in CASES]
 NONZERO_CASE_IDS = [c[0] for c in CASES if c[2] != "zero"]
 ZERO_CASE_IDS = [c[0] for c in CASES if c[2] == "zero"]
 
+# ---- plr.LARGE_CASES (tiles with eight neighbours; 256 and 289 tile partials, where wloss_reduce_kernel and
+# wloss_exposure_reduce_kernel -- sum_records<3> and <12>, records rec[i * K + k] -- take their loop's second step) x the
+# weights that differ per pixel x the exposure that makes dL/dE an output; and the 289 tiles once with both options NULL
+# and once with W = 0.  Same format as CASES; they do not feed E_REF_W.
+LARGE_CASES = [("%s_%s_general" % (base, mask), base, mask, "general") for base in plr.LARGE_CASE_IDS
+               for mask in ("random", "binary")]
+LARGE_CASES += [("tiles_289_scalar_none_none", "tiles_289_scalar", "none", "none"),
+                ("tiles_289_scalar_zero_general", "tiles_289_scalar", "zero", "general")]
+LARGE_CASE_IDS = [c[0] for c in LARGE_CASES]
+LARGE_NONZERO_CASE_IDS = [c[0] for c in LARGE_CASES if c[2] != "zero"]
+LARGE_ZERO_CASE_IDS = [c[0] for c in LARGE_CASES if c[2] == "zero"]
+_ALL_CASES = CASES + LARGE_CASES
+_ALL_IDS = CASE_IDS + LARGE_CASE_IDS
+
 
 def case_geometry(name):
     """(tensor shape (A, B), region (a, b), floats the base pointers are moved by) of the named case."""
-    base = CASES[CASE_IDS.index(name)][1]
-    _, shape, region, skip = plr.CASES[plr.CASE_IDS.index(base)]
+    base = _ALL_CASES[_ALL_IDS.index(name)][1]
+    _, shape, region, skip = plr.case_of(base)
     return shape, region, skip
 
 
 def case_inputs(name):
     """(frame, target float32 (A, B, 3); weight float32 (A, B) or None; exposure float32 (3, 4) or None) of the named case.
     Outside the region the weight holds values a correct call never reads (random, or ones for the all-zero mask)."""
-    idx = CASE_IDS.index(name)
-    _, base, mask, expo = CASES[idx]
+    idx = _ALL_IDS.index(name)
+    _, base, mask, expo = _ALL_CASES[idx]
     shape, (a, b), _ = case_geometry(name)
     x, y = plr.case_inputs(base)
     rs = np.random.RandomState(500 + idx)

@@ -12,6 +12,13 @@ The unit over-counts what float32 loses, as in test_geometry_backward_host.py, a
 of every Gaussian, which cancel, while the scale adds their absolute values.  The max-normalised errors of the same data
 are 1e-7 .. 5e-6.  The kernel is held to 12 E_REF against the restatement and 13 E_REF against the fixtures
 (tests/test_hip_camera_gradient.py), the multiples test_geometry_backward_host.py uses.
+
+E_SUM: what a plain float32 sum of 2048, 2049 and 2305 per-Gaussian terms loses, in the same unit (LARGE_EDGES below: more
+Gaussians than any fixture has, 8, 9 and 10 partial rows for the kernel's one-workgroup reduce), measured on the CPU by
+test_plain_float32_sum_over_the_large_edges_is_e_sum:
+    world2view   2.130e-11  (2048 kept)
+    full_proj    4.205e-10  (2305 kept)
+Both are below E_REF, so the kernel's bound there, 12 max(E_REF, E_SUM), is 12 E_REF.
 """
 import os
 import re
@@ -101,6 +108,112 @@ def test_culled_and_unlisted_gaussians_contribute_nothing():
     unlit = np.abs(base["grad_colors"][order]).sum(1) == 0
     assert unlit.sum() > 0 and not tV[unlit].any() and not tF[unlit].any()
     assert order.size == 400 - 112          # the culled rows are not even in the sum
+
+
+# ---- the sum over more Gaussians than any fixture has: 2048, 2049 and 2305 on the tile lists
+# camera_reduce_kernel adds one partial row per 256 KEPT depth ranks (GsxFrameStats.n_kept: the Gaussians that reach a tile;
+# a visible Gaussian outside the rendered tiles has no rank in the backward pass) in 8 stripes.  (kept, seed): 8 rows, every
+# stripe exactly one; 9 rows, stripe 0 takes a second; 10 rows, the tenth holding one rank.  make_few_visible_scene on the
+# 48 x 48 frame with the scales halved, and of its visible Gaussians only such as reach a tile: visible = kept.  The farthest
+# one -- the last row's only rank at 2049 and 2305 -- is made opaque (logit 3) and `grow` times as large: the error unit adds
+# the absolute terms of all the Gaussians, and one ordinary Gaussian's terms are about the bound's size in it.  With these
+# its share is 20 bounds and more (asserted on the CPU), so a sum that loses the last row alone leaves the bound.
+# (kept, seed, grow)
+LARGE_EDGES = [(2048, 50, 4.0), (2049, 51, 8.0), (2305, 50, 4.0)]
+LARGE_EDGE_LAST_ROW_BOUNDS = 20.0
+LARGE_EDGE_SHRINK = 0.5
+LARGE_EDGE_BEHIND = 300
+# The plainest float32 evaluation of these sums -- the restatement's per-Gaussian terms rounded to float32 and added in
+# float32 one after the other in depth-rank order -- against their float64 sum, in scaled_error units, measured on the CPU
+# by test_plain_float32_sum_over_the_large_edges_is_e_sum, per count.  No reference fixture exists at these counts (E_REF
+# is measured on at most 600 Gaussians); the kernel is held to 12 max(E_REF, E_SUM) there.
+# The figures are far below E_REF: the unit adds the absolute moments of every Gaussian while the float32 sum only loses
+# 2^-24 of its running value per add, so on these scenes max(E_REF, E_SUM) is E_REF and the bound is the fixtures' 12 E_REF.
+E_SUM_MEASURED = {2048: {"world2view": 2.130e-11, "full_proj": 3.921e-10},
+                  2049: {"world2view": 8.803e-12, "full_proj": 2.004e-10},
+                  2305: {"world2view": 5.334e-12, "full_proj": 4.205e-10}}
+E_SUM = {k: max(v[k] for v in E_SUM_MEASURED.values()) for k in OUTPUTS}
+BOUND_LARGE = {k: 12 * max(E_REF[k], E_SUM[k]) for k in OUTPUTS}
+_LARGE_EDGE_SCENES = {}
+
+
+def _cpu_camera_and_stage1(sc):
+    """(cpu_ref.Camera, the C restatement's stage 1) of a synthetic scene with the container's colours (rgb / 256): no GPU."""
+    from oracle import c_oracle, cpu_ref
+    from intro_to_gaussian_splatting_amd import GaussianImage
+    from intro_to_gaussian_splatting_amd.colmap import Camera, Image
+
+    im = GaussianImage(Camera(1, "PINHOLE", int(sc["width"]), int(sc["height"]),
+                              np.array([sc["fx"], sc["fy"], sc["cx"], sc["cy"]], np.float64)),
+                       Image(1, np.asarray(sc["qvec"]), np.asarray(sc["tvec"]), 1, "v"), device="cpu")
+    c = im.gsx_camera()
+    cam = cpu_ref.Camera(im.world2view.numpy(), im.full_proj_transform.numpy(), np.float32(c.tan_fovx), np.float32(c.tan_fovy),
+                         np.float32(c.fx), np.float32(c.fy), c.width, c.height)
+    colors = (sc["colors_0_255"] / np.float32(256.0)).astype(np.float32)
+    return cam, c_oracle.preprocess(sc["points"], colors, sc["scales"], sc["quaternions"], sc["opacity"], cam)
+
+
+def large_edge_scene(kept, seed, grow):
+    """make_few_visible_scene with twice `kept` Gaussians in front of the camera, their scales halved; of those the first
+    `kept` rows that reach a tile of the 48 x 48 frame, and the 300 rows behind the camera; the farthest kept one opaque and
+    `grow` times as large.  Whether a row reaches a tile is its own projection's business, so the choice survives the others'
+    removal: visible = kept, asserted by the callers.  Computed once per session (treat as read only)."""
+    from intro_to_gaussian_splatting_amd.synthetic import make_few_visible_scene
+
+    if (kept, seed) not in _LARGE_EDGE_SCENES:
+        sc = make_few_visible_scene(2 * kept + LARGE_EDGE_BEHIND, 48, 48, seed=seed, visible=2 * kept)
+        sc["scales"] = (sc["scales"] * np.float32(LARGE_EDGE_SHRINK)).astype(np.float32)
+        pre = _cpu_camera_and_stage1(sc)[1]
+        on = gbr.listed_only(pre, 48, 48, 16)[1]
+        listed = np.sort(np.asarray(pre.order, np.int64)[on])
+        assert listed.size >= kept and listed.max() < 2 * kept
+        rows = np.concatenate([listed[:kept], np.arange(2 * kept, 2 * kept + LARGE_EDGE_BEHIND)])
+        for key in ("points", "scales", "quaternions", "opacity", "colors_0_255"):
+            sc[key] = np.ascontiguousarray(sc[key][rows])
+        far = int(np.asarray(_cpu_camera_and_stage1(sc)[1].order)[-1])
+        sc["scales"][far] *= np.float32(grow)
+        sc["opacity"][far] = np.float32(3.0)
+        _LARGE_EDGE_SCENES[(kept, seed)] = sc
+    return _LARGE_EDGE_SCENES[(kept, seed)]
+
+
+def large_edge_kept(sc):
+    """(visible, kept) of the scene by the C restatement's stage 1 and its tile lists: no GPU."""
+    pre = _cpu_camera_and_stage1(sc)[1]
+    return int(np.asarray(pre.order).size), int(gbr.listed_only(pre, 48, 48, 16)[1].sum())
+
+
+@pytest.mark.parametrize("kept,seed,grow", LARGE_EDGES)
+def test_plain_float32_sum_over_the_large_edges_is_e_sum(kept, seed, grow):
+    from oracle import c_oracle
+
+    sc = large_edge_scene(kept, seed, grow)
+    assert large_edge_kept(sc) == (kept, kept) and sc["points"].shape[0] == kept + LARGE_EDGE_BEHIND
+    cam, pre = _cpu_camera_and_stage1(sc)
+    frame = c_oracle.render(pre, 48, 48, 16)[0]
+    W = np.random.default_rng(seed).standard_normal((48, 48, 3)).astype(np.float32)
+    mom = gbr.moments(pre, frame, W, 48, 48, 16)
+    args = (pre, sc["points"], sc["scales"], sc["quaternions"], cam, None, None, 48, 48, 16)
+    gV, gF, tV, tF = cgr.camera_backward(*args, moments=mom, per_gaussian=True)
+    aV, aF = cgr.camera_backward(*args, absolute=True, moments=mom)
+    assert tV.shape == tF.shape == (kept, 4, 4)
+    # every partial row of 256 ranks holds a term that is not zero, the tenth's single rank included
+    row_of = np.arange(kept) // 256
+    assert all(tV[row_of == r].any() and tF[row_of == r].any() for r in range(-(-kept // 256)))
+    measured, last_row = {}, {}
+    for key, t, g, scale in (("world2view", tV, gV, aV), ("full_proj", tF, gF, aF)):
+        assert np.array_equal(t.sum(0), g) and np.abs(g).max() > 0
+        plain = np.cumsum(t.astype(np.float32), axis=0, dtype=np.float32)[-1]       # one float32 add per Gaussian, in order
+        measured[key] = cgr.scaled_error(plain, g, scale)
+        last = np.abs(t[row_of == row_of[-1]].sum(0))
+        last_row[key] = float((last[scale > 0] / scale[scale > 0]).max())
+        print("%d kept: %s: plain float32 sum vs float64, max error / scale %.4g (recorded %.4g; E_REF %.4g); the last row's "
+              "share of the scale %.3g" % (kept, key, measured[key], E_SUM_MEASURED[kept][key], E_REF[key],
+                                           last_row[key]))
+    assert max(last_row[key] / BOUND_LARGE[key] for key in OUTPUTS) >= LARGE_EDGE_LAST_ROW_BOUNDS, last_row
+    for key, e in measured.items():
+        want = E_SUM_MEASURED[kept][key]
+        assert want / E_REF_SLACK <= e <= want * E_REF_SLACK, (kept, key, e)
 
 
 # ---- finite differences of a float64 forward

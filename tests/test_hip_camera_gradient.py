@@ -14,7 +14,8 @@ import torch
 import camera_gradient_restatement as cgr
 import geometry_backward_restatement as gbr
 import screen_gradient_restatement as sgr
-from test_camera_gradient_host import BOUND_FIXTURE, BOUND_RESTATEMENT, CAM_SCENES, fixture_inputs
+from test_camera_gradient_host import (BOUND_FIXTURE, BOUND_LARGE, BOUND_RESTATEMENT, CAM_SCENES, LARGE_EDGES, fixture_inputs,
+                                       large_edge_kept, large_edge_scene)
 from test_hip_backward import DEV, _golden_scene, _oracle_pre, _scene
 from test_hip_geometry_backward import _camera
 
@@ -25,6 +26,12 @@ pytestmark = pytest.mark.gpu
 #   world2view    5.83e-09  (rows1_48x48_n1)               6.27e-09  (rows1_48x48_n1)
 #   full_proj     6.41e-09  (edge: 1 of 500 visible)       9.11e-09  (tiny_48x48_n600)
 # (bounds: 12 E_REF = 3.49e-08, 6.64e-08 and 13 E_REF = 3.79e-08, 7.19e-08.)
+# The large edges (2048, 2049 and 2305 kept ranks: 8, 9, 10 partial rows), against the restatement, bound 12 max(E_REF, E_SUM)
+# = the same 12 E_REF:
+#   world2view    2.60e-11  (2305 kept)
+#   full_proj     2.01e-10  (2305 kept)
+# EDGES' "256" and "257" are VISIBLE counts: 185 and 186 of them reach a tile, and the backward pass ranks only those
+# (GsxFrameStats.n_kept), so both are one partial row.  The second row is first reached by the large edges.
 
 
 def _bits(t):
@@ -55,18 +62,18 @@ def _restate(scene, sc, frame, W, tile, idx=1):
     return cgr.camera_backward(*args, moments=mom) + cgr.camera_backward(*args, absolute=True, moments=mom)
 
 
-def _check(tag, got_v, got_f, restated, fixture=None):
+def _check(tag, got_v, got_f, restated, fixture=None, bound=BOUND_RESTATEMENT):
     gV, gF, aV, aF = restated
     for key, got, ref, scale in (("world2view", got_v, gV, aV), ("full_proj", got_f, gF, aF)):
         got = got.cpu().numpy().astype(np.float64)
         e = cgr.scaled_error(got, ref, scale)
-        line = "%s: %s: kernel vs restatement, max error / scale %.4g (bound %.3g)" % (tag, key, e, BOUND_RESTATEMENT[key])
+        line = "%s: %s: kernel vs restatement, max error / scale %.4g (bound %.3g)" % (tag, key, e, bound[key])
         if fixture is not None:
             ef = cgr.scaled_error(got, fixture["grad_" + key], scale)
             line += "; vs reference autograd %.4g (bound %.3g)" % (ef, BOUND_FIXTURE[key])
         print(line)
         assert np.isfinite(got).all(), (tag, key)
-        assert e <= BOUND_RESTATEMENT[key], (tag, key, e)
+        assert e <= bound[key], (tag, key, e)
         if fixture is not None:
             assert ef <= BOUND_FIXTURE[key], (tag, key, ef)
     # the structural zeros are exact +0
@@ -142,6 +149,25 @@ def test_reduction_edges(tmp_path, n, visible, seed):
     assert int(st["n_visible"]) == visible and frame.abs().max() > 0
     _check("edge %d visible" % visible, outs[-2], outs[-1], _restate(scene, sc, frame, W, 16))
     assert outs[-2].abs().max() > 0
+    _, again, _ = _entry(scene, W)
+    assert _same(again[-2], outs[-2]) and _same(again[-1], outs[-1])
+
+
+@pytest.mark.parametrize("kept,seed,grow", LARGE_EDGES)
+def test_reduction_edges_where_a_stripe_takes_a_second_row(tmp_path, kept, seed, grow):
+    """2048, 2049 and 2305 Gaussians on the tile lists (n_kept: the ranks of the backward pass): 8, 9 and 10 partial rows of
+    256 ranks for camera_reduce_kernel's 8 stripes -- every stripe one row; stripe 0 a second one; stripes 0 and 1 a second,
+    the tenth row holding one rank.  Bound: 12 max(E_REF, E_SUM) of test_camera_gradient_host.py, E_SUM the plain float32
+    sum's own error on these scenes; the last row's share of the unit is 20 bounds and more (asserted there)."""
+    sc = large_edge_scene(kept, seed, grow)
+    assert large_edge_kept(sc) == (kept, kept)          # on the CPU first: that many depth ranks, all of them on a tile list
+    assert -(-kept // 256) == {2048: 8, 2049: 9, 2305: 10}[kept]
+    scene = _scene(tmp_path, sc)
+    W = torch.from_numpy(np.random.default_rng(seed).standard_normal((48, 48, 3)).astype(np.float32)).to(DEV)
+    frame, outs, st = _entry(scene, W)
+    assert int(st["n_visible"]) == kept and int(st["n_kept"]) == kept and frame.abs().max() > 0
+    _check("edge %d kept" % kept, outs[-2], outs[-1], _restate(scene, sc, frame, W, 16), bound=BOUND_LARGE)
+    assert outs[-2].abs().max() > 0 and outs[-1].abs().max() > 0
     _, again, _ = _entry(scene, W)
     assert _same(again[-2], outs[-2]) and _same(again[-1], outs[-1])
 

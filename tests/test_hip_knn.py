@@ -10,6 +10,9 @@ Printed on an MI355X:
     eight clusters of 1024 (+3) points under the Morton order: candidates 5832285 = n^2 / 11.51, 712 per query
     tools/bench_knn.py, 10^6 points: C3 2.809 ms, 1951 candidates per query; trained-like 3.178 ms, 2383 per query (no cliff:
       22 % more evaluations, 13 % more time); cdist + topk in chunks on the same GPU 12.3 s
+    past 256 boxes (65 536, 65 537, 65 795 points; the oracle there is the restatement's brute force in torch on the device,
+      first held to the numpy one bit for bit): under the Morton order n^2 / 42.5 .. n^2 / 44.8 candidates on `uniform` and
+      `clustered`; as given and at random n^2 / 1.00 .. 1.01
 """
 import ctypes
 import functools
@@ -89,6 +92,50 @@ def test_bits_equal_the_restatement_in_every_order(kind, n):
     assert none is None and np.array_equal(_bits(dist3), _bits(c["dist3"]))
 
 
+# ---- more than 256 boxes: knn_search_kernel tests the boxes 256 at a time (`for (b0 = 0; b0 < nb; b0 += 256)`), refreshes
+# r3max and rebuilds list[] per pass.  256 boxes are one pass exactly; 257 a second pass over one box of one point; 258 a
+# second pass over two, the last a tail of three.
+LARGE_SIZES = [256 * 256, 256 * 256 + 1, 257 * 256 + 3]
+LARGE_CLOUDS = ("uniform", "clustered")
+
+
+@functools.lru_cache(maxsize=None)
+def _large_case(kind, n):
+    """The cloud and its three smallest q by the torch brute force on the device, computed once and shared."""
+    p = kr.cloud(kind, n)
+    q3 = kr.nearest3_sq_torch(p, DEV)
+    for a in (p, q3):
+        a.setflags(write=False)
+    return p, q3
+
+
+@pytest.mark.parametrize("kind", LARGE_CLOUDS)
+def test_the_torch_brute_force_is_the_numpy_restatement_bit_for_bit(kind):
+    """What makes kr.nearest3_sq_torch an oracle at the large sizes: at 8195 points it is kr.nearest3_sq, bit for bit."""
+    c = kr.case(kind, 8195)
+    assert np.array_equal(_bits(kr.nearest3_sq_torch(c["points"], DEV)), _bits(c["q3"]))
+    assert np.array_equal(_bits(kr.nearest3_sq_torch(c["points"], DEV, chunk=1000)), _bits(c["q3"]))     # a partial last chunk
+
+
+@pytest.mark.parametrize("n", LARGE_SIZES)
+@pytest.mark.parametrize("kind", LARGE_CLOUDS)
+def test_bits_equal_the_brute_force_past_256_boxes(kind, n):
+    p, q3 = _large_case(kind, n)
+    assert -(-n // 256) == {256 * 256: 256, 256 * 256 + 1: 257, 257 * 256 + 3: 258}[n] and np.isfinite(q3).all()
+    want_dist3, want_scale = np.sqrt(q3), kr.scale_of(q3, kr.REFERENCE)
+    for label, order in _orders(p):
+        dist3, scale, counted = _call(p, order, kr.REFERENCE, count=True)
+        assert np.array_equal(_bits(dist3), _bits(want_dist3)), (kind, n, label)
+        assert np.array_equal(_bits(scale), _bits(want_scale)), (kind, n, label)
+        assert 0 <= counted <= n * (n - 1), (kind, n, label, counted)
+        print("%s n = %d, %s order: candidates %d = n^2 / %.2f" % (kind, n, label, counted, n * n / max(counted, 1)))
+        if label == "morton":
+            if kind == "uniform":
+                assert counted <= n * n // 4, counted          # pruning still happens across the passes
+            none, scale, _ = _call(p, order, kr.PUBLISHED, want_dist3=False)
+            assert none is None and np.array_equal(_bits(scale), _bits(kr.scale_of(q3, kr.PUBLISHED))), (kind, n)
+
+
 def test_a_cloud_of_identical_points_stays_linear_and_n_zero_writes_nothing():
     """Skip on bound >= r3: every distance is 0 after the own block, every other box's bound is 0, nothing else is scanned."""
     n = 8195
@@ -97,6 +144,15 @@ def test_a_cloud_of_identical_points_stays_linear_and_n_zero_writes_nothing():
     assert not dist3.any() and np.array_equal(_bits(scale), _bits(np.full((n, 1), 1e-5, dtype=F)))
     # (the tail's three lanes have two neighbours at home: they scan one more block, then their r3 is 0 as well)
     assert counted == 32 * 256 * 255 + 3 * (2 + 256)
+    # 258 boxes, two passes over them: the 257 full blocks find their three at home (255 pairs per lane) and list nothing in
+    # either pass (every bound is 0 = r3max).  The tail's three lanes have two neighbours at home (2 pairs each) and r3 = inf,
+    # so the first pass lists its 256 boxes; they scan the first of them (256 pairs each), after which r3 = 0 >= every
+    # other box's distance: the other 255 are staged and scanned by nobody, and in the second pass r3max = 0 lists nothing.
+    n = 257 * 256 + 3
+    p = np.full((n, 3), 1.25, dtype=F)
+    dist3, scale, counted = _call(p, None, kr.REFERENCE, count=True)
+    assert not dist3.any() and np.array_equal(_bits(scale), _bits(np.full((n, 1), 1e-5, dtype=F)))
+    assert counted == 257 * 256 * 255 + 3 * (2 + 256)
     _ffi, lib = _lib()
     d = Guarded(3)
     assert lib.gsx_knn3(None, 0, None, 0, d.view.data_ptr(), None, None, None, 0, _stream()) == 0

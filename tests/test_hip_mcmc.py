@@ -5,7 +5,11 @@ The plan is compared element for element with the integer restatement evaluated 
 to +-1 of the float64 restatement: the device's double exp); the apply bit for bit, except the relocated opacity logits and
 scales: within 1 float32 ulp of the float64 restatement rounded to float32 (a 1e-9 relative difference before rounding can
 move the rounded value by one).  The two per-step kernels are held to 12 x the recorded float32 reference errors of
-tests/test_mcmc_host.py, in the units fixed there; the largest measured multiple is printed."""
+tests/test_mcmc_host.py, in the units fixed there; the largest measured multiple is printed.
+
+Measured on an MI355X at the sizes where mcmc_blocks_kernel takes a second pass (262 144, 262 145 and 263 644 rows, 4097 new):
+the weights within 1 of the restatement's, source / count / header exact on them, the same bits twice; the apply at 262 145 rows: 107 511 moved rows,
+largest N 8, relocated values within 0.00 ulp."""
 import ctypes
 import math
 import os
@@ -102,6 +106,63 @@ def test_plan_equals_the_integer_restatement(n):
             assert w[o == np.float32(20.0)].min() == 2 ** 22 and counts[0] > 0          # sigma saturates: the largest weight
 
 
+# mcmc_blocks_kernel scans the 1024-row block sums 256 at a time with a carry between the passes, and mcmc_draw_kernel
+# bisects what it leaves: 256 blocks are one pass exactly, one row more is a second pass of one block that holds one row,
+# and 1500 rows more a second pass of two blocks with dead and live rows in it.
+BLOCK_ROWS, PASS_BLOCKS = 1024, 256
+ONE_PASS = PASS_BLOCKS * BLOCK_ROWS
+BIG_PLAN_SIZES = (ONE_PASS, ONE_PASS + 1, ONE_PASS + 1500)
+BIG_NEW = 4097                              # n_out - n: new rows exist, and the draw kernel's last workgroup is partial
+
+
+def _big_plan_case(n):
+    """plan_case(n, n + BIG_NEW) with a saturated row at the head of block 256 (where n reaches it) and the uniforms of the
+    first two new rows aimed: row n at the middle of that row's weight (n > ONE_PASS; 2^21 units from either end, far more
+    than the +-1 per row the device's weights may differ by), row n + 1 just below 1.  Returns (o, dead_logit, n_out, u)
+    after asserting on the restatement's weights what the sizes are for."""
+    n_out = n + BIG_NEW
+    o, dead_logit, u = plan_case(n, n_out)
+    second = n > ONE_PASS
+    if second:
+        o[ONE_PASS] = np.float32(20.0)
+    u[n + 1] = 1.0 - 2.0 ** -53
+    w = mr.weights_of(o, dead_logit).astype(np.uint64)
+    P = np.concatenate([[0], np.cumsum(w)])
+    total = int(P[-1])
+    dead = mr.dead_rows(o, dead_logit)
+    last_live = int(np.nonzero(w)[0][-1])
+    nb = -(-n // BLOCK_ROWS)
+    assert (n_out % 256 != 0) and nb == {0: 256, 1: 257, 1500: 258}[n - ONE_PASS]
+    # a uniform just below 1 maps to the very last live row, which lies in the last block
+    assert min(total - 1, int(math.floor(u[n + 1] * float(total)))) == total - 1 and last_live // BLOCK_ROWS == nb - 1
+    assert dead[:ONE_PASS].any()
+    if second:
+        # rows ONE_PASS.. hold live weight: the bisection reaches bsum[256], which is the first pass's carry
+        assert w[ONE_PASS:].sum() > 0 and int(P[ONE_PASS]) > 2 ** 32
+        # a uniform maps to the first row of block 256
+        u[n] = (float(P[ONE_PASS]) + 2.0 ** 21) / float(total)
+        t = int(math.floor(u[n] * float(total)))
+        assert int(w[ONE_PASS]) == 2 ** 22 and abs(t - int(P[ONE_PASS]) - 2 ** 21) <= 2 ** 10
+        # dead rows in both passes, so that n_dead adds across them -- where the second pass has more than its one live row
+        assert dead[ONE_PASS:].any() == (n > ONE_PASS + 1) and (w[ONE_PASS:] > 0).sum() >= 1
+    return o, dead_logit, n_out, u
+
+
+@pytest.mark.parametrize("n", BIG_PLAN_SIZES)
+def test_plan_equals_the_integer_restatement_where_the_block_scan_takes_a_second_pass(n):
+    o, dead_logit, n_out, u = _big_plan_case(n)
+    w, source, count, counts = _check_plan(o, dead_logit, n_out, u)
+    again = _plan(o, dead_logit, n_out, u)                           # the same inputs twice: the same bits
+    assert np.array_equal(again[0], w) and np.array_equal(again[1], source) and np.array_equal(again[2], count)
+    assert again[3] == counts
+    assert w[o == np.float32(20.0)].min() == 2 ** 22
+    assert counts == (int(mr.dead_rows(o, dead_logit).sum()), int((w > 0).sum()), BIG_NEW)
+    # the two aimed draws, on the kernel's own weights
+    assert source[n + 1] == np.nonzero(w)[0][-1]
+    if n > ONE_PASS:
+        assert source[n] == ONE_PASS and (source[n:] >= ONE_PASS).sum() >= 2
+
+
 def test_plan_one_live_row_among_two_thousand_dead_and_nobody_alive():
     n = 2001
     o = np.full(n, -9.0, np.float32)
@@ -133,12 +194,13 @@ def test_relocate_raises_when_nobody_is_alive_and_rewrites_nothing():
 # ---------------------------------------------------------------------------------------------------- apply
 SPEC = [("copy1", 1, mr.COPY), ("copy4", 4, mr.COPY), ("copy48", 48, mr.COPY), ("m3", 3, mr.ZERO_MOVED), ("m48", 48, mr.ZERO_MOVED),
         ("opacity", 1, mr.OPACITY), ("scales", 3, mr.SCALES)]
+SMALL_SPEC = [g for g in SPEC if g[1] <= 4]             # one group per role, no 48-wide rows: for the large size
 
 
-def _apply_case(o, rs):
+def _apply_case(o, rs, spec=SPEC):
     n = len(o)
     src = {}
-    for name, width, role in SPEC:
+    for name, width, role in spec:
         if role == mr.OPACITY:
             a = o.reshape(n, 1).copy()          # (NaN and infinite rows have weight 0: never a source, copied as bits)
         elif role == mr.SCALES:
@@ -149,34 +211,34 @@ def _apply_case(o, rs):
     return src
 
 
-def _apply(src, n_out, source, count, lead=0):
+def _apply(src, n_out, source, count, lead=0, spec=SPEC):
     _ffi, lib = _lib()
     n = len(count)
-    groups = (_ffi.GsxDensityGroup * len(SPEC))()
+    groups = (_ffi.GsxDensityGroup * len(spec))()
     keep, dst = [], {}
-    for i, (name, width, role) in enumerate(SPEC):
+    for i, (name, width, role) in enumerate(spec):
         whole, view = _based(src[name], lead)
         wd, out = _based(np.full((n_out, width), 12345.0, np.float32), lead)
         keep += [whole, wd]
         dst[name] = out
         groups[i].src, groups[i].dst, groups[i].width, groups[i].role = view.data_ptr(), out.data_ptr(), width, role
     sd, cd = _dev(source), _dev(count.view(np.int32))
-    rc = lib.gsx_mcmc_apply(groups, len(SPEC), n, n_out, sd.data_ptr(), cd.data_ptr(), MIN_OPACITY, _stream())
+    rc = lib.gsx_mcmc_apply(groups, len(spec), n, n_out, sd.data_ptr(), cd.data_ptr(), MIN_OPACITY, _stream())
     _ffi.check(rc)
     torch.cuda.synchronize()
     return {name: t.cpu().numpy() for name, t in dst.items()}
 
 
-def _check_apply(o, dead_logit, n_out, u, lead=0, seed=0):
+def _check_apply(o, dead_logit, n_out, u, lead=0, seed=0, spec=SPEC):
     n = len(o)
     _, source, count, _ = _plan(o, dead_logit, n_out, u)
-    src = _apply_case(o, np.random.RandomState(77 + seed + n))
-    got = _apply(src, n_out, source, count, lead)
-    want, moved = mr.apply([(src[name], role) for name, _, role in SPEC], source, count, MIN_OPACITY)
+    src = _apply_case(o, np.random.RandomState(77 + seed + n), spec)
+    got = _apply(src, n_out, source, count, lead, spec)
+    want, moved = mr.apply([(src[name], role) for name, _, role in spec], source, count, MIN_OPACITY)
     N = np.minimum(count.astype(np.int64)[source] + 1, mr.N_MAX)
     assert np.array_equal(moved, N > 1) and (source[~moved] == np.arange(n_out)[~moved]).all()
     worst = 0.0
-    for (name, width, role), ref in zip(SPEC, want):
+    for (name, width, role), ref in zip(spec, want):
         out = got[name]
         assert out.shape == ref.shape
         assert _same(out[~moved], src[name][source[~moved]]), name                  # N = 1: the row's bits, moments included
@@ -206,6 +268,14 @@ def test_apply_equals_the_restatement(n):
         o, dead_logit, u = plan_case(n, n_out)
         worst, n_moved, n_top = _check_apply(o, dead_logit, n_out, u)
         print("n = %d, n_out = %d: %d moved rows, largest N %d, relocated values within %.2f ulp" % (n, n_out, n_moved, n_top, worst))
+
+
+def test_apply_equals_the_restatement_on_a_plan_of_two_block_scan_passes():
+    n = ONE_PASS + 1
+    o, dead_logit, n_out, u = _big_plan_case(n)
+    worst, n_moved, n_top = _check_apply(o, dead_logit, n_out, u, spec=SMALL_SPEC)
+    print("n = %d, n_out = %d: %d moved rows, largest N %d, relocated values within %.2f ulp" % (n, n_out, n_moved, n_top, worst))
+    assert n_moved > BIG_NEW and n_top > 1
 
 
 @pytest.mark.parametrize("lead", [1, 3])

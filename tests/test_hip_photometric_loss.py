@@ -9,6 +9,10 @@ Bound: 12 E_REF per output, E_REF the float32 reference's own error (tests/test_
 CPU: value 1.110e-06, grad 2.228e-06).  What the kernels measured on an MI355X over the ten cases x three lambdas, same units:
     value  6.934e-07  (halo_across_a_neighbour, lambda 1)
     grad   6.888e-07  (two_tiles_plus_5_by_3, lambda 1)
+and over the five LARGE_CASES (9, 16, 256 and 289 tiles: a tile with eight neighbours, and the sizes at which a thread of
+the one-workgroup reduce takes its first and its second record) x three lambdas, same bound:
+    value  1.014e-07  (tiles_4x4_scalar, lambda 1)
+    grad   7.039e-07  (tiles_289_vector_cropped, lambda 1)
 """
 import ctypes
 import functools
@@ -105,7 +109,7 @@ def _evaluate(x, y, region, skip, lam):
 
 @functools.lru_cache(maxsize=None)          # one float64 reference per (case, lambda), shared
 def _reference(name, lam):
-    _, _, (a, b), _ = plr.CASES[plr.CASE_IDS.index(name)]
+    _, _, (a, b), _ = plr.case_of(name)
     x, y = plr.case_inputs(name)
     return plr.forward(x[:a, :b], y[:a, :b], lam), plr.gradient(x[:a, :b], y[:a, :b], lam)
 
@@ -126,6 +130,22 @@ def test_value_and_gradient_match_the_restatement_at_every_edge(name):
     _, shape, region, skip = plr.CASES[plr.CASE_IDS.index(name)]
     x, y = plr.case_inputs(name)
     a, b = region
+    for lam in plr.LAMBDAS:
+        out, grad = _evaluate(x, y, region, skip, lam)
+        ref, ref_grad = _reference(name, lam)
+        _check_against(out, grad[:a, :b], ref, ref_grad, "%s lambda %.1f" % (name, lam))
+
+
+@pytest.mark.parametrize("name", plr.LARGE_CASE_IDS)
+def test_value_and_gradient_match_the_restatement_where_the_reduce_loop_repeats(name):
+    """The same checks (value, l1, ssim, dL/dframe within 12 E_REF; with and without a gradient; two calls, equal bits) at
+    the shapes of plr.LARGE_CASES: tiles with neighbours on all eight sides, and 256 / 289 tile partials, where a thread of
+    the one-workgroup reduce first takes a second record."""
+    _, shape, region, skip = plr.case_of(name)
+    a, b = region
+    assert plr.tiles_of(region) == {"tiles_3x3_vector": 9, "tiles_4x4_scalar": 16, "tiles_256": 256}.get(name, 289)
+    assert ((shape[1] * 3) % 4 == 0) == ("vector" in name or name == "tiles_256")
+    x, y = plr.case_inputs(name)
     for lam in plr.LAMBDAS:
         out, grad = _evaluate(x, y, region, skip, lam)
         ref, ref_grad = _reference(name, lam)

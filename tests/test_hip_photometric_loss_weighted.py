@@ -14,6 +14,11 @@ the twelve cases with a non-zero mask x three lambdas, same units:
     value          1.181e-06  (halo_across_a_neighbour_single_none, lambda 1)
     grad           1.044e-06  (halo_across_a_neighbour_random_general, lambda 1)
     grad_exposure  6.674e-07  (one_pixel_ones_general, lambda 1)
+and over the eleven LARGE_CASES with a non-zero mask (9, 16, 256 and 289 tiles: where the two one-workgroup reduces take
+their loops' first and second step) x three lambdas, same bound:
+    value          8.156e-08  (tiles_4x4_scalar_random_general, lambda 1)
+    grad           9.153e-07  (tiles_289_scalar_binary_general, lambda 1)
+    grad_exposure  1.472e-07  (tiles_289_scalar_binary_general, lambda 0)
 """
 import ctypes
 import functools
@@ -136,8 +141,7 @@ def _reference(name, lam):
     return wr.forward(x, y, lam, m, E), wr.gradient(x, y, lam, m, E)
 
 
-@pytest.mark.parametrize("name", wr.NONZERO_CASE_IDS)
-def test_value_and_gradients_match_the_restatement_at_every_edge(name):
+def _held_to_the_restatement(name):
     _, (a, b), skip = wr.case_geometry(name)
     x, y, m, E = wr.case_inputs(name)
     for lam in wr.LAMBDAS:
@@ -153,8 +157,22 @@ def test_value_and_gradients_match_the_restatement_at_every_edge(name):
         assert abs(float(out[3]) - ref[3]) <= BOUND_W["value"] * ref[3], (out, ref)
 
 
-@pytest.mark.parametrize("name", wr.ZERO_CASE_IDS)
-def test_an_all_zero_weight_gives_exact_zeros(name):
+@pytest.mark.parametrize("name", wr.NONZERO_CASE_IDS)
+def test_value_and_gradients_match_the_restatement_at_every_edge(name):
+    _held_to_the_restatement(name)
+
+
+@pytest.mark.parametrize("name", wr.LARGE_NONZERO_CASE_IDS)
+def test_value_and_gradients_match_the_restatement_where_the_reduce_loops_repeat(name):
+    """wr.LARGE_CASES: loss, l1, ssim, W, dL/dimage and dL/dE within the same 12 E_REF_W at 9, 16, 256 and 289 tile
+    partials -- at 289 threads 0..32 of wloss_reduce_kernel and of wloss_exposure_reduce_kernel (the only user of
+    sum_records<12>) take a second record."""
+    _, region, _ = wr.case_geometry(name)
+    assert plr.tiles_of(region) in (9, 16, 256, 289) and (plr.tiles_of(region) == 289) == name.startswith("tiles_289")
+    _held_to_the_restatement(name)
+
+
+def _zero_weight_gives_exact_zeros(name):
     _, (a, b), skip = wr.case_geometry(name)
     x, y, m, E = wr.case_inputs(name)
     assert not m[:a, :b].any() and m[a:].all() and m[:, b:].all()
@@ -163,6 +181,18 @@ def test_an_all_zero_weight_gives_exact_zeros(name):
         assert not out.view(np.uint32).any()                                  # +0, bit for bit
         assert not np.ascontiguousarray(grad[:a, :b]).view(np.uint32).any()
         assert grad_e is None or not grad_e.view(np.uint32).any()
+
+
+@pytest.mark.parametrize("name", wr.ZERO_CASE_IDS)
+def test_an_all_zero_weight_gives_exact_zeros(name):
+    _zero_weight_gives_exact_zeros(name)
+
+
+@pytest.mark.parametrize("name", wr.LARGE_ZERO_CASE_IDS)
+def test_an_all_zero_weight_gives_exact_zeros_over_289_tiles(name):
+    x, y, m, E = wr.case_inputs(name)
+    assert plr.tiles_of(wr.case_geometry(name)[1]) == 289 and E is not None
+    _zero_weight_gives_exact_zeros(name)
 
 
 @pytest.mark.parametrize("base", ["tile_minus_1_by_tile_plus_1", "cropped_45x50_of_48x64", "unaligned_base"])

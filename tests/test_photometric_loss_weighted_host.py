@@ -15,6 +15,10 @@ The kernels are held to BOUND_W = 12 E_REF_W (tests/test_hip_photometric_loss_we
 convolution sums in an order that depends on the CPU it runs on: the test accepts a factor of 1.5 either way, as
 tests/test_photometric_loss_host.py does, and BOUND_W is built from the RECORDED figures.  The all-zero masks are left out
 here (every output is an exact zero: asserted as such).
+
+wr.LARGE_CASES (9 .. 289 tiles) do not feed E_REF_W.  The same reference measured on them on the CPU: value at most 1.178e-06
+(tiles_289_vector_cropped_random_general, lambda 1), grad 2.403e-06 (tiles_289_scalar_random_general, lambda 1),
+grad_exposure 3.399e-07 (tiles_4x4_scalar_binary_general, lambda 1) -- each case is held to E_REF_W x 1.5.
 """
 import ctypes
 import os
@@ -163,6 +167,33 @@ def test_float32_reference_error_is_e_ref_w():
     for key, (val, where) in worst.items():
         print("E_REF_W %s = %.4g at %s (recorded %.4g)" % (key, val, where, E_REF_W[key]))
         assert E_REF_W[key] / E_REF_WINDOW <= val <= E_REF_W[key] * E_REF_WINDOW, (key, val)
+
+
+@pytest.mark.parametrize("name", wr.LARGE_NONZERO_CASE_IDS)
+def test_float32_reference_stays_within_the_window_of_e_ref_w_at_the_large_cases(name):
+    """wr.LARGE_CASES do not feed E_REF_W; the kernels are held to the same 12 E_REF_W there, so the reference itself has
+    to meet E_REF_W x E_REF_WINDOW at them."""
+    x, y, m, E = wr.cropped_inputs(name)
+    for lam in wr.LAMBDAS:
+        tx = torch.from_numpy(x).requires_grad_(True)
+        tE = None if E is None else torch.from_numpy(E.copy()).requires_grad_(True)
+        loss = wr.torch_loss(tx, torch.from_numpy(y), lam, None if m is None else torch.from_numpy(m), tE)[0]
+        assert loss.dtype == torch.float32
+        loss.backward()
+        ref, (ref_g, ref_gE) = wr.forward(x, y, lam, m, E), wr.gradient(x, y, lam, m, E)
+        e = wr.errors(loss.detach(), tx.grad.numpy(), None if tE is None else tE.grad.numpy(), ref[0], ref_g, ref_gE)
+        print("%s lambda %.1f: float32 torch vs restatement: %s" % (
+            name, lam, ", ".join("%s %.4g" % kv for kv in sorted(e.items()))))
+        for key, val in e.items():
+            assert val <= E_REF_W[key] * E_REF_WINDOW, (name, lam, key, val, E_REF_W[key])
+
+
+@pytest.mark.parametrize("name", wr.LARGE_ZERO_CASE_IDS)
+def test_all_zero_weight_over_289_tiles_is_exactly_zero_in_the_restatement(name):
+    x, y, m, E = wr.cropped_inputs(name)
+    assert not m.any()
+    g, gE = wr.gradient(x, y, 0.2, m, E)
+    assert wr.forward(x, y, 0.2, m, E) == (0.0, 0.0, 0.0, 0.0) and not g.any() and not gE.any()
 
 
 # ---- C ABI
